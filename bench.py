@@ -19,6 +19,16 @@ the winners do not depend on N; --shard candidates splits every label's
 candidates instead (rank r scores [r C/N, (r+1) C/N)).
 
     python bench.py [--gpus N] [--steps K] [--warmup W] [--precision f64|f32]
+                    [--dump-outputs DIR] [--full]
+
+A plain run sets up, warms up, times the K steps and prints the result line
+(the headline figures and what the timed steps themselves report: per-family
+times, the screen's counts, the dominant kernel's roofline).  --dump-outputs
+DIR writes the winners of the last timed step as DIR/<name>.npy.  --full adds
+the legs that take runs of their own: the other BASELINE configs, the
+posterior-build timing, the warm rounds, the unscreened fp64 comparison, the
+oracle agreement, the 8-GPU projections, the fp32 agreement, the tpe.suggest
+latency, config 1 and the CPU baselines.
 """
 import argparse
 import json
@@ -68,6 +78,14 @@ def parse():
     ap.add_argument('--steps', type=int, default=5)
     ap.add_argument('--warmup', type=int, default=2)
     ap.add_argument('--precision', default='f64', choices=['f64', 'f32'])
+    ap.add_argument('--full', action='store_true',
+                    help='after the timed steps, also run the legs that take runs of their own (other '
+                         'configs, posterior-build timing, warm rounds, unscreened fp64 comparison, oracle '
+                         'agreement, 8-GPU projections, fp32 agreement, suggest latency, config 1, CPU '
+                         'baselines); the --no-* switches below drop single legs of a --full run')
+    ap.add_argument('--dump-outputs', default=None, metavar='DIR',
+                    help='write the winners of the last timed step (what the step returns to its caller) '
+                         'as DIR/<name>.npy, float64')
     ap.add_argument('--config', type=int, default=3, choices=[2, 3, 4, 5],
                     help='BASELINE.json config: 3 (headline, default), 2 (Hartmann-6, 2k '
                          'history, 2^20 candidates), 4 (nested SVM/RF/GBM choice space, 5k '
@@ -217,7 +235,7 @@ def other_configs(args):
     import subprocess
     out = {}
     for cfg in (2, 4, 5):
-        cmd = [sys.executable, os.path.join(REPO, 'bench.py'), '--config', str(cfg), '--steps',
+        cmd = [sys.executable, os.path.join(REPO, 'bench.py'), '--full', '--config', str(cfg), '--steps',
                str(args.steps), '--warmup', str(args.warmup), '--no-cpu-baseline', '--no-latency']
         t0 = time.perf_counter()
         try:
@@ -248,6 +266,26 @@ def other_configs(args):
             'oracle_agree': {k: ag.get(k) for k in ('cells', 'agree', 'rate')} if ag else None,
             'child_wall_s': round(wall, 1)}
     return out
+
+
+DUMP_MAX_BYTES = 64 << 20
+
+
+def dump_outputs(dirname, res, value_only):
+    """The winners of one step (engine.RESULT_DTYPE records, one per label or
+    per (new_id, label)) as dirname/<field>.npy in float64: value and index
+    (exact: below 2^53), and score, lpdf_below, lpdf_above unless the step
+    ran value-only rounds (whose decided cells carry no lpdfs).  More than
+    DUMP_MAX_BYTES in all: a fixed sample of the cells (RandomState(0), in
+    cell order), the same from run to run."""
+    res = np.asarray(res)
+    fields = ['value', 'index'] + ([] if value_only else ['score', 'lpdf_below', 'lpdf_above'])
+    cap = DUMP_MAX_BYTES // (8 * len(fields))
+    if res.size > cap:
+        res = res.reshape(-1)[np.sort(np.random.RandomState(0).choice(res.size, cap, replace=False))]
+    os.makedirs(dirname, exist_ok=True)
+    for f in fields:
+        np.save(os.path.join(dirname, f + '.npy'), np.ascontiguousarray(res[f], dtype=np.float64))
 
 
 def cpu_baseline_numpy(posts, n_cand):
@@ -600,7 +638,7 @@ def main():
             world, args.gpus, ' (--devices runs one process)' if args.devices else ''))
         sys.exit(3)
     others = None
-    if (world == 1 and args.config == 3 and not args.devices and not args.no_other_configs
+    if (args.full and world == 1 and args.config == 3 and not args.devices and not args.no_other_configs
             and args.precision == 'f64' and args.labels == 32 and args.cand_log2 == 24
             and not args.dry_run):
         others = other_configs(args)   # (child processes, before this one touches the GPU)
@@ -667,16 +705,18 @@ def main():
     t_host = time.perf_counter() - t_host
     inputs = hist.device_inputs()
     dev_call, dev_kern = [], []
-    for _ in range(3):
+    for _ in range(3 if args.full else 1):   # (one build is set-up: warm mode's resident posterior)
         t0 = time.perf_counter()
         eng.build_posterior(*inputs, gamma=0.25, prior_weight=1.0)
         dev_call.append(time.perf_counter() - t0)
         dev_kern.append(eng.last_build_ms())
-    post_build = {'device_call_ms': round(1e3 * float(np.median(dev_call)), 3),
-                  'device_kernels_ms': round(float(np.median(dev_kern)), 3),
-                  'host_numpy_ms': round(1e3 * t_host, 3),
-                  'note': 'tpe_build_posterior (split, sort, Parzen, fold on the GPU; call '
-                          'includes the H2D of the history) vs posterior.py + pack'}
+    post_build = None
+    if args.full:
+        post_build = {'device_call_ms': round(1e3 * float(np.median(dev_call)), 3),
+                      'device_kernels_ms': round(float(np.median(dev_kern)), 3),
+                      'host_numpy_ms': round(1e3 * t_host, 3),
+                      'note': 'tpe_build_posterior (split, sort, Parzen, fold on the GPU; call '
+                              'includes the H2D of the history) vs posterior.py + pack'}
     C_total = 24 if args.config == 5 else 1 << args.cand_log2
     from hyperopt_amd.parallel import gather_labels, label_shards
     # label shards whenever every rank gets a label (r4am: config 4's 13 labels
@@ -726,6 +766,7 @@ def main():
         if desc:
             xch.share()                       # (warm mode: the shared posterior of that history)
     results = {}
+    last_res = [None]   # what the newest step of timed() returned
 
     def step(i, fresh, n=None, e=None, lp=None, gather=True):
         """One step; n: the candidates per label of this rank's candidate
@@ -791,6 +832,7 @@ def main():
         t0 = time.perf_counter()
         for i in range(n_steps):
             res = step(first + i, fresh, n)
+            last_res[0] = res
             if keep:
                 results[first + i] = res
             for k, (ms, ev) in eng.last_mode_stats().items():
@@ -853,15 +895,18 @@ def main():
     dt, mode_ms, mode_ev, scr = timed(args.steps, args.warmup, fresh_mode)
     phases, P.PHASES = P.PHASES, None
     smode_timed = eng.last_screen_mode()   # (the timed rounds' screen; later legs run others)
+    if args.dump_outputs and rank == 0:
+        dump_outputs(args.dump_outputs, last_res[0], value_only)
     # the same rounds on the posterior of the last step, reused (no append):
     # the round alone, and the reference for the unscreened comparison
     warm_first = args.warmup + args.steps
-    wdt, _, _, _ = timed(args.steps, warm_first, False, keep=True) if fresh_mode else (None,) * 4
+    wdt, _, _, _ = (timed(args.steps, warm_first, False, keep=True) if fresh_mode and args.full
+                    else (None,) * 4)
     # the plain fp64 round on the SAME (seed, round) as screened steps on
     # the same posterior -- before anything else advances it: winners,
     # values and lpdfs bit for bit
     unscreened = None
-    if screen and args.unscreened_steps > 0 and world == 1 and devs is None:
+    if args.full and screen and args.unscreened_steps > 0 and world == 1 and devs is None:
         # (fresh mode compares the warm steps' rounds: at most args.steps of them)
         nu = min(args.unscreened_steps, args.steps) if fresh_mode else args.unscreened_steps
         first = warm_first if fresh_mode else args.warmup + args.steps
@@ -910,7 +955,8 @@ def main():
     # candidate shards: C/8 candidates per label at the whole round's map
     # choices, the per-posterior work repeated), fresh and warm
     proj = None
-    if fresh_mode and world == 1 and devs is None and not args.no_projection and (by_label or (args.config != 5 and C % 8 == 0)):
+    if (args.full and fresh_mode and world == 1 and devs is None and not args.no_projection
+            and (by_label or (args.config != 5 and C % 8 == 0))):
         p0 = warm_first + args.steps
         if by_label:
             per = []
@@ -961,9 +1007,9 @@ def main():
     # slice of the round (C/8 candidates of every label; config 5: 1/8 of
     # the new_ids) -- the slowest build + import + slice
     dproj = None
-    if (fresh_mode and world == 1 and devs is None and not args.no_projection and args.precision == 'f64'
-            and args.shard in ('auto', 'descriptors') and (args.config == 5 or C % 8 == 0)
-            and len(hist_full.labels) >= 8):
+    if (args.full and fresh_mode and world == 1 and devs is None and not args.no_projection
+            and args.precision == 'f64' and args.shard in ('auto', 'descriptors')
+            and (args.config == 5 or C % 8 == 0) and len(hist_full.labels) >= 8):
         dproj = descriptor_projection(args, hist_full, local, screen, value_only, C_total,
                                       warm_first + args.steps, dt / args.steps * 1e3,
                                       wdt / args.steps * 1e3)
@@ -1125,17 +1171,20 @@ def main():
                                             'argsorts_under_round (max of the two), rebuild, quant_round '
                                             '(the quantized labels after their rebuild); step_total = '
                                             'all of it',
-                  'warm_round_ms': round(wdt / args.steps * 1e3, 3),
+                  'warm_round_ms': round(wdt / args.steps * 1e3, 3) if wdt is not None else None,
                   'warm_note': 'the same rounds on one resident posterior (no append, no rebuild, '
-                               'no index): the round alone'}
+                               'no index): the round alone (--full)'}
                  if fresh_mode else
                  {'kind': 'warm (one resident posterior)',
                   'fresh_posterior_round_ms': (round(post_build['device_call_ms'] + prep_ms
-                                                     + dt / args.steps * 1e3, 3) if prep_ms else None)}),
+                                                     + dt / args.steps * 1e3, 3)
+                                               if prep_ms and post_build else None)}),
+        'full': bool(args.full),
         'scaling_projection': proj,
         'scaling_projection_descriptors': dproj,
         'device_memory': mem,
-        'posterior_build': dict(post_build, expansion_index_ms=(round(prep_ms, 3) if prep_ms else None),
+        'posterior_build': dict(post_build or {},
+                                expansion_index_ms=(round(prep_ms, 3) if prep_ms else None),
                                 expansion_index_note='the first index of the run (bin tables, lists, '
                                 'sub-bin bounds; wall ms with the kernels)'),
         'per_family_ms': {k: round(v / args.steps, 3) for k, v in mode_ms.items() if v},
@@ -1188,7 +1237,7 @@ def main():
                             ' of every label, bytewise, on rounds %d..%d of the last posterior (the '
                             'screened runs are the warm steps)' % (first, first + nu - 1),
                 'bit_identical': bool(same)}
-    if prec == 'f32' and args.agreement_steps > 0 and args.config != 5:
+    if args.full and prec == 'f32' and args.agreement_steps > 0 and args.config != 5:
         # fp32 winners vs the exact fp64 round's on the same candidate sets
         ref = Engine(devs if devs else local, 'f64')
         if loop is not None:   # the posterior the fp32 engine holds now
@@ -1218,13 +1267,13 @@ def main():
     if args.config == 5:
         line['config']['new_ids_per_step'] = args.new_ids
         line['config']['new_ids_per_gpu_per_step'] = ids_local
-    if rank == 0 and not args.no_latency and args.config == 3:
+    if args.full and rank == 0 and not args.no_latency and args.config == 3:
         lat = suggest_latency(args.labels, args.trials)
         line['suggest_latency_ms'] = {
             'value': round(lat, 3), 'n_EI_candidates': 24, 'history': args.trials,
             'labels': args.labels, 'note': 'end-to-end tpe.suggest wall time, median of 20; '
                                            'reference CPU: 1330 ms (BASELINE.md)'}
-    if rank == 0 and not args.no_latency and args.config == 3:
+    if args.full and rank == 0 and not args.no_latency and args.config == 3:
         wall, bx = config1_fmin()
         line['config1_fmin'] = {
             'wall_s': round(wall, 4), 'trials': 100, 'n_EI_candidates': 24, 'best_x': bx,
@@ -1233,7 +1282,7 @@ def main():
                     '(20 random startup + 80 TPE suggestions), RandomState(0), objective included; '
                     'median of 3 runs; every TPE suggestion is the oracle argmax of its 24 '
                     'candidates (tests/test_config1.py)'}
-    if rank == 0 and world == 1 and not args.no_cpu_baseline and args.config == 3:
+    if args.full and rank == 0 and world == 1 and not args.no_cpu_baseline and args.config == 3:
         rate, sec, ev, thr = cpu_baseline_c(eng, posts, args.cpu_sample_c, 1234, 0)
         nrate, nsec, nev = cpu_baseline_numpy(posts, args.cpu_sample)
         line['cpu_baseline'] = {

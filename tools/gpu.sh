@@ -8,8 +8,8 @@
 #   tests            the whole -m gpu suite (one pytest process)
 #   tests=<expr>     the -m gpu tests matching pytest -k <expr> (commas for spaces)
 #   smoke            __graft_entry__.smoke()
-#   bench            the default bench.py line (what the driver runs)
-#   bench=<args>     bench.py with extra arguments (commas for spaces)
+#   bench            the whole bench.py line (bench.py --full: every leg)
+#   bench=<args>     bench.py with extra arguments (commas for spaces; --full for the legs beyond the timed steps)
 #   var=<name>[,args] bench.py on the variant library tools/var_<name>.so (tools/build_variant.py)
 #   htrace=<script,args> rocprofv3 kernel + memory-copy + HIP API trace of a script -> <tag>/htrace<n>
 #   vpy=<name>,<script,args> a python script of the tree on that variant library
@@ -54,7 +54,7 @@ for s in "$@"; do
         smoke)
             run smoke 200 python -u -c "import __graft_entry__ as g; g.smoke()" || exit 1 ;;
         bench)
-            run bench 600 python -u bench.py || exit 1 ;;
+            run bench 600 python -u bench.py --full || exit 1 ;;
         bench=*)
             a=${s#bench=}
             run bench$n 600 python -u bench.py ${a//,/ } || exit 1 ;;

@@ -19,7 +19,7 @@ step() { local name=$1 secs=$2; shift 2; echo "== $name"; timeout -k 10 "$secs" 
 Q="--no-cpu-baseline --no-latency --unscreened-steps 0 --no-projection --no-other-configs --no-agreement"
 pmc() { local name=$1; shift; step $name 150 rocprofv3 --pmc "$@" -d $OUT/$name -o run --output-format csv -- python -u bench.py $ARGS --steps 1 --warmup 3 $Q; }
 ARGS="$*"
-step bench 400 python -u bench.py "$@" || exit $?
+step bench 400 python -u bench.py --full "$@" || exit $?
 step trace 300 rocprofv3 --kernel-trace --stats -d $OUT/trace -o run --output-format csv -- python -u bench.py "$@" --steps 3 --warmup 1 $Q || exit $?
 pmc pmc_fetch FETCH_SIZE || exit $?
 pmc pmc_write WRITE_SIZE || exit $?
