@@ -114,11 +114,14 @@ def test_fused_round_matches_oracle(eng, C):
     multi-label posterior; the candidates are re-drawn through the sampler
     entry point with the same (seed, stream, round) and scored by the CPU
     oracle, whose argmax must equal the engine's."""
-    pairs = [(m, r) for fx, m, r in _all_cases()
-             if m['n_hist'] in (26, 300) and m['variant'] == 'plain']
+    from oracle import draw_oracle as D
+    from tests import draw_cases
+    from tests.draw_check import check_draws
+    # (the labels with n_hist in (26, 300), variant 'plain'; seed 12345, round 7)
+    pairs, seed, rnd, counts = draw_cases.fused_round_cases()
+    assert C in counts and (seed, rnd) == (12345, 7) and len(pairs) == 20
     d, w, m, s = stack_cases(pairs)
     eng.set_posterior(d, w, m, s)
-    seed, rnd = 12345, 7
     res = eng.suggest(seed, C, round=rnd)
     for li, (meta, rec) in enumerate(pairs):
         kw = meta['lpdf_kwargs']
@@ -133,6 +136,11 @@ def test_fused_round_matches_oracle(eng, C):
             f = O.gmm1_lpdf if meta['sampler'] == 'GMM1' else O.lgmm1_lpdf
             lb = f(cand, rec['w_b'], rec['mu_b'], rec['sigma_b'], **kw)
             la = f(cand, rec['w_a'], rec['mu_a'], rec['sigma_a'], **kw)
+        # the re-drawn candidates are the draw reference's (not only the
+        # engine's own): the chain round -> candidates -> oracle is not circular
+        f = draw_cases.golden_fold(meta, rec)
+        wp, wu = D.draw_words(seed, li, rnd, np.arange(C, dtype=np.uint64), categorical=f.categorical)
+        check_draws(f, wp, wu, cand, 'fused round', '%s C %d' % (meta['kind'], C))
         best = O.broadcast_best_index(lb, la)
         assert int(res[li]['index']) == best, (li, meta['kind'])
         assert res[li]['value'] == cand[best]
@@ -281,9 +289,13 @@ def test_sampler_ks(eng, log, bounds):
 # with wu one 32-bit Philox word and r = (wp - tlo + 1/2) / (thi - tlo) the
 # pick word's position in its component's interval: a one-component normal
 # reaches v = 2^-65 at the least, so every draw has |z| <= -Phi^-1(2^-65)
-# = 9.1553 (the reference's MT19937 normals reach ~8.3 sigma in practice);
-# the distributions differ by total variation 2^-64 per draw
-# (test_oracle.py test_normal_draw_cap_mass).
+# = 9.1553 (the reference's MT19937 normals reach ~8.3 sigma in practice).
+# The bound is per mixture: a component that holds n_k of the 2^32 pick
+# words has v >= 2^-33 / n_k, so its cap is -Phi^-1(2^-33 / n_k) (9.155 only
+# for n_k = 2^32; 6.55 for n_k = 4), the tail mass cut off is 2^-64 per
+# component (K 2^-64 per draw of a K-component mixture), and the pick itself
+# is within total variation K 2^-33 of w_k m_k / sum w m
+# (test_oracle.py test_normal_draw_cap_mass; test_draw_oracle.py).
 Z_CAP = 9.155293772686072
 
 
