@@ -62,6 +62,8 @@ TPE_OPT_PK_SLICED = 23
 TPE_OPT_DEFER_REPORT = 24
 TPE_OPT_LABEL_SHARDS = 25
 
+TPE_JOINT_STREAM = 0x7FFFFFFF
+
 TPE_OBS_IDENTITY = 0
 TPE_OBS_LOG = 1
 TPE_OBS_LOG_FLOOR = 2
@@ -88,6 +90,13 @@ class LabelResult(ctypes.Structure):
                 ('index', ctypes.c_int64), ('label', ctypes.c_int32), ('status', ctypes.c_int32)]
 
 
+class JointDim(ctypes.Structure):
+    _fields_ = [('kind', ctypes.c_int32), ('flags', ctypes.c_int32),
+                ('low', ctypes.c_double), ('high', ctypes.c_double),
+                ('stream', ctypes.c_int32)]
+
+
+assert ctypes.sizeof(JointDim) == 32
 assert ctypes.sizeof(LabelDesc) == 56
 assert ctypes.sizeof(LabelResult) == 48
 assert ctypes.sizeof(LabelSpec) == 72
@@ -154,6 +163,10 @@ SIGNATURES = {
     'tpe_screen_probe': (ctypes.c_int, [_P, _I32, _P, _I64, _P, _P]),
     'tpe_export_posterior': (ctypes.c_int, [_P, _P, _I64, _P]),
     'tpe_import_posterior': (ctypes.c_int, [_P, _P, _I64, _P, _I32, _P, _P]),
+    'tpe_joint_set_posterior': (ctypes.c_int, [_P, _P, _I32, _I32, _P, _P, _P, _I32, _P, _P, _P]),
+    'tpe_joint_draw': (ctypes.c_int, [_P, _U64, _U32, _I64, _I64, _P, _P]),
+    'tpe_joint_score': (ctypes.c_int, [_P, _P, _I64, _P, _P]),
+    'tpe_joint_suggest': (ctypes.c_int, [_P, _U64, _U32, _I64, _P, _P, _PD, _PD]),
 }
 
 _lib = None

@@ -606,6 +606,9 @@ struct tpe_ctx {
     int32_t lsh_L = 0;
     bool lsh_enable = true;              // TPE_OPT_LABEL_SHARDS
 
+    // the joint (multivariate) posterior and its scratch (tpe_joint.hip)
+    std::shared_ptr<void> joint;
+
     int fail(int code, const std::string& m) {
         err = m;
         return code;

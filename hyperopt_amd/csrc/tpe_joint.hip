@@ -1,0 +1,735 @@
+// tpe_joint.hip -- multivariate (joint) TPE: one product kernel per trial.
+//
+// The joint mixture of a side S has K = n_S + 1 components (0: the prior)
+// over the D labels of the joint group, in each label's working space (log
+// space for the log kinds):
+//   f_S(y) = (1/A_S) sum_k W_k prod_d phi(y_d; mu_kd, s_kd)
+//   A_S    = sum_k W_k prod_d m_kd,   m_kd the mass of N(mu_kd, s_kd) in [low_d, high_d)
+//   lpdf_S = log f_S(y) - sum_{d log kind} y_d,   score = lpdf_below - lpdf_above
+// Candidate g picks a below component with the pick word of the reserved
+// stream TPE_JOINT_STREAM (thresholds ceil(cdf 2^32) of W_k prod_d m_kd) and
+// draws every dimension from that component's normal truncated to the box
+// with the label's own Philox words: icdf_draw on a one-component DrawComp.
+//
+// Kernels:
+//   k_joint_fold / k_joint_fold_sum   records [k][d], masses, log A, thresholds
+//   k_joint_round<DR, TABC, SAMPLE>   draw (or read) -> (max, sum) per slice of
+//                                     kJSlice components -> merged in slice
+//                                     order -> lpdfs -> per-workgroup best;
+//                                     with few candidates one workgroup per
+//                                     (tile, slice) stores the slice's pair and
+//   k_joint_merge                     merges them, in the same order with the
+//                                     same arithmetic: the same bits
+//   k_joint_best                      the round's winner; its D values are
+//                                     drawn again from Philox by index
+//   k_joint_draw                      candidates and their components (tpe_joint_draw)
+//
+// Arithmetic: component records are recentred and pre-scaled like the dense
+// labels' (tpe_device.h, Comp): (m' = (mu - centre_d) a, a = sqrt(K/2)/s) with
+// K = N/ln 2, so E_k = c_k - sum_d (y'_d a_kd - m'_kd)^2 is the exponent in
+// exp_scaled's units; plain VALU FMAs, two per (candidate, component,
+// dimension).  Records are wave-uniform; each lane holds one candidate, its
+// y' in registers up to kJReg dimensions, beyond in LDS (dimension-major:
+// consecutive lanes read consecutive words).
+#include "tpe_ctx.h"
+
+namespace {
+using namespace tpe;
+
+constexpr int kJSlice = 32;        // components per (max, sum) slice
+constexpr int kJU = 4;             // components sharing one read of y'_d
+constexpr int kJReg = 32;          // dimensions a lane keeps in registers
+constexpr int kJRegSmall = 8;
+constexpr int kJLdsLanes = 64;     // workgroup of the LDS variant (one wave)
+constexpr int kJLdsTabD = 64;      // up to here the exp table shares the LDS with y'
+constexpr int kJMaxD = 128;
+constexpr int kJBlock = 256;
+constexpr int kJMaxBelow = 4096;
+constexpr uint32_t kJointStream = TPE_JOINT_STREAM;
+constexpr double kInf = __builtin_inf();
+
+struct JDim {
+    double low, high, centre;
+    int32_t flags, stream, log, pad;
+};
+
+struct JDraw {   // one-component sampling terms of (k, d) (SampRec's)
+    double mu, ssg, p0, q0, m;
+};
+
+struct JP {   // the folded joint posterior
+    const JDim* __restrict__ dims;
+    const double2* __restrict__ rec;   // [k][d] (m', a); below components first
+    const double* __restrict__ cst;    // [k] K (log W_k - sum_d log(s_kd sqrt(2 pi)))
+    const double* __restrict__ logA;   // below, above
+    const uint64_t* __restrict__ thr;  // [Kb] pick thresholds
+    const JDraw* __restrict__ draw;    // [Kb][d]
+    int32_t D, Kb, Ka;
+};
+
+__device__ __forceinline__ DLabel jlabel(const JDim& j) {
+    DLabel L{};
+    L.mode = j.log ? DENSE_LGMM : DENSE_GMM;
+    L.flags = j.flags;
+    L.low = j.low;
+    L.high = j.high;
+    L.stream = j.stream;
+    return L;
+}
+
+// ------------------------------------------------------------------ fold ----
+__global__ __launch_bounds__(kJBlock) void k_joint_fold(
+    const JDim* __restrict__ dims, int32_t D, int32_t Kb, int32_t Ka, const double* __restrict__ W,
+    const double* __restrict__ mu, const double* __restrict__ sig, double2* __restrict__ rec,
+    double* __restrict__ cst, double* __restrict__ P, JDraw* __restrict__ draw) {
+#pragma clang fp contract(off)
+    const int k = blockIdx.x * kJBlock + threadIdx.x;
+    if (k >= Kb + Ka) return;
+    double sl = 0.0, prod = 1.0;
+    for (int d = 0; d < D; ++d) {
+        const JDim j = dims[d];
+        const size_t o = (size_t)k * D + d;
+        const double s = sig[o], m = mu[o];
+        const double a = sqrt(0.5 * kExpScale) / s;
+        rec[o] = make_double2((m - j.centre) * a, a);
+        sl += log(s * 2.50662827463100050242);
+        SampRec r{};
+        r.mu = m;
+        r.sigma = s;
+        samp_trunc(jlabel(j), r);
+        prod *= r.m;
+        if (k < Kb) draw[o] = JDraw{r.mu, r.ssg, r.p0, r.q0, r.m};
+    }
+    cst[k] = (log(W[k]) - sl) * kExpScale;
+    P[k] = W[k] * prod;
+}
+
+// block b: log A of side b (0 below, 1 above), by the same tree on both
+// sides -- equal mixtures get equal log A; block 0 also the pick thresholds of
+// the below side: its sum and cumulative weights in component order on one
+// thread, as samp_fold_block forms them
+__global__ __launch_bounds__(kJBlock) void k_joint_fold_sum(const double* __restrict__ P, int32_t Kb, int32_t Ka,
+                                                            double* __restrict__ logA, uint64_t* __restrict__ thr,
+                                                            int32_t* __restrict__ err) {
+#pragma clang fp contract(off)
+    const int side = blockIdx.x, K = side ? Ka : Kb;
+    const double* Ps = P + (side ? Kb : 0);
+    __shared__ double sh[kJBlock];
+    double a = 0.0;
+    for (int k = threadIdx.x; k < K; k += kJBlock) a += Ps[k];
+    sh[threadIdx.x] = a;
+    __syncthreads();
+    for (int w = kJBlock / 2; w > 0; w >>= 1) {
+        if ((int)threadIdx.x < w) sh[threadIdx.x] += sh[threadIdx.x + w];
+        __syncthreads();
+    }
+    if (threadIdx.x) return;
+    logA[side] = log(sh[0]);
+    if (side) return;
+    double Z = 0.0;
+    for (int k = 0; k < Kb; ++k) Z += P[k];
+    const bool zero = !(Z > 0.0);
+    if (zero) atomicOr(err, 1);
+    double run = 0.0;
+    for (int k = 0; k < Kb; ++k) {
+        run += P[k];
+        thr[k] = pick_thr((k == Kb - 1 || zero) ? 1.0 : run / Z);
+    }
+}
+
+// ------------------------------------------------------------------ draw ----
+// the component of candidate g: the first k with thr[k] > wp of the joint stream
+__device__ __forceinline__ int jpick(const JP& p, uint32_t k0, uint32_t k1, uint32_t g, uint32_t round) {
+    DLabel L{};
+    L.stream = (int32_t)kJointStream;
+    uint32_t wp, wu;
+    draw_words(L, k0, k1, g, round, wp, wu);
+    int lo = 0, hi = p.Kb - 1;
+    while (lo < hi) {
+        const int mid = (lo + hi) >> 1;
+        if (p.thr[mid] > (uint64_t)wp) hi = mid; else lo = mid + 1;
+    }
+    return lo;
+}
+
+// dimension d of candidate g from component k: the label's value (after the
+// exp of a log kind)
+__device__ __forceinline__ double jdraw(const JP& p, const JDim& j, int d, int k, uint32_t k0, uint32_t k1,
+                                        uint32_t g, uint32_t round) {
+    const DLabel L = jlabel(j);
+    uint32_t wp, wu;
+    draw_words(L, k0, k1, g, round, wp, wu);
+    const JDraw r = p.draw[(size_t)k * p.D + d];
+    DrawComp c;
+    c.mu = r.mu;
+    c.ssg = r.ssg;
+    c.p0 = r.p0;
+    c.q0 = r.q0;
+    c.m = r.m;
+    c.iw = 0x1.0p-32;
+    c.tlo = 0;
+    c.thi = 1ull << 32;
+    const double y = icdf_draw(L, c, wp, wu);
+    return j.log ? lgmm_value(y) : y;
+}
+
+__global__ __launch_bounds__(kJBlock) void k_joint_draw(JP p, int64_t n, int64_t cand_offset, uint64_t seed,
+                                                        uint32_t round, double* __restrict__ values,
+                                                        int32_t* __restrict__ comp, int32_t* __restrict__ err) {
+    const int64_t i = (int64_t)blockIdx.x * kJBlock + threadIdx.x;
+    if (i >= n) return;
+    const uint32_t k0 = (uint32_t)seed, k1 = (uint32_t)(seed >> 32), g = (uint32_t)(cand_offset + i);
+    const int k = jpick(p, k0, k1, g, round);
+    comp[i] = k;
+    bool bad = false;
+    for (int d = 0; d < p.D; ++d) {
+        const double x = jdraw(p, p.dims[d], d, k, k0, k1, g, round);
+        bad |= x != x;
+        values[(size_t)i * p.D + d] = x;
+    }
+    if (bad) atomicOr(err, 1);
+}
+
+// ----------------------------------------------------------------- score ----
+template <bool TABC>
+__device__ __forceinline__ double jexp(double u, const double* __restrict__ tab) {
+    // (beyond -8e6 the result is 0 either way; the clamp keeps rint(u) an int)
+    return exp_scaled(fmax(u, -8.0e6), TABC ? kExp2Tab : tab);
+}
+
+// (max, sum) of exp(E_k - max) over components [k0, k1), online in groups of
+// kJU; an empty or all -inf range gives (-inf, 0).  DR > 0: y' in yr (D <= DR),
+// else in LDS at yl[d * kJLdsLanes].
+template <int DR, bool TABC>
+__device__ __forceinline__ void slice_ms(const double2* __restrict__ rec, const double* __restrict__ cst, int D,
+                                         int k0, int k1, const double* yr, const double* yl,
+                                         const double* __restrict__ tab, double& m, double& s) {
+#pragma clang fp contract(off)
+    m = -kInf;
+    s = 0.0;
+    for (int k = k0; k < k1; k += kJU) {
+        const double2* r[kJU];
+        double acc[kJU];
+#pragma unroll
+        for (int j = 0; j < kJU; ++j) {
+            r[j] = rec + (size_t)min(k + j, k1 - 1) * D;
+            acc[j] = 0.0;
+        }
+        if constexpr (DR > 0) {
+#pragma unroll
+            for (int d = 0; d < DR; ++d)
+                if (d < D) {
+                    const double y = yr[d];
+#pragma unroll
+                    for (int j = 0; j < kJU; ++j) {
+                        const double2 q = r[j][d];
+                        const double z = fma(y, q.y, -q.x);
+                        acc[j] = fma(z, z, acc[j]);
+                    }
+                }
+        } else {
+            for (int d = 0; d < D; ++d) {
+                const double y = yl[d * kJLdsLanes];
+#pragma unroll
+                for (int j = 0; j < kJU; ++j) {
+                    const double2 q = r[j][d];
+                    const double z = fma(y, q.y, -q.x);
+                    acc[j] = fma(z, z, acc[j]);
+                }
+            }
+        }
+        double e[kJU], gm = -kInf;
+#pragma unroll
+        for (int j = 0; j < kJU; ++j) {
+            e[j] = (k + j < k1) ? cst[min(k + j, k1 - 1)] - acc[j] : -kInf;
+            gm = fmax(gm, e[j]);
+        }
+        const double M = fmax(m, gm);
+        if (M > -kInf) {
+            double t = (m > -kInf) ? s * jexp<TABC>(m - M, tab) : 0.0;
+#pragma unroll
+            for (int j = 0; j < kJU; ++j)
+                if (e[j] > -kInf) t += jexp<TABC>(e[j] - M, tab);
+            s = t;
+            m = M;
+        }
+    }
+}
+
+template <bool TABC>
+__device__ __forceinline__ void ms_merge(double& m, double& s, double m2, double s2,
+                                         const double* __restrict__ tab) {
+#pragma clang fp contract(off)
+    if (!(m2 > -kInf)) return;
+    if (!(m > -kInf)) {
+        m = m2;
+        s = s2;
+        return;
+    }
+    const double M = fmax(m, m2);
+    const double t1 = s * jexp<TABC>(m - M, tab), t2 = s2 * jexp<TABC>(m2 - M, tab);
+    s = t1 + t2;
+    m = M;
+}
+
+// lpdf of one side from its merged (max, sum); ylog = sum of the log kinds'
+// y_d, NaN when a value is NaN
+__device__ __forceinline__ double jfinish(double m, double s, double logA, double ylog) {
+#pragma clang fp contract(off)
+    const double lse = (m > -kInf) ? flog(s) + m * kExpScaleInv : -kInf;
+    return (lse - logA) - ylog;
+}
+
+__device__ __forceinline__ int jslices(int K) { return (K + kJSlice - 1) / kJSlice; }
+
+// the best (key, index) of a workgroup with its lpdfs -> *out (thread 0)
+// (scratch: 32 bytes of LDS per thread, free for reuse)
+__device__ __forceinline__ void jblock_best(uint64_t key, int64_t idx, double ll, double lg, Partial* out,
+                                            double* scratch) {
+    const int t = threadIdx.x, nt = blockDim.x;
+    uint64_t* skey = reinterpret_cast<uint64_t*>(scratch);
+    int64_t* sidx = reinterpret_cast<int64_t*>(scratch + nt);
+    double *sll = scratch + 2 * nt, *slg = scratch + 3 * nt;
+    skey[t] = key;
+    sidx[t] = idx;
+    sll[t] = ll;
+    slg[t] = lg;
+    __syncthreads();
+    for (int w = nt >> 1; w > 0; w >>= 1) {
+        if (t < w && better(skey[t + w], sidx[t + w], skey[t], sidx[t])) {
+            skey[t] = skey[t + w];
+            sidx[t] = sidx[t + w];
+            sll[t] = sll[t + w];
+            slg[t] = slg[t + w];
+        }
+        __syncthreads();
+    }
+    if (t == 0) {
+        Partial r;
+        r.key = skey[0];
+        r.idx = sidx[0];
+        r.value = 0.0;
+        r.lb = sll[0];
+        r.la = slg[0];
+        *out = r;
+    }
+}
+
+// (rec and cst are the posterior's records again, as plain read-only kernel
+// arguments: the compiler then reads them through the scalar unit)
+// grid (tiles, 1): the whole round of a tile; grid (tiles, slices): one slice
+// per workgroup, its (max, sum) to part[slice][i] and the candidate's ylog to
+// aux[i] (k_joint_merge finishes).  SAMPLE: candidate i is drawn (index
+// cand_offset + i), else read from vals[i][d].
+template <int DR, bool TABC, bool SAMPLE>
+__global__ __launch_bounds__(DR > 0 ? kJBlock : kJLdsLanes) void k_joint_round(
+    JP p, const double2* __restrict__ rec, const double* __restrict__ cst, const double* __restrict__ vals, int64_t n, int64_t cand_offset, uint64_t seed, uint32_t round,
+    int32_t split, double2* __restrict__ part, double* __restrict__ aux, double* __restrict__ out_ll,
+    double* __restrict__ out_lg, Partial* __restrict__ partials, int32_t* __restrict__ err) {
+    extern __shared__ double jsm[];
+    const double* tab = jsm;
+    if constexpr (!TABC) load_exp_table(jsm);
+    double* yl = jsm + (TABC ? 0 : kExpTabSize) + threadIdx.x;
+    constexpr int NR = DR > 0 ? DR : 1;
+    double yr[NR];
+    const int64_t i = (int64_t)blockIdx.x * blockDim.x + threadIdx.x;
+    const bool valid = i < n;
+    const int D = p.D;
+    const uint32_t k0 = (uint32_t)seed, k1 = (uint32_t)(seed >> 32), g = (uint32_t)(cand_offset + i);
+    int kc = 0;
+    if constexpr (SAMPLE)
+        if (valid) kc = jpick(p, k0, k1, g, round);
+    double ylog = 0.0;
+    bool bad = false;
+    auto load = [&](int d) -> double {
+        const JDim j = p.dims[d];
+        double y = j.centre;
+        if (valid) {
+            double x;
+            if constexpr (SAMPLE) {
+                x = jdraw(p, j, d, kc, k0, k1, g, round);
+                if (x != x) atomicOr(err, 1);
+            } else {
+                x = vals[(size_t)i * D + d];
+            }
+            y = j.log ? flog(x) : x;
+            if (j.log) ylog += y;
+            bad |= y != y;
+        }
+        return y - j.centre;
+    };
+    if constexpr (DR > 0) {
+        // (the draw stays a loop: placed by selects, one copy of its code)
+#pragma unroll
+        for (int e = 0; e < DR; ++e) yr[e] = 0.0;
+        for (int d = 0; d < D; ++d) {
+            const double y = load(d);
+#pragma unroll
+            for (int e = 0; e < DR; ++e) yr[e] = e == d ? y : yr[e];
+        }
+    } else {
+        for (int d = 0; d < D; ++d) yl[d * kJLdsLanes] = load(d);
+        yr[0] = 0.0;
+    }
+    if (bad) ylog = __builtin_nan("");
+    const int nsb = jslices(p.Kb);
+    if (split) {
+        const int sl = blockIdx.y;
+        const bool above = sl >= nsb;
+        const int K = above ? p.Ka : p.Kb, base = above ? p.Kb : 0, q = above ? sl - nsb : sl;
+        const int a0 = q * kJSlice, a1 = min(a0 + kJSlice, K);
+        double m, s;
+        slice_ms<DR, TABC>(rec, cst, D, base + a0, base + a1, yr, yl, tab, m, s);
+        if (valid) {
+            part[(size_t)sl * n + i] = make_double2(m, s);
+            if (sl == 0) aux[i] = ylog;
+        }
+        return;
+    }
+    double lp[2];
+#pragma unroll 1
+    for (int side = 0; side < 2; ++side) {
+        const int K = side ? p.Ka : p.Kb, base = side ? p.Kb : 0;
+        double m = -kInf, s = 0.0;
+        for (int a0 = 0; a0 < K; a0 += kJSlice) {
+            double m2, s2;
+            slice_ms<DR, TABC>(rec, cst, D, base + a0, base + min(a0 + kJSlice, K), yr, yl, tab, m2, s2);
+            ms_merge<TABC>(m, s, m2, s2, tab);
+        }
+        lp[side] = jfinish(m, s, p.logA[side], ylog);
+    }
+    if (out_ll && valid) {
+        out_ll[i] = lp[0];
+        out_lg[i] = lp[1];
+    }
+    __syncthreads();   // (the table and y' are done with: their LDS is the reduction's)
+    jblock_best(valid ? order_key(lp[0] - lp[1]) : 0ull, valid ? i : INT64_MAX, lp[0], lp[1],
+                partials + blockIdx.x, jsm);
+}
+
+__global__ __launch_bounds__(kJBlock) void k_joint_merge(JP p, int64_t n, const double2* __restrict__ part,
+                                                         const double* __restrict__ aux,
+                                                         double* __restrict__ out_ll, double* __restrict__ out_lg,
+                                                         Partial* __restrict__ partials) {
+    const int64_t i = (int64_t)blockIdx.x * kJBlock + threadIdx.x;
+    const bool valid = i < n;
+    const int nsb = jslices(p.Kb), nsa = jslices(p.Ka);
+    double lp[2] = {0.0, 0.0};
+    if (valid) {
+        const double ylog = aux[i];
+#pragma unroll 1
+        for (int side = 0; side < 2; ++side) {
+            const int s0 = side ? nsb : 0, s1 = side ? nsb + nsa : nsb;
+            double m = -kInf, s = 0.0;
+            for (int sl = s0; sl < s1; ++sl) {
+                const double2 q = part[(size_t)sl * n + i];
+                ms_merge<true>(m, s, q.x, q.y, nullptr);
+            }
+            lp[side] = jfinish(m, s, p.logA[side], ylog);
+        }
+        if (out_ll) {
+            out_ll[i] = lp[0];
+            out_lg[i] = lp[1];
+        }
+    }
+    __shared__ double scr[4 * kJBlock];
+    jblock_best(valid ? order_key(lp[0] - lp[1]) : 0ull, valid ? i : INT64_MAX, lp[0], lp[1],
+                partials + blockIdx.x, scr);
+}
+
+// res: lpdf_below, lpdf_above, index, then (SAMPLE rounds) the winner's D values
+__global__ __launch_bounds__(kJBlock) void k_joint_best(JP p, const Partial* __restrict__ partials, int32_t nparts,
+                                                        int64_t cand_offset, uint64_t seed, uint32_t round,
+                                                        int32_t sample, double* __restrict__ res) {
+    uint64_t bk = 0;
+    int64_t bi = INT64_MAX;
+    double ll = 0.0, lg = 0.0;
+    for (int j = threadIdx.x; j < nparts; j += kJBlock) {
+        const Partial q = partials[j];
+        if (better(q.key, q.idx, bk, bi)) {
+            bk = q.key;
+            bi = q.idx;
+            ll = q.lb;
+            lg = q.la;
+        }
+    }
+    __shared__ Partial win;
+    __shared__ double scr[4 * kJBlock];
+    jblock_best(bk, bi, ll, lg, &win, scr);
+    __syncthreads();
+    const Partial w = win;
+    if (threadIdx.x == 0) {
+        res[0] = w.lb;
+        res[1] = w.la;
+        res[2] = (double)w.idx;
+    }
+    if (!sample || w.idx == INT64_MAX) return;
+    const uint32_t k0 = (uint32_t)seed, k1 = (uint32_t)(seed >> 32), g = (uint32_t)(cand_offset + w.idx);
+    const int kc = jpick(p, k0, k1, g, round);
+    for (int d = threadIdx.x; d < p.D; d += kJBlock) res[3 + d] = jdraw(p, p.dims[d], d, kc, k0, k1, g, round);
+}
+
+// ------------------------------------------------------------- host side ----
+template <typename T>
+using DevBuf = tpe_rt::DevBuf<T>;
+
+struct JointState {
+    int32_t D = 0, Kb = 0, Ka = 0;
+    bool ready = false, zero = false;
+    DevBuf<JDim> dims;
+    DevBuf<double> W, mu, sig, cst, P, logA, vals, ll, lg, aux, res;
+    DevBuf<double2> rec, part;
+    DevBuf<JDraw> draw;
+    DevBuf<uint64_t> thr;
+    DevBuf<int32_t> err, comp;
+    DevBuf<Partial> partials;
+    JP jp() const {
+        JP p;
+        p.dims = dims.p;
+        p.rec = rec.p;
+        p.cst = cst.p;
+        p.logA = logA.p;
+        p.thr = thr.p;
+        p.draw = draw.p;
+        p.D = D;
+        p.Kb = Kb;
+        p.Ka = Ka;
+        return p;
+    }
+};
+
+JointState* jstate(tpe_ctx* ctx, bool make) {
+    if (!ctx->joint && make) ctx->joint = std::shared_ptr<void>(new JointState(), [](void* q) {
+        delete static_cast<JointState*>(q);
+    });
+    return static_cast<JointState*>(ctx->joint.get());
+}
+
+constexpr size_t kJPartBytes = (size_t)64 << 20;   // the split map's (max, sum) pairs at most
+constexpr int64_t kJSplitTiles = 512;              // tiles from which one workgroup runs a tile's whole round
+
+// the round of n candidates (drawn, or J->vals): lpdfs to J->ll / J->lg when
+// `lpdfs`, per-workgroup bests to J->partials; *nparts of them
+int launch_round(tpe_ctx* ctx, JointState* J, bool sample, int64_t n, int64_t cand_offset, uint64_t seed,
+                 uint32_t round, bool lpdfs, int32_t* nparts) {
+    const int D = J->D;
+    const int dr = D <= kJRegSmall ? kJRegSmall : (D <= kJReg ? kJReg : 0);
+    const bool tabc = dr == 0 && D > kJLdsTabD;
+    const int threads = dr ? kJBlock : kJLdsLanes;
+    const int64_t tiles = (n + threads - 1) / threads;
+    const int64_t nsl = (J->Kb + kJSlice - 1) / kJSlice + (J->Ka + kJSlice - 1) / kJSlice;
+    const bool split = tiles < kJSplitTiles && nsl > 2 && (size_t)nsl * n * sizeof(double2) <= kJPartBytes &&
+                       nsl <= 65535;
+    const size_t lds = (tabc ? 0 : kExpTabSize * sizeof(double)) + (dr ? 0 : (size_t)D * kJLdsLanes * sizeof(double));
+    const int64_t mtiles = (n + kJBlock - 1) / kJBlock;
+    *nparts = (int32_t)(split ? mtiles : tiles);
+    HIPCHK(ctx, J->partials.reserve(*nparts));
+    if (split) {
+        HIPCHK(ctx, J->part.reserve((size_t)nsl * n));
+        HIPCHK(ctx, J->aux.reserve(n));
+    }
+    if (lpdfs) {
+        HIPCHK(ctx, J->ll.reserve(n));
+        HIPCHK(ctx, J->lg.reserve(n));
+    }
+    const dim3 grid((unsigned)tiles, split ? (unsigned)nsl : 1u);
+    double* oll = lpdfs ? J->ll.p : nullptr;
+    double* olg = lpdfs ? J->lg.p : nullptr;
+    const JP p = J->jp();
+#define JLAUNCH(DR, TABC)                                                                                       \
+    do {                                                                                                        \
+        if (sample)                                                                                             \
+            hipLaunchKernelGGL((k_joint_round<DR, TABC, true>), grid, dim3(threads), lds, ctx->stream, p,       \
+                               J->rec.p, J->cst.p, nullptr, n, cand_offset, seed, round, (int32_t)split, J->part.p, J->aux.p,       \
+                               split ? nullptr : oll, split ? nullptr : olg, J->partials.p, J->err.p);          \
+        else                                                                                                    \
+            hipLaunchKernelGGL((k_joint_round<DR, TABC, false>), grid, dim3(threads), lds, ctx->stream, p,      \
+                               J->rec.p, J->cst.p, J->vals.p, n, cand_offset, seed, round, (int32_t)split, J->part.p, J->aux.p,     \
+                               split ? nullptr : oll, split ? nullptr : olg, J->partials.p, J->err.p);          \
+    } while (0)
+    if (dr == kJRegSmall) JLAUNCH(kJRegSmall, false);
+    else if (dr == kJReg) JLAUNCH(kJReg, false);
+    else if (!tabc) JLAUNCH(0, false);
+    else JLAUNCH(0, true);
+#undef JLAUNCH
+    HIPCHK(ctx, hipGetLastError());
+    if (split) {
+        hipLaunchKernelGGL(k_joint_merge, dim3((unsigned)mtiles), dim3(kJBlock), 0, ctx->stream, p, n, J->part.p,
+                           J->aux.p, oll, olg, J->partials.p);
+        HIPCHK(ctx, hipGetLastError());
+    }
+    return TPE_OK;
+}
+
+int joint_ready(tpe_ctx* ctx, JointState** out, const char* who) {
+    JointState* J = jstate(ctx, false);
+    if (!J || !J->ready) return ctx->fail(TPE_ERR_ARG, std::string(who) + ": no joint posterior set");
+    if (J->zero)
+        return ctx->fail(TPE_ERR_SAMPLE, "truncated sampler: the box holds none of the below mixture's mass");
+    *out = J;
+    return TPE_OK;
+}
+
+int check_range(tpe_ctx* ctx, int64_t n, int64_t cand_offset) {
+    if (n <= 0) return ctx->fail(TPE_ERR_ARG, "the number of candidates must be positive");
+    if (cand_offset < 0 || cand_offset + n > (int64_t)UINT32_MAX)
+        return ctx->fail(TPE_ERR_ARG, "candidate indices must stay below 2^32");
+    return TPE_OK;
+}
+
+int read_err(tpe_ctx* ctx, JointState* J) {
+    int32_t e = 0;
+    HIPCHK(ctx, hipMemcpyAsync(&e, J->err.p, sizeof(int32_t), hipMemcpyDeviceToHost, ctx->stream));
+    HIPCHK(ctx, hipStreamSynchronize(ctx->stream));
+    if (e & 1) return ctx->fail(TPE_ERR_SAMPLE, "truncated sampler: interval [low, high) not reached");
+    return TPE_OK;
+}
+}  // namespace
+
+extern "C" {
+
+int tpe_joint_set_posterior(tpe_ctx* ctx, const tpe_joint_dim* dims, int32_t n_dims, int32_t n_below,
+                            const double* wb, const double* mub, const double* sigb, int32_t n_above,
+                            const double* wa, const double* mua, const double* siga) {
+    if (!ctx) return TPE_ERR_ARG;
+    if (!dims || !wb || !mub || !sigb || !wa || !mua || !siga) return ctx->fail(TPE_ERR_ARG, "null pointer");
+    if (n_dims < 1 || n_dims > kJMaxD)
+        return ctx->fail(TPE_ERR_ARG, "a joint group holds 1 to " + std::to_string(kJMaxD) + " dimensions");
+    if (n_below < 1 || n_below > kJMaxBelow || n_above < 1)
+        return ctx->fail(TPE_ERR_ARG, "each side needs its prior component (below: at most " +
+                                          std::to_string(kJMaxBelow) + ")");
+    TPE_NOT_LSHARD(ctx);
+    const int D = n_dims, Kb = n_below, Ka = n_above, K = Kb + Ka;
+    std::vector<JDim> hd(D);
+    for (int d = 0; d < D; ++d) {
+        const tpe_joint_dim& s = dims[d];
+        if (s.kind != TPE_GMM1 && s.kind != TPE_LGMM1)
+            return ctx->fail(TPE_ERR_ARG, "a joint dimension is TPE_GMM1 or TPE_LGMM1");
+        if (s.flags & ~(TPE_HAS_LOW | TPE_HAS_HIGH)) return ctx->fail(TPE_ERR_ARG, "joint dimensions are not quantized");
+        if ((s.flags & 3) == 3 && !(s.low < s.high)) return ctx->fail(TPE_ERR_VALUE, "low >= high");
+        hd[d] = JDim{s.low, s.high, mub[d], s.flags, s.stream, s.kind == TPE_LGMM1 ? 1 : 0, 0};
+    }
+    for (int side = 0; side < 2; ++side) {
+        const double *w = side ? wa : wb, *sg = side ? siga : sigb;
+        const int Ks = side ? Ka : Kb;
+        for (int k = 0; k < Ks; ++k)
+            if (!(w[k] >= 0.0)) return ctx->fail(TPE_ERR_VALUE, "negative or NaN weight");
+        for (size_t o = 0; o < (size_t)Ks * D; ++o)
+            if (!(sg[o] > 0.0 && sg[o] < __builtin_inf())) return ctx->fail(TPE_ERR_VALUE, "sigma must be positive");
+    }
+    HIPCHK(ctx, hipSetDevice(ctx->device));
+    JointState* J = jstate(ctx, true);
+    J->ready = false;
+    HIPCHK(ctx, J->dims.reserve(D));
+    HIPCHK(ctx, J->W.reserve(K));
+    HIPCHK(ctx, J->mu.reserve((size_t)K * D));
+    HIPCHK(ctx, J->sig.reserve((size_t)K * D));
+    HIPCHK(ctx, J->rec.reserve((size_t)K * D));
+    HIPCHK(ctx, J->cst.reserve(K));
+    HIPCHK(ctx, J->P.reserve(K));
+    HIPCHK(ctx, J->logA.reserve(2));
+    HIPCHK(ctx, J->draw.reserve((size_t)Kb * D));
+    HIPCHK(ctx, J->thr.reserve(Kb));
+    HIPCHK(ctx, J->err.reserve(1));
+    hipStream_t st = ctx->stream;
+    const size_t nb = (size_t)Kb * D, na = (size_t)Ka * D;
+    HIPCHK(ctx, hipMemcpyAsync(J->dims.p, hd.data(), D * sizeof(JDim), hipMemcpyHostToDevice, st));
+    HIPCHK(ctx, hipMemcpyAsync(J->W.p, wb, Kb * sizeof(double), hipMemcpyHostToDevice, st));
+    HIPCHK(ctx, hipMemcpyAsync(J->W.p + Kb, wa, Ka * sizeof(double), hipMemcpyHostToDevice, st));
+    HIPCHK(ctx, hipMemcpyAsync(J->mu.p, mub, nb * sizeof(double), hipMemcpyHostToDevice, st));
+    HIPCHK(ctx, hipMemcpyAsync(J->mu.p + nb, mua, na * sizeof(double), hipMemcpyHostToDevice, st));
+    HIPCHK(ctx, hipMemcpyAsync(J->sig.p, sigb, nb * sizeof(double), hipMemcpyHostToDevice, st));
+    HIPCHK(ctx, hipMemcpyAsync(J->sig.p + nb, siga, na * sizeof(double), hipMemcpyHostToDevice, st));
+    HIPCHK(ctx, hipMemsetAsync(J->err.p, 0, sizeof(int32_t), st));
+    hipLaunchKernelGGL(k_joint_fold, dim3((K + kJBlock - 1) / kJBlock), dim3(kJBlock), 0, st, J->dims.p, D, Kb, Ka,
+                       J->W.p, J->mu.p, J->sig.p, J->rec.p, J->cst.p, J->P.p, J->draw.p);
+    HIPCHK(ctx, hipGetLastError());
+    hipLaunchKernelGGL(k_joint_fold_sum, dim3(2), dim3(kJBlock), 0, st, J->P.p, Kb, Ka, J->logA.p, J->thr.p,
+                       J->err.p);
+    HIPCHK(ctx, hipGetLastError());
+    int32_t e = 0;
+    HIPCHK(ctx, hipMemcpyAsync(&e, J->err.p, sizeof(int32_t), hipMemcpyDeviceToHost, st));
+    HIPCHK(ctx, hipStreamSynchronize(st));
+    J->D = D;
+    J->Kb = Kb;
+    J->Ka = Ka;
+    J->zero = (e & 1) != 0;
+    J->ready = true;
+    if (J->zero)
+        return ctx->fail(TPE_ERR_SAMPLE, "truncated sampler: the box holds none of the below mixture's mass");
+    return TPE_OK;
+}
+
+int tpe_joint_draw(tpe_ctx* ctx, uint64_t seed, uint32_t round, int64_t n, int64_t cand_offset, double* values,
+                   int32_t* comp) {
+    if (!ctx) return TPE_ERR_ARG;
+    JointState* J = nullptr;
+    int rc = joint_ready(ctx, &J, "tpe_joint_draw");
+    if (rc) return rc;
+    if (!values || !comp) return ctx->fail(TPE_ERR_ARG, "null pointer");
+    if ((rc = check_range(ctx, n, cand_offset))) return rc;
+    HIPCHK(ctx, hipSetDevice(ctx->device));
+    HIPCHK(ctx, J->vals.reserve((size_t)n * J->D));
+    HIPCHK(ctx, J->comp.reserve(n));
+    HIPCHK(ctx, hipMemsetAsync(J->err.p, 0, sizeof(int32_t), ctx->stream));
+    hipLaunchKernelGGL(k_joint_draw, dim3((unsigned)((n + kJBlock - 1) / kJBlock)), dim3(kJBlock), 0, ctx->stream,
+                       J->jp(), n, cand_offset, seed, round, J->vals.p, J->comp.p, J->err.p);
+    HIPCHK(ctx, hipGetLastError());
+    HIPCHK(ctx, hipMemcpyAsync(values, J->vals.p, (size_t)n * J->D * sizeof(double), hipMemcpyDeviceToHost,
+                               ctx->stream));
+    HIPCHK(ctx, hipMemcpyAsync(comp, J->comp.p, n * sizeof(int32_t), hipMemcpyDeviceToHost, ctx->stream));
+    return read_err(ctx, J);
+}
+
+int tpe_joint_score(tpe_ctx* ctx, const double* values, int64_t n, double* ll, double* lg) {
+    if (!ctx) return TPE_ERR_ARG;
+    JointState* J = nullptr;
+    int rc = joint_ready(ctx, &J, "tpe_joint_score");
+    if (rc) return rc;
+    if (!values || !ll || !lg) return ctx->fail(TPE_ERR_ARG, "null pointer");
+    if ((rc = check_range(ctx, n, 0))) return rc;
+    HIPCHK(ctx, hipSetDevice(ctx->device));
+    HIPCHK(ctx, J->vals.reserve((size_t)n * J->D));
+    HIPCHK(ctx, hipMemcpyAsync(J->vals.p, values, (size_t)n * J->D * sizeof(double), hipMemcpyHostToDevice,
+                               ctx->stream));
+    int32_t nparts = 0;
+    if ((rc = launch_round(ctx, J, false, n, 0, 0, 0, true, &nparts))) return rc;
+    HIPCHK(ctx, hipMemcpyAsync(ll, J->ll.p, n * sizeof(double), hipMemcpyDeviceToHost, ctx->stream));
+    HIPCHK(ctx, hipMemcpyAsync(lg, J->lg.p, n * sizeof(double), hipMemcpyDeviceToHost, ctx->stream));
+    HIPCHK(ctx, hipStreamSynchronize(ctx->stream));
+    return TPE_OK;
+}
+
+int tpe_joint_suggest(tpe_ctx* ctx, uint64_t seed, uint32_t round, int64_t n_candidates, double* values,
+                      int64_t* index, double* ll, double* lg) {
+    if (!ctx) return TPE_ERR_ARG;
+    JointState* J = nullptr;
+    int rc = joint_ready(ctx, &J, "tpe_joint_suggest");
+    if (rc) return rc;
+    if (!values || !index || !ll || !lg) return ctx->fail(TPE_ERR_ARG, "null pointer");
+    if ((rc = check_range(ctx, n_candidates, 0))) return rc;
+    HIPCHK(ctx, hipSetDevice(ctx->device));
+    HIPCHK(ctx, J->res.reserve(3 + J->D));
+    HIPCHK(ctx, hipMemsetAsync(J->err.p, 0, sizeof(int32_t), ctx->stream));
+    int32_t nparts = 0;
+    if (ctx->timing) HIPCHK(ctx, hipEventRecord(ctx->ev0, ctx->stream));
+    if ((rc = launch_round(ctx, J, true, n_candidates, 0, seed, round, false, &nparts))) return rc;
+    hipLaunchKernelGGL(k_joint_best, dim3(1), dim3(kJBlock), 0, ctx->stream, J->jp(), J->partials.p, nparts,
+                       (int64_t)0, seed, round, 1, J->res.p);
+    HIPCHK(ctx, hipGetLastError());
+    if (ctx->timing) HIPCHK(ctx, hipEventRecord(ctx->ev1, ctx->stream));
+    std::vector<double> h(3 + J->D);
+    HIPCHK(ctx, hipMemcpyAsync(h.data(), J->res.p, h.size() * sizeof(double), hipMemcpyDeviceToHost, ctx->stream));
+    if ((rc = read_err(ctx, J))) return rc;
+    if (ctx->timing) {   // the round's device time (tpe_last_timing: both figures)
+        HIPCHK(ctx, hipEventElapsedTime(&ctx->round_ms, ctx->ev0, ctx->ev1));
+        ctx->score_ms = ctx->round_ms;
+    }
+    *ll = h[0];
+    *lg = h[1];
+    *index = (int64_t)h[2];
+    for (int d = 0; d < J->D; ++d) values[d] = h[3 + d];
+    return TPE_OK;
+}
+
+}  // extern "C"

@@ -54,6 +54,12 @@ SPEC_DTYPE = np.dtype([('kind', '<i4'), ('flags', '<i4'), ('low', '<f8'), ('high
 assert SPEC_DTYPE.itemsize == ctypes.sizeof(L.LabelSpec)
 
 
+JOINT_DIM_DTYPE = np.dtype({'names': ['kind', 'flags', 'low', 'high', 'stream'],
+                            'formats': ['<i4', '<i4', '<f8', '<f8', '<i4'],
+                            'offsets': [0, 4, 8, 16, 24], 'itemsize': 32})
+assert JOINT_DIM_DTYPE.itemsize == ctypes.sizeof(L.JointDim)
+
+
 def bounds_flags(low, high, q):
     f = 0
     if low is not None:
@@ -394,6 +400,67 @@ class Engine(object):
             self.h, ctypes.c_void_p(d_blobs.data_ptr()), d_blobs.numel() * d_blobs.element_size(),
             _ptr(off), len(off), _ptr(counts), _ptr(ids)))
         self._labels()
+
+    # -- joint (multivariate) posterior ---------------------------------------
+    def set_joint_posterior(self, dims, wb, mub, sigb, wa, mua, siga):
+        """The joint mixtures of a group of D dense labels
+        (posterior.joint_mixture): dims a JOINT_DIM_DTYPE array, weights [K],
+        means and sigmas [K, D], component 0 the prior
+        (tpe_joint_set_posterior)."""
+        dims = np.ascontiguousarray(dims, dtype=JOINT_DIM_DTYPE)
+        D = len(dims)
+        arrs = []
+        for w, m, s in ((wb, mub, sigb), (wa, mua, siga)):
+            w, m, s = _f64(w).ravel(), _f64(m), _f64(s)
+            if m.shape != (len(w), D) or s.shape != (len(w), D):
+                raise ValueError('joint means and sigmas must be [components, dimensions]')
+            arrs.append((w, m, s))
+        (wb, mub, sigb), (wa, mua, siga) = arrs
+        rc = self.lib.tpe_joint_set_posterior(
+            self.h, _ptr(dims), D, len(wb), _ptr(wb), _ptr(mub), _ptr(sigb), len(wa), _ptr(wa),
+            _ptr(mua), _ptr(siga))
+        # (a box without below mass is set, and every draw reports it again)
+        self.joint_dims = D if rc in (L.TPE_OK, L.TPE_ERR_SAMPLE) else 0
+        self._check(rc)
+
+    def _joint_dims(self):
+        D = getattr(self, 'joint_dims', 0)
+        if not D:
+            raise EngineError('no joint posterior set (Engine.set_joint_posterior)')
+        return D
+
+    def joint_draw(self, seed, n, round=0, cand_offset=0):
+        """(values [n, D], component [n]) of candidates cand_offset ..
+        cand_offset + n - 1 of (seed, round) (tpe_joint_draw)."""
+        D = self._joint_dims()
+        values = np.empty((int(n), D))
+        comp = np.empty(int(n), dtype=np.int32)
+        self._check(self.lib.tpe_joint_draw(self.h, int(seed) & 0xFFFFFFFFFFFFFFFF, int(round) & 0xFFFFFFFF,
+                                            int(n), int(cand_offset), _ptr(values), _ptr(comp)))
+        return values, comp
+
+    def joint_score(self, values):
+        """(lpdf_below, lpdf_above) of configurations values [n, D]
+        (tpe_joint_score)."""
+        D = self._joint_dims()
+        values = _f64(values)
+        if values.ndim != 2 or values.shape[1] != D:
+            raise ValueError('values must be [n, %d]' % D)
+        ll, lg = np.empty(len(values)), np.empty(len(values))
+        self._check(self.lib.tpe_joint_score(self.h, _ptr(values), len(values), _ptr(ll), _ptr(lg)))
+        return ll, lg
+
+    def joint_suggest(self, seed, n_candidates, round=0):
+        """One fused joint round: (values [D], index, lpdf_below, lpdf_above)
+        of broadcast_best's winner among n_candidates (tpe_joint_suggest)."""
+        D = self._joint_dims()
+        values = np.empty(D)
+        idx = ctypes.c_int64()
+        ll, lg = ctypes.c_double(), ctypes.c_double()
+        self._check(self.lib.tpe_joint_suggest(self.h, int(seed) & 0xFFFFFFFFFFFFFFFF,
+                                               int(round) & 0xFFFFFFFF, int(n_candidates), _ptr(values),
+                                               ctypes.byref(idx), ctypes.byref(ll), ctypes.byref(lg)))
+        return values, int(idx.value), ll.value, lg.value
 
     def score(self, label, cand, want_lpdf=True):
         cand = _f64(cand).ravel()

@@ -167,6 +167,26 @@ def always_active(expr):
     return True
 
 
+def unconditional_labels(expr):
+    """Labels reached without entering any option of a switch (hp.choice /
+    pchoice): they take part in every evaluation.  A switch's index
+    expression is not an option, so a top-level choice's own label counts."""
+    out, seen, stack = set(), set(), [as_apply(expr)]
+    while stack:
+        n = stack.pop()
+        if id(n) in seen:
+            continue
+        seen.add(id(n))
+        if n.name == 'hyperopt_param':
+            out.add(param_label(n))
+            continue
+        if n.name == 'switch':
+            stack.append(n.pos_args[0])
+            continue
+        stack.extend(inputs(n))
+    return out
+
+
 def coerce(kind, v):
     """Python type of a hyperparameter value in trial docs."""
     if kind in ('randint', 'categorical'):

@@ -197,6 +197,101 @@ def label_posterior(label, kind, args, below, above, prior_weight):
     return LabelPosterior(label, fam, mix[0], mix[1], q=q)
 
 
+JOINT_KINDS = ('uniform', 'loguniform', 'normal', 'lognormal')
+
+
+def _parzen_positions(mus, prior_mu):
+    """Where adaptive_parzen_normal(mus, ., prior_mu, .) puts its inputs:
+    (position of the prior, position of mus[t] per t) in its sorted output
+    -- the same np.argsort and np.searchsorted calls on the same array."""
+    mus = np.asarray(mus, dtype=float)
+    n = len(mus)
+    if n == 0:
+        return 0, np.zeros(0, dtype=np.int64)
+    if n == 1:
+        pos = 0 if prior_mu < mus[0] else 1
+        return pos, np.array([1 - pos], dtype=np.int64)
+    order = np.argsort(mus)
+    pos = int(np.searchsorted(mus[order], prior_mu))
+    j = np.arange(n)
+    where = np.empty(n, dtype=np.int64)
+    where[order] = np.where(j < pos, j, j + 1)
+    return pos, where
+
+
+def joint_prior(kind, args):
+    """(tpe kind, bounded, low, high, prior_mu, prior_sigma, transform) of a
+    joint-group label: the prior mapping label_posterior uses."""
+    if kind not in JOINT_KINDS:
+        raise ValueError('%r labels cannot join a joint group' % (kind,))
+    log = kind in ('loguniform', 'lognormal')
+    if kind in ('uniform', 'loguniform'):
+        low, high = float(args['low']), float(args['high'])
+        return log, True, low, high, 0.5 * (high + low), 1.0 * (high - low)
+    return log, False, 0.0, 0.0, float(args['mu']), float(args['sigma'])
+
+
+def joint_mixture(group_specs, obs, splitter, prior_weight, streams=None):
+    """The joint (multivariate) mixtures of a group of dense continuous
+    labels whose observations belong to the same trials.
+
+    group_specs: the group's LabelSpecs (or (label, kind, args) tuples);
+    obs[label] = (idxs, vals); splitter: the history's Splitter; streams: each
+    label's Philox stream (default its position in the group).
+
+    Per side and label d the unchanged univariate build
+    adaptive_parzen_normal(o[:, d], ...) supplies sigma and weight of every
+    trial at the position its own np.argsort gave the trial; component 0 is
+    the prior, component t trial t of the side in the order Splitter.split
+    returns them.  The weights depend on the trial order alone: those of the
+    group's first label are the mixture's, and every other label's must agree
+    with them to rounding (each label normalises by a sum of the same terms
+    taken in its own sorted order, so the last bits can differ).
+
+    Returns (dims, wb, mub, sigb, wa, mua, siga): dims a JOINT_DIM_DTYPE
+    array, weights [K], means and sigmas [K, D] in the labels' working space
+    (log space for the log kinds)."""
+    from .engine import JOINT_DIM_DTYPE
+    group = [(g.label, g.kind, g.args) if hasattr(g, 'kind') else tuple(g) for g in group_specs]
+    D = len(group)
+    pw = float(prior_weight)
+    dims = np.zeros(D, dtype=JOINT_DIM_DTYPE)
+    sides = [[], []]
+    ids0 = None
+    for d, (label, kind, args) in enumerate(group):
+        log, bounded, low, high, pmu, psig = joint_prior(kind, args)
+        dims[d]['kind'] = L.TPE_LGMM1 if log else L.TPE_GMM1
+        dims[d]['flags'] = (L.TPE_HAS_LOW | L.TPE_HAS_HIGH) if bounded else 0
+        dims[d]['low'], dims[d]['high'] = low, high
+        dims[d]['stream'] = d if streams is None else int(streams[d])
+        oi, ov = obs[label]
+        oi = np.asarray(oi)
+        if ids0 is None:
+            ids0 = oi
+        elif not np.array_equal(ids0, oi):
+            raise ValueError('joint group: label %r is not observed in the same trials as %r'
+                             % (label, group[0][0]))
+        for side, o in enumerate(splitter.split(oi, ov)):
+            o = np.asarray(o, dtype=float)
+            if log:
+                o = np.log(o)
+            w, mu, sigma = adaptive_parzen_normal(o, pw, pmu, psig)
+            p, where = _parzen_positions(o, pmu)
+            assert mu[p] == pmu and np.array_equal(mu[where], o)
+            at = np.concatenate([[p], where]).astype(np.int64)
+            sides[side].append((w[at], np.concatenate([[pmu], o]), sigma[at]))
+    out = [dims]
+    for cols in sides:
+        W = cols[0][0]
+        for w, _, _ in cols[1:]:
+            # equal up to the rounding of each label's own normalising sum
+            assert len(w) == len(W) and np.allclose(w, W, rtol=4e-16 * (len(W) + 1), atol=0.0), \
+                'joint group: weights differ between labels'
+        out += [np.ascontiguousarray(W), np.ascontiguousarray(np.stack([c[1] for c in cols], axis=1)),
+                np.ascontiguousarray(np.stack([c[2] for c in cols], axis=1))]
+    return tuple(out)
+
+
 def label_spec(kind, args):
     """The tpe_label_spec fields of one hyperparameter and its observation
     transform (the prior mapping of the ap_*_sampler registry, tpe.py:493-617):

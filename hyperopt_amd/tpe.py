@@ -18,7 +18,9 @@
      labels are independent given the history, so evaluating every branch
      and keeping the selected one is the same distribution).
 
-Extra keyword arguments (not in the reference): `precision` ('f64'; 'f32'
+Extra keyword arguments (not in the reference): `multivariate` (True: the
+unconditional dense continuous labels are modelled jointly, see `suggest`),
+`precision` ('f64'; 'f32'
 is accepted and runs the same exact path -- see `suggest`), `device` (HIP ordinal), `devices` (a list of ordinals: one
 multi-device context splits every round over those GPUs, same documents as
 one GPU; tpe_ctx_create_multi), `batch` (True: one independent
@@ -187,13 +189,61 @@ def _resident_posterior(eng, domain, trials, specs, view, gathered, gamma, prior
     return n_docs, None
 
 
+def joint_group(domain, specs, obs=None):
+    """The joint group of a space: its unconditional labels of a dense
+    continuous kind, in the order of `specs` -- or None (with the reason
+    logged) when multivariate TPE falls back to the independent path: fewer
+    than two such labels, or (obs given: label -> (idxs, vals)) labels that
+    are not observed in exactly the same trials."""
+    free = getattr(domain, '_hyperopt_amd_free', None)
+    if free is None:
+        free = _labels.unconditional_labels(domain.expr)
+        try:
+            domain._hyperopt_amd_free = free
+        except AttributeError:
+            pass
+    group = [k for k, s in specs.items() if k in free and s.kind in _post.JOINT_KINDS]
+    if len(group) < 2:
+        logger.info('multivariate TPE: %d joint label(s), using the independent path' % len(group))
+        return None
+    if obs is not None:
+        ids0 = np.asarray(obs[group[0]][0])
+        for k in group[1:]:
+            if not np.array_equal(ids0, np.asarray(obs[k][0])):
+                logger.info('multivariate TPE: labels %r and %r are observed in different trials, '
+                            'using the independent path' % (group[0], k))
+                return None
+    return group
+
+
+def _joint_rounds(eng, domain, trials, specs, gathered, gamma, prior_weight, seed, ids, n_candidates):
+    """One joint round per id for the joint group: [label -> value] per id,
+    or None when the call falls back to the independent path.  The mixtures
+    are built on the host (posterior.joint_mixture); a label's Philox stream
+    is its position in the space, as in the independent round."""
+    labels = list(specs)
+    tids, losses, obs = gathered or _history.gather(domain, trials, labels)
+    group = joint_group(domain, specs, obs)
+    if group is None:
+        return None
+    splitter = _post.Splitter(tids, losses, gamma)
+    eng.set_joint_posterior(*_post.joint_mixture([specs[k] for k in group], obs, splitter, prior_weight,
+                                                 streams=[labels.index(k) for k in group]))
+    out = []
+    for new_id in ids:
+        values = eng.joint_suggest(seed, n_candidates, round=new_id)[0]
+        out.append({k: float(v) for k, v in zip(group, values)})
+    return out
+
+
 def suggest(new_ids, domain, trials, seed,
             prior_weight=_default_prior_weight,
             n_startup_jobs=_default_n_startup_jobs,
             n_EI_candidates=_default_n_EI_candidates,
             gamma=_default_gamma,
             linear_forgetting=_default_linear_forgetting,
-            precision='f64', device=0, batch=False, posterior_builder='auto', devices=None):
+            precision='f64', device=0, batch=False, posterior_builder='auto', devices=None,
+            multivariate=False):
     """tpe.py:823-916.  Past the startup phase one document for new_ids[0],
     like the reference; `batch` (not in the reference) asks for one document
     per new_id:
@@ -213,6 +263,15 @@ def suggest(new_ids, domain, trials, seed,
     During the startup phase (fewer than n_startup_jobs documents) the
     reference's rand.suggest(new_ids, ...) answers, for every new_id.
 
+    multivariate=True (not in the reference) models the joint group -- the
+    unconditional labels of kind uniform, loguniform, normal or lognormal --
+    together: one product kernel per trial, whole configurations drawn from
+    one below trial's neighbourhood and scored under the joint densities
+    ("Multivariate TPE"; Engine.joint_suggest).  Every other label
+    keeps its independent round, bit for bit.  The call is the independent
+    one when the group has fewer than two labels or its labels are not
+    observed in the same trials; more than one device is not supported.
+
     precision='f32' runs the exact fp64 path: a round draws every candidate
     and proves all but ~0.5 % of them out of the race from per-sub-bin score
     bounds before any lpdf is summed, so scoring the rest in fp32 would save
@@ -226,10 +285,12 @@ def suggest(new_ids, domain, trials, seed,
         raise ValueError('posterior_builder must be auto, host or device')
     if batch not in (False, True, 'pending'):
         raise ValueError("batch must be False, True or 'pending'")
+    if multivariate and devices and len(list(devices)) > 1:
+        raise ValueError('multivariate=True runs on one device')
     kw = dict(prior_weight=prior_weight, n_startup_jobs=n_startup_jobs,
               n_EI_candidates=n_EI_candidates, gamma=gamma, linear_forgetting=linear_forgetting,
               precision=precision, device=device, posterior_builder=posterior_builder,
-              devices=devices)
+              devices=devices, multivariate=multivariate)
     specs = specs_of(domain)
     labels = list(specs)
     # the device-resident history's view of the trials (None when the fast
@@ -279,10 +340,14 @@ def suggest(new_ids, domain, trials, seed,
                                  round_call=round_call)
     if res is None:
         res = round_call()
+    joint = _joint_rounds(eng, domain, trials, specs, gathered, gamma, prior_weight, seed, ids,
+                          n_EI_candidates) if multivariate else None
     rval = []
     for j, new_id in enumerate(ids):
         values = {s.label: _labels.coerce(s.kind, res[j][i]['value'])
                   for i, s in enumerate(specs.values())}
+        if joint is not None:
+            values.update(joint[j])
         rval.extend(_doc(new_id, domain, trials, specs, values))
     logger.info('tpe.suggest: %d trials, %d labels, %.1f ms' % (
         n_docs, len(specs), (time.time() - t0) * 1e3))

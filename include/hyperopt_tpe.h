@@ -380,6 +380,46 @@ int tpe_export_posterior(tpe_ctx *ctx, void *d_out, int64_t cap, int64_t *bytes)
 int tpe_import_posterior(tpe_ctx *ctx, const void *d_blobs, int64_t blob_bytes, const int64_t *part_off,
                          int32_t n_parts, const int32_t *part_labels, const int32_t *label_ids);
 
+/* ---- multivariate (joint) TPE ---------------------------------------------
+ * A joint group of D dense continuous labels modelled together: each side's
+ * mixture has one product kernel per trial (component 0 is the prior),
+ *   f_S(y) = (1/A_S) sum_k W_k prod_d phi(y_d; mu_kd, s_kd)  on the box
+ *   prod_d [low_d, high_d),  A_S = sum_k W_k prod_d m_kd  (m_kd: the mass of
+ *   N(mu_kd, s_kd) in [low_d, high_d), 1 without both bounds),
+ * in each label's working space (y = log x for TPE_LGMM1 dimensions; low and
+ * high are working-space bounds), lpdf_S(x) = log f_S(y) - sum_{d log} y_d.
+ * Candidate g of a round picks a below component with the pick word of the
+ * reserved Philox stream TPE_JOINT_STREAM (cumulative W_k prod_d m_kd / A) and
+ * draws dimension d from that component's normal truncated to [low_d, high_d)
+ * with the two words of the dimension's own stream.  The joint posterior is
+ * separate from the resident per-label posterior; single-device contexts. */
+#define TPE_JOINT_STREAM 0x7FFFFFFF
+
+typedef struct {
+    int32_t kind;        /* TPE_GMM1 | TPE_LGMM1 */
+    int32_t flags;       /* TPE_HAS_LOW | TPE_HAS_HIGH */
+    double low, high;
+    int32_t stream;      /* the label's Philox stream */
+} tpe_joint_dim;         /* 32 bytes */
+
+/* Upload and fold both mixtures: weights w[k], means and sigmas row-major
+ * [k][d], k = 0 the prior.  TPE_ERR_SAMPLE when the box holds none of the
+ * below mixture's mass (the draw and suggest calls then return it too). */
+int tpe_joint_set_posterior(tpe_ctx *ctx, const tpe_joint_dim *dims, int32_t n_dims,
+                            int32_t n_below, const double *wb, const double *mub, const double *sigb,
+                            int32_t n_above, const double *wa, const double *mua, const double *siga);
+/* Candidates cand_offset .. cand_offset + n - 1 of (seed, round): values[n D]
+ * row-major and the below component each was drawn from. */
+int tpe_joint_draw(tpe_ctx *ctx, uint64_t seed, uint32_t round, int64_t n, int64_t cand_offset,
+                   double *values, int32_t *comp);
+/* Joint lpdfs of supplied configurations values[n D]: ll below, lg above. */
+int tpe_joint_score(tpe_ctx *ctx, const double *values, int64_t n, double *ll, double *lg);
+/* One fused round: draw n_candidates, score both sides, broadcast_best's
+ * winner (NaN greatest, lowest index on ties): its D values, index and lpdfs.
+ * The three calls above return TPE_ERR_ARG before a joint posterior is set. */
+int tpe_joint_suggest(tpe_ctx *ctx, uint64_t seed, uint32_t round, int64_t n_candidates,
+                      double *values, int64_t *index, double *ll, double *lg);
+
 /* Score a caller-supplied candidate set for one resident label (the parity
  * entry point: identical candidates in, both lpdf vectors and the winner
  * out).  lpdf_below / lpdf_above may be NULL. */

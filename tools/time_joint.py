@@ -1,0 +1,172 @@
+"""Timings and a quality record of multivariate (joint) TPE (needs the GPU).
+
+    python tools/time_joint.py [--dims 32] [--trials 10000] [--reps 20] [--quality] [--out FILE]
+
+On a synthetic history of `--trials` trials over `--dims` dense continuous
+labels (kinds cycled over uniform / loguniform / normal / lognormal):
+
+* the host build of the joint mixtures (posterior.joint_mixture, wall time)
+  and Engine.set_joint_posterior (upload + device fold, wall time), apart;
+* Engine.joint_suggest at 24 and at 2^16 candidates: device time between HIP
+  events on the engine's stream (tpe_last_timing) and wall time, medians;
+  for the 2^16 shape the fp64 rate over 4 flops (two FMAs) per (candidate,
+  component, dimension) and its fraction of the MI355X's fp64 vector peak;
+* the independent round (Engine.suggest) on the same labels, history and
+  candidate counts;
+* the numpy definition (tests/joint_reference.py) on one CPU core, scoring
+  the 24 candidates of one round under both mixtures.
+
+--quality: fmin for 100 evaluations over seeds 0..9 on the coupled objective
+(x - y)^2 + 0.01 (x + y)^2 over uniform(-5, 5)^2, with and without
+multivariate=True; the medians of the best losses.  A record, not a gate.
+
+Prints one JSON document (and writes it to --out).
+"""
+import argparse
+import json
+import os
+import sys
+import time
+from functools import partial
+
+import numpy as np
+
+sys.path.insert(0, os.path.dirname(os.path.dirname(os.path.abspath(__file__))))
+
+FP64_VECTOR_PEAK = 78.6e12   # MI355X data sheet, fp64 vector FLOP/s
+KINDS = ('uniform', 'loguniform', 'normal', 'lognormal')
+
+
+def history(n_dims, n_trials, seed=0):
+    rng = np.random.RandomState(seed)
+    tids = np.arange(n_trials)
+    losses = rng.randn(n_trials)
+    group, obs = [], {}
+    for d in range(n_dims):
+        kind = KINDS[d % 4]
+        label = 'h%03d' % d
+        if kind == 'uniform':
+            args, v = dict(low=-5.0, high=5.0), rng.uniform(-5, 5, n_trials)
+        elif kind == 'loguniform':
+            args, v = dict(low=-3.0, high=2.0), np.exp(rng.uniform(-3, 2, n_trials))
+        elif kind == 'normal':
+            args, v = dict(mu=1.0, sigma=2.0), 1.0 + 2.0 * rng.randn(n_trials)
+        else:
+            args, v = dict(mu=0.0, sigma=1.0), np.exp(rng.randn(n_trials))
+        group.append((label, kind, args))
+        obs[label] = (tids, v)
+    return group, tids, losses, obs
+
+
+def median_ms(fn, reps):
+    out = []
+    for _ in range(reps):
+        t = time.perf_counter()
+        fn()
+        out.append((time.perf_counter() - t) * 1e3)
+    return float(np.median(out))
+
+
+def timings(n_dims, n_trials, reps):
+    from hyperopt_amd import posterior as P
+    from hyperopt_amd.engine import Engine
+    from tests import joint_reference as JR
+    group, tids, losses, obs = history(n_dims, n_trials)
+    splitter = P.Splitter(tids, losses, 0.25)
+    res = dict(dims=n_dims, trials=n_trials, reps=reps)
+    mix = P.joint_mixture(group, obs, splitter, 1.0)
+    res['host_build_ms'] = median_ms(lambda: P.joint_mixture(group, obs, splitter, 1.0), max(3, reps // 4))
+    res['k_below'], res['k_above'] = len(mix[1]), len(mix[4])
+    eng = Engine(0, 'f64')
+    eng.set_joint_posterior(*mix)
+    res['upload_fold_ms'] = median_ms(lambda: eng.set_joint_posterior(*mix), reps)
+    terms = (res['k_below'] + res['k_above']) * n_dims
+    for n in (24, 1 << 16):
+        eng.joint_suggest(1, n, round=0)
+        dev, wall = [], []
+        for r in range(reps):
+            t = time.perf_counter()
+            eng.joint_suggest(1, n, round=r + 1)
+            wall.append((time.perf_counter() - t) * 1e3)
+            dev.append(eng.last_timing()[1])
+        key = 'joint_%d' % n
+        res[key] = dict(device_ms=float(np.median(dev)), wall_ms=float(np.median(wall)))
+        if n > 24:
+            rate = 4.0 * n * terms / (res[key]['device_ms'] * 1e-3)
+            res[key].update(fp64_flops=rate, fraction_of_fp64_vector_peak=rate / FP64_VECTOR_PEAK)
+    # the independent round on the same labels and counts
+    posts = []
+    for label, kind, args in group:
+        b, a = splitter.split(*obs[label])
+        posts.append(P.label_posterior(label, kind, args, b, a, 1.0))
+    eng.set_posterior(*P.pack(posts))
+    for n in (24, 1 << 16):
+        eng.suggest(1, n, round=0)
+        dev, wall = [], []
+        for r in range(reps):
+            t = time.perf_counter()
+            eng.suggest(1, n, round=r + 1)
+            wall.append((time.perf_counter() - t) * 1e3)
+            dev.append(eng.last_timing()[1])
+        res['independent_%d' % n] = dict(device_ms=float(np.median(dev)), wall_ms=float(np.median(wall)))
+    # the numpy definition, one core, the 24-candidate shape
+    dims = []
+    for d, (label, kind, args) in enumerate(group):
+        log, low, high, _, _ = JR.prior_of(kind, args)
+        dims.append(JR.Dim(log, low, high, d))
+    ref = JR.JointRef(dims, mix[1:4], mix[4:7])
+    eng.set_joint_posterior(*mix)
+    vals, _ = eng.joint_draw(1, 24, round=1)
+    t = time.perf_counter()
+    ll, lg = ref.joint_lpdf(vals, 'below'), ref.joint_lpdf(vals, 'above')
+    res['numpy_24_ms'] = (time.perf_counter() - t) * 1e3
+    dl, dg = eng.joint_score(vals)
+    res['numpy_vs_device_max_abs'] = float(max(np.max(np.abs(ll - dl)), np.max(np.abs(lg - dg))))
+    eng.close()
+    return res
+
+
+def quality(evals=100, seeds=10):
+    import hyperopt_amd as H
+    from hyperopt_amd import hp, tpe
+    space = {'x': hp.uniform('x', -5, 5), 'y': hp.uniform('y', -5, 5)}
+
+    def loss(d):
+        return (d['x'] - d['y']) ** 2 + 0.01 * (d['x'] + d['y']) ** 2
+
+    out = {}
+    for name, mv in (('independent', False), ('multivariate', True)):
+        best = []
+        for seed in range(seeds):
+            trials = H.Trials()
+            H.fmin(loss, space, algo=partial(tpe.suggest, multivariate=mv), max_evals=evals, trials=trials,
+                   rstate=np.random.RandomState(seed))
+            best.append(float(min(trials.losses())))
+        out[name] = dict(best=best, median=float(np.median(best)))
+    out.update(evals=evals, seeds=seeds, objective='(x-y)^2 + 0.01 (x+y)^2 on uniform(-5,5)^2')
+    return out
+
+
+def main(argv):
+    ap = argparse.ArgumentParser()
+    ap.add_argument('--dims', type=int, default=32)
+    ap.add_argument('--trials', type=int, default=10000)
+    ap.add_argument('--reps', type=int, default=20)
+    ap.add_argument('--quality', action='store_true')
+    ap.add_argument('--no-timings', action='store_true')
+    ap.add_argument('--out')
+    a = ap.parse_args(argv)
+    res = {}
+    if not a.no_timings:
+        res['timings'] = timings(a.dims, a.trials, a.reps)
+    if a.quality:
+        res['quality'] = quality()
+    txt = json.dumps(res, indent=1, sort_keys=True)
+    print(txt)
+    if a.out:
+        with open(a.out, 'w') as f:
+            f.write(txt + '\n')
+
+
+if __name__ == '__main__':
+    main(sys.argv[1:])
