@@ -61,8 +61,10 @@ TPE_OPT_BX_T = 22
 TPE_OPT_PK_SLICED = 23
 TPE_OPT_DEFER_REPORT = 24
 TPE_OPT_LABEL_SHARDS = 25
+TPE_OPT_JOINT_CAP = 26
 
 TPE_JOINT_STREAM = 0x7FFFFFFF
+TPE_JOINT_MAX_GROUPS = 64
 
 TPE_OBS_IDENTITY = 0
 TPE_OBS_LOG = 1
@@ -167,6 +169,12 @@ SIGNATURES = {
     'tpe_joint_draw': (ctypes.c_int, [_P, _U64, _U32, _I64, _I64, _P, _P]),
     'tpe_joint_score': (ctypes.c_int, [_P, _P, _I64, _P, _P]),
     'tpe_joint_suggest': (ctypes.c_int, [_P, _U64, _U32, _I64, _P, _P, _PD, _PD]),
+    'tpe_joint_set_group': (ctypes.c_int, [_P, _I32, _U32, _P, _I32, _I32, _P, _P, _P, _I32, _P, _P, _P]),
+    'tpe_joint_clear_groups': (ctypes.c_int, [_P]),
+    'tpe_joint_draw_group': (ctypes.c_int, [_P, _I32, _U64, _U32, _I64, _I64, _P, _P]),
+    'tpe_joint_score_group': (ctypes.c_int, [_P, _I32, _P, _I64, _P, _P]),
+    'tpe_joint_suggest_group': (ctypes.c_int, [_P, _I32, _U64, _U32, _I64, _P, _P, _PD, _PD]),
+    'tpe_joint_suggest_batch': (ctypes.c_int, [_P, _U64, _P, _I32, _I64, _P, _P, _P, _P]),
 }
 
 _lib = None

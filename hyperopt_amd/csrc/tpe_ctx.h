@@ -608,6 +608,7 @@ struct tpe_ctx {
 
     // the joint (multivariate) posterior and its scratch (tpe_joint.hip)
     std::shared_ptr<void> joint;
+    int64_t joint_flat_cap = 0;          // TPE_OPT_JOINT_CAP (0: tpe_joint.hip's kJFlatCap)
 
     int fail(int code, const std::string& m) {
         err = m;

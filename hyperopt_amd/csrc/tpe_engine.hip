@@ -5646,6 +5646,11 @@ TPE_DEV int tpe1_set_option(tpe_ctx* ctx, int32_t option, int64_t value) {
             if (!ctx->peers.empty() && value) return ctx->fail(TPE_ERR_ARG, "deferred reports: single-device contexts only");
             ctx->build.defer = value != 0;
             break;
+        case TPE_OPT_JOINT_CAP:
+            if (value < 0 || value > ((int64_t)1 << 30))
+                return ctx->fail(TPE_ERR_ARG, "joint flat candidate cap must be in [0, 2^30]");
+            ctx->joint_flat_cap = value;
+            break;
         case TPE_OPT_BX_SPLIT:
             if (value < 0 || value > 8) return ctx->fail(TPE_ERR_ARG, "index window split must be in [0, 8]");
             ctx->bx_split = (int32_t)value;

@@ -23,6 +23,15 @@
 //   k_joint_best                      the round's winner; its D values are
 //                                     drawn again from Philox by index
 //   k_joint_draw                      candidates and their components (tpe_joint_draw)
+//   k_joint_best_cells                packed rounds (tpe_joint_suggest_batch): the
+//                                     lanes of k_joint_round run over the flat
+//                                     index f = r n + g of R rounds of n
+//                                     candidates and store every candidate's
+//                                     lpdfs; one workgroup per round slot r
+//                                     reduces its n pairs and draws the winner
+//
+// A context holds up to TPE_JOINT_MAX_GROUPS folded posteriors (slots), each
+// with the Philox stream of its component pick; the scratch is shared.
 //
 // Arithmetic: component records are recentred and pre-scaled like the dense
 // labels' (tpe_device.h, Comp): (m' = (mu - centre_d) a, a = sqrt(K/2)/s) with
@@ -32,6 +41,8 @@
 // y' in registers up to kJReg dimensions, beyond in LDS (dimension-major:
 // consecutive lanes read consecutive words).
 #include "tpe_ctx.h"
+
+#include <cstring>
 
 namespace {
 using namespace tpe;
@@ -45,7 +56,7 @@ constexpr int kJLdsTabD = 64;      // up to here the exp table shares the LDS wi
 constexpr int kJMaxD = 128;
 constexpr int kJBlock = 256;
 constexpr int kJMaxBelow = 4096;
-constexpr uint32_t kJointStream = TPE_JOINT_STREAM;
+constexpr int kJMaxGroups = TPE_JOINT_MAX_GROUPS;
 constexpr double kInf = __builtin_inf();
 
 struct JDim {
@@ -65,6 +76,7 @@ struct JP {   // the folded joint posterior
     const uint64_t* __restrict__ thr;  // [Kb] pick thresholds
     const JDraw* __restrict__ draw;    // [Kb][d]
     int32_t D, Kb, Ka;
+    uint32_t stream;                   // the pick word's Philox stream
 };
 
 __device__ __forceinline__ DLabel jlabel(const JDim& j) {
@@ -138,10 +150,10 @@ __global__ __launch_bounds__(kJBlock) void k_joint_fold_sum(const double* __rest
 }
 
 // ------------------------------------------------------------------ draw ----
-// the component of candidate g: the first k with thr[k] > wp of the joint stream
+// the component of candidate g: the first k with thr[k] > wp of the group's pick stream
 __device__ __forceinline__ int jpick(const JP& p, uint32_t k0, uint32_t k1, uint32_t g, uint32_t round) {
     DLabel L{};
-    L.stream = (int32_t)kJointStream;
+    L.stream = (int32_t)p.stream;
     uint32_t wp, wu;
     draw_words(L, k0, k1, g, round, wp, wu);
     int lo = 0, hi = p.Kb - 1;
@@ -320,11 +332,14 @@ __device__ __forceinline__ void jblock_best(uint64_t key, int64_t idx, double ll
 // grid (tiles, 1): the whole round of a tile; grid (tiles, slices): one slice
 // per workgroup, its (max, sum) to part[slice][i] and the candidate's ylog to
 // aux[i] (k_joint_merge finishes).  SAMPLE: candidate i is drawn (index
-// cand_offset + i), else read from vals[i][d].
+// cand_offset + i), else read from vals[i][d].  Packed (rounds != nullptr): i
+// is the flat index over rounds of ncell candidates each -- candidate i %
+// ncell of round rounds[i / ncell]; every candidate's lpdfs are stored, and
+// without `partials` no workgroup best is formed.
 template <int DR, bool TABC, bool SAMPLE>
 __global__ __launch_bounds__(DR > 0 ? kJBlock : kJLdsLanes) void k_joint_round(
     JP p, const double2* __restrict__ rec, const double* __restrict__ cst, const double* __restrict__ vals, int64_t n, int64_t cand_offset, uint64_t seed, uint32_t round,
-    int32_t split, double2* __restrict__ part, double* __restrict__ aux, double* __restrict__ out_ll,
+    const uint32_t* __restrict__ rounds, uint32_t ncell, int32_t split, double2* __restrict__ part, double* __restrict__ aux, double* __restrict__ out_ll,
     double* __restrict__ out_lg, Partial* __restrict__ partials, int32_t* __restrict__ err) {
     extern __shared__ double jsm[];
     const double* tab = jsm;
@@ -335,7 +350,13 @@ __global__ __launch_bounds__(DR > 0 ? kJBlock : kJLdsLanes) void k_joint_round(
     const int64_t i = (int64_t)blockIdx.x * blockDim.x + threadIdx.x;
     const bool valid = i < n;
     const int D = p.D;
-    const uint32_t k0 = (uint32_t)seed, k1 = (uint32_t)(seed >> 32), g = (uint32_t)(cand_offset + i);
+    const uint32_t k0 = (uint32_t)seed, k1 = (uint32_t)(seed >> 32);
+    uint32_t g = (uint32_t)(cand_offset + i);
+    if (rounds && valid) {   // (n < 2^31 in packed launches)
+        const uint32_t r = (uint32_t)i / ncell;
+        g = (uint32_t)i - r * ncell;
+        round = rounds[r];
+    }
     int kc = 0;
     if constexpr (SAMPLE)
         if (valid) kc = jpick(p, k0, k1, g, round);
@@ -402,6 +423,7 @@ __global__ __launch_bounds__(DR > 0 ? kJBlock : kJLdsLanes) void k_joint_round(
         out_ll[i] = lp[0];
         out_lg[i] = lp[1];
     }
+    if (!partials) return;
     __syncthreads();   // (the table and y' are done with: their LDS is the reduction's)
     jblock_best(valid ? order_key(lp[0] - lp[1]) : 0ull, valid ? i : INT64_MAX, lp[0], lp[1],
                 partials + blockIdx.x, jsm);
@@ -432,6 +454,7 @@ __global__ __launch_bounds__(kJBlock) void k_joint_merge(JP p, int64_t n, const 
             out_lg[i] = lp[1];
         }
     }
+    if (!partials) return;
     __shared__ double scr[4 * kJBlock];
     jblock_best(valid ? order_key(lp[0] - lp[1]) : 0ull, valid ? i : INT64_MAX, lp[0], lp[1],
                 partials + blockIdx.x, scr);
@@ -469,20 +492,57 @@ __global__ __launch_bounds__(kJBlock) void k_joint_best(JP p, const Partial* __r
     for (int d = threadIdx.x; d < p.D; d += kJBlock) res[3 + d] = jdraw(p, p.dims[d], d, kc, k0, k1, g, round);
 }
 
+// packed rounds: workgroup b reduces the ncell (ll, lg) pairs of round slot b
+// with k_joint_round's key and order, and writes the slot's row like
+// k_joint_best: lpdf_below, lpdf_above, index, the winner's D values
+__global__ __launch_bounds__(kJBlock) void k_joint_best_cells(JP p, const double* __restrict__ ll,
+                                                              const double* __restrict__ lg,
+                                                              const uint32_t* __restrict__ rounds, uint32_t ncell,
+                                                              uint64_t seed, double* __restrict__ res) {
+    const size_t base = (size_t)blockIdx.x * ncell;
+    uint64_t bk = 0;
+    int64_t bi = INT64_MAX;
+    double bl = 0.0, bg = 0.0;
+    for (uint32_t j = threadIdx.x; j < ncell; j += kJBlock) {
+        const double a = ll[base + j], b = lg[base + j];
+        const uint64_t key = order_key(a - b);
+        if (better(key, (int64_t)j, bk, bi)) {
+            bk = key;
+            bi = (int64_t)j;
+            bl = a;
+            bg = b;
+        }
+    }
+    __shared__ Partial win;
+    __shared__ double scr[4 * kJBlock];
+    jblock_best(bk, bi, bl, bg, &win, scr);
+    __syncthreads();
+    const Partial w = win;
+    double* row = res + (size_t)blockIdx.x * (3 + p.D);
+    if (threadIdx.x == 0) {
+        row[0] = w.lb;
+        row[1] = w.la;
+        row[2] = (double)w.idx;
+    }
+    if (w.idx == INT64_MAX) return;
+    const uint32_t k0 = (uint32_t)seed, k1 = (uint32_t)(seed >> 32), g = (uint32_t)w.idx, round = rounds[blockIdx.x];
+    const int kc = jpick(p, k0, k1, g, round);
+    for (int d = threadIdx.x; d < p.D; d += kJBlock) row[3 + d] = jdraw(p, p.dims[d], d, kc, k0, k1, g, round);
+}
+
 // ------------------------------------------------------------- host side ----
 template <typename T>
 using DevBuf = tpe_rt::DevBuf<T>;
 
-struct JointState {
+struct JointState {   // one slot's folded posterior
     int32_t D = 0, Kb = 0, Ka = 0;
+    uint32_t stream = TPE_JOINT_STREAM;
     bool ready = false, zero = false;
     DevBuf<JDim> dims;
-    DevBuf<double> W, mu, sig, cst, P, logA, vals, ll, lg, aux, res;
-    DevBuf<double2> rec, part;
+    DevBuf<double> W, mu, sig, cst, P, logA;
+    DevBuf<double2> rec;
     DevBuf<JDraw> draw;
     DevBuf<uint64_t> thr;
-    DevBuf<int32_t> err, comp;
-    DevBuf<Partial> partials;
     JP jp() const {
         JP p;
         p.dims = dims.p;
@@ -494,24 +554,41 @@ struct JointState {
         p.D = D;
         p.Kb = Kb;
         p.Ka = Ka;
+        p.stream = stream;
         return p;
     }
 };
 
-JointState* jstate(tpe_ctx* ctx, bool make) {
-    if (!ctx->joint && make) ctx->joint = std::shared_ptr<void>(new JointState(), [](void* q) {
-        delete static_cast<JointState*>(q);
+struct JointGroups {   // a context's slots and the scratch they share (one stream: one user at a time)
+    std::unique_ptr<JointState> slot[kJMaxGroups];
+    DevBuf<double> vals, ll, lg, aux, res, bres;
+    DevBuf<double2> part;
+    DevBuf<int32_t> err, comp;
+    DevBuf<Partial> partials;
+    DevBuf<uint32_t> rounds;
+    std::vector<double> hres;
+};
+
+JointGroups* jgroups(tpe_ctx* ctx, bool make) {
+    if (!ctx->joint && make) ctx->joint = std::shared_ptr<void>(new JointGroups(), [](void* q) {
+        delete static_cast<JointGroups*>(q);
     });
-    return static_cast<JointState*>(ctx->joint.get());
+    return static_cast<JointGroups*>(ctx->joint.get());
 }
 
 constexpr size_t kJPartBytes = (size_t)64 << 20;   // the split map's (max, sum) pairs at most
 constexpr int64_t kJSplitTiles = 512;              // tiles from which one workgroup runs a tile's whole round
+// flat candidates (rounds x candidates) of one packed launch at most: 16 B of
+// lpdfs each, 16 MiB, beside at most kJPartBytes of the split map
+constexpr int64_t kJFlatCap = (int64_t)1 << 20;
 
-// the round of n candidates (drawn, or J->vals): lpdfs to J->ll / J->lg when
-// `lpdfs`, per-workgroup bests to J->partials; *nparts of them
-int launch_round(tpe_ctx* ctx, JointState* J, bool sample, int64_t n, int64_t cand_offset, uint64_t seed,
-                 uint32_t round, bool lpdfs, int32_t* nparts) {
+// the round of n candidates (drawn, or G->vals): lpdfs to G->ll / G->lg when
+// `lpdfs`, per-workgroup bests to G->partials, *nparts of them.  Packed
+// (rounds: device pointer to the round numbers, ncell candidates each, n =
+// their flat count): every candidate's lpdfs, no bests
+int launch_round(tpe_ctx* ctx, JointGroups* G, JointState* J, bool sample, int64_t n, int64_t cand_offset,
+                 uint64_t seed, uint32_t round, bool lpdfs, int32_t* nparts, int32_t* err,
+                 const uint32_t* rounds = nullptr, uint32_t ncell = 0) {
     const int D = J->D;
     const int dr = D <= kJRegSmall ? kJRegSmall : (D <= kJReg ? kJReg : 0);
     const bool tabc = dr == 0 && D > kJLdsTabD;
@@ -523,29 +600,32 @@ int launch_round(tpe_ctx* ctx, JointState* J, bool sample, int64_t n, int64_t ca
     const size_t lds = (tabc ? 0 : kExpTabSize * sizeof(double)) + (dr ? 0 : (size_t)D * kJLdsLanes * sizeof(double));
     const int64_t mtiles = (n + kJBlock - 1) / kJBlock;
     *nparts = (int32_t)(split ? mtiles : tiles);
-    HIPCHK(ctx, J->partials.reserve(*nparts));
+    if (!rounds) HIPCHK(ctx, G->partials.reserve(*nparts));
     if (split) {
-        HIPCHK(ctx, J->part.reserve((size_t)nsl * n));
-        HIPCHK(ctx, J->aux.reserve(n));
+        HIPCHK(ctx, G->part.reserve((size_t)nsl * n));
+        HIPCHK(ctx, G->aux.reserve(n));
     }
     if (lpdfs) {
-        HIPCHK(ctx, J->ll.reserve(n));
-        HIPCHK(ctx, J->lg.reserve(n));
+        HIPCHK(ctx, G->ll.reserve(n));
+        HIPCHK(ctx, G->lg.reserve(n));
     }
     const dim3 grid((unsigned)tiles, split ? (unsigned)nsl : 1u);
-    double* oll = lpdfs ? J->ll.p : nullptr;
-    double* olg = lpdfs ? J->lg.p : nullptr;
+    double* oll = lpdfs ? G->ll.p : nullptr;
+    double* olg = lpdfs ? G->lg.p : nullptr;
+    Partial* parts = rounds ? nullptr : G->partials.p;
     const JP p = J->jp();
 #define JLAUNCH(DR, TABC)                                                                                       \
     do {                                                                                                        \
         if (sample)                                                                                             \
             hipLaunchKernelGGL((k_joint_round<DR, TABC, true>), grid, dim3(threads), lds, ctx->stream, p,       \
-                               J->rec.p, J->cst.p, nullptr, n, cand_offset, seed, round, (int32_t)split, J->part.p, J->aux.p,       \
-                               split ? nullptr : oll, split ? nullptr : olg, J->partials.p, J->err.p);          \
+                               J->rec.p, J->cst.p, nullptr, n, cand_offset, seed, round, rounds, ncell,         \
+                               (int32_t)split, G->part.p, G->aux.p, split ? nullptr : oll,                      \
+                               split ? nullptr : olg, parts, err);                                              \
         else                                                                                                    \
             hipLaunchKernelGGL((k_joint_round<DR, TABC, false>), grid, dim3(threads), lds, ctx->stream, p,      \
-                               J->rec.p, J->cst.p, J->vals.p, n, cand_offset, seed, round, (int32_t)split, J->part.p, J->aux.p,     \
-                               split ? nullptr : oll, split ? nullptr : olg, J->partials.p, J->err.p);          \
+                               J->rec.p, J->cst.p, G->vals.p, n, cand_offset, seed, round, rounds, ncell,       \
+                               (int32_t)split, G->part.p, G->aux.p, split ? nullptr : oll,                      \
+                               split ? nullptr : olg, parts, err);                                              \
     } while (0)
     if (dr == kJRegSmall) JLAUNCH(kJRegSmall, false);
     else if (dr == kJReg) JLAUNCH(kJReg, false);
@@ -554,18 +634,25 @@ int launch_round(tpe_ctx* ctx, JointState* J, bool sample, int64_t n, int64_t ca
 #undef JLAUNCH
     HIPCHK(ctx, hipGetLastError());
     if (split) {
-        hipLaunchKernelGGL(k_joint_merge, dim3((unsigned)mtiles), dim3(kJBlock), 0, ctx->stream, p, n, J->part.p,
-                           J->aux.p, oll, olg, J->partials.p);
+        hipLaunchKernelGGL(k_joint_merge, dim3((unsigned)mtiles), dim3(kJBlock), 0, ctx->stream, p, n, G->part.p,
+                           G->aux.p, oll, olg, parts);
         HIPCHK(ctx, hipGetLastError());
     }
     return TPE_OK;
 }
 
-int joint_ready(tpe_ctx* ctx, JointState** out, const char* who) {
-    JointState* J = jstate(ctx, false);
+int zero_mass(tpe_ctx* ctx) {
+    return ctx->fail(TPE_ERR_SAMPLE, "truncated sampler: the box holds none of the below mixture's mass");
+}
+
+int joint_ready(tpe_ctx* ctx, int32_t slot, JointGroups** Gout, JointState** out, const char* who) {
+    if (slot < 0 || slot >= kJMaxGroups)
+        return ctx->fail(TPE_ERR_ARG, std::string(who) + ": slot must be in [0, " + std::to_string(kJMaxGroups) + ")");
+    JointGroups* G = jgroups(ctx, false);
+    JointState* J = G ? G->slot[slot].get() : nullptr;
     if (!J || !J->ready) return ctx->fail(TPE_ERR_ARG, std::string(who) + ": no joint posterior set");
-    if (J->zero)
-        return ctx->fail(TPE_ERR_SAMPLE, "truncated sampler: the box holds none of the below mixture's mass");
+    if (J->zero) return zero_mass(ctx);
+    *Gout = G;
     *out = J;
     return TPE_OK;
 }
@@ -577,21 +664,26 @@ int check_range(tpe_ctx* ctx, int64_t n, int64_t cand_offset) {
     return TPE_OK;
 }
 
-int read_err(tpe_ctx* ctx, JointState* J) {
+int not_reached(tpe_ctx* ctx) {
+    return ctx->fail(TPE_ERR_SAMPLE, "truncated sampler: interval [low, high) not reached");
+}
+
+int read_err(tpe_ctx* ctx, JointGroups* G) {
     int32_t e = 0;
-    HIPCHK(ctx, hipMemcpyAsync(&e, J->err.p, sizeof(int32_t), hipMemcpyDeviceToHost, ctx->stream));
+    HIPCHK(ctx, hipMemcpyAsync(&e, G->err.p, sizeof(int32_t), hipMemcpyDeviceToHost, ctx->stream));
     HIPCHK(ctx, hipStreamSynchronize(ctx->stream));
-    if (e & 1) return ctx->fail(TPE_ERR_SAMPLE, "truncated sampler: interval [low, high) not reached");
+    if (e & 1) return not_reached(ctx);
     return TPE_OK;
 }
-}  // namespace
 
-extern "C" {
-
-int tpe_joint_set_posterior(tpe_ctx* ctx, const tpe_joint_dim* dims, int32_t n_dims, int32_t n_below,
-                            const double* wb, const double* mub, const double* sigb, int32_t n_above,
-                            const double* wa, const double* mua, const double* siga) {
+// upload and fold one slot's posterior; `only`: the other slots are cleared
+// once the arguments are accepted (tpe_joint_set_posterior)
+int joint_set(tpe_ctx* ctx, int32_t slot, uint32_t pick_stream, bool only, const tpe_joint_dim* dims,
+              int32_t n_dims, int32_t n_below, const double* wb, const double* mub, const double* sigb,
+              int32_t n_above, const double* wa, const double* mua, const double* siga) {
     if (!ctx) return TPE_ERR_ARG;
+    if (slot < 0 || slot >= kJMaxGroups)
+        return ctx->fail(TPE_ERR_ARG, "a joint slot is in [0, " + std::to_string(kJMaxGroups) + ")");
     if (!dims || !wb || !mub || !sigb || !wa || !mua || !siga) return ctx->fail(TPE_ERR_ARG, "null pointer");
     if (n_dims < 1 || n_dims > kJMaxD)
         return ctx->fail(TPE_ERR_ARG, "a joint group holds 1 to " + std::to_string(kJMaxD) + " dimensions");
@@ -618,7 +710,12 @@ int tpe_joint_set_posterior(tpe_ctx* ctx, const tpe_joint_dim* dims, int32_t n_d
             if (!(sg[o] > 0.0 && sg[o] < __builtin_inf())) return ctx->fail(TPE_ERR_VALUE, "sigma must be positive");
     }
     HIPCHK(ctx, hipSetDevice(ctx->device));
-    JointState* J = jstate(ctx, true);
+    JointGroups* G = jgroups(ctx, true);
+    if (only)   // (an unset slot keeps its buffers for the next posterior: no hipFree per call)
+        for (int j = 0; j < kJMaxGroups; ++j)
+            if (j != slot && G->slot[j]) G->slot[j]->ready = false;
+    if (!G->slot[slot]) G->slot[slot].reset(new JointState());
+    JointState* J = G->slot[slot].get();
     J->ready = false;
     HIPCHK(ctx, J->dims.reserve(D));
     HIPCHK(ctx, J->W.reserve(K));
@@ -630,7 +727,7 @@ int tpe_joint_set_posterior(tpe_ctx* ctx, const tpe_joint_dim* dims, int32_t n_d
     HIPCHK(ctx, J->logA.reserve(2));
     HIPCHK(ctx, J->draw.reserve((size_t)Kb * D));
     HIPCHK(ctx, J->thr.reserve(Kb));
-    HIPCHK(ctx, J->err.reserve(1));
+    HIPCHK(ctx, G->err.reserve(1));
     hipStream_t st = ctx->stream;
     const size_t nb = (size_t)Kb * D, na = (size_t)Ka * D;
     HIPCHK(ctx, hipMemcpyAsync(J->dims.p, hd.data(), D * sizeof(JDim), hipMemcpyHostToDevice, st));
@@ -640,87 +737,123 @@ int tpe_joint_set_posterior(tpe_ctx* ctx, const tpe_joint_dim* dims, int32_t n_d
     HIPCHK(ctx, hipMemcpyAsync(J->mu.p + nb, mua, na * sizeof(double), hipMemcpyHostToDevice, st));
     HIPCHK(ctx, hipMemcpyAsync(J->sig.p, sigb, nb * sizeof(double), hipMemcpyHostToDevice, st));
     HIPCHK(ctx, hipMemcpyAsync(J->sig.p + nb, siga, na * sizeof(double), hipMemcpyHostToDevice, st));
-    HIPCHK(ctx, hipMemsetAsync(J->err.p, 0, sizeof(int32_t), st));
+    HIPCHK(ctx, hipMemsetAsync(G->err.p, 0, sizeof(int32_t), st));
     hipLaunchKernelGGL(k_joint_fold, dim3((K + kJBlock - 1) / kJBlock), dim3(kJBlock), 0, st, J->dims.p, D, Kb, Ka,
                        J->W.p, J->mu.p, J->sig.p, J->rec.p, J->cst.p, J->P.p, J->draw.p);
     HIPCHK(ctx, hipGetLastError());
     hipLaunchKernelGGL(k_joint_fold_sum, dim3(2), dim3(kJBlock), 0, st, J->P.p, Kb, Ka, J->logA.p, J->thr.p,
-                       J->err.p);
+                       G->err.p);
     HIPCHK(ctx, hipGetLastError());
     int32_t e = 0;
-    HIPCHK(ctx, hipMemcpyAsync(&e, J->err.p, sizeof(int32_t), hipMemcpyDeviceToHost, st));
+    HIPCHK(ctx, hipMemcpyAsync(&e, G->err.p, sizeof(int32_t), hipMemcpyDeviceToHost, st));
     HIPCHK(ctx, hipStreamSynchronize(st));
     J->D = D;
     J->Kb = Kb;
     J->Ka = Ka;
+    J->stream = pick_stream;
     J->zero = (e & 1) != 0;
     J->ready = true;
-    if (J->zero)
-        return ctx->fail(TPE_ERR_SAMPLE, "truncated sampler: the box holds none of the below mixture's mass");
+    if (J->zero) return zero_mass(ctx);
+    return TPE_OK;
+}
+}  // namespace
+
+extern "C" {
+
+int tpe_joint_set_posterior(tpe_ctx* ctx, const tpe_joint_dim* dims, int32_t n_dims, int32_t n_below,
+                            const double* wb, const double* mub, const double* sigb, int32_t n_above,
+                            const double* wa, const double* mua, const double* siga) {
+    return joint_set(ctx, 0, TPE_JOINT_STREAM, true, dims, n_dims, n_below, wb, mub, sigb, n_above, wa, mua, siga);
+}
+
+int tpe_joint_set_group(tpe_ctx* ctx, int32_t slot, uint32_t pick_stream, const tpe_joint_dim* dims, int32_t n_dims,
+                        int32_t n_below, const double* wb, const double* mub, const double* sigb, int32_t n_above,
+                        const double* wa, const double* mua, const double* siga) {
+    return joint_set(ctx, slot, pick_stream, false, dims, n_dims, n_below, wb, mub, sigb, n_above, wa, mua, siga);
+}
+
+int tpe_joint_clear_groups(tpe_ctx* ctx) {
+    if (!ctx) return TPE_ERR_ARG;
+    JointGroups* G = jgroups(ctx, false);
+    if (!G) return TPE_OK;
+    for (int j = 0; j < kJMaxGroups; ++j)
+        if (G->slot[j]) G->slot[j]->ready = false;   // (buffers kept, as above)
     return TPE_OK;
 }
 
-int tpe_joint_draw(tpe_ctx* ctx, uint64_t seed, uint32_t round, int64_t n, int64_t cand_offset, double* values,
-                   int32_t* comp) {
+int tpe_joint_draw_group(tpe_ctx* ctx, int32_t slot, uint64_t seed, uint32_t round, int64_t n, int64_t cand_offset,
+                         double* values, int32_t* comp) {
     if (!ctx) return TPE_ERR_ARG;
+    JointGroups* G = nullptr;
     JointState* J = nullptr;
-    int rc = joint_ready(ctx, &J, "tpe_joint_draw");
+    int rc = joint_ready(ctx, slot, &G, &J, "tpe_joint_draw");
     if (rc) return rc;
     if (!values || !comp) return ctx->fail(TPE_ERR_ARG, "null pointer");
     if ((rc = check_range(ctx, n, cand_offset))) return rc;
     HIPCHK(ctx, hipSetDevice(ctx->device));
-    HIPCHK(ctx, J->vals.reserve((size_t)n * J->D));
-    HIPCHK(ctx, J->comp.reserve(n));
-    HIPCHK(ctx, hipMemsetAsync(J->err.p, 0, sizeof(int32_t), ctx->stream));
+    HIPCHK(ctx, G->vals.reserve((size_t)n * J->D));
+    HIPCHK(ctx, G->comp.reserve(n));
+    HIPCHK(ctx, hipMemsetAsync(G->err.p, 0, sizeof(int32_t), ctx->stream));
     hipLaunchKernelGGL(k_joint_draw, dim3((unsigned)((n + kJBlock - 1) / kJBlock)), dim3(kJBlock), 0, ctx->stream,
-                       J->jp(), n, cand_offset, seed, round, J->vals.p, J->comp.p, J->err.p);
+                       J->jp(), n, cand_offset, seed, round, G->vals.p, G->comp.p, G->err.p);
     HIPCHK(ctx, hipGetLastError());
-    HIPCHK(ctx, hipMemcpyAsync(values, J->vals.p, (size_t)n * J->D * sizeof(double), hipMemcpyDeviceToHost,
+    HIPCHK(ctx, hipMemcpyAsync(values, G->vals.p, (size_t)n * J->D * sizeof(double), hipMemcpyDeviceToHost,
                                ctx->stream));
-    HIPCHK(ctx, hipMemcpyAsync(comp, J->comp.p, n * sizeof(int32_t), hipMemcpyDeviceToHost, ctx->stream));
-    return read_err(ctx, J);
+    HIPCHK(ctx, hipMemcpyAsync(comp, G->comp.p, n * sizeof(int32_t), hipMemcpyDeviceToHost, ctx->stream));
+    return read_err(ctx, G);
 }
 
-int tpe_joint_score(tpe_ctx* ctx, const double* values, int64_t n, double* ll, double* lg) {
+int tpe_joint_draw(tpe_ctx* ctx, uint64_t seed, uint32_t round, int64_t n, int64_t cand_offset, double* values,
+                   int32_t* comp) {
+    return tpe_joint_draw_group(ctx, 0, seed, round, n, cand_offset, values, comp);
+}
+
+int tpe_joint_score_group(tpe_ctx* ctx, int32_t slot, const double* values, int64_t n, double* ll, double* lg) {
     if (!ctx) return TPE_ERR_ARG;
+    JointGroups* G = nullptr;
     JointState* J = nullptr;
-    int rc = joint_ready(ctx, &J, "tpe_joint_score");
+    int rc = joint_ready(ctx, slot, &G, &J, "tpe_joint_score");
     if (rc) return rc;
     if (!values || !ll || !lg) return ctx->fail(TPE_ERR_ARG, "null pointer");
     if ((rc = check_range(ctx, n, 0))) return rc;
     HIPCHK(ctx, hipSetDevice(ctx->device));
-    HIPCHK(ctx, J->vals.reserve((size_t)n * J->D));
-    HIPCHK(ctx, hipMemcpyAsync(J->vals.p, values, (size_t)n * J->D * sizeof(double), hipMemcpyHostToDevice,
+    HIPCHK(ctx, G->vals.reserve((size_t)n * J->D));
+    HIPCHK(ctx, hipMemcpyAsync(G->vals.p, values, (size_t)n * J->D * sizeof(double), hipMemcpyHostToDevice,
                                ctx->stream));
     int32_t nparts = 0;
-    if ((rc = launch_round(ctx, J, false, n, 0, 0, 0, true, &nparts))) return rc;
-    HIPCHK(ctx, hipMemcpyAsync(ll, J->ll.p, n * sizeof(double), hipMemcpyDeviceToHost, ctx->stream));
-    HIPCHK(ctx, hipMemcpyAsync(lg, J->lg.p, n * sizeof(double), hipMemcpyDeviceToHost, ctx->stream));
+    if ((rc = launch_round(ctx, G, J, false, n, 0, 0, 0, true, &nparts, G->err.p))) return rc;
+    HIPCHK(ctx, hipMemcpyAsync(ll, G->ll.p, n * sizeof(double), hipMemcpyDeviceToHost, ctx->stream));
+    HIPCHK(ctx, hipMemcpyAsync(lg, G->lg.p, n * sizeof(double), hipMemcpyDeviceToHost, ctx->stream));
     HIPCHK(ctx, hipStreamSynchronize(ctx->stream));
     return TPE_OK;
 }
 
-int tpe_joint_suggest(tpe_ctx* ctx, uint64_t seed, uint32_t round, int64_t n_candidates, double* values,
-                      int64_t* index, double* ll, double* lg) {
+int tpe_joint_score(tpe_ctx* ctx, const double* values, int64_t n, double* ll, double* lg) {
+    return tpe_joint_score_group(ctx, 0, values, n, ll, lg);
+}
+
+int tpe_joint_suggest_group(tpe_ctx* ctx, int32_t slot, uint64_t seed, uint32_t round, int64_t n_candidates,
+                            double* values, int64_t* index, double* ll, double* lg) {
     if (!ctx) return TPE_ERR_ARG;
+    JointGroups* G = nullptr;
     JointState* J = nullptr;
-    int rc = joint_ready(ctx, &J, "tpe_joint_suggest");
+    int rc = joint_ready(ctx, slot, &G, &J, "tpe_joint_suggest");
     if (rc) return rc;
     if (!values || !index || !ll || !lg) return ctx->fail(TPE_ERR_ARG, "null pointer");
     if ((rc = check_range(ctx, n_candidates, 0))) return rc;
     HIPCHK(ctx, hipSetDevice(ctx->device));
-    HIPCHK(ctx, J->res.reserve(3 + J->D));
-    HIPCHK(ctx, hipMemsetAsync(J->err.p, 0, sizeof(int32_t), ctx->stream));
+    HIPCHK(ctx, G->res.reserve(3 + J->D));
+    HIPCHK(ctx, hipMemsetAsync(G->err.p, 0, sizeof(int32_t), ctx->stream));
     int32_t nparts = 0;
     if (ctx->timing) HIPCHK(ctx, hipEventRecord(ctx->ev0, ctx->stream));
-    if ((rc = launch_round(ctx, J, true, n_candidates, 0, seed, round, false, &nparts))) return rc;
-    hipLaunchKernelGGL(k_joint_best, dim3(1), dim3(kJBlock), 0, ctx->stream, J->jp(), J->partials.p, nparts,
-                       (int64_t)0, seed, round, 1, J->res.p);
+    if ((rc = launch_round(ctx, G, J, true, n_candidates, 0, seed, round, false, &nparts, G->err.p))) return rc;
+    hipLaunchKernelGGL(k_joint_best, dim3(1), dim3(kJBlock), 0, ctx->stream, J->jp(), G->partials.p, nparts,
+                       (int64_t)0, seed, round, 1, G->res.p);
     HIPCHK(ctx, hipGetLastError());
     if (ctx->timing) HIPCHK(ctx, hipEventRecord(ctx->ev1, ctx->stream));
     std::vector<double> h(3 + J->D);
-    HIPCHK(ctx, hipMemcpyAsync(h.data(), J->res.p, h.size() * sizeof(double), hipMemcpyDeviceToHost, ctx->stream));
-    if ((rc = read_err(ctx, J))) return rc;
+    HIPCHK(ctx, hipMemcpyAsync(h.data(), G->res.p, h.size() * sizeof(double), hipMemcpyDeviceToHost, ctx->stream));
+    if ((rc = read_err(ctx, G))) return rc;
     if (ctx->timing) {   // the round's device time (tpe_last_timing: both figures)
         HIPCHK(ctx, hipEventElapsedTime(&ctx->round_ms, ctx->ev0, ctx->ev1));
         ctx->score_ms = ctx->round_ms;
@@ -729,6 +862,103 @@ int tpe_joint_suggest(tpe_ctx* ctx, uint64_t seed, uint32_t round, int64_t n_can
     *lg = h[1];
     *index = (int64_t)h[2];
     for (int d = 0; d < J->D; ++d) values[d] = h[3 + d];
+    return TPE_OK;
+}
+
+int tpe_joint_suggest(tpe_ctx* ctx, uint64_t seed, uint32_t round, int64_t n_candidates, double* values,
+                      int64_t* index, double* ll, double* lg) {
+    return tpe_joint_suggest_group(ctx, 0, seed, round, n_candidates, values, index, ll, lg);
+}
+
+// Every set slot's rounds in packed launches: per slot, chunks of whole
+// rounds whose flat candidate count stays within the cap -- one k_joint_round
+// (+ k_joint_merge) and one k_joint_best_cells each; a round beyond the cap
+// runs alone as tpe_joint_suggest runs it.  The result rows of all slots and,
+// in front of them, the error word are one device buffer: one copy back, one
+// synchronisation.
+int tpe_joint_suggest_batch(tpe_ctx* ctx, uint64_t seed, const uint32_t* rounds, int32_t n_rounds,
+                            int64_t n_candidates, double* values, int64_t* index, double* ll, double* lg) {
+    if (!ctx) return TPE_ERR_ARG;
+    if (!rounds || !values || !index || !ll || !lg) return ctx->fail(TPE_ERR_ARG, "null pointer");
+    if (n_rounds < 1) return ctx->fail(TPE_ERR_ARG, "the number of rounds must be positive");
+    int rc = check_range(ctx, n_candidates, 0);
+    if (rc) return rc;
+    JointGroups* G = jgroups(ctx, false);
+    std::vector<JointState*> set;
+    if (G)
+        for (int j = 0; j < kJMaxGroups; ++j)
+            if (G->slot[j] && G->slot[j]->ready) set.push_back(G->slot[j].get());
+    if (set.empty()) return ctx->fail(TPE_ERR_ARG, "tpe_joint_suggest_batch: no joint posterior set");
+    size_t rows = 0, sumD = 0;
+    for (JointState* J : set) {
+        if (J->zero) return zero_mass(ctx);
+        rows += 3 + J->D;
+        sumD += J->D;
+    }
+    const int64_t R = n_rounds, n = n_candidates;
+    const int64_t cap = ctx->joint_flat_cap > 0 ? ctx->joint_flat_cap : kJFlatCap;
+    const int64_t per = n <= cap ? std::min<int64_t>(R, cap / n) : 0;   // rounds of a packed chunk
+    HIPCHK(ctx, hipSetDevice(ctx->device));
+    hipStream_t st = ctx->stream;
+    const size_t total = 1 + (size_t)R * rows;
+    HIPCHK(ctx, G->bres.reserve(total));
+    HIPCHK(ctx, G->rounds.reserve(R));
+    if (per) {
+        HIPCHK(ctx, G->ll.reserve(per * n));
+        HIPCHK(ctx, G->lg.reserve(per * n));
+    }
+    int32_t* err = reinterpret_cast<int32_t*>(G->bres.p);
+    HIPCHK(ctx, hipMemsetAsync(G->bres.p, 0, sizeof(double), st));
+    HIPCHK(ctx, hipMemcpyAsync(G->rounds.p, rounds, R * sizeof(uint32_t), hipMemcpyHostToDevice, st));
+    if (ctx->timing) HIPCHK(ctx, hipEventRecord(ctx->ev0, st));
+    double* row0 = G->bres.p + 1;
+    for (JointState* J : set) {
+        const size_t w = 3 + J->D;
+        int32_t nparts = 0;
+        if (per) {
+            for (int64_t r0 = 0; r0 < R; r0 += per) {
+                const int64_t rc_n = std::min(per, R - r0);
+                if ((rc = launch_round(ctx, G, J, true, rc_n * n, 0, seed, 0, true, &nparts, err, G->rounds.p + r0,
+                                       (uint32_t)n)))
+                    return rc;
+                hipLaunchKernelGGL(k_joint_best_cells, dim3((unsigned)rc_n), dim3(kJBlock), 0, st, J->jp(), G->ll.p,
+                                   G->lg.p, G->rounds.p + r0, (uint32_t)n, seed, row0 + r0 * w);
+                HIPCHK(ctx, hipGetLastError());
+            }
+        } else {
+            for (int64_t r = 0; r < R; ++r) {
+                if ((rc = launch_round(ctx, G, J, true, n, 0, seed, rounds[r], false, &nparts, err))) return rc;
+                hipLaunchKernelGGL(k_joint_best, dim3(1), dim3(kJBlock), 0, st, J->jp(), G->partials.p, nparts,
+                                   (int64_t)0, seed, rounds[r], 1, row0 + r * w);
+                HIPCHK(ctx, hipGetLastError());
+            }
+        }
+        row0 += (size_t)R * w;
+    }
+    if (ctx->timing) HIPCHK(ctx, hipEventRecord(ctx->ev1, st));
+    G->hres.resize(total);
+    HIPCHK(ctx, hipMemcpyAsync(G->hres.data(), G->bres.p, total * sizeof(double), hipMemcpyDeviceToHost, st));
+    HIPCHK(ctx, hipStreamSynchronize(st));
+    int32_t e = 0;
+    std::memcpy(&e, G->hres.data(), sizeof(e));
+    if (e & 1) return not_reached(ctx);
+    if (ctx->timing) {
+        HIPCHK(ctx, hipEventElapsedTime(&ctx->round_ms, ctx->ev0, ctx->ev1));
+        ctx->score_ms = ctx->round_ms;
+    }
+    const size_t ns = set.size();
+    const double* h = G->hres.data() + 1;
+    size_t doff = 0;
+    for (size_t si = 0; si < ns; ++si) {
+        const int D = set[si]->D;
+        for (int64_t r = 0; r < R; ++r, h += 3 + D) {
+            ll[r * ns + si] = h[0];
+            lg[r * ns + si] = h[1];
+            index[r * ns + si] = (int64_t)h[2];
+            for (int d = 0; d < D; ++d) values[r * sumD + doff + d] = h[3 + d];
+        }
+        doff += D;
+    }
     return TPE_OK;
 }
 

@@ -407,6 +407,14 @@ class Engine(object):
         (posterior.joint_mixture): dims a JOINT_DIM_DTYPE array, weights [K],
         means and sigmas [K, D], component 0 the prior
         (tpe_joint_set_posterior)."""
+        args = self._joint_args(dims, wb, mub, sigb, wa, mua, siga)
+        rc = self.lib.tpe_joint_set_posterior(self.h, *args)
+        # (a box without below mass is set, and every draw reports it again)
+        self.joint_slots = {0: args[1]} if rc in (L.TPE_OK, L.TPE_ERR_SAMPLE) else {}
+        self._check(rc)
+
+    @staticmethod
+    def _joint_args(dims, wb, mub, sigb, wa, mua, siga):
         dims = np.ascontiguousarray(dims, dtype=JOINT_DIM_DTYPE)
         D = len(dims)
         arrs = []
@@ -416,51 +424,92 @@ class Engine(object):
                 raise ValueError('joint means and sigmas must be [components, dimensions]')
             arrs.append((w, m, s))
         (wb, mub, sigb), (wa, mua, siga) = arrs
-        rc = self.lib.tpe_joint_set_posterior(
-            self.h, _ptr(dims), D, len(wb), _ptr(wb), _ptr(mub), _ptr(sigb), len(wa), _ptr(wa),
-            _ptr(mua), _ptr(siga))
-        # (a box without below mass is set, and every draw reports it again)
-        self.joint_dims = D if rc in (L.TPE_OK, L.TPE_ERR_SAMPLE) else 0
+        # (data_as pointers hold their arrays)
+        return (_ptr(dims), D, len(wb), _ptr(wb), _ptr(mub), _ptr(sigb), len(wa), _ptr(wa), _ptr(mua),
+                _ptr(siga))
+
+    def set_joint_group(self, slot, pick_stream, dims, wb, mub, sigb, wa, mua, siga):
+        """set_joint_posterior for one of the context's L.TPE_JOINT_MAX_GROUPS
+        slots, the other slots left as they are; pick_stream: the Philox
+        stream of the slot's component pick (tpe_joint_set_group)."""
+        args = self._joint_args(dims, wb, mub, sigb, wa, mua, siga)
+        rc = self.lib.tpe_joint_set_group(self.h, int(slot), int(pick_stream) & 0xFFFFFFFF, *args)
+        slots = self.__dict__.setdefault('joint_slots', {})
+        if rc in (L.TPE_OK, L.TPE_ERR_SAMPLE):
+            slots[int(slot)] = args[1]
+        elif 0 <= int(slot) < L.TPE_JOINT_MAX_GROUPS:
+            slots.pop(int(slot), None)
         self._check(rc)
 
-    def _joint_dims(self):
-        D = getattr(self, 'joint_dims', 0)
+    def clear_joint_groups(self):
+        """Unset every joint slot (tpe_joint_clear_groups)."""
+        self.joint_slots = {}
+        self._check(self.lib.tpe_joint_clear_groups(self.h))
+
+    @property
+    def joint_dims(self):
+        return getattr(self, 'joint_slots', {}).get(0, 0)
+
+    def _joint_dims(self, slot=0):
+        D = getattr(self, 'joint_slots', {}).get(int(slot), 0)
         if not D:
-            raise EngineError('no joint posterior set (Engine.set_joint_posterior)')
+            raise EngineError('no joint posterior set in slot %d (Engine.set_joint_posterior / '
+                              'set_joint_group)' % int(slot))
         return D
 
-    def joint_draw(self, seed, n, round=0, cand_offset=0):
+    def joint_draw(self, seed, n, round=0, cand_offset=0, slot=0):
         """(values [n, D], component [n]) of candidates cand_offset ..
-        cand_offset + n - 1 of (seed, round) (tpe_joint_draw)."""
-        D = self._joint_dims()
+        cand_offset + n - 1 of (seed, round) (tpe_joint_draw_group)."""
+        D = self._joint_dims(slot)
         values = np.empty((int(n), D))
         comp = np.empty(int(n), dtype=np.int32)
-        self._check(self.lib.tpe_joint_draw(self.h, int(seed) & 0xFFFFFFFFFFFFFFFF, int(round) & 0xFFFFFFFF,
-                                            int(n), int(cand_offset), _ptr(values), _ptr(comp)))
+        self._check(self.lib.tpe_joint_draw_group(self.h, int(slot), int(seed) & 0xFFFFFFFFFFFFFFFF,
+                                                  int(round) & 0xFFFFFFFF, int(n), int(cand_offset),
+                                                  _ptr(values), _ptr(comp)))
         return values, comp
 
-    def joint_score(self, values):
+    def joint_score(self, values, slot=0):
         """(lpdf_below, lpdf_above) of configurations values [n, D]
-        (tpe_joint_score)."""
-        D = self._joint_dims()
+        (tpe_joint_score_group)."""
+        D = self._joint_dims(slot)
         values = _f64(values)
         if values.ndim != 2 or values.shape[1] != D:
             raise ValueError('values must be [n, %d]' % D)
         ll, lg = np.empty(len(values)), np.empty(len(values))
-        self._check(self.lib.tpe_joint_score(self.h, _ptr(values), len(values), _ptr(ll), _ptr(lg)))
+        self._check(self.lib.tpe_joint_score_group(self.h, int(slot), _ptr(values), len(values), _ptr(ll),
+                                                   _ptr(lg)))
         return ll, lg
 
-    def joint_suggest(self, seed, n_candidates, round=0):
+    def joint_suggest(self, seed, n_candidates, round=0, slot=0):
         """One fused joint round: (values [D], index, lpdf_below, lpdf_above)
-        of broadcast_best's winner among n_candidates (tpe_joint_suggest)."""
-        D = self._joint_dims()
+        of broadcast_best's winner among n_candidates (tpe_joint_suggest_group)."""
+        D = self._joint_dims(slot)
         values = np.empty(D)
         idx = ctypes.c_int64()
         ll, lg = ctypes.c_double(), ctypes.c_double()
-        self._check(self.lib.tpe_joint_suggest(self.h, int(seed) & 0xFFFFFFFFFFFFFFFF,
-                                               int(round) & 0xFFFFFFFF, int(n_candidates), _ptr(values),
-                                               ctypes.byref(idx), ctypes.byref(ll), ctypes.byref(lg)))
+        self._check(self.lib.tpe_joint_suggest_group(self.h, int(slot), int(seed) & 0xFFFFFFFFFFFFFFFF,
+                                                     int(round) & 0xFFFFFFFF, int(n_candidates), _ptr(values),
+                                                     ctypes.byref(idx), ctypes.byref(ll), ctypes.byref(lg)))
         return values, int(idx.value), ll.value, lg.value
+
+    def joint_suggest_batch(self, seed, rounds, n_candidates):
+        """joint_suggest for every set slot and every round of `rounds`, bit
+        for bit, in packed launches (tpe_joint_suggest_batch): {slot: (values
+        [R, D], index [R], lpdf_below [R], lpdf_above [R])}."""
+        slots = sorted(getattr(self, 'joint_slots', {}).items())
+        rounds = np.ascontiguousarray([int(r) & 0xFFFFFFFF for r in rounds], dtype=np.uint32)
+        R, ns, sumD = len(rounds), len(slots), sum(D for _, D in slots)
+        values = np.empty((R, max(sumD, 1)))
+        index = np.empty((R, max(ns, 1)), dtype=np.int64)
+        ll, lg = np.empty((R, max(ns, 1))), np.empty((R, max(ns, 1)))
+        self._check(self.lib.tpe_joint_suggest_batch(self.h, int(seed) & 0xFFFFFFFFFFFFFFFF, _ptr(rounds), R,
+                                                     int(n_candidates), _ptr(values), _ptr(index), _ptr(ll),
+                                                     _ptr(lg)))
+        out, at = {}, 0
+        for i, (slot, D) in enumerate(slots):
+            out[slot] = (values[:, at:at + D].copy(), index[:, i].copy(), ll[:, i].copy(), lg[:, i].copy())
+            at += D
+        return out
 
     def score(self, label, cand, want_lpdf=True):
         cand = _f64(cand).ravel()
@@ -546,7 +595,7 @@ class Engine(object):
                'aux_families': L.TPE_OPT_AUX_FAMILIES,
                'bx_split': L.TPE_OPT_BX_SPLIT, 'bx_t': L.TPE_OPT_BX_T,
                'pk_sliced': L.TPE_OPT_PK_SLICED, 'defer_report': L.TPE_OPT_DEFER_REPORT,
-               'label_shards': L.TPE_OPT_LABEL_SHARDS}
+               'label_shards': L.TPE_OPT_LABEL_SHARDS, 'joint_cap': L.TPE_OPT_JOINT_CAP}
 
     def set_option(self, name, value):
         """Engine switches (include/hyperopt_tpe.h TPE_OPT_*): 'screen',

@@ -187,6 +187,40 @@ def unconditional_labels(expr):
     return out
 
 
+UNCONDITIONAL = frozenset([frozenset()])
+
+
+def condition_signatures(expr):
+    """label -> condition signature: the frozenset of the path conditions the
+    label is reached under, a path condition being the frozenset of (switch,
+    option) pairs entered on the way from the root -- switch: the label of
+    the switch's index expression when that is a single hyperopt_param (an
+    hp.choice / pchoice), else the switch node's id; option: its position.  A
+    switch's index expression is visited under the current path (it is not an
+    option).  A label reached by the empty path takes part in every
+    evaluation and has the signature UNCONDITIONAL whatever its other paths
+    are: those labels are unconditional_labels(expr).  Labels with equal
+    signatures are active in exactly the same configurations."""
+    paths, seen, stack = {}, set(), [(as_apply(expr), frozenset())]
+    while stack:
+        n, path = stack.pop()
+        if (id(n), path) in seen:
+            continue
+        seen.add((id(n), path))
+        if n.name == 'hyperopt_param':
+            paths.setdefault(param_label(n), set()).add(path)
+            continue
+        if n.name == 'switch':
+            idx = n.pos_args[0]
+            name = param_label(idx) if idx.name == 'hyperopt_param' else id(n)
+            stack.append((idx, path))
+            for pos, opt in enumerate(n.pos_args[1:]):
+                stack.append((opt, path | frozenset([(name, pos)])))
+            continue
+        stack.extend((m, path) for m in inputs(n))
+    return {k: (UNCONDITIONAL if frozenset() in v else frozenset(v)) for k, v in paths.items()}
+
+
 def coerce(kind, v):
     """Python type of a hyperparameter value in trial docs."""
     if kind in ('randint', 'categorical'):

@@ -19,7 +19,9 @@
      and keeping the selected one is the same distribution).
 
 Extra keyword arguments (not in the reference): `multivariate` (True: the
-unconditional dense continuous labels are modelled jointly, see `suggest`),
+unconditional dense continuous labels are modelled jointly, see `suggest`;
+with `group=True` also those that share an hp.choice branch, one joint group
+per branch),
 `precision` ('f64'; 'f32'
 is accepted and runs the same exact path -- see `suggest`), `device` (HIP ordinal), `devices` (a list of ordinals: one
 multi-device context splits every round over those GPUs, same documents as
@@ -216,23 +218,81 @@ def joint_group(domain, specs, obs=None):
     return group
 
 
-def _joint_rounds(eng, domain, trials, specs, gathered, gamma, prior_weight, seed, ids, n_candidates):
-    """One joint round per id for the joint group: [label -> value] per id,
-    or None when the call falls back to the independent path.  The mixtures
-    are built on the host (posterior.joint_mixture); a label's Philox stream
-    is its position in the space, as in the independent round."""
+def joint_groups(domain, specs, obs=None):
+    """The joint groups of a space, [(slot, [labels])]: a structural group is
+    the labels of a dense continuous kind (posterior.JOINT_KINDS) that share
+    one condition signature (labels.condition_signatures: active in exactly
+    the same configurations), at least two of them, in the order of `specs`.
+    Slots number the structural groups -- the unconditional group first when
+    it qualifies, the others by their first label in `specs` -- and do not
+    depend on `obs`.  With obs (label -> (idxs, vals)) a group whose labels
+    are not observed in exactly the same trials is left out (logged): its
+    labels take the independent path and its slot stays unused."""
+    sigs = getattr(domain, '_hyperopt_amd_sigs', None)
+    if sigs is None:
+        sigs = _labels.condition_signatures(domain.expr)
+        try:
+            domain._hyperopt_amd_sigs = sigs
+        except AttributeError:
+            pass
+    by_sig = {}
+    for k, s in specs.items():
+        if s.kind in _post.JOINT_KINDS:
+            by_sig.setdefault(sigs[k], []).append(k)
+    groups = [g for sig, g in by_sig.items() if len(g) >= 2]
+    # (by_sig keeps the order of each signature's first label in specs)
+    groups.sort(key=lambda g: sigs[g[0]] != _labels.UNCONDITIONAL)
+    out = []
+    for slot, g in enumerate(groups):
+        if slot >= _engine.L.TPE_JOINT_MAX_GROUPS:
+            logger.info('multivariate TPE: %d groups beyond the %d joint slots use the independent path'
+                        % (len(groups) - slot, slot))
+            break
+        if obs is not None:
+            ids0 = np.asarray(obs[g[0]][0])
+            odd = [k for k in g[1:] if not np.array_equal(ids0, np.asarray(obs[k][0]))]
+            if odd:
+                logger.info('multivariate TPE: group %r: labels %r and %r are observed in different '
+                            'trials, using the independent path for it' % (g, g[0], odd[0]))
+                continue
+        out.append((slot, g))
+    return out
+
+
+def _joint_rounds(eng, domain, trials, specs, gathered, gamma, prior_weight, seed, ids, n_candidates,
+                  group=False):
+    """One joint round per id and joint group: [label -> value] per id, or
+    None when the call falls back to the independent path.  group=False: the
+    unconditional group alone (joint_group), slot 0; group=True: every group
+    of joint_groups in its slot, slot j's component pick on the Philox stream
+    TPE_JOINT_STREAM - j.  The mixtures are built on the host
+    (posterior.joint_mixture, each group from its own observations); a
+    label's Philox stream is its position in the space, as in the
+    independent round.  One set_joint_group per group, one
+    joint_suggest_batch for all groups and ids."""
     labels = list(specs)
     tids, losses, obs = gathered or _history.gather(domain, trials, labels)
-    group = joint_group(domain, specs, obs)
-    if group is None:
+    if group:
+        groups = joint_groups(domain, specs, obs)
+    else:
+        g = joint_group(domain, specs, obs)
+        groups = [(0, g)] if g is not None else []
+    if group and not groups:
+        logger.info('multivariate TPE: no joint group, using the independent path')
+    if not groups:
         return None
     splitter = _post.Splitter(tids, losses, gamma)
-    eng.set_joint_posterior(*_post.joint_mixture([specs[k] for k in group], obs, splitter, prior_weight,
-                                                 streams=[labels.index(k) for k in group]))
-    out = []
-    for new_id in ids:
-        values = eng.joint_suggest(seed, n_candidates, round=new_id)[0]
-        out.append({k: float(v) for k, v in zip(group, values)})
+    eng.clear_joint_groups()
+    for slot, g in groups:
+        eng.set_joint_group(slot, _engine.L.TPE_JOINT_STREAM - slot,
+                            *_post.joint_mixture([specs[k] for k in g], obs, splitter, prior_weight,
+                                                 streams=[labels.index(k) for k in g]))
+    won = eng.joint_suggest_batch(seed, ids, n_candidates)
+    out = [{} for _ in ids]
+    for slot, g in groups:
+        values = won[slot][0]
+        for j in range(len(ids)):
+            out[j].update({k: float(v) for k, v in zip(g, values[j])})
     return out
 
 
@@ -243,7 +303,7 @@ def suggest(new_ids, domain, trials, seed,
             gamma=_default_gamma,
             linear_forgetting=_default_linear_forgetting,
             precision='f64', device=0, batch=False, posterior_builder='auto', devices=None,
-            multivariate=False):
+            multivariate=False, group=False):
     """tpe.py:823-916.  Past the startup phase one document for new_ids[0],
     like the reference; `batch` (not in the reference) asks for one document
     per new_id:
@@ -272,6 +332,17 @@ def suggest(new_ids, domain, trials, seed,
     one when the group has fewer than two labels or its labels are not
     observed in the same trials; more than one device is not supported.
 
+    group=True (with multivariate=True) models the labels inside hp.choice
+    branches too: every set of at least two such labels that are active in
+    exactly the same configurations (joint_groups) is one joint group with
+    its own mixtures, built from the trials that entered its branch -- a
+    branch without a below trial has the prior alone as its below side, a
+    group never observed the prior on both sides (every score 0: candidate
+    0).  All groups and new ids run in one batched device call
+    (Engine.joint_suggest_batch); labels of an un-chosen branch are dropped
+    from the document as always.  A space whose only group is the
+    unconditional one gives the documents of group=False.
+
     precision='f32' runs the exact fp64 path: a round draws every candidate
     and proves all but ~0.5 % of them out of the race from per-sub-bin score
     bounds before any lpdf is summed, so scoring the rest in fp32 would save
@@ -285,12 +356,14 @@ def suggest(new_ids, domain, trials, seed,
         raise ValueError('posterior_builder must be auto, host or device')
     if batch not in (False, True, 'pending'):
         raise ValueError("batch must be False, True or 'pending'")
+    if group and not multivariate:
+        raise ValueError('group=True needs multivariate=True')
     if multivariate and devices and len(list(devices)) > 1:
         raise ValueError('multivariate=True runs on one device')
     kw = dict(prior_weight=prior_weight, n_startup_jobs=n_startup_jobs,
               n_EI_candidates=n_EI_candidates, gamma=gamma, linear_forgetting=linear_forgetting,
               precision=precision, device=device, posterior_builder=posterior_builder,
-              devices=devices, multivariate=multivariate)
+              devices=devices, multivariate=multivariate, group=group)
     specs = specs_of(domain)
     labels = list(specs)
     # the device-resident history's view of the trials (None when the fast
@@ -341,7 +414,7 @@ def suggest(new_ids, domain, trials, seed,
     if res is None:
         res = round_call()
     joint = _joint_rounds(eng, domain, trials, specs, gathered, gamma, prior_weight, seed, ids,
-                          n_EI_candidates) if multivariate else None
+                          n_EI_candidates, group=group) if multivariate else None
     rval = []
     for j, new_id in enumerate(ids):
         values = {s.label: _labels.coerce(s.kind, res[j][i]['value'])

@@ -420,6 +420,36 @@ int tpe_joint_score(tpe_ctx *ctx, const double *values, int64_t n, double *ll, d
 int tpe_joint_suggest(tpe_ctx *ctx, uint64_t seed, uint32_t round, int64_t n_candidates,
                       double *values, int64_t *index, double *ll, double *lg);
 
+/* Several joint groups at once: a context holds up to TPE_JOINT_MAX_GROUPS
+ * joint posteriors, one per slot, each with the Philox stream of its
+ * component pick (tpe.suggest(group=True) gives slot j TPE_JOINT_STREAM - j).
+ * tpe_joint_set_group is tpe_joint_set_posterior (same validation, same fold)
+ * for one slot and leaves the others; tpe_joint_set_posterior is slot 0 with
+ * TPE_JOINT_STREAM and clears every other slot.  The _group calls are the
+ * three calls above on a slot (those are slot 0); a slot outside [0,
+ * TPE_JOINT_MAX_GROUPS) or not set: TPE_ERR_ARG. */
+#define TPE_JOINT_MAX_GROUPS 64
+int tpe_joint_set_group(tpe_ctx *ctx, int32_t slot, uint32_t pick_stream, const tpe_joint_dim *dims,
+                        int32_t n_dims, int32_t n_below, const double *wb, const double *mub,
+                        const double *sigb, int32_t n_above, const double *wa, const double *mua,
+                        const double *siga);
+int tpe_joint_clear_groups(tpe_ctx *ctx);
+int tpe_joint_draw_group(tpe_ctx *ctx, int32_t slot, uint64_t seed, uint32_t round, int64_t n,
+                         int64_t cand_offset, double *values, int32_t *comp);
+int tpe_joint_score_group(tpe_ctx *ctx, int32_t slot, const double *values, int64_t n, double *ll,
+                          double *lg);
+int tpe_joint_suggest_group(tpe_ctx *ctx, int32_t slot, uint64_t seed, uint32_t round,
+                            int64_t n_candidates, double *values, int64_t *index, double *ll, double *lg);
+/* tpe_joint_suggest_group for every set slot (ascending) and every round
+ * rounds[r], bit for bit, in packed launches: the lanes run over the flat
+ * index of (round, candidate), so the launches, copies and the one stream
+ * synchronisation of a call do not grow with n_rounds.  values[n_rounds][sum
+ * of D over the set slots] (the slots' values concatenated per round); index,
+ * ll, lg [n_rounds][number of set slots].  TPE_ERR_ARG when no slot is set,
+ * TPE_ERR_SAMPLE as tpe_joint_suggest. */
+int tpe_joint_suggest_batch(tpe_ctx *ctx, uint64_t seed, const uint32_t *rounds, int32_t n_rounds,
+                            int64_t n_candidates, double *values, int64_t *index, double *ll, double *lg);
+
 /* Score a caller-supplied candidate set for one resident label (the parity
  * entry point: identical candidates in, both lpdf vectors and the winner
  * out).  lpdf_below / lpdf_above may be NULL. */
@@ -605,6 +635,10 @@ int tpe_screen_probe(tpe_ctx *ctx, int32_t label, const double *cand, int64_t n,
  *                   from the next tpe_history_reset with at least one label
  *                   per device; 0: every device holds every label and the
  *                   rounds split by candidates / rounds                  [1]
+ *   TPE_OPT_JOINT_CAP  flat candidates (rounds x candidates) of one packed
+ *                   launch of tpe_joint_suggest_batch; the rounds run in
+ *                   chunks within it (same rows; tests; 0: the default,
+ *                   at most 2^30)                                      [2^20]
  *   TPE_OPT_WIN_GROUPS  label groups of a windowed round, each sorted on a
  *                   second stream while the previous one is screened
  *                   (0: one group; the chip is busy either way)          [0]
@@ -643,6 +677,7 @@ int tpe_screen_probe(tpe_ctx *ctx, int32_t label, const double *cand, int64_t n,
 #define TPE_OPT_PK_SLICED 23
 #define TPE_OPT_DEFER_REPORT 24
 #define TPE_OPT_LABEL_SHARDS 25
+#define TPE_OPT_JOINT_CAP 26
 int tpe_set_option(tpe_ctx *ctx, int32_t option, int64_t value);
 
 /* Build now what the resident posterior's first round(s) of n_candidates

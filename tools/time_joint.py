@@ -1,6 +1,7 @@
 """Timings and a quality record of multivariate (joint) TPE (needs the GPU).
 
     python tools/time_joint.py [--dims 32] [--trials 10000] [--reps 20] [--quality] [--out FILE]
+    python tools/time_joint.py --groups [--legs loop,batch] [--reps 20] [--out FILE]
 
 On a synthetic history of `--trials` trials over `--dims` dense continuous
 labels (kinds cycled over uniform / loguniform / normal / lognormal):
@@ -19,6 +20,10 @@ labels (kinds cycled over uniform / loguniform / normal / lognormal):
 --quality: fmin for 100 evaluations over seeds 0..9 on the coupled objective
 (x - y)^2 + 0.01 (x + y)^2 over uniform(-5, 5)^2, with and without
 multivariate=True; the medians of the best losses.  A record, not a gate.
+
+--groups: several joint groups and new ids per call (groups_timings): the
+loop over single-posterior calls against set_joint_group +
+joint_suggest_batch, 24 candidates, 1 / 24 / 4096 ids.
 
 Prints one JSON document (and writes it to --out).
 """
@@ -126,6 +131,79 @@ def timings(n_dims, n_trials, reps):
     return res
 
 
+def group_shapes():
+    """name -> list of joint mixtures, one per group: `c4`, the two D = 2
+    groups inside the branches of config 4 (workloads.conditional_history(5000):
+    svm_C with svm_gamma, gbm_lr with gbm_subsample); `d32`, one group of 32
+    dimensions over 10000 trials."""
+    from hyperopt_amd import posterior as P, workloads
+    hist = workloads.conditional_history(5000)
+    by = {n: (n, k, a) for n, k, a in hist.labels}
+    names = [n for n, _, _ in hist.labels]
+    splitter = P.Splitter(hist.tids, hist.losses, 0.25)
+    c4 = [P.joint_mixture([by[k] for k in g], hist.obs, splitter, 1.0, streams=[names.index(k) for k in g])
+          for g in (('svm_C', 'svm_gamma'), ('gbm_lr', 'gbm_subsample'))]
+    group, tids, losses, obs = history(32, 10000)
+    d32 = [P.joint_mixture(group, obs, P.Splitter(tids, losses, 0.25), 1.0)]
+    return {'c4': c4, 'd32': d32}
+
+
+def groups_timings(reps, legs=('loop', 'batch'), rounds=(1, 24, 4096), n=24):
+    """Per shape and number of new ids, medians over `reps` calls of the wall
+    time of a whole call (uploads and folds included) and of the device time
+    of its rounds between HIP events:
+
+    * loop: per group one set_joint_posterior, then one joint_suggest per id
+      -- entry points a context with a single joint posterior has, so this
+      leg runs unchanged on an older checkout (the baseline);
+    * batch: set_joint_group once per group and one joint_suggest_batch."""
+    from hyperopt_amd import _lib as L
+    from hyperopt_amd.engine import Engine
+    eng = Engine(0, 'f64')
+    out = {}
+    for name, mixes in sorted(group_shapes().items()):
+        terms = sum((len(m[1]) + len(m[4])) * len(m[0]) for m in mixes)
+        res = out[name] = dict(groups=len(mixes), dims=[len(m[0]) for m in mixes],
+                               k_below=[len(m[1]) for m in mixes], k_above=[len(m[4]) for m in mixes])
+        for R in rounds:
+            ids = list(range(1000, 1000 + R))
+
+            def loop():
+                dev = 0.0
+                for m in mixes:
+                    eng.set_joint_posterior(*m)
+                    for i in ids:
+                        eng.joint_suggest(1, n, round=i)
+                        dev += eng.last_timing()[1]
+                return dev
+
+            def batch():
+                eng.clear_joint_groups()
+                for j, m in enumerate(mixes):
+                    eng.set_joint_group(j, L.TPE_JOINT_STREAM - j, *m)
+                eng.joint_suggest_batch(1, ids, n)
+                return eng.last_timing()[1]
+
+            for leg, fn in (('loop', loop), ('batch', batch)):
+                if leg not in legs or (leg == 'batch' and not hasattr(eng, 'joint_suggest_batch')):
+                    continue
+                fn()
+                dev, wall = [], []
+                for _ in range(reps):
+                    t = time.perf_counter()
+                    dev.append(fn())
+                    wall.append((time.perf_counter() - t) * 1e3)
+                rec = dict(device_ms=float(np.median(dev)), wall_ms=float(np.median(wall)),
+                           wall_min_ms=float(np.min(wall)), wall_max_ms=float(np.max(wall)))
+                rate = 4.0 * n * R * terms / (rec['device_ms'] * 1e-3)
+                rec.update(fp64_flops=rate, fraction_of_fp64_vector_peak=rate / FP64_VECTOR_PEAK)
+                res['%s_%d' % (leg, R)] = rec
+            if 'loop_%d' % R in res and 'batch_%d' % R in res:
+                res['loop_over_batch_wall_%d' % R] = res['loop_%d' % R]['wall_ms'] / res['batch_%d' % R]['wall_ms']
+    eng.close()
+    return out
+
+
 def quality(evals=100, seeds=10):
     import hyperopt_amd as H
     from hyperopt_amd import hp, tpe
@@ -154,10 +232,14 @@ def main(argv):
     ap.add_argument('--reps', type=int, default=20)
     ap.add_argument('--quality', action='store_true')
     ap.add_argument('--no-timings', action='store_true')
+    ap.add_argument('--groups', action='store_true', help='the loop and batch legs over several groups and ids')
+    ap.add_argument('--legs', default='loop,batch')
     ap.add_argument('--out')
     a = ap.parse_args(argv)
     res = {}
-    if not a.no_timings:
+    if a.groups:
+        res['groups'] = groups_timings(a.reps, legs=tuple(a.legs.split(',')))
+    elif not a.no_timings:
         res['timings'] = timings(a.dims, a.trials, a.reps)
     if a.quality:
         res['quality'] = quality()
