@@ -40,8 +40,28 @@
 // dimension).  Records are wave-uniform; each lane holds one candidate, its
 // y' in registers up to kJReg dimensions, beyond in LDS (dimension-major:
 // consecutive lanes read consecutive words).
+//
+// Quantized dimensions (tpe_joint_set_group_q, q_d > 0): the mixtures, m_kd,
+// A_S, the pick and the draw of y are the dense group's; the drawn value is
+// x_d = rint(v / q_d) q_d (v = exp(y) for a log kind), and the factor of the
+// dimension is the component's mass on the value's interval,
+//   g_kd(x_d) = Phi((ub - mu_kd)/s_kd) - Phi((lb - mu_kd)/s_kd),   0 when ub <= lb,
+// (ub, lb) = quant_bounds(x_d) in the working space (tpe_device.h).  No
+// Jacobian term for a quantized log kind:
+//   f_S(x) = (1/A_S) sum_k W_k prod_d g_kd(x_d)   (g = phi for dense d)
+//   lpdf_S = log f_S(x) - sum_{d dense log kind} y_d
+// Its record is (m' = (mu - centre_d) a, a = 1/(s sqrt 2)): z = bound' a - m',
+// one FMA per interval end, and its -log(s sqrt(2 pi)) stays out of c_k.
+// Accepted groups: S = D + (quantized dimensions) <= 128 values per candidate.
+// A group with a quantized dimension runs k_joint_round<0, true, SAMPLE, true>:
+// one wave per workgroup, the S values in LDS (512 S bytes; the exp table is
+// read from memory) -- no register variant: the loop is bound by the VALU work
+// of the two erfc-class evaluations per (candidate, component, quantized
+// dimension), ~100 times the two LDS reads they share among kJU components.
+// Dense-only groups launch the instantiations they always did.
 #include "tpe_ctx.h"
 
+#include <cmath>
 #include <cstring>
 
 namespace {
@@ -61,7 +81,10 @@ constexpr double kInf = __builtin_inf();
 
 struct JDim {
     double low, high, centre;
-    int32_t flags, stream, log, pad;
+    double q;          // the step of a quantized dimension, 0: dense
+    double elo, ehi;   // exp(low), exp(high) of a bounded quantized log kind
+    int32_t flags, stream, log;
+    int32_t slot;      // quantized groups: the dimension's first per-candidate value
 };
 
 struct JDraw {   // one-component sampling terms of (k, d) (SampRec's)
@@ -102,9 +125,14 @@ __global__ __launch_bounds__(kJBlock) void k_joint_fold(
         const JDim j = dims[d];
         const size_t o = (size_t)k * D + d;
         const double s = sig[o], m = mu[o];
-        const double a = sqrt(0.5 * kExpScale) / s;
-        rec[o] = make_double2((m - j.centre) * a, a);
-        sl += log(s * 2.50662827463100050242);
+        if (j.q > 0.0) {   // z = (bound - mu) / (s sqrt 2); its factor is a mass: no density constant
+            const double a = 0.70710678118654752440 / s;
+            rec[o] = make_double2((m - j.centre) * a, a);
+        } else {
+            const double a = sqrt(0.5 * kExpScale) / s;
+            rec[o] = make_double2((m - j.centre) * a, a);
+            sl += log(s * 2.50662827463100050242);
+        }
         SampRec r{};
         r.mu = m;
         r.sigma = s;
@@ -165,7 +193,8 @@ __device__ __forceinline__ int jpick(const JP& p, uint32_t k0, uint32_t k1, uint
 }
 
 // dimension d of candidate g from component k: the label's value (after the
-// exp of a log kind)
+// exp of a log kind; Q: and the rounding to the grid of a quantized dimension)
+template <bool Q>
 __device__ __forceinline__ double jdraw(const JP& p, const JDim& j, int d, int k, uint32_t k0, uint32_t k1,
                                         uint32_t g, uint32_t round) {
     const DLabel L = jlabel(j);
@@ -182,7 +211,10 @@ __device__ __forceinline__ double jdraw(const JP& p, const JDim& j, int d, int k
     c.tlo = 0;
     c.thi = 1ull << 32;
     const double y = icdf_draw(L, c, wp, wu);
-    return j.log ? lgmm_value(y) : y;
+    const double v = j.log ? lgmm_value(y) : y;
+    if constexpr (Q)
+        if (j.q > 0.0) return quantize(v, j.q);
+    return v;
 }
 
 __global__ __launch_bounds__(kJBlock) void k_joint_draw(JP p, int64_t n, int64_t cand_offset, uint64_t seed,
@@ -195,7 +227,7 @@ __global__ __launch_bounds__(kJBlock) void k_joint_draw(JP p, int64_t n, int64_t
     comp[i] = k;
     bool bad = false;
     for (int d = 0; d < p.D; ++d) {
-        const double x = jdraw(p, p.dims[d], d, k, k0, k1, g, round);
+        const double x = jdraw<true>(p, p.dims[d], d, k, k0, k1, g, round);
         bad |= x != x;
         values[(size_t)i * p.D + d] = x;
     }
@@ -254,6 +286,86 @@ __device__ __forceinline__ void slice_ms(const double2* __restrict__ rec, const 
 #pragma unroll
         for (int j = 0; j < kJU; ++j) {
             e[j] = (k + j < k1) ? cst[min(k + j, k1 - 1)] - acc[j] : -kInf;
+            gm = fmax(gm, e[j]);
+        }
+        const double M = fmax(m, gm);
+        if (M > -kInf) {
+            double t = (m > -kInf) ? s * jexp<TABC>(m - M, tab) : 0.0;
+#pragma unroll
+            for (int j = 0; j < kJU; ++j)
+                if (e[j] > -kInf) t += jexp<TABC>(e[j] - M, tab);
+            s = t;
+            m = M;
+        }
+    }
+}
+
+// Phi(zu sqrt 2) - Phi(zl sqrt 2), the normal mass of a quantized value's
+// interval, from the side it lies on: two upper (or, mirrored, lower) tails
+// when both ends are on one side of the mean, two positive erf terms when it
+// straddles the mean -- never a difference of values near 1/2 or 1.  An empty
+// interval has mass 0 (a NaN end too: the candidate's ylog carries the NaN).
+__device__ __forceinline__ double jmass(double zl, double zu) {
+#pragma clang fp contract(off)
+    if (!(zu > zl)) return 0.0;
+    if (zl >= 0.0 || zu <= 0.0) {
+        const double a = zl >= 0.0 ? zl : -zu, b = zl >= 0.0 ? zu : -zl;
+        return 0.5 * (erfc(a) - erfc(b));
+    }
+    return 0.5 * (erf(zu) + erf(-zl));
+}
+
+// slice_ms of a group with quantized dimensions; the per-candidate values are
+// in LDS at yl[slot * kJLdsLanes]: y' of a dense dimension in its slot, the
+// interval ends (ub', lb') of a quantized one in its slot and the next.  The
+// quantized factors of a component multiply into a mantissa in [1/2, 1) and an
+// integer exponent (60 fine-grid factors are below 1e-320 together); one log
+// per component folds them into E_k.  A zero factor: E_k = -inf.
+template <bool TABC>
+__device__ __forceinline__ void slice_ms_q(const JDim* __restrict__ dims, const double2* __restrict__ rec,
+                                           const double* __restrict__ cst, int D, int k0, int k1, const double* yl,
+                                           const double* __restrict__ tab, double& m, double& s) {
+#pragma clang fp contract(off)
+    m = -kInf;
+    s = 0.0;
+    for (int k = k0; k < k1; k += kJU) {
+        const double2* r[kJU];
+        double acc[kJU], mant[kJU];
+        int ex[kJU];
+#pragma unroll
+        for (int j = 0; j < kJU; ++j) {
+            r[j] = rec + (size_t)min(k + j, k1 - 1) * D;
+            acc[j] = 0.0;
+            mant[j] = 1.0;
+            ex[j] = 0;
+        }
+        for (int d = 0; d < D; ++d) {
+            const int sl = dims[d].slot;
+            if (dims[d].q > 0.0) {
+                const double u = yl[sl * kJLdsLanes], l = yl[(sl + 1) * kJLdsLanes];
+#pragma unroll
+                for (int j = 0; j < kJU; ++j) {
+                    const double2 q = r[j][d];
+                    const double g = jmass(fma(l, q.y, -q.x), fma(u, q.y, -q.x));
+                    int e;
+                    mant[j] = frexp(mant[j] * g, &e);
+                    ex[j] += e;
+                }
+            } else {
+                const double y = yl[sl * kJLdsLanes];
+#pragma unroll
+                for (int j = 0; j < kJU; ++j) {
+                    const double2 q = r[j][d];
+                    const double z = fma(y, q.y, -q.x);
+                    acc[j] = fma(z, z, acc[j]);
+                }
+            }
+        }
+        double e[kJU], gm = -kInf;
+#pragma unroll
+        for (int j = 0; j < kJU; ++j) {
+            const double lq = (log(mant[j]) + (double)ex[j] * 0.69314718055994530942) * kExpScale;
+            e[j] = (k + j < k1) ? (cst[min(k + j, k1 - 1)] - acc[j]) + lq : -kInf;
             gm = fmax(gm, e[j]);
         }
         const double M = fmax(m, gm);
@@ -336,11 +448,13 @@ __device__ __forceinline__ void jblock_best(uint64_t key, int64_t idx, double ll
 // is the flat index over rounds of ncell candidates each -- candidate i %
 // ncell of round rounds[i / ncell]; every candidate's lpdfs are stored, and
 // without `partials` no workgroup best is formed.
-template <int DR, bool TABC, bool SAMPLE>
+// Q: a group with quantized dimensions -- the LDS layout of slice_ms_q (DR = 0).
+template <int DR, bool TABC, bool SAMPLE, bool Q = false>
 __global__ __launch_bounds__(DR > 0 ? kJBlock : kJLdsLanes) void k_joint_round(
     JP p, const double2* __restrict__ rec, const double* __restrict__ cst, const double* __restrict__ vals, int64_t n, int64_t cand_offset, uint64_t seed, uint32_t round,
     const uint32_t* __restrict__ rounds, uint32_t ncell, int32_t split, double2* __restrict__ part, double* __restrict__ aux, double* __restrict__ out_ll,
     double* __restrict__ out_lg, Partial* __restrict__ partials, int32_t* __restrict__ err) {
+    static_assert(!Q || DR == 0, "quantized groups keep their values in LDS");
     extern __shared__ double jsm[];
     const double* tab = jsm;
     if constexpr (!TABC) load_exp_table(jsm);
@@ -368,7 +482,7 @@ __global__ __launch_bounds__(DR > 0 ? kJBlock : kJLdsLanes) void k_joint_round(
         if (valid) {
             double x;
             if constexpr (SAMPLE) {
-                x = jdraw(p, j, d, kc, k0, k1, g, round);
+                x = jdraw<false>(p, j, d, kc, k0, k1, g, round);
                 if (x != x) atomicOr(err, 1);
             } else {
                 x = vals[(size_t)i * D + d];
@@ -379,7 +493,42 @@ __global__ __launch_bounds__(DR > 0 ? kJBlock : kJLdsLanes) void k_joint_round(
         }
         return y - j.centre;
     };
-    if constexpr (DR > 0) {
+    if constexpr (Q) {
+        // a quantized dimension: the ends of the value's interval in the
+        // working space (quant_bounds: the log of a log kind taken here, once
+        // per candidate), recentred like y'; no Jacobian term
+        for (int d = 0; d < D; ++d) {
+            const JDim j = p.dims[d];
+            if (!(j.q > 0.0)) {
+                yl[j.slot * kJLdsLanes] = load(d);
+                continue;
+            }
+            double ub = j.centre, lb = j.centre;
+            if (valid) {
+                double x;
+                if constexpr (SAMPLE) {
+                    x = jdraw<true>(p, j, d, kc, k0, k1, g, round);
+                    if (x != x) atomicOr(err, 1);
+                } else {
+                    x = vals[(size_t)i * D + d];
+                }
+                DLabel L{};
+                L.flags = j.flags;
+                L.q = j.q;
+                L.low = j.low;
+                L.high = j.high;
+                L.exp_low = j.elo;
+                L.exp_high = j.ehi;
+                bool neg;
+                if (j.log) quant_bounds<QUANT_LGMM>(L, x, ub, lb, neg);
+                else quant_bounds<QUANT_GMM>(L, x, ub, lb, neg);
+                bad |= x != x;
+            }
+            yl[j.slot * kJLdsLanes] = ub - j.centre;
+            yl[(j.slot + 1) * kJLdsLanes] = lb - j.centre;
+        }
+        yr[0] = 0.0;
+    } else if constexpr (DR > 0) {
         // (the draw stays a loop: placed by selects, one copy of its code)
 #pragma unroll
         for (int e = 0; e < DR; ++e) yr[e] = 0.0;
@@ -400,7 +549,8 @@ __global__ __launch_bounds__(DR > 0 ? kJBlock : kJLdsLanes) void k_joint_round(
         const int K = above ? p.Ka : p.Kb, base = above ? p.Kb : 0, q = above ? sl - nsb : sl;
         const int a0 = q * kJSlice, a1 = min(a0 + kJSlice, K);
         double m, s;
-        slice_ms<DR, TABC>(rec, cst, D, base + a0, base + a1, yr, yl, tab, m, s);
+        if constexpr (Q) slice_ms_q<TABC>(p.dims, rec, cst, D, base + a0, base + a1, yl, tab, m, s);
+        else slice_ms<DR, TABC>(rec, cst, D, base + a0, base + a1, yr, yl, tab, m, s);
         if (valid) {
             part[(size_t)sl * n + i] = make_double2(m, s);
             if (sl == 0) aux[i] = ylog;
@@ -414,7 +564,10 @@ __global__ __launch_bounds__(DR > 0 ? kJBlock : kJLdsLanes) void k_joint_round(
         double m = -kInf, s = 0.0;
         for (int a0 = 0; a0 < K; a0 += kJSlice) {
             double m2, s2;
-            slice_ms<DR, TABC>(rec, cst, D, base + a0, base + min(a0 + kJSlice, K), yr, yl, tab, m2, s2);
+            if constexpr (Q)
+                slice_ms_q<TABC>(p.dims, rec, cst, D, base + a0, base + min(a0 + kJSlice, K), yl, tab, m2, s2);
+            else
+                slice_ms<DR, TABC>(rec, cst, D, base + a0, base + min(a0 + kJSlice, K), yr, yl, tab, m2, s2);
             ms_merge<TABC>(m, s, m2, s2, tab);
         }
         lp[side] = jfinish(m, s, p.logA[side], ylog);
@@ -489,7 +642,7 @@ __global__ __launch_bounds__(kJBlock) void k_joint_best(JP p, const Partial* __r
     if (!sample || w.idx == INT64_MAX) return;
     const uint32_t k0 = (uint32_t)seed, k1 = (uint32_t)(seed >> 32), g = (uint32_t)(cand_offset + w.idx);
     const int kc = jpick(p, k0, k1, g, round);
-    for (int d = threadIdx.x; d < p.D; d += kJBlock) res[3 + d] = jdraw(p, p.dims[d], d, kc, k0, k1, g, round);
+    for (int d = threadIdx.x; d < p.D; d += kJBlock) res[3 + d] = jdraw<true>(p, p.dims[d], d, kc, k0, k1, g, round);
 }
 
 // packed rounds: workgroup b reduces the ncell (ll, lg) pairs of round slot b
@@ -527,7 +680,7 @@ __global__ __launch_bounds__(kJBlock) void k_joint_best_cells(JP p, const double
     if (w.idx == INT64_MAX) return;
     const uint32_t k0 = (uint32_t)seed, k1 = (uint32_t)(seed >> 32), g = (uint32_t)w.idx, round = rounds[blockIdx.x];
     const int kc = jpick(p, k0, k1, g, round);
-    for (int d = threadIdx.x; d < p.D; d += kJBlock) row[3 + d] = jdraw(p, p.dims[d], d, kc, k0, k1, g, round);
+    for (int d = threadIdx.x; d < p.D; d += kJBlock) row[3 + d] = jdraw<true>(p, p.dims[d], d, kc, k0, k1, g, round);
 }
 
 // ------------------------------------------------------------- host side ----
@@ -536,6 +689,8 @@ using DevBuf = tpe_rt::DevBuf<T>;
 
 struct JointState {   // one slot's folded posterior
     int32_t D = 0, Kb = 0, Ka = 0;
+    int32_t S = 0;        // per-candidate values: D + the number of quantized dimensions
+    bool quant = false;   // a quantized dimension: the Q instantiations of k_joint_round
     uint32_t stream = TPE_JOINT_STREAM;
     bool ready = false, zero = false;
     DevBuf<JDim> dims;
@@ -590,14 +745,19 @@ int launch_round(tpe_ctx* ctx, JointGroups* G, JointState* J, bool sample, int64
                  uint64_t seed, uint32_t round, bool lpdfs, int32_t* nparts, int32_t* err,
                  const uint32_t* rounds = nullptr, uint32_t ncell = 0) {
     const int D = J->D;
-    const int dr = D <= kJRegSmall ? kJRegSmall : (D <= kJReg ? kJReg : 0);
-    const bool tabc = dr == 0 && D > kJLdsTabD;
+    const int S = J->quant ? J->S : D;   // values a lane keeps in LDS (dr == 0)
+    const int dr = J->quant ? 0 : (D <= kJRegSmall ? kJRegSmall : (D <= kJReg ? kJReg : 0));
+    // (a quantized group reads the exp table from memory whatever its size: one
+    // exp per component against two erfc-class evaluations per quantized
+    // dimension, and a table per one-wave workgroup would leave the CU two waves)
+    const bool tabc = dr == 0 && (J->quant || S > kJLdsTabD);
     const int threads = dr ? kJBlock : kJLdsLanes;
     const int64_t tiles = (n + threads - 1) / threads;
     const int64_t nsl = (J->Kb + kJSlice - 1) / kJSlice + (J->Ka + kJSlice - 1) / kJSlice;
     const bool split = tiles < kJSplitTiles && nsl > 2 && (size_t)nsl * n * sizeof(double2) <= kJPartBytes &&
                        nsl <= 65535;
-    const size_t lds = (tabc ? 0 : kExpTabSize * sizeof(double)) + (dr ? 0 : (size_t)D * kJLdsLanes * sizeof(double));
+    size_t lds = (tabc ? 0 : kExpTabSize * sizeof(double)) + (dr ? 0 : (size_t)S * kJLdsLanes * sizeof(double));
+    if (J->quant) lds = std::max(lds, 4 * kJLdsLanes * sizeof(double));   // (jblock_best's scratch)
     const int64_t mtiles = (n + kJBlock - 1) / kJBlock;
     *nparts = (int32_t)(split ? mtiles : tiles);
     if (!rounds) HIPCHK(ctx, G->partials.reserve(*nparts));
@@ -614,20 +774,21 @@ int launch_round(tpe_ctx* ctx, JointGroups* G, JointState* J, bool sample, int64
     double* olg = lpdfs ? G->lg.p : nullptr;
     Partial* parts = rounds ? nullptr : G->partials.p;
     const JP p = J->jp();
-#define JLAUNCH(DR, TABC)                                                                                       \
+#define JLAUNCH(DR, TABC, ...)                                                                                  \
     do {                                                                                                        \
         if (sample)                                                                                             \
-            hipLaunchKernelGGL((k_joint_round<DR, TABC, true>), grid, dim3(threads), lds, ctx->stream, p,       \
+            hipLaunchKernelGGL((k_joint_round<DR, TABC, true __VA_ARGS__>), grid, dim3(threads), lds, ctx->stream, p, \
                                J->rec.p, J->cst.p, nullptr, n, cand_offset, seed, round, rounds, ncell,         \
                                (int32_t)split, G->part.p, G->aux.p, split ? nullptr : oll,                      \
                                split ? nullptr : olg, parts, err);                                              \
         else                                                                                                    \
-            hipLaunchKernelGGL((k_joint_round<DR, TABC, false>), grid, dim3(threads), lds, ctx->stream, p,      \
+            hipLaunchKernelGGL((k_joint_round<DR, TABC, false __VA_ARGS__>), grid, dim3(threads), lds, ctx->stream, p, \
                                J->rec.p, J->cst.p, G->vals.p, n, cand_offset, seed, round, rounds, ncell,       \
                                (int32_t)split, G->part.p, G->aux.p, split ? nullptr : oll,                      \
                                split ? nullptr : olg, parts, err);                                              \
     } while (0)
-    if (dr == kJRegSmall) JLAUNCH(kJRegSmall, false);
+    if (J->quant) JLAUNCH(0, true, , true);
+    else if (dr == kJRegSmall) JLAUNCH(kJRegSmall, false);
     else if (dr == kJReg) JLAUNCH(kJReg, false);
     else if (!tabc) JLAUNCH(0, false);
     else JLAUNCH(0, true);
@@ -679,7 +840,7 @@ int read_err(tpe_ctx* ctx, JointGroups* G) {
 // upload and fold one slot's posterior; `only`: the other slots are cleared
 // once the arguments are accepted (tpe_joint_set_posterior)
 int joint_set(tpe_ctx* ctx, int32_t slot, uint32_t pick_stream, bool only, const tpe_joint_dim* dims,
-              int32_t n_dims, int32_t n_below, const double* wb, const double* mub, const double* sigb,
+              const double* q, int32_t n_dims, int32_t n_below, const double* wb, const double* mub, const double* sigb,
               int32_t n_above, const double* wa, const double* mua, const double* siga) {
     if (!ctx) return TPE_ERR_ARG;
     if (slot < 0 || slot >= kJMaxGroups)
@@ -693,13 +854,28 @@ int joint_set(tpe_ctx* ctx, int32_t slot, uint32_t pick_stream, bool only, const
     TPE_NOT_LSHARD(ctx);
     const int D = n_dims, Kb = n_below, Ka = n_above, K = Kb + Ka;
     std::vector<JDim> hd(D);
+    int S = 0;
     for (int d = 0; d < D; ++d) {
+        const double qd = q ? q[d] : 0.0;
+        if (!(qd >= 0.0 && qd < __builtin_inf()))
+            return ctx->fail(TPE_ERR_ARG, "a quantization step is finite and not negative (0: dense)");
+        S += qd > 0.0 ? 2 : 1;
+    }
+    if (S > kJMaxD)
+        return ctx->fail(TPE_ERR_ARG, "a joint group holds at most " + std::to_string(kJMaxD) +
+                                          " per-candidate values: dimensions plus quantized dimensions");
+    const bool quant = S > D;
+    for (int d = 0, slot = 0; d < D; ++d) {
         const tpe_joint_dim& s = dims[d];
         if (s.kind != TPE_GMM1 && s.kind != TPE_LGMM1)
             return ctx->fail(TPE_ERR_ARG, "a joint dimension is TPE_GMM1 or TPE_LGMM1");
         if (s.flags & ~(TPE_HAS_LOW | TPE_HAS_HIGH)) return ctx->fail(TPE_ERR_ARG, "joint dimensions are not quantized");
         if ((s.flags & 3) == 3 && !(s.low < s.high)) return ctx->fail(TPE_ERR_VALUE, "low >= high");
-        hd[d] = JDim{s.low, s.high, mub[d], s.flags, s.stream, s.kind == TPE_LGMM1 ? 1 : 0, 0};
+        const double qd = q ? q[d] : 0.0;
+        const bool lg = s.kind == TPE_LGMM1;
+        hd[d] = JDim{s.low, s.high, mub[d], qd, lg ? std::exp(s.low) : 0.0, lg ? std::exp(s.high) : 0.0,
+                     s.flags, s.stream, lg ? 1 : 0, quant ? slot : d};
+        slot += qd > 0.0 ? 2 : 1;
     }
     for (int side = 0; side < 2; ++side) {
         const double *w = side ? wa : wb, *sg = side ? siga : sigb;
@@ -748,6 +924,8 @@ int joint_set(tpe_ctx* ctx, int32_t slot, uint32_t pick_stream, bool only, const
     HIPCHK(ctx, hipMemcpyAsync(&e, G->err.p, sizeof(int32_t), hipMemcpyDeviceToHost, st));
     HIPCHK(ctx, hipStreamSynchronize(st));
     J->D = D;
+    J->S = S;
+    J->quant = quant;
     J->Kb = Kb;
     J->Ka = Ka;
     J->stream = pick_stream;
@@ -763,13 +941,21 @@ extern "C" {
 int tpe_joint_set_posterior(tpe_ctx* ctx, const tpe_joint_dim* dims, int32_t n_dims, int32_t n_below,
                             const double* wb, const double* mub, const double* sigb, int32_t n_above,
                             const double* wa, const double* mua, const double* siga) {
-    return joint_set(ctx, 0, TPE_JOINT_STREAM, true, dims, n_dims, n_below, wb, mub, sigb, n_above, wa, mua, siga);
+    return joint_set(ctx, 0, TPE_JOINT_STREAM, true, dims, nullptr, n_dims, n_below, wb, mub, sigb, n_above, wa, mua, siga);
 }
 
 int tpe_joint_set_group(tpe_ctx* ctx, int32_t slot, uint32_t pick_stream, const tpe_joint_dim* dims, int32_t n_dims,
                         int32_t n_below, const double* wb, const double* mub, const double* sigb, int32_t n_above,
                         const double* wa, const double* mua, const double* siga) {
-    return joint_set(ctx, slot, pick_stream, false, dims, n_dims, n_below, wb, mub, sigb, n_above, wa, mua, siga);
+    return joint_set(ctx, slot, pick_stream, false, dims, nullptr, n_dims, n_below, wb, mub, sigb, n_above, wa, mua,
+                     siga);
+}
+
+int tpe_joint_set_group_q(tpe_ctx* ctx, int32_t slot, uint32_t pick_stream, const tpe_joint_dim* dims,
+                          const double* q, int32_t n_dims, int32_t n_below, const double* wb, const double* mub,
+                          const double* sigb, int32_t n_above, const double* wa, const double* mua,
+                          const double* siga) {
+    return joint_set(ctx, slot, pick_stream, false, dims, q, n_dims, n_below, wb, mub, sigb, n_above, wa, mua, siga);
 }
 
 int tpe_joint_clear_groups(tpe_ctx* ctx) {

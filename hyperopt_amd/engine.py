@@ -402,11 +402,17 @@ class Engine(object):
         self._labels()
 
     # -- joint (multivariate) posterior ---------------------------------------
-    def set_joint_posterior(self, dims, wb, mub, sigb, wa, mua, siga):
+    def set_joint_posterior(self, dims, wb, mub, sigb, wa, mua, siga, q=None):
         """The joint mixtures of a group of D dense labels
         (posterior.joint_mixture): dims a JOINT_DIM_DTYPE array, weights [K],
         means and sigmas [K, D], component 0 the prior
-        (tpe_joint_set_posterior)."""
+        (tpe_joint_set_posterior).  q: the quantization step per dimension, 0
+        for a dense one (posterior.joint_mixture(quantized=True)); with a
+        step set the group is slot 0 of tpe_joint_set_group_q, the other
+        slots cleared."""
+        if q is not None and np.any(_f64(q) != 0.0):
+            self.clear_joint_groups()
+            return self.set_joint_group(0, L.TPE_JOINT_STREAM, dims, wb, mub, sigb, wa, mua, siga, q=q)
         args = self._joint_args(dims, wb, mub, sigb, wa, mua, siga)
         rc = self.lib.tpe_joint_set_posterior(self.h, *args)
         # (a box without below mass is set, and every draw reports it again)
@@ -428,12 +434,21 @@ class Engine(object):
         return (_ptr(dims), D, len(wb), _ptr(wb), _ptr(mub), _ptr(sigb), len(wa), _ptr(wa), _ptr(mua),
                 _ptr(siga))
 
-    def set_joint_group(self, slot, pick_stream, dims, wb, mub, sigb, wa, mua, siga):
+    def set_joint_group(self, slot, pick_stream, dims, wb, mub, sigb, wa, mua, siga, q=None):
         """set_joint_posterior for one of the context's L.TPE_JOINT_MAX_GROUPS
         slots, the other slots left as they are; pick_stream: the Philox
-        stream of the slot's component pick (tpe_joint_set_group)."""
+        stream of the slot's component pick (tpe_joint_set_group).  q [D]: the
+        quantization steps, 0 for a dense dimension (tpe_joint_set_group_q:
+        D plus the number of quantized dimensions is at most 128)."""
         args = self._joint_args(dims, wb, mub, sigb, wa, mua, siga)
-        rc = self.lib.tpe_joint_set_group(self.h, int(slot), int(pick_stream) & 0xFFFFFFFF, *args)
+        if q is None:
+            rc = self.lib.tpe_joint_set_group(self.h, int(slot), int(pick_stream) & 0xFFFFFFFF, *args)
+        else:
+            q = _f64(q).ravel()
+            if len(q) != args[1]:
+                raise ValueError('q holds one step per joint dimension')
+            rc = self.lib.tpe_joint_set_group_q(self.h, int(slot), int(pick_stream) & 0xFFFFFFFF, args[0],
+                                                _ptr(q), *args[1:])
         slots = self.__dict__.setdefault('joint_slots', {})
         if rc in (L.TPE_OK, L.TPE_ERR_SAMPLE):
             slots[int(slot)] = args[1]

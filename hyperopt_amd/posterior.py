@@ -198,6 +198,8 @@ def label_posterior(label, kind, args, below, above, prior_weight):
 
 
 JOINT_KINDS = ('uniform', 'loguniform', 'normal', 'lognormal')
+# the kinds a joint group accepts besides, with quantized=True
+JOINT_QUANT_KINDS = ('quniform', 'qloguniform', 'qnormal', 'qlognormal')
 
 
 def _parzen_positions(mus, prior_mu):
@@ -219,19 +221,28 @@ def _parzen_positions(mus, prior_mu):
     return pos, where
 
 
-def joint_prior(kind, args):
+def joint_prior(kind, args, quantized=False):
     """(tpe kind, bounded, low, high, prior_mu, prior_sigma, transform) of a
-    joint-group label: the prior mapping label_posterior uses."""
-    if kind not in JOINT_KINDS:
+    joint-group label: the prior mapping label_posterior uses.
+    quantized=True accepts JOINT_QUANT_KINDS too (the prior of the kind
+    without its q) and returns the step as a seventh element, 0.0 for a
+    dense kind."""
+    if kind not in JOINT_KINDS and not (quantized and kind in JOINT_QUANT_KINDS):
         raise ValueError('%r labels cannot join a joint group' % (kind,))
+    step = ()
+    if quantized:
+        step = (float(args['q']) if kind in JOINT_QUANT_KINDS else 0.0,)
+        if kind in JOINT_QUANT_KINDS and not (0.0 < step[0] < np.inf):
+            raise ValueError('label kind %r needs a positive finite q' % (kind,))
+        kind = kind[1:] if kind in JOINT_QUANT_KINDS else kind
     log = kind in ('loguniform', 'lognormal')
     if kind in ('uniform', 'loguniform'):
         low, high = float(args['low']), float(args['high'])
-        return log, True, low, high, 0.5 * (high + low), 1.0 * (high - low)
-    return log, False, 0.0, 0.0, float(args['mu']), float(args['sigma'])
+        return (log, True, low, high, 0.5 * (high + low), 1.0 * (high - low)) + step
+    return (log, False, 0.0, 0.0, float(args['mu']), float(args['sigma'])) + step
 
 
-def joint_mixture(group_specs, obs, splitter, prior_weight, streams=None):
+def joint_mixture(group_specs, obs, splitter, prior_weight, streams=None, quantized=False):
     """The joint (multivariate) mixtures of a group of dense continuous
     labels whose observations belong to the same trials.
 
@@ -250,16 +261,30 @@ def joint_mixture(group_specs, obs, splitter, prior_weight, streams=None):
 
     Returns (dims, wb, mub, sigb, wa, mua, siga): dims a JOINT_DIM_DTYPE
     array, weights [K], means and sigmas [K, D] in the labels' working space
-    (log space for the log kinds)."""
+    (log space for the log kinds).
+
+    quantized=True accepts the quantized kinds (JOINT_QUANT_KINDS) too and
+    returns the steps q [D] (0 for a dense label) as one more, last element.
+    A quantized log kind's observations enter through the univariate
+    transform of label_spec -- qloguniform: log(max(o, max(EPS, exp(low)))),
+    qlognormal: log(max(o, EPS)) -- so an observed 0 builds."""
     from .engine import JOINT_DIM_DTYPE
     group = [(g.label, g.kind, g.args) if hasattr(g, 'kind') else tuple(g) for g in group_specs]
     D = len(group)
     pw = float(prior_weight)
     dims = np.zeros(D, dtype=JOINT_DIM_DTYPE)
     sides = [[], []]
+    steps = []
     ids0 = None
     for d, (label, kind, args) in enumerate(group):
-        log, bounded, low, high, pmu, psig = joint_prior(kind, args)
+        log, bounded, low, high, pmu, psig = joint_prior(kind, args, quantized)[:6]
+        floor = None
+        if quantized:
+            steps.append(joint_prior(kind, args, True)[6])
+            if kind == 'qloguniform':
+                floor = np.maximum(EPS, np.exp(low))
+            elif kind == 'qlognormal':
+                floor = EPS
         dims[d]['kind'] = L.TPE_LGMM1 if log else L.TPE_GMM1
         dims[d]['flags'] = (L.TPE_HAS_LOW | L.TPE_HAS_HIGH) if bounded else 0
         dims[d]['low'], dims[d]['high'] = low, high
@@ -273,7 +298,9 @@ def joint_mixture(group_specs, obs, splitter, prior_weight, streams=None):
                              % (label, group[0][0]))
         for side, o in enumerate(splitter.split(oi, ov)):
             o = np.asarray(o, dtype=float)
-            if log:
+            if floor is not None:
+                o = np.log(np.maximum(o, floor))
+            elif log:
                 o = np.log(o)
             w, mu, sigma = adaptive_parzen_normal(o, pw, pmu, psig)
             p, where = _parzen_positions(o, pmu)
@@ -289,6 +316,8 @@ def joint_mixture(group_specs, obs, splitter, prior_weight, streams=None):
                 'joint group: weights differ between labels'
         out += [np.ascontiguousarray(W), np.ascontiguousarray(np.stack([c[1] for c in cols], axis=1)),
                 np.ascontiguousarray(np.stack([c[2] for c in cols], axis=1))]
+    if quantized:
+        out.append(np.asarray(steps, dtype=np.float64))
     return tuple(out)
 
 

@@ -19,7 +19,8 @@
      and keeping the selected one is the same distribution).
 
 Extra keyword arguments (not in the reference): `multivariate` (True: the
-unconditional dense continuous labels are modelled jointly, see `suggest`;
+unconditional dense continuous labels are modelled jointly, see `suggest`
+(joint_quantized=True: the quantized continuous ones with them);
 with `group=True` also those that share an hp.choice branch, one joint group
 per branch),
 `precision` ('f64'; 'f32'
@@ -191,9 +192,10 @@ def _resident_posterior(eng, domain, trials, specs, view, gathered, gamma, prior
     return n_docs, None
 
 
-def joint_group(domain, specs, obs=None):
+def joint_group(domain, specs, obs=None, kinds=_post.JOINT_KINDS):
     """The joint group of a space: its unconditional labels of a dense
-    continuous kind, in the order of `specs` -- or None (with the reason
+    continuous kind (or of any of `kinds`: joint_quantized=True passes the
+    quantized kinds too), in the order of `specs` -- or None (with the reason
     logged) when multivariate TPE falls back to the independent path: fewer
     than two such labels, or (obs given: label -> (idxs, vals)) labels that
     are not observed in exactly the same trials."""
@@ -204,7 +206,7 @@ def joint_group(domain, specs, obs=None):
             domain._hyperopt_amd_free = free
         except AttributeError:
             pass
-    group = [k for k, s in specs.items() if k in free and s.kind in _post.JOINT_KINDS]
+    group = [k for k, s in specs.items() if k in free and s.kind in kinds]
     if len(group) < 2:
         logger.info('multivariate TPE: %d joint label(s), using the independent path' % len(group))
         return None
@@ -218,9 +220,10 @@ def joint_group(domain, specs, obs=None):
     return group
 
 
-def joint_groups(domain, specs, obs=None):
+def joint_groups(domain, specs, obs=None, kinds=_post.JOINT_KINDS):
     """The joint groups of a space, [(slot, [labels])]: a structural group is
-    the labels of a dense continuous kind (posterior.JOINT_KINDS) that share
+    the labels of a dense continuous kind (posterior.JOINT_KINDS; or of any
+    of `kinds`, which then also decide the slot numbering) that share
     one condition signature (labels.condition_signatures: active in exactly
     the same configurations), at least two of them, in the order of `specs`.
     Slots number the structural groups -- the unconditional group first when
@@ -237,7 +240,7 @@ def joint_groups(domain, specs, obs=None):
             pass
     by_sig = {}
     for k, s in specs.items():
-        if s.kind in _post.JOINT_KINDS:
+        if s.kind in kinds:
             by_sig.setdefault(sigs[k], []).append(k)
     groups = [g for sig, g in by_sig.items() if len(g) >= 2]
     # (by_sig keeps the order of each signature's first label in specs)
@@ -260,7 +263,7 @@ def joint_groups(domain, specs, obs=None):
 
 
 def _joint_rounds(eng, domain, trials, specs, gathered, gamma, prior_weight, seed, ids, n_candidates,
-                  group=False):
+                  group=False, quantized=False):
     """One joint round per id and joint group: [label -> value] per id, or
     None when the call falls back to the independent path.  group=False: the
     unconditional group alone (joint_group), slot 0; group=True: every group
@@ -269,13 +272,17 @@ def _joint_rounds(eng, domain, trials, specs, gathered, gamma, prior_weight, see
     (posterior.joint_mixture, each group from its own observations); a
     label's Philox stream is its position in the space, as in the
     independent round.  One set_joint_group per group, one
-    joint_suggest_batch for all groups and ids."""
+    joint_suggest_batch for all groups and ids.  quantized=True: the groups
+    take the quantized kinds too (posterior.JOINT_QUANT_KINDS), their values
+    rounded to the label's grid; every group value enters the document
+    through labels.coerce."""
+    kinds = _post.JOINT_KINDS + (_post.JOINT_QUANT_KINDS if quantized else ())
     labels = list(specs)
     tids, losses, obs = gathered or _history.gather(domain, trials, labels)
     if group:
-        groups = joint_groups(domain, specs, obs)
+        groups = joint_groups(domain, specs, obs, kinds)
     else:
-        g = joint_group(domain, specs, obs)
+        g = joint_group(domain, specs, obs, kinds)
         groups = [(0, g)] if g is not None else []
     if group and not groups:
         logger.info('multivariate TPE: no joint group, using the independent path')
@@ -284,15 +291,16 @@ def _joint_rounds(eng, domain, trials, specs, gathered, gamma, prior_weight, see
     splitter = _post.Splitter(tids, losses, gamma)
     eng.clear_joint_groups()
     for slot, g in groups:
-        eng.set_joint_group(slot, _engine.L.TPE_JOINT_STREAM - slot,
-                            *_post.joint_mixture([specs[k] for k in g], obs, splitter, prior_weight,
-                                                 streams=[labels.index(k) for k in g]))
+        mix = _post.joint_mixture([specs[k] for k in g], obs, splitter, prior_weight,
+                                  streams=[labels.index(k) for k in g], quantized=quantized)
+        eng.set_joint_group(slot, _engine.L.TPE_JOINT_STREAM - slot, *mix[:7],
+                            q=mix[7] if quantized else None)
     won = eng.joint_suggest_batch(seed, ids, n_candidates)
     out = [{} for _ in ids]
     for slot, g in groups:
         values = won[slot][0]
         for j in range(len(ids)):
-            out[j].update({k: float(v) for k, v in zip(g, values[j])})
+            out[j].update({k: _labels.coerce(specs[k].kind, v) for k, v in zip(g, values[j])})
     return out
 
 
@@ -303,7 +311,7 @@ def suggest(new_ids, domain, trials, seed,
             gamma=_default_gamma,
             linear_forgetting=_default_linear_forgetting,
             precision='f64', device=0, batch=False, posterior_builder='auto', devices=None,
-            multivariate=False, group=False):
+            multivariate=False, group=False, joint_quantized=False):
     """tpe.py:823-916.  Past the startup phase one document for new_ids[0],
     like the reference; `batch` (not in the reference) asks for one document
     per new_id:
@@ -343,6 +351,16 @@ def suggest(new_ids, domain, trials, seed,
     from the document as always.  A space whose only group is the
     unconditional one gives the documents of group=False.
 
+    joint_quantized=True (with multivariate=True) lets the joint groups hold
+    the quantized kinds quniform, qloguniform, qnormal and qlognormal as well
+    (batch size, depth, width beside a learning rate): a quantized label is
+    drawn from its component and rounded to its grid, and its factor in the
+    joint density is the component's mass on the value's rounding interval
+    ("Quantized labels").  The groups and their slots
+    are those of the widened kinds; categorical labels keep the independent
+    round.  With the default every call returns the documents it always
+    did: a quantized label then keeps its independent round.
+
     precision='f32' runs the exact fp64 path: a round draws every candidate
     and proves all but ~0.5 % of them out of the race from per-sub-bin score
     bounds before any lpdf is summed, so scoring the rest in fp32 would save
@@ -358,12 +376,14 @@ def suggest(new_ids, domain, trials, seed,
         raise ValueError("batch must be False, True or 'pending'")
     if group and not multivariate:
         raise ValueError('group=True needs multivariate=True')
+    if joint_quantized and not multivariate:
+        raise ValueError('joint_quantized=True needs multivariate=True')
     if multivariate and devices and len(list(devices)) > 1:
         raise ValueError('multivariate=True runs on one device')
     kw = dict(prior_weight=prior_weight, n_startup_jobs=n_startup_jobs,
               n_EI_candidates=n_EI_candidates, gamma=gamma, linear_forgetting=linear_forgetting,
               precision=precision, device=device, posterior_builder=posterior_builder,
-              devices=devices, multivariate=multivariate, group=group)
+              devices=devices, multivariate=multivariate, group=group, joint_quantized=joint_quantized)
     specs = specs_of(domain)
     labels = list(specs)
     # the device-resident history's view of the trials (None when the fast
@@ -414,7 +434,7 @@ def suggest(new_ids, domain, trials, seed,
     if res is None:
         res = round_call()
     joint = _joint_rounds(eng, domain, trials, specs, gathered, gamma, prior_weight, seed, ids,
-                          n_EI_candidates, group=group) if multivariate else None
+                          n_EI_candidates, group=group, quantized=bool(joint_quantized)) if multivariate else None
     rval = []
     for j, new_id in enumerate(ids):
         values = {s.label: _labels.coerce(s.kind, res[j][i]['value'])

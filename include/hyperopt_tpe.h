@@ -433,6 +433,32 @@ int tpe_joint_set_group(tpe_ctx *ctx, int32_t slot, uint32_t pick_stream, const 
                         int32_t n_dims, int32_t n_below, const double *wb, const double *mub,
                         const double *sigb, int32_t n_above, const double *wa, const double *mua,
                         const double *siga);
+/* Quantized dimensions in a joint group.  q[d] > 0 makes dimension d
+ * quantized with that step (q NULL or all zeros: tpe_joint_set_group, the
+ * same instantiations and bits).  W_k, mu_kd, s_kd, m_kd, A_S, the component
+ * pick and the draw of y in the working space are those of the dense group;
+ * the drawn value is x_d = rint(v / q_d) q_d with v = exp(y) for TPE_LGMM1,
+ * and the factor of a quantized dimension is the component's mass on the
+ * value's interval,
+ *   g_kd(x_d) = Phi((ub - mu_kd)/s_kd) - Phi((lb - mu_kd)/s_kd),
+ *   ub = x_d + q_d/2, lb = x_d - q_d/2, clipped to [low, high] by the flags
+ *   (TPE_GMM1), or clipped to [exp(low), exp(high)], lb = max(0, lb), then
+ *   ub = log(max(ub, 1e-12)), lb = log(max(lb, 1e-12))  (TPE_LGMM1),
+ * 0 for an empty interval (ub <= lb):
+ *   f_S(x) = (1/A_S) sum_k W_k prod_d g_kd(x_d)     (g = phi for a dense d),
+ *   lpdf_S(x) = log f_S(x) - sum_{d dense, TPE_LGMM1} y_d
+ * (a quantized TPE_LGMM1 dimension has no Jacobian term: its factor is a
+ * probability of the value).  A configuration no component reaches has lpdf
+ * -inf.  Equal configurations get equal lpdf bits, so among them the lowest
+ * index wins.
+ * Accepted groups: n_dims + (number of quantized dimensions) <= 128 -- a
+ * candidate keeps one value per dense and two (ub, lb) per quantized dimension
+ * in LDS; a larger group, or a q[d] that is negative, NaN or infinite:
+ * TPE_ERR_ARG.  The draw, score, suggest and batch calls serve such slots. */
+int tpe_joint_set_group_q(tpe_ctx *ctx, int32_t slot, uint32_t pick_stream, const tpe_joint_dim *dims,
+                          const double *q /* [n_dims], 0 = dense */, int32_t n_dims, int32_t n_below,
+                          const double *wb, const double *mub, const double *sigb, int32_t n_above,
+                          const double *wa, const double *mua, const double *siga);
 int tpe_joint_clear_groups(tpe_ctx *ctx);
 int tpe_joint_draw_group(tpe_ctx *ctx, int32_t slot, uint64_t seed, uint32_t round, int64_t n,
                          int64_t cand_offset, double *values, int32_t *comp);

@@ -25,6 +25,17 @@ multivariate=True; the medians of the best losses.  A record, not a gate.
 loop over single-posterior calls against set_joint_group +
 joint_suggest_batch, 24 candidates, 1 / 24 / 4096 ids.
 
+--quantized: the d32 shape (32 labels, 10000 trials: K 26 / 9976) dense and
+with every second label quantized (quantized_timings), at 24 candidates for
+one id, 24 candidates for 4096 ids (batched) and 2^16 candidates in one
+round; --legs dense,quantized selects.  The dense leg uses the entry points
+of a checkout without quantized groups, so it runs unchanged there.
+
+--quality-quantized: fmin for 100 evaluations over seeds 0..9 on
+(x - n)^2 + 0.01 (x + n)^2 with x uniform(-5, 5) and n quniform(-5, 5, 1):
+independent, multivariate=True, and multivariate=True with
+joint_quantized=True.  A record, not a gate.
+
 Prints one JSON document (and writes it to --out).
 """
 import argparse
@@ -204,6 +215,92 @@ def groups_timings(reps, legs=('loop', 'batch'), rounds=(1, 24, 4096), n=24):
     return out
 
 
+QKINDS = {'uniform': 'quniform', 'loguniform': 'qloguniform', 'normal': 'qnormal', 'lognormal': 'qlognormal'}
+
+
+def quantized_history(n_dims, n_trials, step=0.25):
+    """history() with every second label (odd d) of the quantized kind of
+    its kind, step `step`, its observations on the grid."""
+    group, tids, losses, obs = history(n_dims, n_trials)
+    out = []
+    for d, (label, kind, args) in enumerate(group):
+        if d % 2:
+            kind, args = QKINDS[kind], dict(args, q=step)
+            obs[label] = (tids, np.rint(obs[label][1] / step) * step)
+        out.append((label, kind, args))
+    return out, tids, losses, obs
+
+
+def quantized_timings(reps, legs=('dense', 'quantized'), n_dims=32, n_trials=10000):
+    """Medians (and the range) over `reps` calls of the device time between
+    HIP events and of the wall time of: joint_suggest at 24 candidates,
+    joint_suggest_batch at 24 candidates for 4096 ids, joint_suggest at 2^16
+    candidates -- the dense d32 group and the group with half of its labels
+    quantized."""
+    from hyperopt_amd import _lib as L
+    from hyperopt_amd import posterior as P
+    from hyperopt_amd.engine import Engine
+    eng = Engine(0, 'f64')
+    out = {}
+    for leg in legs:
+        if leg == 'dense':
+            group, tids, losses, obs = history(n_dims, n_trials)
+            mix = P.joint_mixture(group, obs, P.Splitter(tids, losses, 0.25), 1.0)
+            eng.clear_joint_groups()
+            eng.set_joint_group(0, L.TPE_JOINT_STREAM, *mix)
+        else:
+            group, tids, losses, obs = quantized_history(n_dims, n_trials)
+            mix = P.joint_mixture(group, obs, P.Splitter(tids, losses, 0.25), 1.0, quantized=True)
+            eng.clear_joint_groups()
+            eng.set_joint_group(0, L.TPE_JOINT_STREAM, *mix[:7], q=mix[7])
+        res = out[leg] = dict(dims=n_dims, k_below=len(mix[1]), k_above=len(mix[4]),
+                              quantized_dims=int(np.count_nonzero(mix[7])) if leg != 'dense' else 0)
+        ids = list(range(1000, 1000 + 4096))
+        shapes = (('one_24', lambda r: eng.joint_suggest(1, 24, round=r)),
+                  ('batch_4096x24', lambda r: eng.joint_suggest_batch(1, [i + r for i in ids], 24)),
+                  ('one_65536', lambda r: eng.joint_suggest(1, 1 << 16, round=r)))
+        for name, fn in shapes:
+            fn(0)
+            dev, wall = [], []
+            for r in range(reps):
+                t = time.perf_counter()
+                fn(r + 1)
+                wall.append((time.perf_counter() - t) * 1e3)
+                dev.append(eng.last_timing()[1])
+            res[name] = dict(device_ms=float(np.median(dev)), device_min_ms=float(np.min(dev)),
+                             device_max_ms=float(np.max(dev)), wall_ms=float(np.median(wall)),
+                             wall_min_ms=float(np.min(wall)), wall_max_ms=float(np.max(wall)))
+    if 'dense' in out and 'quantized' in out:
+        for name in ('one_24', 'batch_4096x24', 'one_65536'):
+            out['quantized_over_dense_device_' + name] = (out['quantized'][name]['device_ms'] /
+                                                          out['dense'][name]['device_ms'])
+    eng.close()
+    return out
+
+
+def quality_quantized(evals=100, seeds=10):
+    import hyperopt_amd as H
+    from hyperopt_amd import hp, tpe
+    space = {'x': hp.uniform('x', -5, 5), 'n': hp.quniform('n', -5, 5, 1)}
+
+    def loss(d):
+        return (d['x'] - d['n']) ** 2 + 0.01 * (d['x'] + d['n']) ** 2
+
+    out = {}
+    modes = (('independent', {}), ('multivariate', dict(multivariate=True)),
+             ('multivariate_joint_quantized', dict(multivariate=True, joint_quantized=True)))
+    for name, kw in modes:
+        best = []
+        for seed in range(seeds):
+            trials = H.Trials()
+            H.fmin(loss, space, algo=partial(tpe.suggest, **kw), max_evals=evals, trials=trials,
+                   rstate=np.random.RandomState(seed))
+            best.append(float(min(trials.losses())))
+        out[name] = dict(best=best, median=float(np.median(best)))
+    out.update(evals=evals, seeds=seeds, objective='(x-n)^2 + 0.01 (x+n)^2, x uniform(-5,5), n quniform(-5,5,1)')
+    return out
+
+
 def quality(evals=100, seeds=10):
     import hyperopt_amd as H
     from hyperopt_amd import hp, tpe
@@ -233,16 +330,22 @@ def main(argv):
     ap.add_argument('--quality', action='store_true')
     ap.add_argument('--no-timings', action='store_true')
     ap.add_argument('--groups', action='store_true', help='the loop and batch legs over several groups and ids')
-    ap.add_argument('--legs', default='loop,batch')
+    ap.add_argument('--quantized', action='store_true', help='the dense and quantized d32 legs')
+    ap.add_argument('--quality-quantized', action='store_true')
+    ap.add_argument('--legs', default=None, help='--groups: loop,batch; --quantized: dense,quantized')
     ap.add_argument('--out')
     a = ap.parse_args(argv)
     res = {}
     if a.groups:
-        res['groups'] = groups_timings(a.reps, legs=tuple(a.legs.split(',')))
+        res['groups'] = groups_timings(a.reps, legs=tuple((a.legs or 'loop,batch').split(',')))
+    elif a.quantized:
+        res['quantized'] = quantized_timings(a.reps, legs=tuple((a.legs or 'dense,quantized').split(',')))
     elif not a.no_timings:
         res['timings'] = timings(a.dims, a.trials, a.reps)
     if a.quality:
         res['quality'] = quality()
+    if a.quality_quantized:
+        res['quality_quantized'] = quality_quantized()
     txt = json.dumps(res, indent=1, sort_keys=True)
     print(txt)
     if a.out:
