@@ -171,6 +171,8 @@ SIGNATURES = {
     'tpe_joint_suggest': (ctypes.c_int, [_P, _U64, _U32, _I64, _P, _P, _PD, _PD]),
     'tpe_joint_set_group': (ctypes.c_int, [_P, _I32, _U32, _P, _I32, _I32, _P, _P, _P, _I32, _P, _P, _P]),
     'tpe_joint_set_group_q': (ctypes.c_int, [_P, _I32, _U32, _P, _P, _I32, _I32, _P, _P, _P, _I32, _P, _P, _P]),
+    'tpe_joint_set_group_c': (ctypes.c_int, [_P, _I32, _U32, _P, _P, _P, _P, _D, _I32, _I32, _P, _P, _P, _I32, _P,
+                                             _P, _P]),
     'tpe_joint_clear_groups': (ctypes.c_int, [_P]),
     'tpe_joint_draw_group': (ctypes.c_int, [_P, _I32, _U64, _U32, _I64, _I64, _P, _P]),
     'tpe_joint_score_group': (ctypes.c_int, [_P, _I32, _P, _I64, _P, _P]),

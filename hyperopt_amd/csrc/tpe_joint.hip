@@ -59,6 +59,24 @@
 // of the two erfc-class evaluations per (candidate, component, quantized
 // dimension), ~100 times the two LDS reads they share among kJU components.
 // Dense-only groups launch the instantiations they always did.
+//
+// Categorical dimensions (tpe_joint_set_group_c, upper_d = C_d > 0, prior p_d):
+// with a_Sd = C_d prior_weight / K_S the factor of category x in component k is
+//   r_0d[x] = p_d[x],   r_td[x] = ([x == o_td] + a_Sd p_d[x]) / (1 + a_Sd)
+// (o_td: the category trial t observed); m_kd = 1, so A_S and the pick are
+// untouched, and there is no Jacobian term.  Evaluated as
+//   log r_td[x] = log p_d[x] + log(a/(1+a)) + [x == o_td] log1p(1/(a p_d[o_td])):
+// sum_d log p_d[x_d] rides with the candidate's ylog (subtracted), sum_d
+// log(a/(1+a)) is in c_k of k >= 1, and the record is (o_kd, -K hit bonus),
+// (-1, 0) for the prior component -- per (candidate, component, dimension) one
+// compare, one select, one add on the candidate's category, its one LDS value.
+// A value that is no integer in [0, C_d): factor 0, lpdf -inf on both sides.
+// The draw takes word x of the Philox counter (g, 0, stream_d, round) and the
+// first category c with ceil(cdf_kd[c] 2^32) above it, cdf_td[c] = (a P_d[c] +
+// [c >= o_td]) / (a P_d[C-1] + 1) with P_d the running sums of p_d: a binary
+// search over one table per dimension.  Such a group runs
+// k_joint_round<0, true, SAMPLE, true, true>; groups without a categorical
+// dimension launch the instantiations they always did.
 #include "tpe_ctx.h"
 
 #include <cmath>
@@ -85,10 +103,12 @@ struct JDim {
     double elo, ehi;   // exp(low), exp(high) of a bounded quantized log kind
     int32_t flags, stream, log;
     int32_t slot;      // quantized groups: the dimension's first per-candidate value
+    int32_t upper;     // the categories of a categorical dimension, 0: not categorical
+    int32_t cat_off;   // its first entry in the categorical tables
 };
 
-struct JDraw {   // one-component sampling terms of (k, d) (SampRec's)
-    double mu, ssg, p0, q0, m;
+struct JDraw {   // one-component sampling terms of (k, d) (SampRec's);
+    double mu, ssg, p0, q0, m;   // categorical: mu the observed category (-1: the prior), ssg = a_Sd
 };
 
 struct JP {   // the folded joint posterior
@@ -98,6 +118,8 @@ struct JP {   // the folded joint posterior
     const double* __restrict__ logA;   // below, above
     const uint64_t* __restrict__ thr;  // [Kb] pick thresholds
     const JDraw* __restrict__ draw;    // [Kb][d]
+    const double* __restrict__ catP;   // categorical tables at cat_off: running sums of p_d
+    const double* __restrict__ catlp;  // log p_d
     int32_t D, Kb, Ka;
     uint32_t stream;                   // the pick word's Philox stream
 };
@@ -116,7 +138,8 @@ __device__ __forceinline__ DLabel jlabel(const JDim& j) {
 __global__ __launch_bounds__(kJBlock) void k_joint_fold(
     const JDim* __restrict__ dims, int32_t D, int32_t Kb, int32_t Ka, const double* __restrict__ W,
     const double* __restrict__ mu, const double* __restrict__ sig, double2* __restrict__ rec,
-    double* __restrict__ cst, double* __restrict__ P, JDraw* __restrict__ draw) {
+    double* __restrict__ cst, double* __restrict__ P, JDraw* __restrict__ draw, double pw,
+    const double* __restrict__ catp) {
 #pragma clang fp contract(off)
     const int k = blockIdx.x * kJBlock + threadIdx.x;
     if (k >= Kb + Ka) return;
@@ -124,6 +147,19 @@ __global__ __launch_bounds__(kJBlock) void k_joint_fold(
     for (int d = 0; d < D; ++d) {
         const JDim j = dims[d];
         const size_t o = (size_t)k * D + d;
+        if (j.upper > 0) {   // mass 1; mu holds the observed category (validated on the host)
+            const bool prior = k == 0 || k == Kb;
+            const double a = (double)j.upper * pw / (double)(k < Kb ? Kb : Ka);
+            if (prior) {
+                rec[o] = make_double2(-1.0, 0.0);
+            } else {
+                const double c = mu[o];
+                rec[o] = make_double2(c, -(log1p(1.0 / (a * catp[j.cat_off + (int)c])) * kExpScale));
+                sl += log1p(1.0 / a);   // -log(a / (1 + a))
+            }
+            if (k < Kb) draw[o] = JDraw{prior ? -1.0 : mu[o], a, 0.0, 0.0, 1.0};
+            continue;
+        }
         const double s = sig[o], m = mu[o];
         if (j.q > 0.0) {   // z = (bound - mu) / (s sqrt 2); its factor is a mass: no density constant
             const double a = 0.70710678118654752440 / s;
@@ -192,11 +228,35 @@ __device__ __forceinline__ int jpick(const JP& p, uint32_t k0, uint32_t k1, uint
     return lo;
 }
 
+// categorical dimension d of candidate g from component k: the first category
+// whose threshold ceil(cdf 2^32) is above word x of the counter (g, 0, stream,
+// round) -- the independent round's categorical layout (sample_raw<CAT>); the
+// last category's cdf is 1
+__device__ __forceinline__ double jdraw_cat(const JP& p, const JDim& j, int d, int k, uint32_t k0, uint32_t k1,
+                                            uint32_t g, uint32_t round) {
+#pragma clang fp contract(off)
+    const U4 w = philox4x32_10(U4{g, 0u, (uint32_t)j.stream, round}, k0, k1);
+    const JDraw r = p.draw[(size_t)k * p.D + d];
+    const double* __restrict__ P = p.catP + j.cat_off;
+    const bool prior = r.mu < 0.0;
+    const double Z = P[j.upper - 1], den = prior ? Z : r.ssg * Z + 1.0;
+    int lo = 0, hi = j.upper - 1;
+    while (lo < hi) {
+        const int mid = (lo + hi) >> 1;
+        const double num = prior ? P[mid] : r.ssg * P[mid] + ((double)mid >= r.mu ? 1.0 : 0.0);
+        if (pick_thr(num / den) > (uint64_t)w.x) hi = mid; else lo = mid + 1;
+    }
+    return (double)lo;
+}
+
 // dimension d of candidate g from component k: the label's value (after the
-// exp of a log kind; Q: and the rounding to the grid of a quantized dimension)
-template <bool Q>
+// exp of a log kind; Q: and the rounding to the grid of a quantized dimension,
+// or the category of a categorical one)
+template <bool Q, bool C = Q>
 __device__ __forceinline__ double jdraw(const JP& p, const JDim& j, int d, int k, uint32_t k0, uint32_t k1,
                                         uint32_t g, uint32_t round) {
+    if constexpr (C)
+        if (j.upper > 0) return jdraw_cat(p, j, d, k, k0, k1, g, round);
     const DLabel L = jlabel(j);
     uint32_t wp, wu;
     draw_words(L, k0, k1, g, round, wp, wu);
@@ -321,7 +381,10 @@ __device__ __forceinline__ double jmass(double zl, double zu) {
 // quantized factors of a component multiply into a mantissa in [1/2, 1) and an
 // integer exponent (60 fine-grid factors are below 1e-320 together); one log
 // per component folds them into E_k.  A zero factor: E_k = -inf.
-template <bool TABC>
+// C: the group may hold categorical dimensions -- the candidate's category in
+// the dimension's slot (-2: none), the record (o_kd, -K bonus): a hit adds the
+// bonus to E_k.
+template <bool TABC, bool C = false>
 __device__ __forceinline__ void slice_ms_q(const JDim* __restrict__ dims, const double2* __restrict__ rec,
                                            const double* __restrict__ cst, int D, int k0, int k1, const double* yl,
                                            const double* __restrict__ tab, double& m, double& s) {
@@ -341,6 +404,16 @@ __device__ __forceinline__ void slice_ms_q(const JDim* __restrict__ dims, const 
         }
         for (int d = 0; d < D; ++d) {
             const int sl = dims[d].slot;
+            if constexpr (C)
+                if (dims[d].upper > 0) {
+                    const double y = yl[sl * kJLdsLanes];
+#pragma unroll
+                    for (int j = 0; j < kJU; ++j) {
+                        const double2 q = r[j][d];
+                        acc[j] += y == q.x ? q.y : 0.0;
+                    }
+                    continue;
+                }
             if (dims[d].q > 0.0) {
                 const double u = yl[sl * kJLdsLanes], l = yl[(sl + 1) * kJLdsLanes];
 #pragma unroll
@@ -448,13 +521,15 @@ __device__ __forceinline__ void jblock_best(uint64_t key, int64_t idx, double ll
 // is the flat index over rounds of ncell candidates each -- candidate i %
 // ncell of round rounds[i / ncell]; every candidate's lpdfs are stored, and
 // without `partials` no workgroup best is formed.
-// Q: a group with quantized dimensions -- the LDS layout of slice_ms_q (DR = 0).
-template <int DR, bool TABC, bool SAMPLE, bool Q = false>
+// Q: a group with quantized dimensions -- the LDS layout of slice_ms_q (DR = 0);
+// C: that layout with categorical dimensions.
+template <int DR, bool TABC, bool SAMPLE, bool Q = false, bool C = false>
 __global__ __launch_bounds__(DR > 0 ? kJBlock : kJLdsLanes) void k_joint_round(
     JP p, const double2* __restrict__ rec, const double* __restrict__ cst, const double* __restrict__ vals, int64_t n, int64_t cand_offset, uint64_t seed, uint32_t round,
     const uint32_t* __restrict__ rounds, uint32_t ncell, int32_t split, double2* __restrict__ part, double* __restrict__ aux, double* __restrict__ out_ll,
     double* __restrict__ out_lg, Partial* __restrict__ partials, int32_t* __restrict__ err) {
     static_assert(!Q || DR == 0, "quantized groups keep their values in LDS");
+    static_assert(!C || Q, "categorical dimensions run the quantized variant");
     extern __shared__ double jsm[];
     const double* tab = jsm;
     if constexpr (!TABC) load_exp_table(jsm);
@@ -497,8 +572,30 @@ __global__ __launch_bounds__(DR > 0 ? kJBlock : kJLdsLanes) void k_joint_round(
         // a quantized dimension: the ends of the value's interval in the
         // working space (quant_bounds: the log of a log kind taken here, once
         // per candidate), recentred like y'; no Jacobian term
+        bool inval = false;
         for (int d = 0; d < D; ++d) {
             const JDim j = p.dims[d];
+            if constexpr (C)
+                if (j.upper > 0) {
+                    // the category itself; its log p_d[x] leaves through ylog
+                    // (the same on both sides), no integer in [0, C_d): factor 0
+                    double c = -2.0;
+                    if (valid) {
+                        double x;
+                        if constexpr (SAMPLE) x = jdraw_cat(p, j, d, kc, k0, k1, g, round);
+                        else x = vals[(size_t)i * D + d];
+                        if (x != x) {
+                            bad = true;
+                        } else if (x >= 0.0 && x < (double)j.upper && x == floor(x)) {
+                            c = x;
+                            ylog -= p.catlp[j.cat_off + (int)x];
+                        } else {
+                            inval = true;
+                        }
+                    }
+                    yl[j.slot * kJLdsLanes] = c;
+                    continue;
+                }
             if (!(j.q > 0.0)) {
                 yl[j.slot * kJLdsLanes] = load(d);
                 continue;
@@ -507,7 +604,7 @@ __global__ __launch_bounds__(DR > 0 ? kJBlock : kJLdsLanes) void k_joint_round(
             if (valid) {
                 double x;
                 if constexpr (SAMPLE) {
-                    x = jdraw<true>(p, j, d, kc, k0, k1, g, round);
+                    x = jdraw<true, false>(p, j, d, kc, k0, k1, g, round);
                     if (x != x) atomicOr(err, 1);
                 } else {
                     x = vals[(size_t)i * D + d];
@@ -527,6 +624,8 @@ __global__ __launch_bounds__(DR > 0 ? kJBlock : kJLdsLanes) void k_joint_round(
             yl[j.slot * kJLdsLanes] = ub - j.centre;
             yl[(j.slot + 1) * kJLdsLanes] = lb - j.centre;
         }
+        if constexpr (C)
+            if (inval) ylog = kInf;
         yr[0] = 0.0;
     } else if constexpr (DR > 0) {
         // (the draw stays a loop: placed by selects, one copy of its code)
@@ -549,7 +648,7 @@ __global__ __launch_bounds__(DR > 0 ? kJBlock : kJLdsLanes) void k_joint_round(
         const int K = above ? p.Ka : p.Kb, base = above ? p.Kb : 0, q = above ? sl - nsb : sl;
         const int a0 = q * kJSlice, a1 = min(a0 + kJSlice, K);
         double m, s;
-        if constexpr (Q) slice_ms_q<TABC>(p.dims, rec, cst, D, base + a0, base + a1, yl, tab, m, s);
+        if constexpr (Q) slice_ms_q<TABC, C>(p.dims, rec, cst, D, base + a0, base + a1, yl, tab, m, s);
         else slice_ms<DR, TABC>(rec, cst, D, base + a0, base + a1, yr, yl, tab, m, s);
         if (valid) {
             part[(size_t)sl * n + i] = make_double2(m, s);
@@ -565,7 +664,7 @@ __global__ __launch_bounds__(DR > 0 ? kJBlock : kJLdsLanes) void k_joint_round(
         for (int a0 = 0; a0 < K; a0 += kJSlice) {
             double m2, s2;
             if constexpr (Q)
-                slice_ms_q<TABC>(p.dims, rec, cst, D, base + a0, base + min(a0 + kJSlice, K), yl, tab, m2, s2);
+                slice_ms_q<TABC, C>(p.dims, rec, cst, D, base + a0, base + min(a0 + kJSlice, K), yl, tab, m2, s2);
             else
                 slice_ms<DR, TABC>(rec, cst, D, base + a0, base + min(a0 + kJSlice, K), yr, yl, tab, m2, s2);
             ms_merge<TABC>(m, s, m2, s2, tab);
@@ -691,10 +790,13 @@ struct JointState {   // one slot's folded posterior
     int32_t D = 0, Kb = 0, Ka = 0;
     int32_t S = 0;        // per-candidate values: D + the number of quantized dimensions
     bool quant = false;   // a quantized dimension: the Q instantiations of k_joint_round
+    bool cat = false;     // a categorical dimension: the Q, C instantiations
+    int32_t ncat = 0;     // entries of each categorical table
     uint32_t stream = TPE_JOINT_STREAM;
     bool ready = false, zero = false;
     DevBuf<JDim> dims;
     DevBuf<double> W, mu, sig, cst, P, logA;
+    DevBuf<double> ctab;   // categorical tables: p, its running sums, log p (ncat each)
     DevBuf<double2> rec;
     DevBuf<JDraw> draw;
     DevBuf<uint64_t> thr;
@@ -706,6 +808,8 @@ struct JointState {   // one slot's folded posterior
         p.logA = logA.p;
         p.thr = thr.p;
         p.draw = draw.p;
+        p.catP = cat ? ctab.p + ncat : nullptr;
+        p.catlp = cat ? ctab.p + 2 * (size_t)ncat : nullptr;
         p.D = D;
         p.Kb = Kb;
         p.Ka = Ka;
@@ -745,19 +849,20 @@ int launch_round(tpe_ctx* ctx, JointGroups* G, JointState* J, bool sample, int64
                  uint64_t seed, uint32_t round, bool lpdfs, int32_t* nparts, int32_t* err,
                  const uint32_t* rounds = nullptr, uint32_t ncell = 0) {
     const int D = J->D;
-    const int S = J->quant ? J->S : D;   // values a lane keeps in LDS (dr == 0)
-    const int dr = J->quant ? 0 : (D <= kJRegSmall ? kJRegSmall : (D <= kJReg ? kJReg : 0));
+    const bool qv = J->quant || J->cat;   // the quantized variant
+    const int S = qv ? J->S : D;   // values a lane keeps in LDS (dr == 0)
+    const int dr = qv ? 0 : (D <= kJRegSmall ? kJRegSmall : (D <= kJReg ? kJReg : 0));
     // (a quantized group reads the exp table from memory whatever its size: one
     // exp per component against two erfc-class evaluations per quantized
     // dimension, and a table per one-wave workgroup would leave the CU two waves)
-    const bool tabc = dr == 0 && (J->quant || S > kJLdsTabD);
+    const bool tabc = dr == 0 && (qv || S > kJLdsTabD);
     const int threads = dr ? kJBlock : kJLdsLanes;
     const int64_t tiles = (n + threads - 1) / threads;
     const int64_t nsl = (J->Kb + kJSlice - 1) / kJSlice + (J->Ka + kJSlice - 1) / kJSlice;
     const bool split = tiles < kJSplitTiles && nsl > 2 && (size_t)nsl * n * sizeof(double2) <= kJPartBytes &&
                        nsl <= 65535;
     size_t lds = (tabc ? 0 : kExpTabSize * sizeof(double)) + (dr ? 0 : (size_t)S * kJLdsLanes * sizeof(double));
-    if (J->quant) lds = std::max(lds, 4 * kJLdsLanes * sizeof(double));   // (jblock_best's scratch)
+    if (qv) lds = std::max(lds, 4 * kJLdsLanes * sizeof(double));   // (jblock_best's scratch)
     const int64_t mtiles = (n + kJBlock - 1) / kJBlock;
     *nparts = (int32_t)(split ? mtiles : tiles);
     if (!rounds) HIPCHK(ctx, G->partials.reserve(*nparts));
@@ -787,7 +892,8 @@ int launch_round(tpe_ctx* ctx, JointGroups* G, JointState* J, bool sample, int64
                                (int32_t)split, G->part.p, G->aux.p, split ? nullptr : oll,                      \
                                split ? nullptr : olg, parts, err);                                              \
     } while (0)
-    if (J->quant) JLAUNCH(0, true, , true);
+    if (J->cat) JLAUNCH(0, true, , true, true);
+    else if (J->quant) JLAUNCH(0, true, , true);
     else if (dr == kJRegSmall) JLAUNCH(kJRegSmall, false);
     else if (dr == kJReg) JLAUNCH(kJReg, false);
     else if (!tabc) JLAUNCH(0, false);
@@ -841,7 +947,8 @@ int read_err(tpe_ctx* ctx, JointGroups* G) {
 // once the arguments are accepted (tpe_joint_set_posterior)
 int joint_set(tpe_ctx* ctx, int32_t slot, uint32_t pick_stream, bool only, const tpe_joint_dim* dims,
               const double* q, int32_t n_dims, int32_t n_below, const double* wb, const double* mub, const double* sigb,
-              int32_t n_above, const double* wa, const double* mua, const double* siga) {
+              int32_t n_above, const double* wa, const double* mua, const double* siga,
+              const int32_t* upper = nullptr, const double* cat_p = nullptr, double prior_weight = 0.0) {
     if (!ctx) return TPE_ERR_ARG;
     if (slot < 0 || slot >= kJMaxGroups)
         return ctx->fail(TPE_ERR_ARG, "a joint slot is in [0, " + std::to_string(kJMaxGroups) + ")");
@@ -855,18 +962,62 @@ int joint_set(tpe_ctx* ctx, int32_t slot, uint32_t pick_stream, bool only, const
     const int D = n_dims, Kb = n_below, Ka = n_above, K = Kb + Ka;
     std::vector<JDim> hd(D);
     int S = 0;
+    size_t ncat = 0;   // categories of all categorical dimensions
     for (int d = 0; d < D; ++d) {
         const double qd = q ? q[d] : 0.0;
         if (!(qd >= 0.0 && qd < __builtin_inf()))
             return ctx->fail(TPE_ERR_ARG, "a quantization step is finite and not negative (0: dense)");
         S += qd > 0.0 ? 2 : 1;
+        const int32_t C = upper ? upper[d] : 0;
+        if (C < 0) return ctx->fail(TPE_ERR_ARG, "upper is the number of categories, 0: not categorical");
+        if (C > 0 && qd > 0.0) return ctx->fail(TPE_ERR_ARG, "a joint dimension is quantized or categorical, not both");
+        ncat += (size_t)C;
     }
     if (S > kJMaxD)
         return ctx->fail(TPE_ERR_ARG, "a joint group holds at most " + std::to_string(kJMaxD) +
                                           " per-candidate values: dimensions plus quantized dimensions");
-    const bool quant = S > D;
-    for (int d = 0, slot = 0; d < D; ++d) {
+    const bool quant = S > D, cat = ncat > 0;
+    if (ncat > (size_t)INT32_MAX / 4) return ctx->fail(TPE_ERR_ARG, "too many categories");
+    // categorical tables: p, its running sums in category order, log p
+    std::vector<double> ctab(3 * ncat);
+    if (cat) {
+        if (!cat_p) return ctx->fail(TPE_ERR_ARG, "null pointer");
+        if (!(prior_weight > 0.0 && prior_weight < __builtin_inf()))
+            return ctx->fail(TPE_ERR_ARG, "a categorical dimension needs a positive finite prior weight");
+        size_t at = 0;
+        for (int d = 0; d < D; ++d) {
+            const int32_t C = upper[d];
+            double run = 0.0;
+            for (int32_t c = 0; c < C; ++c, ++at) {
+                const double pc = cat_p[at];
+                if (!(pc > 0.0 && pc < __builtin_inf()))
+                    return ctx->fail(TPE_ERR_ARG, "a categorical prior's entries are positive and finite");
+                run += pc;
+                ctab[at] = pc;
+                ctab[ncat + at] = run;
+                ctab[2 * ncat + at] = std::log(pc);
+            }
+            if (C > 0 && !(std::fabs(run - 1.0) <= 1e-9))
+                return ctx->fail(TPE_ERR_ARG, "a categorical prior sums to 1");
+            if (!C) continue;
+            for (int side = 0; side < 2; ++side) {   // the observed categories (row 0, the prior's, is ignored)
+                const double* m = side ? mua : mub;
+                for (int k = 1; k < (side ? Ka : Kb); ++k) {
+                    const double o = m[(size_t)k * D + d];
+                    if (!(o >= 0.0 && o < (double)C && o == std::floor(o)))
+                        return ctx->fail(TPE_ERR_ARG, "an observed category is an integer in [0, upper)");
+                }
+            }
+        }
+    }
+    for (int d = 0, slot = 0, coff = 0; d < D; ++d) {
         const tpe_joint_dim& s = dims[d];
+        if (upper && upper[d] > 0) {   // (kind, flags and bounds of a categorical dimension are not read)
+            hd[d] = JDim{0.0, 0.0, 0.0, 0.0, 0.0, 0.0, 0, s.stream, 0, (quant || cat) ? slot : d, upper[d], coff};
+            slot += 1;
+            coff += upper[d];
+            continue;
+        }
         if (s.kind != TPE_GMM1 && s.kind != TPE_LGMM1)
             return ctx->fail(TPE_ERR_ARG, "a joint dimension is TPE_GMM1 or TPE_LGMM1");
         if (s.flags & ~(TPE_HAS_LOW | TPE_HAS_HIGH)) return ctx->fail(TPE_ERR_ARG, "joint dimensions are not quantized");
@@ -874,7 +1025,7 @@ int joint_set(tpe_ctx* ctx, int32_t slot, uint32_t pick_stream, bool only, const
         const double qd = q ? q[d] : 0.0;
         const bool lg = s.kind == TPE_LGMM1;
         hd[d] = JDim{s.low, s.high, mub[d], qd, lg ? std::exp(s.low) : 0.0, lg ? std::exp(s.high) : 0.0,
-                     s.flags, s.stream, lg ? 1 : 0, quant ? slot : d};
+                     s.flags, s.stream, lg ? 1 : 0, (quant || cat) ? slot : d, 0, 0};
         slot += qd > 0.0 ? 2 : 1;
     }
     for (int side = 0; side < 2; ++side) {
@@ -883,7 +1034,8 @@ int joint_set(tpe_ctx* ctx, int32_t slot, uint32_t pick_stream, bool only, const
         for (int k = 0; k < Ks; ++k)
             if (!(w[k] >= 0.0)) return ctx->fail(TPE_ERR_VALUE, "negative or NaN weight");
         for (size_t o = 0; o < (size_t)Ks * D; ++o)
-            if (!(sg[o] > 0.0 && sg[o] < __builtin_inf())) return ctx->fail(TPE_ERR_VALUE, "sigma must be positive");
+            if (!(cat && upper[o % D] > 0) && !(sg[o] > 0.0 && sg[o] < __builtin_inf()))
+                return ctx->fail(TPE_ERR_VALUE, "sigma must be positive");
     }
     HIPCHK(ctx, hipSetDevice(ctx->device));
     JointGroups* G = jgroups(ctx, true);
@@ -905,6 +1057,10 @@ int joint_set(tpe_ctx* ctx, int32_t slot, uint32_t pick_stream, bool only, const
     HIPCHK(ctx, J->thr.reserve(Kb));
     HIPCHK(ctx, G->err.reserve(1));
     hipStream_t st = ctx->stream;
+    if (cat) {
+        HIPCHK(ctx, J->ctab.reserve(ctab.size()));
+        HIPCHK(ctx, hipMemcpyAsync(J->ctab.p, ctab.data(), ctab.size() * sizeof(double), hipMemcpyHostToDevice, st));
+    }
     const size_t nb = (size_t)Kb * D, na = (size_t)Ka * D;
     HIPCHK(ctx, hipMemcpyAsync(J->dims.p, hd.data(), D * sizeof(JDim), hipMemcpyHostToDevice, st));
     HIPCHK(ctx, hipMemcpyAsync(J->W.p, wb, Kb * sizeof(double), hipMemcpyHostToDevice, st));
@@ -915,7 +1071,8 @@ int joint_set(tpe_ctx* ctx, int32_t slot, uint32_t pick_stream, bool only, const
     HIPCHK(ctx, hipMemcpyAsync(J->sig.p + nb, siga, na * sizeof(double), hipMemcpyHostToDevice, st));
     HIPCHK(ctx, hipMemsetAsync(G->err.p, 0, sizeof(int32_t), st));
     hipLaunchKernelGGL(k_joint_fold, dim3((K + kJBlock - 1) / kJBlock), dim3(kJBlock), 0, st, J->dims.p, D, Kb, Ka,
-                       J->W.p, J->mu.p, J->sig.p, J->rec.p, J->cst.p, J->P.p, J->draw.p);
+                       J->W.p, J->mu.p, J->sig.p, J->rec.p, J->cst.p, J->P.p, J->draw.p, prior_weight,
+                       cat ? J->ctab.p : nullptr);
     HIPCHK(ctx, hipGetLastError());
     hipLaunchKernelGGL(k_joint_fold_sum, dim3(2), dim3(kJBlock), 0, st, J->P.p, Kb, Ka, J->logA.p, J->thr.p,
                        G->err.p);
@@ -926,6 +1083,8 @@ int joint_set(tpe_ctx* ctx, int32_t slot, uint32_t pick_stream, bool only, const
     J->D = D;
     J->S = S;
     J->quant = quant;
+    J->cat = cat;
+    J->ncat = (int32_t)ncat;
     J->Kb = Kb;
     J->Ka = Ka;
     J->stream = pick_stream;
@@ -956,6 +1115,14 @@ int tpe_joint_set_group_q(tpe_ctx* ctx, int32_t slot, uint32_t pick_stream, cons
                           const double* sigb, int32_t n_above, const double* wa, const double* mua,
                           const double* siga) {
     return joint_set(ctx, slot, pick_stream, false, dims, q, n_dims, n_below, wb, mub, sigb, n_above, wa, mua, siga);
+}
+
+int tpe_joint_set_group_c(tpe_ctx* ctx, int32_t slot, uint32_t pick_stream, const tpe_joint_dim* dims,
+                          const double* q, const int32_t* upper, const double* cat_p, double prior_weight,
+                          int32_t n_dims, int32_t n_below, const double* wb, const double* mub, const double* sigb,
+                          int32_t n_above, const double* wa, const double* mua, const double* siga) {
+    return joint_set(ctx, slot, pick_stream, false, dims, q, n_dims, n_below, wb, mub, sigb, n_above, wa, mua, siga,
+                     upper, cat_p, prior_weight);
 }
 
 int tpe_joint_clear_groups(tpe_ctx* ctx) {

@@ -200,6 +200,17 @@ def label_posterior(label, kind, args, below, above, prior_weight):
 JOINT_KINDS = ('uniform', 'loguniform', 'normal', 'lognormal')
 # the kinds a joint group accepts besides, with quantized=True
 JOINT_QUANT_KINDS = ('quniform', 'qloguniform', 'qnormal', 'qlognormal')
+# and with categorical=True (hp.randint and hp.choice: 'randint'; hp.pchoice: 'categorical')
+JOINT_CAT_KINDS = ('randint', 'categorical')
+
+
+def joint_cat_prior(kind, args):
+    """(upper, p) of a categorical joint-group label: p uniform for
+    'randint', the label's own for 'categorical'."""
+    upper = int(args['upper'])
+    if kind == 'randint':
+        return upper, np.full(upper, 1.0 / upper)
+    return upper, np.asarray(args['p'], dtype=float)
 
 
 def _parzen_positions(mus, prior_mu):
@@ -221,14 +232,24 @@ def _parzen_positions(mus, prior_mu):
     return pos, where
 
 
-def joint_prior(kind, args, quantized=False):
+def joint_prior(kind, args, quantized=False, categorical=False):
     """(tpe kind, bounded, low, high, prior_mu, prior_sigma, transform) of a
     joint-group label: the prior mapping label_posterior uses.
     quantized=True accepts JOINT_QUANT_KINDS too (the prior of the kind
     without its q) and returns the step as a seventh element, 0.0 for a
-    dense kind."""
+    dense kind.  categorical=True accepts JOINT_CAT_KINDS too and returns
+    two more, last elements: the number of categories (0 for any other kind)
+    and the prior p (None); a categorical label's first six elements are
+    placeholders (False, False, 0, 0, 0, 1), its p must be positive."""
+    if categorical and kind in JOINT_CAT_KINDS:
+        upper, p = joint_cat_prior(kind, args)
+        if upper < 1 or len(p) != upper or not np.all((p > 0.0) & np.isfinite(p)):
+            raise ValueError('a categorical joint label needs upper >= 1 positive finite probabilities')
+        return (False, False, 0.0, 0.0, 0.0, 1.0) + ((0.0,) if quantized else ()) + (upper, p)
     if kind not in JOINT_KINDS and not (quantized and kind in JOINT_QUANT_KINDS):
         raise ValueError('%r labels cannot join a joint group' % (kind,))
+    if categorical:
+        return joint_prior(kind, args, quantized) + (0, None)
     step = ()
     if quantized:
         step = (float(args['q']) if kind in JOINT_QUANT_KINDS else 0.0,)
@@ -242,7 +263,7 @@ def joint_prior(kind, args, quantized=False):
     return (log, False, 0.0, 0.0, float(args['mu']), float(args['sigma'])) + step
 
 
-def joint_mixture(group_specs, obs, splitter, prior_weight, streams=None, quantized=False):
+def joint_mixture(group_specs, obs, splitter, prior_weight, streams=None, quantized=False, categorical=False):
     """The joint (multivariate) mixtures of a group of dense continuous
     labels whose observations belong to the same trials.
 
@@ -267,7 +288,19 @@ def joint_mixture(group_specs, obs, splitter, prior_weight, streams=None, quanti
     returns the steps q [D] (0 for a dense label) as one more, last element.
     A quantized log kind's observations enter through the univariate
     transform of label_spec -- qloguniform: log(max(o, max(EPS, exp(low)))),
-    qlognormal: log(max(o, EPS)) -- so an observed 0 builds."""
+    qlognormal: log(max(o, EPS)) -- so an observed 0 builds.
+
+    categorical=True accepts the categorical kinds (JOINT_CAT_KINDS) too and
+    returns, as two further last elements, upper [D] (int32: the number of
+    categories, 0 for any other label) and the categorical labels' priors p
+    concatenated (uniform for 'randint').  A categorical label's column of
+    the means holds the observed categories (row 0: 0), its column of the
+    sigmas ones, its dims entry kind TPE_CATEGORICAL and the stream.  The
+    weights are those of the group's first non-categorical label; a group of
+    categorical labels alone has W = w / w.sum() with w = concatenate([
+    prior_weight], linear_forgetting_weights(n, 25)) in Splitter.split order
+    -- what every continuous label's weights are up to rounding, which is
+    asserted where the group has one."""
     from .engine import JOINT_DIM_DTYPE
     group = [(g.label, g.kind, g.args) if hasattr(g, 'kind') else tuple(g) for g in group_specs]
     D = len(group)
@@ -275,8 +308,31 @@ def joint_mixture(group_specs, obs, splitter, prior_weight, streams=None, quanti
     dims = np.zeros(D, dtype=JOINT_DIM_DTYPE)
     sides = [[], []]
     steps = []
+    uppers, cat_p = [], []
     ids0 = None
     for d, (label, kind, args) in enumerate(group):
+        if categorical and kind in JOINT_CAT_KINDS:
+            upper, p = joint_prior(kind, args, quantized, True)[-2:]
+            uppers.append(upper)
+            cat_p.append(p)
+            if quantized:
+                steps.append(0.0)
+            dims[d]['kind'] = L.TPE_CATEGORICAL
+            dims[d]['stream'] = d if streams is None else int(streams[d])
+            oi, ov = obs[label]
+            oi = np.asarray(oi)
+            if ids0 is None:
+                ids0 = oi
+            elif not np.array_equal(ids0, oi):
+                raise ValueError('joint group: label %r is not observed in the same trials as %r'
+                                 % (label, group[0][0]))
+            for side, o in enumerate(splitter.split(oi, ov)):
+                o = np.asarray(o, dtype=float)
+                if len(o) and not np.all((o >= 0) & (o < upper) & (o == np.floor(o))):
+                    raise ValueError('joint group: label %r has an observation outside its categories' % (label,))
+                sides[side].append((None, np.concatenate([[0.0], o]), np.ones(len(o) + 1)))
+            continue
+        uppers.append(0)
         log, bounded, low, high, pmu, psig = joint_prior(kind, args, quantized)[:6]
         floor = None
         if quantized:
@@ -309,8 +365,12 @@ def joint_mixture(group_specs, obs, splitter, prior_weight, streams=None, quanti
             sides[side].append((w[at], np.concatenate([[pmu], o]), sigma[at]))
     out = [dims]
     for cols in sides:
-        W = cols[0][0]
-        for w, _, _ in cols[1:]:
+        ws = [c[0] for c in cols if c[0] is not None]
+        if len(ws) < len(cols):   # a categorical label: the weights by their rule
+            w = np.concatenate([[pw], linear_forgetting_weights(len(cols[0][1]) - 1, DEFAULT_LF)])
+            ws.append(w / w.sum())
+        W = ws[0]
+        for w in ws[1:]:
             # equal up to the rounding of each label's own normalising sum
             assert len(w) == len(W) and np.allclose(w, W, rtol=4e-16 * (len(W) + 1), atol=0.0), \
                 'joint group: weights differ between labels'
@@ -318,6 +378,9 @@ def joint_mixture(group_specs, obs, splitter, prior_weight, streams=None, quanti
                 np.ascontiguousarray(np.stack([c[2] for c in cols], axis=1))]
     if quantized:
         out.append(np.asarray(steps, dtype=np.float64))
+    if categorical:
+        out.append(np.asarray(uppers, dtype=np.int32))
+        out.append(np.concatenate(cat_p).astype(np.float64) if cat_p else np.zeros(0))
     return tuple(out)
 
 

@@ -20,7 +20,8 @@
 
 Extra keyword arguments (not in the reference): `multivariate` (True: the
 unconditional dense continuous labels are modelled jointly, see `suggest`
-(joint_quantized=True: the quantized continuous ones with them);
+(joint_quantized=True: the quantized continuous ones with them,
+joint_categorical=True: the categorical ones too);
 with `group=True` also those that share an hp.choice branch, one joint group
 per branch),
 `precision` ('f64'; 'f32'
@@ -192,13 +193,28 @@ def _resident_posterior(eng, domain, trials, specs, view, gathered, gamma, prior
     return n_docs, None
 
 
+def _joins(spec, kinds):
+    """Whether a label's kind is one of `kinds` and the label can join a
+    joint group: a 'categorical' label (hp.pchoice) whose p has a zero entry
+    cannot -- its rows would not be strictly positive -- and keeps the
+    independent round (logged)."""
+    if spec.kind not in kinds:
+        return False
+    if spec.kind == 'categorical' and not np.all(np.asarray(spec.args['p'], dtype=float) > 0.0):
+        logger.info('multivariate TPE: label %r has a zero prior probability, using the independent '
+                    'path for it' % (spec.label,))
+        return False
+    return True
+
+
 def joint_group(domain, specs, obs=None, kinds=_post.JOINT_KINDS):
     """The joint group of a space: its unconditional labels of a dense
     continuous kind (or of any of `kinds`: joint_quantized=True passes the
-    quantized kinds too), in the order of `specs` -- or None (with the reason
-    logged) when multivariate TPE falls back to the independent path: fewer
-    than two such labels, or (obs given: label -> (idxs, vals)) labels that
-    are not observed in exactly the same trials."""
+    quantized kinds too, joint_categorical=True the categorical ones), in the
+    order of `specs` -- or None (with the reason logged) when multivariate
+    TPE falls back to the independent path: fewer than two such labels, or
+    (obs given: label -> (idxs, vals)) labels that are not observed in
+    exactly the same trials."""
     free = getattr(domain, '_hyperopt_amd_free', None)
     if free is None:
         free = _labels.unconditional_labels(domain.expr)
@@ -206,7 +222,7 @@ def joint_group(domain, specs, obs=None, kinds=_post.JOINT_KINDS):
             domain._hyperopt_amd_free = free
         except AttributeError:
             pass
-    group = [k for k, s in specs.items() if k in free and s.kind in kinds]
+    group = [k for k, s in specs.items() if k in free and _joins(s, kinds)]
     if len(group) < 2:
         logger.info('multivariate TPE: %d joint label(s), using the independent path' % len(group))
         return None
@@ -240,7 +256,7 @@ def joint_groups(domain, specs, obs=None, kinds=_post.JOINT_KINDS):
             pass
     by_sig = {}
     for k, s in specs.items():
-        if s.kind in kinds:
+        if _joins(s, kinds):
             by_sig.setdefault(sigs[k], []).append(k)
     groups = [g for sig, g in by_sig.items() if len(g) >= 2]
     # (by_sig keeps the order of each signature's first label in specs)
@@ -263,7 +279,7 @@ def joint_groups(domain, specs, obs=None, kinds=_post.JOINT_KINDS):
 
 
 def _joint_rounds(eng, domain, trials, specs, gathered, gamma, prior_weight, seed, ids, n_candidates,
-                  group=False, quantized=False):
+                  group=False, quantized=False, categorical=False):
     """One joint round per id and joint group: [label -> value] per id, or
     None when the call falls back to the independent path.  group=False: the
     unconditional group alone (joint_group), slot 0; group=True: every group
@@ -274,9 +290,12 @@ def _joint_rounds(eng, domain, trials, specs, gathered, gamma, prior_weight, see
     independent round.  One set_joint_group per group, one
     joint_suggest_batch for all groups and ids.  quantized=True: the groups
     take the quantized kinds too (posterior.JOINT_QUANT_KINDS), their values
-    rounded to the label's grid; every group value enters the document
-    through labels.coerce."""
-    kinds = _post.JOINT_KINDS + (_post.JOINT_QUANT_KINDS if quantized else ())
+    rounded to the label's grid; categorical=True: and the categorical kinds
+    (posterior.JOINT_CAT_KINDS; a label with a zero prior probability stays
+    out), their values category indices; every group value enters the
+    document through labels.coerce."""
+    kinds = _post.JOINT_KINDS + (_post.JOINT_QUANT_KINDS if quantized else ()) + \
+        (_post.JOINT_CAT_KINDS if categorical else ())
     labels = list(specs)
     tids, losses, obs = gathered or _history.gather(domain, trials, labels)
     if group:
@@ -292,9 +311,11 @@ def _joint_rounds(eng, domain, trials, specs, gathered, gamma, prior_weight, see
     eng.clear_joint_groups()
     for slot, g in groups:
         mix = _post.joint_mixture([specs[k] for k in g], obs, splitter, prior_weight,
-                                  streams=[labels.index(k) for k in g], quantized=quantized)
+                                  streams=[labels.index(k) for k in g], quantized=quantized,
+                                  categorical=categorical)
+        cat = dict(upper=mix[-2], cat_p=mix[-1], prior_weight=prior_weight) if categorical else {}
         eng.set_joint_group(slot, _engine.L.TPE_JOINT_STREAM - slot, *mix[:7],
-                            q=mix[7] if quantized else None)
+                            q=mix[7] if quantized else None, **cat)
     won = eng.joint_suggest_batch(seed, ids, n_candidates)
     out = [{} for _ in ids]
     for slot, g in groups:
@@ -311,7 +332,7 @@ def suggest(new_ids, domain, trials, seed,
             gamma=_default_gamma,
             linear_forgetting=_default_linear_forgetting,
             precision='f64', device=0, batch=False, posterior_builder='auto', devices=None,
-            multivariate=False, group=False, joint_quantized=False):
+            multivariate=False, group=False, joint_quantized=False, joint_categorical=False):
     """tpe.py:823-916.  Past the startup phase one document for new_ids[0],
     like the reference; `batch` (not in the reference) asks for one document
     per new_id:
@@ -357,9 +378,23 @@ def suggest(new_ids, domain, trials, seed,
     drawn from its component and rounded to its grid, and its factor in the
     joint density is the component's mass on the value's rounding interval
     ("Quantized labels").  The groups and their slots
-    are those of the widened kinds; categorical labels keep the independent
-    round.  With the default every call returns the documents it always
-    did: a quantized label then keeps its independent round.
+    are those of the widened kinds.  With the default every call returns
+    the documents it always did: a quantized label then keeps its
+    independent round.
+
+    joint_categorical=True (with multivariate=True) lets the joint groups
+    hold hp.choice, hp.pchoice and hp.randint labels as well (optimizer x
+    learning rate, kernel x C): a trial's kernel in such a dimension puts
+    ([c == observed] + a p[c]) / (1 + a) on category c, a = C prior_weight /
+    K with K the side's components -- Optuna's categorical kernel with this
+    label's prior p in place of the uniform one -- and the prior component p
+    itself ("Categorical labels in joint groups").
+    With group=True an unconditional hp.choice index joins the
+    unconditional group, the labels inside its branches keep the group of
+    their own signature.  An hp.pchoice label with a zero probability stays
+    out of every group.  The groups and their slots are those of the widened
+    kinds; the keyword composes with joint_quantized and group, and with the
+    default every call returns the documents it always did.
 
     precision='f32' runs the exact fp64 path: a round draws every candidate
     and proves all but ~0.5 % of them out of the race from per-sub-bin score
@@ -378,12 +413,15 @@ def suggest(new_ids, domain, trials, seed,
         raise ValueError('group=True needs multivariate=True')
     if joint_quantized and not multivariate:
         raise ValueError('joint_quantized=True needs multivariate=True')
+    if joint_categorical and not multivariate:
+        raise ValueError('joint_categorical=True needs multivariate=True')
     if multivariate and devices and len(list(devices)) > 1:
         raise ValueError('multivariate=True runs on one device')
     kw = dict(prior_weight=prior_weight, n_startup_jobs=n_startup_jobs,
               n_EI_candidates=n_EI_candidates, gamma=gamma, linear_forgetting=linear_forgetting,
               precision=precision, device=device, posterior_builder=posterior_builder,
-              devices=devices, multivariate=multivariate, group=group, joint_quantized=joint_quantized)
+              devices=devices, multivariate=multivariate, group=group, joint_quantized=joint_quantized,
+              joint_categorical=joint_categorical)
     specs = specs_of(domain)
     labels = list(specs)
     # the device-resident history's view of the trials (None when the fast
@@ -434,7 +472,8 @@ def suggest(new_ids, domain, trials, seed,
     if res is None:
         res = round_call()
     joint = _joint_rounds(eng, domain, trials, specs, gathered, gamma, prior_weight, seed, ids,
-                          n_EI_candidates, group=group, quantized=bool(joint_quantized)) if multivariate else None
+                          n_EI_candidates, group=group, quantized=bool(joint_quantized),
+                          categorical=bool(joint_categorical)) if multivariate else None
     rval = []
     for j, new_id in enumerate(ids):
         values = {s.label: _labels.coerce(s.kind, res[j][i]['value'])

@@ -459,6 +459,38 @@ int tpe_joint_set_group_q(tpe_ctx *ctx, int32_t slot, uint32_t pick_stream, cons
                           const double *q /* [n_dims], 0 = dense */, int32_t n_dims, int32_t n_below,
                           const double *wb, const double *mub, const double *sigb, int32_t n_above,
                           const double *wa, const double *mua, const double *siga);
+/* Categorical dimensions in a joint group.  upper[d] = C_d > 0 makes dimension
+ * d categorical with categories 0 .. C_d - 1 and prior p_d, the next C_d
+ * entries of cat_p (upper NULL or all zeros: tpe_joint_set_group_q, the same
+ * instantiations and bits; cat_p and prior_weight are then not read).  With
+ * K_S = n_S the side's components and a_Sd = C_d prior_weight / K_S the factor
+ * of category x in component k is
+ *   r_0d[x] = p_d[x]                                        (the prior),
+ *   r_td[x] = ([x == o_td] + a_Sd p_d[x]) / (1 + a_Sd)      (trial t observed o_td),
+ *   f_S(x) = (1/A_S) sum_k W_k prod_d g_kd(x_d),  g_kd(x_d) = r_kd[x_d],  m_kd = 1:
+ * A_S, the pick thresholds and the pick stream are those of the group without
+ * the dimension, and it has no Jacobian term.  The observed category of trial t
+ * travels in mu*[k][d] (k >= 1), integer-valued; row 0 and sig*[.][d] of the
+ * dimension are not read, nor are kind, flags, low and high of dims[d] -- its
+ * stream is.  Values are doubles holding the category index.  A value that is
+ * no integer in [0, C_d) has factor 0: lpdf -inf on both sides; NaN gives NaN.
+ * The draw of dimension d takes word x of the Philox counter (g, 0, stream_d,
+ * round) -- the categorical layout of the independent round -- and the first
+ * category c with ceil(cdf_kd[c] 2^32) above it, cdf_kd the running sum of
+ * r_kd in category order over its total, the last entry 1.
+ * TPE_ERR_ARG: upper[d] < 0; q[d] > 0 and upper[d] > 0; a p entry that is not
+ * positive and finite; a p whose sum is not within 1e-9 of 1; an observed
+ * category that is no integer in [0, upper[d]); prior_weight not positive and
+ * finite; n_dims + (number of quantized dimensions) > 128 -- a categorical
+ * dimension keeps one value per candidate in LDS, like a dense one.  A group
+ * with a categorical dimension runs the quantized variant of the round. */
+int tpe_joint_set_group_c(tpe_ctx *ctx, int32_t slot, uint32_t pick_stream, const tpe_joint_dim *dims,
+                          const double *q /* [n_dims], 0 = dense; NULL */,
+                          const int32_t *upper /* [n_dims], 0 = not categorical */,
+                          const double *cat_p /* the categorical dimensions' priors, concatenated */,
+                          double prior_weight, int32_t n_dims, int32_t n_below, const double *wb,
+                          const double *mub, const double *sigb, int32_t n_above, const double *wa,
+                          const double *mua, const double *siga);
 int tpe_joint_clear_groups(tpe_ctx *ctx);
 int tpe_joint_draw_group(tpe_ctx *ctx, int32_t slot, uint64_t seed, uint32_t round, int64_t n,
                          int64_t cand_offset, double *values, int32_t *comp);

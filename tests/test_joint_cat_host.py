@@ -1,0 +1,236 @@
+"""Categorical labels in joint TPE groups, host side (CPU): the numpy
+definition (tests/joint_cat_reference.py) against its own statements,
+posterior.joint_mixture(categorical=True) and its weight rule, the widened
+joint_group / joint_groups, and -- through the fp64 draw port -- the
+conditions test_joint_cat_gpu.py rests on: the committed draw seeds exclude
+nothing and every committed round's best configuration leads every other by a
+clear margin."""
+import inspect
+import logging
+
+import numpy as np
+import pytest
+
+from hyperopt_amd import hp, posterior as P, tpe
+from hyperopt_amd.base import Domain, Trials
+from tests import joint_cat_cases as CC
+
+WIDE = P.JOINT_KINDS + P.JOINT_CAT_KINDS
+
+
+# -- the definition -----------------------------------------------------------------
+@pytest.mark.parametrize('name', sorted(CC.GROUPS))
+def test_rows_sum_to_one_and_masses_are_one(name):
+    ref = CC.group(name)
+    ncat = 0
+    for side in ('below', 'above'):
+        m = ref.masses(side)
+        for d, dim in enumerate(ref.dims):
+            if not dim.upper:
+                continue
+            ncat += 1
+            r = ref.rows(side, d)
+            assert r.shape == (len(ref.sides[side][0]), dim.upper) and np.all(r > 0.0)
+            assert np.all(np.abs(r.sum(axis=1) - 1.0) <= 4e-16 * dim.upper)
+            assert np.all(m[:, d] == 1.0)
+            assert np.array_equal(r[0], dim.p)
+    assert ncat >= 2
+
+
+def test_one_dimension_is_the_mixture_of_rows():
+    ref = CC.group('c1')
+    x = np.arange(3.0)[:, None]
+    for side in ('below', 'above'):
+        W = ref.sides[side][0]
+        want = np.log(W @ ref.rows(side, 0))
+        assert np.allclose(ref.joint_lpdf(x, side), want, rtol=0.0, atol=1e-14)
+    # the trial's kernel: a = C pw / K on the side's own K
+    r = ref.rows('below', 0)
+    a = 3 * 1.0 / 2
+    o = int(ref.sides['below'][1][1, 0])
+    want = np.full(3, a / 3.0)
+    want[o] += 1.0
+    assert np.allclose(r[1], want / (1.0 + a), rtol=1e-15)
+    odd = np.array([[3.0], [-1.0], [0.5], [np.nan]])
+    got = ref.joint_lpdf(odd, 'below')
+    assert np.all(got[:3] == -np.inf) and np.isnan(got[3])
+
+
+def test_group_shapes():
+    for name, (Dn, Kb, Ka, _, _, _) in CC.GROUPS.items():
+        ref = CC.group(name)
+        assert ref.D == Dn and len(ref.sides['below'][0]) == Kb and len(ref.sides['above'][0]) == Ka
+        assert Dn + int(np.count_nonzero(ref.steps)) <= 128
+        assert len(ref.cat_p) == int(ref.uppers.sum())
+    assert np.all(CC.group('c33_cat').uppers > 0) and np.all(CC.group(CC.ALL_CAT).uppers > 0)
+    mixed = CC.group('c5_k300')
+    kinds = [(bool(d.upper), d.q is not None) for d in mixed.dims]
+    assert (True, False) in kinds and (False, True) in kinds and (False, False) in kinds
+    for name in ('c9', 'c33'):
+        ref = CC.group(name)
+        assert np.count_nonzero(ref.uppers) >= 2 and np.count_nonzero(ref.steps) >= 3
+    assert CC.group('c_wide').uppers.tolist() == [0, 1000]
+    vals = CC.group(CC.ALL_CAT).port_draw(6, 5, np.arange(300, dtype=np.uint64))[1]
+    assert len(np.unique(vals, axis=0)) <= 30                       # real ties
+
+
+# -- joint_mixture(categorical=True) ----------------------------------------------------
+def _history(n_trials, seed):
+    rng = np.random.RandomState(seed)
+    tids = np.arange(n_trials) * 2 + 1
+    losses = np.round(rng.randn(n_trials), 1)
+    group = [('u', 'uniform', dict(low=-5.0, high=5.0)), ('r', 'randint', dict(upper=4)),
+             ('c', 'categorical', dict(upper=3, p=[0.5, 0.3, 0.2])), ('q', 'quniform', dict(low=0.0, high=8.0, q=2.0))]
+    obs = {'u': (tids.copy(), rng.uniform(-5, 5, n_trials)), 'r': (tids.copy(), rng.randint(0, 4, n_trials)),
+           'c': (tids.copy(), rng.randint(0, 3, n_trials)),
+           'q': (tids.copy(), np.rint(rng.uniform(0, 8, n_trials) / 2.0) * 2.0)}
+    return group, tids, losses, obs
+
+
+@pytest.mark.parametrize('n_trials,gamma', [(200, 0.25), (200, 4.0), (30, 0.25), (1, 0.25), (0, 0.25)])
+def test_mixture_carries_the_categories_and_the_weight_rule(n_trials, gamma):
+    """Observed categories in the means, upper and p as last elements, and W:
+    the first continuous label's in a mixed group, concatenate([pw], lfw) /
+    sum in an all-categorical one -- the two within 4e-16 (K + 1) relative,
+    with the ramp (the above side of 200 trials) and without."""
+    group, tids, losses, obs = _history(n_trials, 300 + n_trials)
+    sp = P.Splitter(tids, losses, gamma)
+    mixed = P.joint_mixture(group[:3], obs, sp, 1.0, categorical=True)
+    assert len(mixed) == 9
+    dims, wb, mub, sigb, wa, mua, siga, upper, cat_p = mixed
+    assert upper.tolist() == [0, 4, 3] and upper.dtype == np.int32
+    assert cat_p.tolist() == [0.25] * 4 + [0.5, 0.3, 0.2]
+    assert dims['stream'].tolist() == [0, 1, 2]
+    cats = P.joint_mixture(group[1:3], obs, sp, 1.0, categorical=True)
+    dense = P.joint_mixture(group[:1], obs, sp, 1.0)
+    for side, (W, mu, Wc, Wd) in enumerate(((wb, mub, cats[1], dense[1]), (wa, mua, cats[4], dense[4]))):
+        n = len(W) - 1
+        for d, label in ((1, 'r'), (2, 'c')):
+            o = sp.split(*obs[label])[side]
+            assert np.array_equal(mu[1:, d], np.asarray(o, dtype=float))
+        w = np.concatenate([[1.0], P.linear_forgetting_weights(n, 25)])
+        assert np.array_equal(Wc, w / w.sum())
+        assert np.array_equal(W, Wd)                         # the first non-categorical label's
+        assert np.allclose(Wc, Wd, rtol=4e-16 * (n + 2), atol=0.0)
+        if n_trials == 200 and side == 1:
+            assert n > 25 and len(np.unique(w)) > 2          # the ramp
+    allq = P.joint_mixture(group, obs, sp, 1.0, quantized=True, categorical=True)
+    assert len(allq) == 10 and allq[7].tolist() == [0.0, 0.0, 0.0, 2.0] and allq[8].tolist() == [0, 4, 3, 0]
+    assert np.array_equal(allq[0][:3], dims) and np.array_equal(allq[1], wb) and np.array_equal(allq[4], wa)
+    for i in (2, 3, 5, 6):
+        assert np.array_equal(allq[i][:, :3], mixed[i])
+
+
+def test_default_call_is_unchanged():
+    group, tids, losses, obs = _history(30, 5)
+    sp = P.Splitter(tids, losses, 0.25)
+    for kw in (dict(), dict(quantized=True), dict(categorical=False)):
+        with pytest.raises(ValueError):
+            P.joint_mixture(group[:3], obs, sp, 1.0, **kw)
+        with pytest.raises(ValueError):
+            P.joint_prior('randint', dict(upper=3), **kw)
+        with pytest.raises(ValueError):
+            P.joint_prior('categorical', dict(upper=2, p=[0.5, 0.5]), **kw)
+    a = P.joint_mixture(group[:1], obs, sp, 1.0)
+    b = P.joint_mixture(group[:1], obs, sp, 1.0, categorical=True)
+    assert len(a) == 7 and len(b) == 9 and b[7].tolist() == [0] and len(b[8]) == 0
+    for x, y in zip(a, b):
+        assert np.array_equal(x, y)
+    assert P.joint_prior('uniform', dict(low=0.0, high=2.0), categorical=True) == \
+        (False, True, 0.0, 2.0, 1.0, 2.0, 0, None)
+    got = P.joint_prior('randint', dict(upper=4), categorical=True)
+    assert got[6] == 4 and got[7].tolist() == [0.25] * 4
+    with pytest.raises(ValueError):
+        P.joint_prior('categorical', dict(upper=3, p=[0.5, 0.5, 0.0]), categorical=True)
+    assert P.JOINT_CAT_KINDS == ('randint', 'categorical')
+    bad = dict(obs)
+    bad['r'] = (obs['r'][0], obs['r'][1] + 0.5)
+    with pytest.raises(ValueError):
+        P.joint_mixture(group[:3], bad, sp, 1.0, categorical=True)
+
+
+# -- groups -------------------------------------------------------------------------------
+def test_a_number_and_a_choice_group_only_with_the_keyword():
+    d = Domain(lambda c: 0.0, {'lr': hp.loguniform('lr', -5, 0), 'opt': hp.choice('opt', ['sgd', 'adam', 'rms'])})
+    s = tpe.specs_of(d)
+    assert tpe.joint_group(d, s) is None and tpe.joint_groups(d, s) == []
+    assert tpe.joint_group(d, s, None, WIDE) == ['lr', 'opt']
+    assert tpe.joint_groups(d, s, None, WIDE) == [(0, ['lr', 'opt'])]
+    for fn in (tpe.joint_group, tpe.joint_groups):
+        ps = list(inspect.signature(fn).parameters.values())
+        assert [p.name for p in ps[:3]] == ['domain', 'specs', 'obs'] and ps[3].default == P.JOINT_KINDS
+
+
+def cond_space():
+    return {'x': hp.uniform('x', -5, 5),
+            'o': hp.choice('o', [{'k': hp.choice('k', ['a', 'b', 'c']), 'u': hp.uniform('u', 0, 4)},
+                                 {'e': hp.uniform('e', 0, 1)}])}
+
+
+def test_a_choice_index_and_a_uniform_inside_one_branch():
+    d = Domain(lambda c: 0.0, cond_space())
+    s = tpe.specs_of(d)
+    assert tpe.joint_groups(d, s) == []
+    # the outer index joins the unconditional group; the inner index and u share their branch's group
+    assert tpe.joint_groups(d, s, None, WIDE) == [(0, ['o', 'x']), (1, ['k', 'u'])]
+    assert tpe.joint_group(d, s, None, WIDE) == ['o', 'x']
+
+
+def test_a_zero_probability_keeps_the_label_out(caplog):
+    d = Domain(lambda c: 0.0, {'x': hp.uniform('x', 0, 1), 'z': hp.pchoice('z', [(0.5, 'a'), (0.5, 'b'), (0.0, 'c')]),
+                               'p': hp.pchoice('p', [(0.7, 'a'), (0.3, 'b')])})
+    s = tpe.specs_of(d)
+    with caplog.at_level(logging.INFO):
+        assert tpe.joint_group(d, s, None, WIDE) == ['p', 'x']
+    assert any("'z'" in r.getMessage() and 'zero prior probability' in r.getMessage() for r in caplog.records)
+    caplog.clear()
+    with caplog.at_level(logging.INFO):
+        assert tpe.joint_groups(d, s, None, WIDE) == [(0, ['p', 'x'])]
+    assert any("'z'" in r.getMessage() for r in caplog.records)
+    caplog.clear()
+    with caplog.at_level(logging.INFO):
+        assert tpe.joint_group(d, s) is None                  # not asked: no line about z
+    assert not any("'z'" in r.getMessage() for r in caplog.records)
+
+
+def test_keyword_needs_multivariate():
+    domain = Domain(lambda d: 0.0, {'x': hp.uniform('x', 0, 1), 'r': hp.randint('r', 3)})
+    with pytest.raises(ValueError):
+        tpe.suggest([0], domain, Trials(), 0, joint_categorical=True, multivariate=False)
+    with pytest.raises(ValueError):
+        tpe.suggest([0], domain, Trials(), 0, joint_categorical=True)
+    assert inspect.signature(tpe.suggest).parameters['joint_categorical'].default is False
+
+
+# -- what the GPU tests rest on ------------------------------------------------------------
+@pytest.mark.parametrize('case', range(len(CC.DRAWS)))
+def test_committed_draw_seeds_exclude_nothing(case):
+    name, seed, rnd, offset, n = CC.DRAWS[case]
+    ref = CC.group(name)
+    _, vals, excl = ref.port_draw(seed, rnd, offset + np.arange(n, dtype=np.uint64))
+    assert int(excl.sum()) == 0 and np.all(np.isfinite(vals))
+    for d, dim in enumerate(ref.dims):
+        if dim.upper:
+            assert np.all((vals[:, d] >= 0) & (vals[:, d] < dim.upper) & (vals[:, d] == np.floor(vals[:, d])))
+
+
+@pytest.mark.parametrize('case', range(len(CC.ROUNDS)))
+def test_committed_round_seeds_leave_a_margin(case):
+    """The reference alone: the port's candidates exclude nothing and the best
+    reference score leads the best different configuration by more than 1e-9
+    (|ll| + |lg|)."""
+    name, seed, rnd, n = CC.ROUNDS[case]
+    ref = CC.group(name)
+    _, vals, excl = ref.port_draw(seed, rnd, np.arange(n, dtype=np.uint64))
+    assert int(excl.sum()) == 0
+    ll, lg = ref.joint_lpdf(vals, 'below'), ref.joint_lpdf(vals, 'above')
+    assert np.all(np.isfinite(ll)) and np.all(np.isfinite(lg))
+    ok, _ = CC.margin_ok(vals, ll, lg)
+    assert ok
+
+
+def test_layout_round_excludes_nothing():
+    name, seed, rnd, n, first = CC.LAYOUT
+    ref = CC.group(name)
+    _, vals, excl = ref.port_draw(seed, rnd, np.arange(first, dtype=np.uint64))
+    assert int(excl.sum()) == 0 and np.all(np.isfinite(vals))

@@ -2,6 +2,8 @@
 
     python tools/time_joint.py [--dims 32] [--trials 10000] [--reps 20] [--quality] [--out FILE]
     python tools/time_joint.py --groups [--legs loop,batch] [--reps 20] [--out FILE]
+    python tools/time_joint.py --quantized | --categorical [--legs dense,...] [--reps 20] [--out FILE]
+    python tools/time_joint.py --no-timings --quality-quantized | --quality-categorical [--out FILE]
 
 On a synthetic history of `--trials` trials over `--dims` dense continuous
 labels (kinds cycled over uniform / loguniform / normal / lognormal):
@@ -35,6 +37,16 @@ of a checkout without quantized groups, so it runs unchanged there.
 (x - n)^2 + 0.01 (x + n)^2 with x uniform(-5, 5) and n quniform(-5, 5, 1):
 independent, multivariate=True, and multivariate=True with
 joint_quantized=True.  A record, not a gate.
+
+--categorical: the d32 shape dense and with every fourth label replaced by
+randint(8) (categorical_timings), the shapes of --quantized; --legs
+dense,categorical selects.  The dense leg is --quantized --legs dense, which a
+checkout without categorical groups runs too.
+
+--quality-categorical: fmin for 100 evaluations over seeds 0..9 on
+(x - [-3, 0, 3][k])^2 + 0.1 k with x uniform(-5, 5) and k a 3-way choice:
+independent, multivariate=True, and multivariate=True with
+joint_categorical=True.  A record, not a gate.
 
 Prints one JSON document (and writes it to --out).
 """
@@ -231,6 +243,30 @@ def quantized_history(n_dims, n_trials, step=0.25):
     return out, tids, losses, obs
 
 
+def _round_shapes(eng, reps):
+    """Slot 0's rounds: joint_suggest at 24 candidates, joint_suggest_batch
+    at 24 candidates for 4096 ids, joint_suggest at 2^16 candidates -- medians
+    and the range over `reps` calls of the device time between HIP events and
+    of the wall time."""
+    res = {}
+    ids = list(range(1000, 1000 + 4096))
+    shapes = (('one_24', lambda r: eng.joint_suggest(1, 24, round=r)),
+              ('batch_4096x24', lambda r: eng.joint_suggest_batch(1, [i + r for i in ids], 24)),
+              ('one_65536', lambda r: eng.joint_suggest(1, 1 << 16, round=r)))
+    for name, fn in shapes:
+        fn(0)
+        dev, wall = [], []
+        for r in range(reps):
+            t = time.perf_counter()
+            fn(r + 1)
+            wall.append((time.perf_counter() - t) * 1e3)
+            dev.append(eng.last_timing()[1])
+        res[name] = dict(device_ms=float(np.median(dev)), device_min_ms=float(np.min(dev)),
+                         device_max_ms=float(np.max(dev)), wall_ms=float(np.median(wall)),
+                         wall_min_ms=float(np.min(wall)), wall_max_ms=float(np.max(wall)))
+    return res
+
+
 def quantized_timings(reps, legs=('dense', 'quantized'), n_dims=32, n_trials=10000):
     """Medians (and the range) over `reps` calls of the device time between
     HIP events and of the wall time of: joint_suggest at 24 candidates,
@@ -255,26 +291,82 @@ def quantized_timings(reps, legs=('dense', 'quantized'), n_dims=32, n_trials=100
             eng.set_joint_group(0, L.TPE_JOINT_STREAM, *mix[:7], q=mix[7])
         res = out[leg] = dict(dims=n_dims, k_below=len(mix[1]), k_above=len(mix[4]),
                               quantized_dims=int(np.count_nonzero(mix[7])) if leg != 'dense' else 0)
-        ids = list(range(1000, 1000 + 4096))
-        shapes = (('one_24', lambda r: eng.joint_suggest(1, 24, round=r)),
-                  ('batch_4096x24', lambda r: eng.joint_suggest_batch(1, [i + r for i in ids], 24)),
-                  ('one_65536', lambda r: eng.joint_suggest(1, 1 << 16, round=r)))
-        for name, fn in shapes:
-            fn(0)
-            dev, wall = [], []
-            for r in range(reps):
-                t = time.perf_counter()
-                fn(r + 1)
-                wall.append((time.perf_counter() - t) * 1e3)
-                dev.append(eng.last_timing()[1])
-            res[name] = dict(device_ms=float(np.median(dev)), device_min_ms=float(np.min(dev)),
-                             device_max_ms=float(np.max(dev)), wall_ms=float(np.median(wall)),
-                             wall_min_ms=float(np.min(wall)), wall_max_ms=float(np.max(wall)))
+        res.update(_round_shapes(eng, reps))
     if 'dense' in out and 'quantized' in out:
         for name in ('one_24', 'batch_4096x24', 'one_65536'):
             out['quantized_over_dense_device_' + name] = (out['quantized'][name]['device_ms'] /
                                                           out['dense'][name]['device_ms'])
     eng.close()
+    return out
+
+
+def categorical_history(n_dims, n_trials, upper=8):
+    """history() with every fourth label (d % 4 == 3) replaced by
+    randint(upper), its observations uniform over the categories."""
+    group, tids, losses, obs = history(n_dims, n_trials)
+    rng = np.random.RandomState(1)
+    out = []
+    for d, (label, kind, args) in enumerate(group):
+        if d % 4 == 3:
+            kind, args = 'randint', dict(upper=upper)
+            obs[label] = (tids, rng.randint(0, upper, n_trials))
+        out.append((label, kind, args))
+    return out, tids, losses, obs
+
+
+def categorical_timings(reps, legs=('dense', 'categorical'), n_dims=32, n_trials=10000):
+    """quantized_timings' shapes for the dense d32 group and the group with
+    every fourth label a randint(8) (`mixed`).  The dense leg uses the entry
+    points of a checkout without categorical groups, so it runs unchanged
+    there (--quantized --legs dense on that checkout is the same leg)."""
+    from hyperopt_amd import _lib as L
+    from hyperopt_amd import posterior as P
+    from hyperopt_amd.engine import Engine
+    eng = Engine(0, 'f64')
+    out = {}
+    for leg in legs:
+        eng.clear_joint_groups()
+        if leg == 'dense':
+            group, tids, losses, obs = history(n_dims, n_trials)
+            mix = P.joint_mixture(group, obs, P.Splitter(tids, losses, 0.25), 1.0)
+            eng.set_joint_group(0, L.TPE_JOINT_STREAM, *mix)
+            ncat = 0
+        else:
+            group, tids, losses, obs = categorical_history(n_dims, n_trials)
+            mix = P.joint_mixture(group, obs, P.Splitter(tids, losses, 0.25), 1.0, categorical=True)
+            eng.set_joint_group(0, L.TPE_JOINT_STREAM, *mix[:7], upper=mix[7], cat_p=mix[8], prior_weight=1.0)
+            ncat = int(np.count_nonzero(mix[7]))
+        res = out[leg] = dict(dims=n_dims, k_below=len(mix[1]), k_above=len(mix[4]), categorical_dims=ncat)
+        res.update(_round_shapes(eng, reps))
+    if 'dense' in out and 'categorical' in out:
+        for name in ('one_24', 'batch_4096x24', 'one_65536'):
+            out['categorical_over_dense_device_' + name] = (out['categorical'][name]['device_ms'] /
+                                                            out['dense'][name]['device_ms'])
+    eng.close()
+    return out
+
+
+def quality_categorical(evals=100, seeds=10):
+    import hyperopt_amd as H
+    from hyperopt_amd import hp, tpe
+    space = {'x': hp.uniform('x', -5, 5), 'k': hp.choice('k', [0, 1, 2])}
+    centre = (-3.0, 0.0, 3.0)
+
+    def loss(d):
+        return (d['x'] - centre[d['k']]) ** 2 + 0.1 * d['k']
+
+    out = {}
+    modes = (('independent', {}), ('multivariate', dict(multivariate=True)),
+             ('multivariate_joint_categorical', dict(multivariate=True, joint_categorical=True)))
+    for name, kw in modes:
+        best = []
+        for seed in range(seeds):
+            trials = H.Trials()
+            H.fmin(loss, space, algo=partial(tpe.suggest, **kw), max_evals=evals, trials=trials,
+                   rstate=np.random.RandomState(seed))
+            best.append(float(min(trials.losses())))
+        out[name] = dict(best=best, median=float(np.median(best)))
+    out.update(evals=evals, seeds=seeds, objective='(x - [-3,0,3][k])^2 + 0.1 k, x uniform(-5,5), k choice(3)')
     return out
 
 
@@ -332,7 +424,10 @@ def main(argv):
     ap.add_argument('--groups', action='store_true', help='the loop and batch legs over several groups and ids')
     ap.add_argument('--quantized', action='store_true', help='the dense and quantized d32 legs')
     ap.add_argument('--quality-quantized', action='store_true')
-    ap.add_argument('--legs', default=None, help='--groups: loop,batch; --quantized: dense,quantized')
+    ap.add_argument('--categorical', action='store_true', help='the dense and categorical d32 legs')
+    ap.add_argument('--quality-categorical', action='store_true')
+    ap.add_argument('--legs', default=None,
+                    help='--groups: loop,batch; --quantized: dense,quantized; --categorical: dense,categorical')
     ap.add_argument('--out')
     a = ap.parse_args(argv)
     res = {}
@@ -340,12 +435,16 @@ def main(argv):
         res['groups'] = groups_timings(a.reps, legs=tuple((a.legs or 'loop,batch').split(',')))
     elif a.quantized:
         res['quantized'] = quantized_timings(a.reps, legs=tuple((a.legs or 'dense,quantized').split(',')))
+    elif a.categorical:
+        res['categorical'] = categorical_timings(a.reps, legs=tuple((a.legs or 'dense,categorical').split(',')))
     elif not a.no_timings:
         res['timings'] = timings(a.dims, a.trials, a.reps)
     if a.quality:
         res['quality'] = quality()
     if a.quality_quantized:
         res['quality_quantized'] = quality_quantized()
+    if a.quality_categorical:
+        res['quality_categorical'] = quality_categorical()
     txt = json.dumps(res, indent=1, sort_keys=True)
     print(txt)
     if a.out:
