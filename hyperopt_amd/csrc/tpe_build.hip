@@ -53,7 +53,7 @@ constexpr int kParzenBlock = 1024;
 // each ~0.2 ms (r5an).  Per component the arithmetic is unchanged; the
 // loops' reductions are counts, min / max and flags (order-free).
 constexpr int kFoldU = 4;
-constexpr int kMaxLF = 64;          // below-list capacity per label (lf <= kMaxLF)
+constexpr int kMaxLF = kBuildMaxLF;   // below-list capacity per label (lf <= kMaxLF)
 constexpr int kCatChunk = 8192;     // categorical bincount: observations staged in LDS
 constexpr int kCatFewBins = 32;     // categorical bincount by ordered bin compaction up to here
 constexpr int kCatFewChunk = 4096;  // its chunk: 64 groups of 64 (one wave scans the groups)
@@ -1912,7 +1912,14 @@ int build_resident(tpe_ctx* ctx, const double* losses, int64_t n_trials, int64_t
         HIPCHK(ctx, B.only.reserve(n_only));
         put(only_h, n_only * (int64_t)sizeof(int32_t), B.only.p);
         only_d = B.only.p;
-    } else {
+    }
+    // (an upload of orders replaces the ones other labels were built with)
+    if (order_off_d || (int32_t)B.ord_cur.size() != n_labels) B.ord_cur.assign(n_labels, 0);
+    for (int32_t i = 0; i < nl_run; ++i) {
+        const int32_t l = subset ? only_h[i] : i;
+        B.ord_cur[l] = order_off_d && order_off_h[l + 1] > order_off_h[l];
+    }
+    if (!subset) {
         put(losses, T * (int64_t)sizeof(double), B.losses.p);
         if (below_h) put(below_h, T, B.below.p);
         put(mix.data(), (int64_t)mix.size() * (int64_t)sizeof(int64_t), B.mix_off.p);

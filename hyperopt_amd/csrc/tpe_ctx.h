@@ -311,6 +311,7 @@ int settle_build(tpe_ctx* ctx);
 
 // The device posterior builder (tpe_build.hip): the resident history pool
 // and the per-build scratch, grown on demand.
+constexpr int kBuildMaxLF = 64;   // below-list capacity per label: the row length of BuildBufs::below_val
 struct BuildBufs {
     // resident history (tpe_history_reset / tpe_history_append)
     std::vector<tpe_label_spec> specs_h;
@@ -372,6 +373,9 @@ struct BuildBufs {
     std::unique_ptr<BuildTail> pending;   //   its report, not yet applied
     std::vector<int32_t> last_ties;       // the last applied build's tie report (tpe_build_report)
     int32_t last_n_below = 0;
+    // per label: its current above mixture was built with the np.argsort order
+    // that order_off / order hold now (tpe_joint_build_groups reads it there)
+    std::vector<uint8_t> ord_cur;
     // a build's inputs: one pinned staging block, one H2D copy, one scatter
     // launch (tpe_build.hip k_build_inputs); the next build waits for ev_up
     PinVec<uint8_t> h_up, h_rep;

@@ -29,6 +29,9 @@
 //                                     candidates and store every candidate's
 //                                     lpdfs; one workgroup per round slot r
 //                                     reduces its n pairs and draws the winner
+//   k_joint_gather                    tpe_joint_build_groups: W, mu, sigma of every
+//                                     group un-permuted out of the resident
+//                                     univariate build (tpe_build.hip), one launch
 //
 // A context holds up to TPE_JOINT_MAX_GROUPS folded posteriors (slots), each
 // with the Philox stream of its component pick; the scratch is shared.
@@ -818,11 +821,19 @@ struct JointState {   // one slot's folded posterior
     }
 };
 
+struct JBDim {   // one dimension of one group of a tpe_joint_build_groups call (k_joint_gather)
+    double *W, *mu, *sig;   // the slot's arrays
+    int32_t label, group, d, D, Kb, Ka;
+    int32_t upper;          // > 0: categorical
+    int32_t flags;          // 1: the build holds this label's above order; 2: this dimension supplies W
+};
+
 struct JointGroups {   // a context's slots and the scratch they share (one stream: one user at a time)
     std::unique_ptr<JointState> slot[kJMaxGroups];
     DevBuf<double> vals, ll, lg, aux, res, bres;
     DevBuf<double2> part;
-    DevBuf<int32_t> err, comp;
+    DevBuf<int32_t> err, comp, berr;
+    DevBuf<JBDim> btask;
     DevBuf<Partial> partials;
     DevBuf<uint32_t> rounds;
     std::vector<double> hres;
@@ -1093,6 +1104,296 @@ int joint_set(tpe_ctx* ctx, int32_t slot, uint32_t pick_stream, bool only, const
     if (J->zero) return zero_mass(ctx);
     return TPE_OK;
 }
+
+// ------------------------------------------------- device-resident build ----
+// tpe_joint_build_groups: the unfolded arrays W [K], mu and sig [K][D] of every
+// group, gathered from the resident univariate build (tpe_build.hip) instead
+// of uploaded.  posterior.joint_mixture is that build's per-label mixtures
+// read back in trial order -- row 0 the prior, row t + 1 the side's t-th
+// observation -- so one launch un-permutes them: a thread per (dimension,
+// side, sorted slot) reads the slot's trial from the build's own map (the
+// above list's rank beside the sorted keys, or the supplied np.argsort order;
+// the <= kBuildMaxLF below values are ranked in place, as k_parzen ranks them)
+// and stores the slot's (w, mu, sigma) in the trial's row.
+constexpr int32_t kJFlagTie = TPE_JOINT_FLAG_TIE, kJFlagCat = TPE_JOINT_FLAG_CATEGORY,
+                  kJFlagCount = TPE_JOINT_FLAG_COUNT;
+
+__global__ __launch_bounds__(kJBlock) void k_joint_gather(
+    const JBDim* __restrict__ tasks, const tpe_label_spec* __restrict__ specs, const int64_t* __restrict__ p_off,
+    const int32_t* __restrict__ counts, const double* __restrict__ below_val, const double* __restrict__ keys,
+    const int32_t* __restrict__ idx, const int64_t* __restrict__ order_off, const int32_t* __restrict__ order,
+    const int64_t* __restrict__ mix_off, const double* __restrict__ w, const double* __restrict__ sigma,
+    int32_t* __restrict__ flags) {
+    const JBDim t = tasks[blockIdx.y];
+    const int side = blockIdx.z, Ks = side ? t.Ka : t.Kb;
+    const int p = blockIdx.x * kJBlock + threadIdx.x;   // row 0: the prior; above: sorted slot p - 1; else trial p - 1
+    if (p >= Ks) return;
+    const int l = t.label;
+    const int64_t n = counts[2 * l + side];
+    const size_t row0 = side ? (size_t)t.Kb : 0;
+    auto put = [&](int64_t row, double wv, double m, double s) {
+        const size_t k = row0 + (size_t)row;
+        t.mu[k * t.D + t.d] = m;
+        t.sig[k * t.D + t.d] = s;
+        if (t.flags & 2) t.W[k] = wv;
+    };
+    const double pmu = specs[l].prior_mu;
+    if (n != Ks - 1 || (side == 0 && n > tpe_rt::kBuildMaxLF)) {   // not the group's trials: rows that fold, flagged
+        atomicOr(flags + t.group, kJFlagCount);
+        put(p, 1.0 / (double)Ks, t.upper > 0 ? 0.0 : pmu, 1.0);
+        return;
+    }
+    const int64_t off = p_off[l];
+    const double* __restrict__ bv = below_val + (size_t)l * tpe_rt::kBuildMaxLF;
+    if (t.upper > 0) {   // the observed category, in observation order on both sides
+        double c = 0.0;
+        if (p > 0) {
+            c = side ? keys[off + p - 1] : bv[p - 1];
+            if (!(c >= 0.0 && c < (double)t.upper && c == floor(c))) {
+                atomicOr(flags + t.group, kJFlagCat);
+                c = 0.0;   // (k_joint_fold indexes the prior with it)
+            }
+        }
+        put(p, 0.0, c, 1.0);
+        return;
+    }
+    const int64_t o = mix_off[2 * l + side];
+    const double* __restrict__ sk = keys + off;
+    // the prior's slot: np.searchsorted(sorted, prior_mu), side='left' (k_parzen)
+    int64_t pos = 0;
+    if (n == 1) {
+        pos = pmu < (side ? sk[0] : bv[0]) ? 0 : 1;
+    } else if (side == 0) {
+        for (int64_t j = 0; j < n; ++j) pos += bv[j] < pmu ? 1 : 0;
+    } else {
+        int64_t lo = 0, hi = n;
+        while (lo < hi) {
+            const int64_t mid = (lo + hi) >> 1;
+            if (sk[mid] < pmu) lo = mid + 1; else hi = mid;
+        }
+        pos = lo;
+    }
+    if (p == 0) {
+        put(0, w[o + pos], pmu, sigma[o + pos]);
+        return;
+    }
+    if (side == 0) {   // trial p - 1: its rank among the below values, ties by position
+        const int64_t ti = p - 1;
+        const double v = bv[ti];
+        int64_t rank = 0;
+        bool tie = v != v;
+        for (int64_t j = 0; j < n; ++j) {
+            const double vj = bv[j];
+            rank += (vj < v || (vj == v && j < ti)) ? 1 : 0;
+            tie |= j != ti && vj == v;
+        }
+        if (tie) atomicOr(flags + t.group, kJFlagTie);
+        const int64_t j = rank < pos ? rank : rank + 1;
+        put(p, w[o + j], v, sigma[o + j]);
+        return;
+    }
+    const int64_t q = p - 1;   // sorted slot q: the above list's trial r
+    const double v = sk[q];
+    const bool sup = (t.flags & 1) != 0;
+    const int32_t r = sup ? order[order_off[l] + q] : idx[off + q];
+    if (v != v || (!sup && q > 0 && sk[q - 1] == v)) atomicOr(flags + t.group, kJFlagTie);
+    if (r < 0 || r >= n) {
+        atomicOr(flags + t.group, kJFlagCount);
+        return;
+    }
+    const int64_t j = q < pos ? q : q + 1;
+    put((int64_t)r + 1, w[o + j], v, sigma[o + j]);
+}
+
+int joint_build_groups(tpe_ctx* ctx, int32_t n_groups, const int32_t* slots, const uint32_t* pick_streams,
+                       const int64_t* group_off, const int32_t* labels, const int32_t* streams, const double* q,
+                       const int32_t* upper, const double* cat_p, double prior_weight, int32_t* flags) {
+    auto& B = ctx->build;
+    if (n_groups < 1 || n_groups > kJMaxGroups)
+        return ctx->fail(TPE_ERR_ARG, "tpe_joint_build_groups: 1 to " + std::to_string(kJMaxGroups) + " groups");
+    if (!slots || !pick_streams || !group_off || !labels || !streams || !flags)
+        return ctx->fail(TPE_ERR_ARG, "null pointer");
+    TPE_NOT_LSHARD(ctx);
+    const int32_t L = B.n_labels;
+    if (!B.hist_ready || !B.built_ok || B.built_gen != B.hist_gen || L < 1 || (int32_t)B.specs_h.size() != L ||
+        (int32_t)ctx->resident.h_labels.size() != L || ctx->resident.n_labels != L ||
+        (int32_t)B.ord_cur.size() != L)
+        return ctx->fail(TPE_ERR_ARG, "tpe_joint_build_groups: no current build of the resident history");
+    if (group_off[0] != 0) return ctx->fail(TPE_ERR_ARG, "group offsets start at 0");
+    struct GInfo {
+        int32_t D, S, Kb, Ka, ncat;
+        bool quant, cat;
+        std::vector<JDim> hd;
+        std::vector<double> ctab;
+    };
+    std::vector<GInfo> gi(n_groups);
+    std::vector<uint8_t> seen(L, 0), slot_seen(kJMaxGroups, 0);
+    size_t cat_at = 0;
+    int32_t maxK = 1;
+    for (int32_t g = 0; g < n_groups; ++g) {
+        GInfo& I = gi[g];
+        if (slots[g] < 0 || slots[g] >= kJMaxGroups || slot_seen[slots[g]])
+            return ctx->fail(TPE_ERR_ARG, "joint slots are distinct and in [0, " + std::to_string(kJMaxGroups) + ")");
+        slot_seen[slots[g]] = 1;
+        const int64_t a = group_off[g], b = group_off[g + 1];
+        if (b - a < 1 || b - a > kJMaxD)
+            return ctx->fail(TPE_ERR_ARG, "a joint group holds 1 to " + std::to_string(kJMaxD) + " dimensions");
+        const int D = I.D = (int32_t)(b - a);
+        I.hd.resize(D);
+        int S = 0, first = -1;
+        size_t ncat = 0;
+        for (int d = 0; d < D; ++d) {
+            const int32_t l = labels[a + d];
+            if (l < 0 || l >= L) return ctx->fail(TPE_ERR_ARG, "tpe_joint_build_groups: label index out of range");
+            if (seen[l]) return ctx->fail(TPE_ERR_ARG, "tpe_joint_build_groups: a label is listed twice");
+            seen[l] = 1;
+            const tpe_label_spec& s = B.specs_h[l];
+            const double qd = q ? q[a + d] : 0.0;
+            const int32_t C = upper ? upper[a + d] : 0;
+            if (!(qd >= 0.0 && qd < __builtin_inf()))
+                return ctx->fail(TPE_ERR_ARG, "a quantization step is finite and not negative (0: dense)");
+            if (C < 0) return ctx->fail(TPE_ERR_ARG, "upper is the number of categories, 0: not categorical");
+            if (C > 0 && qd > 0.0) return ctx->fail(TPE_ERR_ARG, "a joint dimension is quantized or categorical, not both");
+            if ((C > 0) != (s.kind == TPE_CATEGORICAL) || (C > 0 && C != s.upper))
+                return ctx->fail(TPE_ERR_ARG, "upper must be the resident label's categories, 0 for a continuous label");
+            if (C == 0 && first < 0) first = d;
+            S += qd > 0.0 ? 2 : 1;
+            ncat += (size_t)C;
+        }
+        if (first < 0) return ctx->fail(TPE_ERR_ARG, "a device-built joint group needs a label that is not categorical");
+        if (S > kJMaxD)
+            return ctx->fail(TPE_ERR_ARG, "a joint group holds at most " + std::to_string(kJMaxD) +
+                                              " per-candidate values: dimensions plus quantized dimensions");
+        if (ncat > (size_t)INT32_MAX / 4) return ctx->fail(TPE_ERR_ARG, "too many categories");
+        I.S = S;
+        I.quant = S > D;
+        I.cat = ncat > 0;
+        I.ncat = (int32_t)ncat;
+        const DLabel& f = ctx->resident.h_labels[labels[a + first]];
+        I.Kb = f.nb;
+        I.Ka = f.na;
+        if (I.Kb < 1 || I.Kb > kJMaxBelow || I.Ka < 1)
+            return ctx->fail(TPE_ERR_ARG, "each side needs its prior component (below: at most " +
+                                              std::to_string(kJMaxBelow) + ")");
+        maxK = std::max(maxK, std::max(I.Kb, I.Ka));
+        I.ctab.resize(3 * ncat);
+        if (I.cat) {
+            if (!cat_p) return ctx->fail(TPE_ERR_ARG, "null pointer");
+            if (!(prior_weight > 0.0 && prior_weight < __builtin_inf()))
+                return ctx->fail(TPE_ERR_ARG, "a categorical dimension needs a positive finite prior weight");
+        }
+        size_t at = 0;
+        for (int d = 0, vs = 0, coff = 0; d < D; ++d) {
+            const tpe_label_spec& s = B.specs_h[labels[a + d]];
+            const int32_t C = upper ? upper[a + d] : 0;
+            if (C > 0) {   // tables: p, its running sums in category order, log p (joint_set)
+                double run = 0.0;
+                for (int32_t c = 0; c < C; ++c, ++at, ++cat_at) {
+                    const double pc = cat_p[cat_at];
+                    if (!(pc > 0.0 && pc < __builtin_inf()))
+                        return ctx->fail(TPE_ERR_ARG, "a categorical prior's entries are positive and finite");
+                    run += pc;
+                    I.ctab[at] = pc;
+                    I.ctab[ncat + at] = run;
+                    I.ctab[2 * ncat + at] = std::log(pc);
+                }
+                if (!(std::fabs(run - 1.0) <= 1e-9)) return ctx->fail(TPE_ERR_ARG, "a categorical prior sums to 1");
+                I.hd[d] = JDim{0.0, 0.0, 0.0, 0.0, 0.0, 0.0, 0, streams[a + d], 0, vs, C, coff};
+                vs += 1;
+                coff += C;
+                continue;
+            }
+            const int32_t fl = s.flags & (TPE_HAS_LOW | TPE_HAS_HIGH);
+            if (fl == 3 && !(s.low < s.high)) return ctx->fail(TPE_ERR_VALUE, "low >= high");
+            const double qd = q ? q[a + d] : 0.0;
+            const bool lg = s.kind == TPE_LGMM1;
+            // (an unbounded label's low and high are 0, as joint_prior's)
+            const double lo = fl ? s.low : 0.0, hi = fl ? s.high : 0.0;
+            I.hd[d] = JDim{lo, hi, s.prior_mu, qd, lg ? std::exp(lo) : 0.0, lg ? std::exp(hi) : 0.0,
+                           fl, streams[a + d], lg ? 1 : 0, (I.quant || I.cat) ? vs : d, 0, 0};
+            vs += qd > 0.0 ? 2 : 1;
+        }
+    }
+    HIPCHK(ctx, hipSetDevice(ctx->device));
+    JointGroups* G = jgroups(ctx, true);
+    hipStream_t st = ctx->stream;
+    std::vector<JBDim> tasks;
+    for (int32_t g = 0; g < n_groups; ++g) {
+        const GInfo& I = gi[g];
+        if (!G->slot[slots[g]]) G->slot[slots[g]].reset(new JointState());
+        JointState* J = G->slot[slots[g]].get();
+        J->ready = false;
+        const int D = I.D, Kb = I.Kb, K = I.Kb + I.Ka;
+        HIPCHK(ctx, J->dims.reserve(D));
+        HIPCHK(ctx, J->W.reserve(K));
+        HIPCHK(ctx, J->mu.reserve((size_t)K * D));
+        HIPCHK(ctx, J->sig.reserve((size_t)K * D));
+        HIPCHK(ctx, J->rec.reserve((size_t)K * D));
+        HIPCHK(ctx, J->cst.reserve(K));
+        HIPCHK(ctx, J->P.reserve(K));
+        HIPCHK(ctx, J->logA.reserve(2));
+        HIPCHK(ctx, J->draw.reserve((size_t)Kb * D));
+        HIPCHK(ctx, J->thr.reserve(Kb));
+        if (I.cat) HIPCHK(ctx, J->ctab.reserve(I.ctab.size()));
+        bool first = true;
+        for (int d = 0; d < D; ++d) {
+            const int32_t l = labels[group_off[g] + d], C = I.hd[d].upper;
+            int32_t fl = B.ord_cur[l] ? 1 : 0;
+            if (C == 0 && first) {
+                fl |= 2;
+                first = false;
+            }
+            tasks.push_back(JBDim{J->W.p, J->mu.p, J->sig.p, l, g, d, D, I.Kb, I.Ka, C, fl});
+        }
+    }
+    HIPCHK(ctx, G->err.reserve(1));
+    HIPCHK(ctx, G->btask.reserve(tasks.size()));
+    HIPCHK(ctx, G->berr.reserve(2 * (size_t)n_groups));   // flags | fold errors, per group
+    HIPCHK(ctx, hipMemcpyAsync(G->btask.p, tasks.data(), tasks.size() * sizeof(JBDim), hipMemcpyHostToDevice, st));
+    HIPCHK(ctx, hipMemsetAsync(G->berr.p, 0, 2 * (size_t)n_groups * sizeof(int32_t), st));
+    hipLaunchKernelGGL(k_joint_gather, dim3((unsigned)((maxK + kJBlock - 1) / kJBlock), (unsigned)tasks.size(), 2),
+                       dim3(kJBlock), 0, st, G->btask.p, B.specs.p, B.p_off.p, B.counts.p, B.below_val.p, B.keys.p,
+                       B.idx.p, B.order_off.p, B.order.p, B.mix_off.p, B.w.p, B.sigma.p, G->berr.p);
+    HIPCHK(ctx, hipGetLastError());
+    for (int32_t g = 0; g < n_groups; ++g) {
+        const GInfo& I = gi[g];
+        JointState* J = G->slot[slots[g]].get();
+        if (I.cat)
+            HIPCHK(ctx, hipMemcpyAsync(J->ctab.p, I.ctab.data(), I.ctab.size() * sizeof(double), hipMemcpyHostToDevice,
+                                       st));
+        HIPCHK(ctx, hipMemcpyAsync(J->dims.p, I.hd.data(), I.D * sizeof(JDim), hipMemcpyHostToDevice, st));
+        const int K = I.Kb + I.Ka;
+        hipLaunchKernelGGL(k_joint_fold, dim3((K + kJBlock - 1) / kJBlock), dim3(kJBlock), 0, st, J->dims.p, I.D, I.Kb,
+                           I.Ka, J->W.p, J->mu.p, J->sig.p, J->rec.p, J->cst.p, J->P.p, J->draw.p, prior_weight,
+                           I.cat ? J->ctab.p : nullptr);
+        HIPCHK(ctx, hipGetLastError());
+        hipLaunchKernelGGL(k_joint_fold_sum, dim3(2), dim3(kJBlock), 0, st, J->P.p, I.Kb, I.Ka, J->logA.p, J->thr.p,
+                           G->berr.p + n_groups + g);
+        HIPCHK(ctx, hipGetLastError());
+    }
+    std::vector<int32_t> eh(2 * (size_t)n_groups);
+    HIPCHK(ctx, hipMemcpyAsync(eh.data(), G->berr.p, eh.size() * sizeof(int32_t), hipMemcpyDeviceToHost, st));
+    HIPCHK(ctx, hipStreamSynchronize(st));   // the call's one synchronisation
+    bool zero = false;
+    for (int32_t g = 0; g < n_groups; ++g) {
+        const GInfo& I = gi[g];
+        JointState* J = G->slot[slots[g]].get();
+        flags[g] = eh[g];
+        J->D = I.D;
+        J->S = I.S;
+        J->quant = I.quant;
+        J->cat = I.cat;
+        J->ncat = I.ncat;
+        J->Kb = I.Kb;
+        J->Ka = I.Ka;
+        J->stream = pick_streams[g];
+        J->zero = (eh[n_groups + g] & 1) != 0;
+        J->ready = eh[g] == 0;   // a flagged group is the host build's
+        zero |= J->ready && J->zero;
+    }
+    if (zero) return zero_mass(ctx);
+    return TPE_OK;
+}
 }  // namespace
 
 extern "C" {
@@ -1131,6 +1432,37 @@ int tpe_joint_clear_groups(tpe_ctx* ctx) {
     if (!G) return TPE_OK;
     for (int j = 0; j < kJMaxGroups; ++j)
         if (G->slot[j]) G->slot[j]->ready = false;   // (buffers kept, as above)
+    return TPE_OK;
+}
+
+int tpe_joint_build_groups(tpe_ctx* ctx, int32_t n_groups, const int32_t* slots, const uint32_t* pick_streams,
+                           const int64_t* group_off, const int32_t* labels, const int32_t* streams, const double* q,
+                           const int32_t* upper, const double* cat_p, double prior_weight, int32_t* flags) {
+    if (!ctx) return TPE_ERR_ARG;
+    TPE_SETTLE(ctx);   // (a deferred rebuild's report: its buffers are read here)
+    return joint_build_groups(ctx, n_groups, slots, pick_streams, group_off, labels, streams, q, upper, cat_p,
+                              prior_weight, flags);
+}
+
+int tpe_joint_get_group(tpe_ctx* ctx, int32_t slot, int32_t side, double* w, double* mu, double* sigma, int32_t cap,
+                        int32_t* n_components, int32_t* n_dims) {
+    if (!ctx) return TPE_ERR_ARG;
+    if (slot < 0 || slot >= kJMaxGroups || side < 0 || side > 1)
+        return ctx->fail(TPE_ERR_ARG, "tpe_joint_get_group: slot in [0, " + std::to_string(kJMaxGroups) +
+                                          "), side 0 (below) or 1 (above)");
+    JointGroups* G = jgroups(ctx, false);
+    JointState* J = G ? G->slot[slot].get() : nullptr;
+    if (!J || !J->ready) return ctx->fail(TPE_ERR_ARG, "tpe_joint_get_group: no joint posterior set");
+    const int32_t K = side ? J->Ka : J->Kb, D = J->D;
+    if (n_components) *n_components = K;
+    if (n_dims) *n_dims = D;
+    const size_t m = (size_t)std::min(K, std::max(cap, 0)), r0 = side ? (size_t)J->Kb : 0;
+    HIPCHK(ctx, hipSetDevice(ctx->device));
+    if (m > 0) {
+        if (w) HIPCHK(ctx, hipMemcpy(w, J->W.p + r0, m * sizeof(double), hipMemcpyDeviceToHost));
+        if (mu) HIPCHK(ctx, hipMemcpy(mu, J->mu.p + r0 * D, m * D * sizeof(double), hipMemcpyDeviceToHost));
+        if (sigma) HIPCHK(ctx, hipMemcpy(sigma, J->sig.p + r0 * D, m * D * sizeof(double), hipMemcpyDeviceToHost));
+    }
     return TPE_OK;
 }
 

@@ -488,6 +488,74 @@ class Engine(object):
         self.joint_slots = {}
         self._check(self.lib.tpe_joint_clear_groups(self.h))
 
+    def build_joint_groups(self, groups, q=None, upper=None, cat_p=None, prior_weight=None):
+        """Joint groups built on the device from the current build of the
+        resident history (tpe_joint_build_groups): groups = [(slot,
+        pick_stream, label indices, streams)], the indices those of the
+        resident history's labels, streams each label's Philox stream.  q,
+        upper: per group, one entry per label (None: all dense / none
+        categorical), with the meaning they have in set_joint_group; cat_p:
+        per group the categorical labels' priors, concatenated; prior_weight
+        as there.  The mixtures are posterior.joint_mixture's, bit for bit,
+        without its arrays crossing the bus.  Returns the int32 flags, one
+        per group: 0 -- the slot is set; else (L.TPE_JOINT_FLAG_TIE |
+        _CATEGORY | _COUNT) the group is left unset for the host build."""
+        groups = [(int(s), int(ps) & 0xFFFFFFFF, [int(l) for l in ls], [int(t) for t in ts])
+                  for s, ps, ls, ts in groups]
+        n = len(groups)
+        for _, _, ls, ts in groups:
+            if len(ls) != len(ts):
+                raise ValueError('streams holds one entry per label')
+        off = np.zeros(n + 1, dtype=np.int64)
+        off[1:] = np.cumsum([len(g[2]) for g in groups])
+        slots = np.ascontiguousarray([g[0] for g in groups], dtype=np.int32)
+        picks = np.ascontiguousarray([g[1] for g in groups], dtype=np.uint32)
+        labels = np.ascontiguousarray([l for g in groups for l in g[2]], dtype=np.int32)
+        streams = np.ascontiguousarray([t for g in groups for t in g[3]], dtype=np.int32)
+
+        def flat(per_group, dtype, what):
+            if per_group is None:
+                return None
+            if len(per_group) != n:
+                raise ValueError('%s holds one entry per group' % what)
+            parts = [np.zeros(len(g[2]), dtype=dtype) if a is None else np.asarray(a, dtype=dtype).ravel()
+                     for g, a in zip(groups, per_group)]
+            if any(len(a) != len(g[2]) for g, a in zip(groups, parts)):
+                raise ValueError('%s holds one entry per label of each group' % what)
+            return np.ascontiguousarray(np.concatenate(parts) if parts else np.zeros(0, dtype=dtype))
+        qf = flat(q, np.float64, 'q')
+        uf = flat(upper, np.int32, 'upper')
+        cp = None
+        if uf is not None and np.any(uf > 0):
+            if cat_p is None or len(cat_p) != n or prior_weight is None:
+                raise ValueError('categorical joint dimensions need cat_p per group and prior_weight')
+            cp = _f64(np.concatenate([_f64(a if a is not None else []).ravel() for a in cat_p]))
+            if len(cp) != int(np.sum(np.maximum(uf, 0))):
+                raise ValueError('cat_p holds the priors of the categorical dimensions, concatenated')
+        flags = np.zeros(max(n, 1), dtype=np.int32)
+        rc = self.lib.tpe_joint_build_groups(self.h, n, _ptr(slots), _ptr(picks), _ptr(off), _ptr(labels),
+                                             _ptr(streams), _ptr(qf), _ptr(uf), _ptr(cp),
+                                             float(prior_weight if prior_weight is not None else 0.0), _ptr(flags))
+        known = self.__dict__.setdefault('joint_slots', {})
+        for (slot, _, ls, _), f in zip(groups, flags):
+            if 0 <= slot < L.TPE_JOINT_MAX_GROUPS:
+                known.pop(slot, None)
+            if rc in (L.TPE_OK, L.TPE_ERR_SAMPLE) and not f:
+                known[slot] = len(ls)
+        self._check(rc)
+        return flags[:n]
+
+    def joint_get_group(self, slot, side):
+        """(W [K], mu [K, D], sigma [K, D]) of a set slot's unfolded mixture,
+        side 0 below, 1 above, however the slot was set (tpe_joint_get_group)."""
+        K, D = ctypes.c_int32(), ctypes.c_int32()
+        self._check(self.lib.tpe_joint_get_group(self.h, int(slot), int(side), None, None, None, 0,
+                                                 ctypes.byref(K), ctypes.byref(D)))
+        w, m, s = np.empty(K.value), np.empty((K.value, D.value)), np.empty((K.value, D.value))
+        self._check(self.lib.tpe_joint_get_group(self.h, int(slot), int(side), _ptr(w), _ptr(m), _ptr(s), K.value,
+                                                 ctypes.byref(K), ctypes.byref(D)))
+        return w, m, s
+
     @property
     def joint_dims(self):
         return getattr(self, 'joint_slots', {}).get(0, 0)

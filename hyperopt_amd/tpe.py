@@ -61,6 +61,10 @@ _default_gamma = 0.25
 _default_n_startup_jobs = 20
 _default_linear_forgetting = DEFAULT_LF
 DEVICE_BUILD_MIN_OBS = 16384
+# multivariate=True behind a device build of the resident history: the joint
+# groups are built on the device from it too (False: always on the host -- the
+# same documents; for timing one against the other, tools/time_joint.py)
+JOINT_DEVICE_BUILD = True
 
 # host-side restatements, exported under the reference's names
 ap_filter_trials_split = _post.split_history
@@ -147,12 +151,15 @@ PREPARE_MIN = 8192   # candidate slots of a round from which it uses the expansi
 
 
 def _resident_posterior(eng, domain, trials, specs, view, gathered, gamma, prior_weight,
-                        builder, n_candidates=0, n_rounds=1, round_call=None):
+                        builder, n_candidates=0, n_rounds=1, round_call=None, info=None):
     """Put the posterior of the current history on the engine, from the
     device-resident history's `view` or the general gather (tids, losses,
     obs); returns (the number of trial documents it was built from, the
     results of round_call when the incremental device build ran it -- the
-    dense labels' round under the host's tie-order argsorts -- else None)."""
+    dense labels' round under the host's tie-order argsorts -- else None).
+    info (a dict, optional): info['resident'] is set when the posterior was
+    built on the device from the resident history of `view` -- what the
+    joint groups' device build reads (_joint_rounds)."""
     labels = list(specs)
     if view is not None:
         n_docs = view[2]
@@ -173,6 +180,8 @@ def _resident_posterior(eng, domain, trials, specs, view, gathered, gamma, prior
                                   prior_weight, prepare=((n_candidates, n_rounds)
                                                          if n_candidates * n_rounds >= PREPARE_MIN else None),
                                   round_call=round_call)
+                if info is not None:
+                    info['resident'] = True
                 return n_docs, res
             eng.build_posterior(*device_inputs(specs, tids, losses, obs), gamma=gamma,
                                 prior_weight=prior_weight)
@@ -278,26 +287,77 @@ def joint_groups(domain, specs, obs=None, kinds=_post.JOINT_KINDS):
     return out
 
 
+def _view_columns(view):
+    """label -> (tids, vals) of a device view, restricted to the trials the
+    general gather keeps (HistoryCache._gather_own: a NaN loss, or a document
+    no longer among the trials, drops its observations) -- the columns
+    themselves when it keeps every one."""
+    tids, losses, n_valid, cols, owner = view
+    if n_valid == len(tids) and len(tids) == len(getattr(owner, 'seen', tids)):
+        return cols
+    keep = tids[losses == losses]
+    out = {}
+    for k, (ti, tv) in cols.items():
+        m = np.isin(ti, keep)
+        out[k] = (ti[m], tv[m])
+    return out
+
+
+def _joint_device_args(specs, labels, groups, quantized, categorical, prior_weight):
+    """Arguments of Engine.build_joint_groups for [(slot, [label names])]:
+    label indices and streams are positions in the space (the resident
+    history holds the labels in that order), slot j's pick stream
+    TPE_JOINT_STREAM - j; steps and categorical priors from the same
+    joint_prior the host build asks (it raises what that raises)."""
+    at = {k: i for i, k in enumerate(labels)}
+    args, qs, uppers, cat_ps = [], [], [], []
+    for slot, g in groups:
+        ids = [at[k] for k in g]
+        args.append((slot, _engine.L.TPE_JOINT_STREAM - slot, ids, ids))
+        pri = [_post.joint_prior(specs[k].kind, specs[k].args, quantized, categorical) for k in g]
+        if quantized:
+            qs.append([p[6] for p in pri])
+        if categorical:
+            uppers.append([p[-2] for p in pri])
+            ps = [p[-1] for p in pri if p[-2] > 0]
+            cat_ps.append(np.concatenate(ps) if ps else np.zeros(0))
+    kw = dict(q=qs if quantized else None)
+    if categorical:
+        kw.update(upper=uppers, cat_p=cat_ps, prior_weight=prior_weight)
+    return args, kw
+
+
 def _joint_rounds(eng, domain, trials, specs, gathered, gamma, prior_weight, seed, ids, n_candidates,
-                  group=False, quantized=False, categorical=False):
+                  group=False, quantized=False, categorical=False, view=None):
     """One joint round per id and joint group: [label -> value] per id, or
     None when the call falls back to the independent path.  group=False: the
     unconditional group alone (joint_group), slot 0; group=True: every group
     of joint_groups in its slot, slot j's component pick on the Philox stream
-    TPE_JOINT_STREAM - j.  The mixtures are built on the host
-    (posterior.joint_mixture, each group from its own observations); a
-    label's Philox stream is its position in the space, as in the
-    independent round.  One set_joint_group per group, one
-    joint_suggest_batch for all groups and ids.  quantized=True: the groups
-    take the quantized kinds too (posterior.JOINT_QUANT_KINDS), their values
-    rounded to the label's grid; categorical=True: and the categorical kinds
-    (posterior.JOINT_CAT_KINDS; a label with a zero prior probability stays
-    out), their values category indices; every group value enters the
-    document through labels.coerce."""
+    TPE_JOINT_STREAM - j.  A label's Philox stream is its position in the
+    space, as in the independent round.
+
+    view: the device view this call's univariate posterior was built from, on
+    the engine's resident history (None: it was not).  With it the groups are
+    read off the view's columns and every group with a label that is not
+    categorical is built on the device from that build
+    (Engine.build_joint_groups: one call, no gather, nothing uploaded); a
+    group the device flags (a tie whose order it was not given, a category
+    out of range) and a group of categorical labels alone are built on the
+    host like every group without a view: posterior.joint_mixture from the
+    gathered observations, one set_joint_group each.  The mixtures are the
+    same bits either way.  One joint_suggest_batch for all groups and ids.
+
+    quantized=True: the groups take the quantized kinds too
+    (posterior.JOINT_QUANT_KINDS), their values rounded to the label's grid;
+    categorical=True: and the categorical kinds (posterior.JOINT_CAT_KINDS; a
+    label with a zero prior probability stays out), their values category
+    indices; every group value enters the document through labels.coerce."""
     kinds = _post.JOINT_KINDS + (_post.JOINT_QUANT_KINDS if quantized else ()) + \
         (_post.JOINT_CAT_KINDS if categorical else ())
     labels = list(specs)
-    tids, losses, obs = gathered or _history.gather(domain, trials, labels)
+    if view is None:
+        gathered = gathered or _history.gather(domain, trials, labels)
+    obs = _view_columns(view) if view is not None else gathered[2]
     if group:
         groups = joint_groups(domain, specs, obs, kinds)
     else:
@@ -307,15 +367,28 @@ def _joint_rounds(eng, domain, trials, specs, gathered, gamma, prior_weight, see
         logger.info('multivariate TPE: no joint group, using the independent path')
     if not groups:
         return None
-    splitter = _post.Splitter(tids, losses, gamma)
     eng.clear_joint_groups()
-    for slot, g in groups:
-        mix = _post.joint_mixture([specs[k] for k in g], obs, splitter, prior_weight,
-                                  streams=[labels.index(k) for k in g], quantized=quantized,
-                                  categorical=categorical)
-        cat = dict(upper=mix[-2], cat_p=mix[-1], prior_weight=prior_weight) if categorical else {}
-        eng.set_joint_group(slot, _engine.L.TPE_JOINT_STREAM - slot, *mix[:7],
-                            q=mix[7] if quantized else None, **cat)
+    on_device = [(slot, g) for slot, g in groups
+                 if view is not None and any(specs[k].kind not in _post.JOINT_CAT_KINDS for k in g)]
+    flagged = []
+    if on_device:
+        args, kw = _joint_device_args(specs, labels, on_device, quantized, categorical, prior_weight)
+        flags = eng.build_joint_groups(args, **kw)
+        flagged = [sg for sg, f in zip(on_device, flags) if f]
+    built = [sg for sg in on_device if sg not in flagged]
+    on_host = [sg for sg in groups if sg not in built]
+    logger.info('multivariate TPE: %d group(s) built on the device, %d on the host (%d flagged by the device)'
+                % (len(built), len(on_host), len(flagged)))
+    if on_host:
+        tids, losses, obs = gathered or _history.gather(domain, trials, labels)
+        splitter = _post.Splitter(tids, losses, gamma)
+        for slot, g in on_host:
+            mix = _post.joint_mixture([specs[k] for k in g], obs, splitter, prior_weight,
+                                      streams=[labels.index(k) for k in g], quantized=quantized,
+                                      categorical=categorical)
+            cat = dict(upper=mix[-2], cat_p=mix[-1], prior_weight=prior_weight) if categorical else {}
+            eng.set_joint_group(slot, _engine.L.TPE_JOINT_STREAM - slot, *mix[:7],
+                                q=mix[7] if quantized else None, **cat)
     won = eng.joint_suggest_batch(seed, ids, n_candidates)
     out = [{} for _ in ids]
     for slot, g in groups:
@@ -396,6 +469,17 @@ def suggest(new_ids, domain, trials, seed,
     kinds; the keyword composes with joint_quantized and group, and with the
     default every call returns the documents it always did.
 
+    Where the call's posterior is built on the device from the resident
+    history (posterior_builder 'device', or 'auto' past its threshold; one
+    device), the joint groups are built there too, from that build
+    (Engine.build_joint_groups: no gather, no upload, one synchronisation
+    for all groups) -- the same mixtures bit for bit, so the same documents.
+    A group in which a label's side holds two equal observations whose
+    np.argsort order the univariate build did not need (common for quantized
+    labels), one with an out-of-range category and one of categorical labels
+    alone are built on the host as before (_joint_rounds; one logger.info
+    line per call names the path).
+
     precision='f32' runs the exact fp64 path: a round draws every candidate
     and proves all but ~0.5 % of them out of the race from per-sub-bin score
     bounds before any lpdf is summed, so scoring the rest in fp32 would save
@@ -466,14 +550,19 @@ def suggest(new_ids, domain, trials, seed,
         if len(ids) == 1:
             return eng.suggest(seed, n_EI_candidates, round=ids[0])[None]
         return eng.suggest_batch(seed, ids, n_EI_candidates)
+    info = {}
     _, res = _resident_posterior(eng, domain, trials, specs, view, gathered, gamma, prior_weight,
                                  posterior_builder, n_candidates=n_EI_candidates, n_rounds=len(ids),
-                                 round_call=round_call)
+                                 round_call=round_call, info=info)
     if res is None:
         res = round_call()
+    # the joint groups are built on the device when this call's univariate
+    # posterior was: from the resident history, on one device
+    jview = view if (JOINT_DEVICE_BUILD and info.get('resident') and
+                     len(getattr(eng, 'devices', (0,))) == 1) else None
     joint = _joint_rounds(eng, domain, trials, specs, gathered, gamma, prior_weight, seed, ids,
                           n_EI_candidates, group=group, quantized=bool(joint_quantized),
-                          categorical=bool(joint_categorical)) if multivariate else None
+                          categorical=bool(joint_categorical), view=jview) if multivariate else None
     rval = []
     for j, new_id in enumerate(ids):
         values = {s.label: _labels.coerce(s.kind, res[j][i]['value'])

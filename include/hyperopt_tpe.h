@@ -492,6 +492,52 @@ int tpe_joint_set_group_c(tpe_ctx *ctx, int32_t slot, uint32_t pick_stream, cons
                           const double *mub, const double *sigb, int32_t n_above, const double *wa,
                           const double *mua, const double *siga);
 int tpe_joint_clear_groups(tpe_ctx *ctx);
+/* Joint groups built on the device from the current build of the resident
+ * history (tpe_build_posterior_resident and its kin) -- nothing is uploaded but
+ * the arguments.  The joint mixture of a group is its labels' univariate
+ * mixtures read back in trial order (row 0 the prior, row t + 1 the t-th
+ * observation of the side in observation order, each with the sigma and the
+ * weight its own sorted position gave it; W is the first non-categorical
+ * label's; a categorical label's rows hold the observed categories, sigma 1):
+ * one launch un-permutes them into the arrays tpe_joint_set_group_c takes,
+ * then each slot is folded as that call folds it -- the same bits wherever the
+ * univariate mixtures are the host's.  One stream synchronisation per call.
+ * Group g is labels[group_off[g] .. group_off[g + 1]) -- indices of the
+ * resident history's labels, whose tpe_label_spec supplies kind, bounds and
+ * prior -- in slot slots[g] with pick stream pick_streams[g]; streams, q and
+ * upper are parallel to labels (q, upper: NULL or 0 as in
+ * tpe_joint_set_group_c; upper[i] must be the label's own), cat_p the
+ * categorical labels' priors concatenated in that order.
+ * flags[g] != 0: the group was not built and its slot is left unset (the other
+ * groups are built) --
+ *   TPE_JOINT_FLAG_TIE       a label's side holds two equal observations (or a
+ *                            NaN) whose np.argsort order the build was not given
+ *                            (tpe_build_posterior_resident_ordered /
+ *                            tpe_rebuild_labels): which trial gets which sigma
+ *                            would depend on the tie order,
+ *   TPE_JOINT_FLAG_CATEGORY  an observed category is no integer in [0, upper),
+ *   TPE_JOINT_FLAG_COUNT     the group's labels do not hold the same number of
+ *                            observations on a side.
+ * TPE_ERR_ARG: no build of the resident history is current (none, a failed one,
+ * or the history appended to or reset since); a label index out of range or
+ * listed twice; a slot out of range or used twice; a group without a
+ * non-categorical label; upper[i] not the label's; more than 128 dimensions
+ * (plus quantized dimensions), 4096 below components or TPE_JOINT_MAX_GROUPS
+ * groups; a label-sharded context.  TPE_ERR_SAMPLE as tpe_joint_set_group. */
+#define TPE_JOINT_FLAG_TIE 1
+#define TPE_JOINT_FLAG_CATEGORY 2
+#define TPE_JOINT_FLAG_COUNT 4
+int tpe_joint_build_groups(tpe_ctx *ctx, int32_t n_groups, const int32_t *slots,
+                           const uint32_t *pick_streams, const int64_t *group_off /* [n_groups + 1] */,
+                           const int32_t *labels, const int32_t *streams, const double *q,
+                           const int32_t *upper, const double *cat_p, double prior_weight,
+                           int32_t *flags /* [n_groups] */);
+/* A set slot's unfolded arrays, however it was set (tests, diagnostics): the
+ * first min(cap, K) components of side 0 (below) or 1 (above) -- w[k], mu and
+ * sigma [k][D] row-major; K and D through n_components and n_dims.  Output
+ * pointers may be NULL. */
+int tpe_joint_get_group(tpe_ctx *ctx, int32_t slot, int32_t side, double *w, double *mu, double *sigma,
+                        int32_t cap, int32_t *n_components, int32_t *n_dims);
 int tpe_joint_draw_group(tpe_ctx *ctx, int32_t slot, uint64_t seed, uint32_t round, int64_t n,
                          int64_t cand_offset, double *values, int32_t *comp);
 int tpe_joint_score_group(tpe_ctx *ctx, int32_t slot, const double *values, int64_t n, double *ll,

@@ -4,6 +4,7 @@
     python tools/time_joint.py --groups [--legs loop,batch] [--reps 20] [--out FILE]
     python tools/time_joint.py --quantized | --categorical [--legs dense,...] [--reps 20] [--out FILE]
     python tools/time_joint.py --no-timings --quality-quantized | --quality-categorical [--out FILE]
+    python tools/time_joint.py --build [--dims 32] [--trials 10000] [--reps 20] [--out FILE]
 
 On a synthetic history of `--trials` trials over `--dims` dense continuous
 labels (kinds cycled over uniform / loguniform / normal / lognormal):
@@ -47,6 +48,12 @@ checkout without categorical groups runs too.
 (x - [-3, 0, 3][k])^2 + 0.1 k with x uniform(-5, 5) and k a 3-way choice:
 independent, multivariate=True, and multivariate=True with
 joint_categorical=True.  A record, not a gate.
+
+--build: on the --dims x --trials history (default d32: 32 x 10000),
+Engine.build_joint_groups on the resident history against
+posterior.joint_mixture + Engine.set_joint_posterior, and a whole
+tpe.suggest(multivariate=True) call with posterior_builder='device' against
+'host' (build_timings); medians of --reps calls after a warm-up call.
 
 Prints one JSON document (and writes it to --out).
 """
@@ -346,6 +353,81 @@ def categorical_timings(reps, legs=('dense', 'categorical'), n_dims=32, n_trials
     return out
 
 
+def build_timings(reps, n_dims=32, n_trials=10000):
+    """The joint build on the device against the host's, on the d32 shape,
+    medians (and the range) of the wall time over `reps` calls after one
+    warm-up call each:
+
+    * device_build: Engine.build_joint_groups on the resident history, its
+      univariate posterior built once before (gather launch + fold + the
+      call's one synchronisation);
+    * host_build + upload_fold: posterior.joint_mixture, then
+      Engine.set_joint_posterior with its arrays -- what the same call costs
+      without the device build (the expectation to report against);
+    * suggest_device / suggest_host: a whole tpe.suggest(multivariate=True)
+      call for one new id on that history as Trials, posterior_builder
+      'device' against 'host' (each on a warm engine: the history resident,
+      nothing new to upload).
+
+    Checks first that both builds give the same winner bits."""
+    from hyperopt_amd import _lib as L
+    from hyperopt_amd import posterior as P, tpe, workloads
+    from hyperopt_amd.base import Domain
+    from hyperopt_amd.engine import Engine
+    group, tids, losses, obs = history(n_dims, n_trials)
+    splitter = P.Splitter(tids, losses, 0.25)
+
+    class Owner(object):
+        pass
+    view = (tids, losses, n_trials, obs, Owner())
+    eng = Engine(0, 'f64')
+    P.DeviceHistoryUploader().build(eng, group, view, 0.25, 1.0)
+    ids = list(range(n_dims))
+    args = [(0, L.TPE_JOINT_STREAM, ids, ids)]
+    assert not eng.build_joint_groups(args)[0], 'the device flagged the timing history'
+    won_dev = eng.joint_suggest(1, 24, round=5)
+    mix = P.joint_mixture(group, obs, splitter, 1.0)
+    eng.set_joint_posterior(*mix)
+    won_host = eng.joint_suggest(1, 24, round=5)
+    assert np.array_equal(won_dev[0], won_host[0]) and won_dev[1:] == won_host[1:]
+
+    def spread(fn, n):
+        fn()
+        out = []
+        for _ in range(n):
+            t = time.perf_counter()
+            fn()
+            out.append((time.perf_counter() - t) * 1e3)
+        return dict(median_ms=float(np.median(out)), min_ms=float(np.min(out)), max_ms=float(np.max(out)), reps=n)
+    res = dict(dims=n_dims, trials=n_trials, k_below=len(mix[1]), k_above=len(mix[4]))
+    res['device_build'] = spread(lambda: eng.build_joint_groups(args), reps)
+    res['host_build'] = spread(lambda: P.joint_mixture(group, obs, splitter, 1.0), reps)
+    res['upload_fold'] = spread(lambda: eng.set_joint_posterior(*mix), reps)
+    res['host_build_plus_upload'] = spread(lambda: eng.set_joint_posterior(*P.joint_mixture(group, obs, splitter, 1.0)),
+                                           reps)
+    res['host_over_device'] = res['host_build_plus_upload']['median_ms'] / res['device_build']['median_ms']
+    eng.close()
+    hist = workloads.History(group, tids, losses, obs)
+    trials = workloads.history_trials(hist)
+    space = workloads.hp_space(group)
+    domain = Domain(lambda d: 0.0, space)
+    for builder in ('device', 'host'):
+        res['suggest_' + builder] = spread(
+            lambda: tpe.suggest([n_trials], domain, trials, 3, multivariate=True, posterior_builder=builder), reps)
+    # the device univariate build with the joint groups built on the host: what
+    # posterior_builder='device' did before the joint build moved to the device
+    tpe.JOINT_DEVICE_BUILD = False
+    try:
+        res['suggest_device_joint_on_host'] = spread(
+            lambda: tpe.suggest([n_trials], domain, trials, 3, multivariate=True, posterior_builder='device'), reps)
+    finally:
+        tpe.JOINT_DEVICE_BUILD = True
+    res['suggest_independent_device'] = spread(
+        lambda: tpe.suggest([n_trials], domain, trials, 3, posterior_builder='device'), reps)
+    res['suggest_host_over_device'] = res['suggest_host']['median_ms'] / res['suggest_device']['median_ms']
+    return res
+
+
 def quality_categorical(evals=100, seeds=10):
     import hyperopt_amd as H
     from hyperopt_amd import hp, tpe
@@ -426,6 +508,7 @@ def main(argv):
     ap.add_argument('--quality-quantized', action='store_true')
     ap.add_argument('--categorical', action='store_true', help='the dense and categorical d32 legs')
     ap.add_argument('--quality-categorical', action='store_true')
+    ap.add_argument('--build', action='store_true', help='the device joint build against the host build')
     ap.add_argument('--legs', default=None,
                     help='--groups: loop,batch; --quantized: dense,quantized; --categorical: dense,categorical')
     ap.add_argument('--out')
@@ -437,6 +520,8 @@ def main(argv):
         res['quantized'] = quantized_timings(a.reps, legs=tuple((a.legs or 'dense,quantized').split(',')))
     elif a.categorical:
         res['categorical'] = categorical_timings(a.reps, legs=tuple((a.legs or 'dense,categorical').split(',')))
+    elif a.build:
+        res['build'] = build_timings(a.reps, a.dims, a.trials)
     elif not a.no_timings:
         res['timings'] = timings(a.dims, a.trials, a.reps)
     if a.quality:
