@@ -165,6 +165,7 @@ SIGNATURES = {
     'tpe_last_hot': (ctypes.c_int, [_P, _P, _P]),
     'tpe_last_prepare': (ctypes.c_int, [_P, _P]),
     'tpe_hot_probe': (ctypes.c_int, [_P, ctypes.c_int32, _P, ctypes.c_int64, _P, _P, _P]),
+    'tpe_bx_layout': (ctypes.c_int, [_P, _I32, _PD, _PD, ctypes.POINTER(_I32), ctypes.POINTER(_I32), _PD, _PD]),
     'tpe_screen_probe': (ctypes.c_int, [_P, _I32, _P, _I64, _P, _P]),
     'tpe_export_posterior': (ctypes.c_int, [_P, _P, _I64, _P]),
     'tpe_import_posterior': (ctypes.c_int, [_P, _P, _I64, _P, _I32, _P, _P]),

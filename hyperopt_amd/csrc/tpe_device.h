@@ -1187,7 +1187,12 @@ __device__ __forceinline__ float float_down(double v) {   // largest float <= v 
 }
 
 // |lpdf64 - lpdf| of the fp64 path (tpe_device.h lse_acc<double>): a
-// sequential sum of K terms, each within ~2.5e-14 + 2 ulp
+// sequential sum of K terms, each within ~2.5e-14 + 2 ulp.  mag: what the
+// lpdfs' logs, shifts and (LGMM1) - y round at.  bx_score leaves |y| and
+// |centre| out of it for a GMM1 label, whose x' = x - centre and sums are the
+// fp64 round's own bits; k_screen and the windowed screen (tpe_window.hip)
+// keep them for every label, which is only conservative there: their fp32
+// bounds are ~1e-6, far above mag 2^-50.
 __device__ __forceinline__ double fp64_err(int K, double mag) {
     return ((double)K + 64.0) * 0x1.0p-52 + 1e-13 + mag * 0x1.0p-50;
 }

@@ -618,11 +618,17 @@ __device__ __forceinline__ int bx_score(const DLabel& L, const BxLabel& B,
         if (fabs(delta) <= B.rmax && t <= 2e-3 && sum >= 1e-280 && ab >= 1e-290 && eps <= 1e-6) {
             // s = (log acc_b + shift_b) - (log S + shift_a): one log of the
             // ratio; the fp64 round's own logs, shifts and (LGMM) - y terms
-            // add at most mag 2^-50 (fp64_err), mag from the exponents
+            // add at most mag 2^-50 (fp64_err), mag from the exponents.  The
+            // candidate's own magnitude enters an LGMM1 label only: its lpdfs
+            // carry - y and its x' = flog(x) - centre a rounding of y, while
+            // a GMM1 label's x' = x - centre and every sum after it are the
+            // fp64 round's own bits (a bound that grew with |x| made a label
+            // at 1e6 re-score near-ties 1e4 times wider than one at 0)
             const double lq = flog(ab / sum);
             s[r] = lq + (L.shift_b - L.shift_a);
             const double mag = (double)(abs(ilogb(ab)) + abs(ilogb(sum)) + 2) * 0.6931471805599453 +
-                               fabs(L.shift_b) + fabs(L.shift_a) + 2.0 * fabs(y[r]) + fabs(L.centre);
+                               fabs(L.shift_b) + fabs(L.shift_a) +
+                               (lgmm ? 2.0 * fabs(y[r]) + fabs(L.centre) : 0.0);
             E[r] = 1.25 * (1.001 * eps + 0x1.0p-52 * (fabs(lq) + 1.0) + fp64_err(L.nb + L.na, mag));
         }
     }
@@ -5417,6 +5423,32 @@ int tpe_hot_probe(tpe_ctx* ctx, int32_t label, const double* cand, int64_t n, do
     HIPCHK(ctx, hipMemcpyAsync(lower, ctx->out_la.p, n * sizeof(double), hipMemcpyDeviceToHost, ctx->stream));
     HIPCHK(ctx, hipMemcpyAsync(mass, ctx->xs.p, n * sizeof(double), hipMemcpyDeviceToHost, ctx->stream));
     HIPCHK(ctx, hipStreamSynchronize(ctx->stream));
+    return TPE_OK;
+}
+
+int tpe_bx_layout(tpe_ctx* ctx, int32_t label, double* xlo, double* bw, int32_t* nbins, int32_t* n_nc,
+                  double* tcut, double* centre) {
+    if (!ctx) return TPE_ERR_ARG;
+    TPE_NOT_LSHARD(ctx);
+    TPE_SETTLE(ctx);
+    if (label < 0 || label >= ctx->P->n_labels) return ctx->fail(TPE_ERR_ARG, "label out of range");
+    const DLabel& d = ctx->P->h_labels[label];
+    if (d.mode != DENSE_GMM && d.mode != DENSE_LGMM)
+        return ctx->fail(TPE_ERR_ARG, "index layout: label is not a dense GMM1/LGMM1 label");
+    HIPCHK(ctx, hipSetDevice(ctx->device));
+    ctx->bx_t_next = kBxTTile;   // (the tile rounds' index, as the probes)
+    int rc = tpe_rt::bx_prepare(ctx);
+    if (rc) return rc;
+    tpe_rt::Posterior& P = *ctx->P;
+    if (!P.bx_ok || (size_t)label >= P.bx_h.size())
+        return ctx->fail(TPE_ERR_ARG, "index layout: the posterior has no expansion index");
+    const BxLabel& B = P.bx_h[label];
+    if (xlo) *xlo = B.xlo;
+    if (bw) *bw = B.bw;
+    if (nbins) *nbins = B.nbins;
+    if (n_nc) *n_nc = B.n_nc;
+    if (tcut) *tcut = B.tcut;
+    if (centre) *centre = d.centre;
     return TPE_OK;
 }
 

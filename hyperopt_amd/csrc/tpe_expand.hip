@@ -54,7 +54,7 @@ namespace {
 constexpr double kInf = __builtin_inf();
 constexpr double kLn2 = 0.6931471805599453;
 constexpr double kU = 0x1.0p-53;
-constexpr int kScanFields = 6;   // xlo, xhi, a*, unclipped, clipped, pad
+constexpr int kScanFields = 6;   // xlo, xhi, a*, unclipped, clipped, out of mu order
 constexpr int32_t kMaxUnclipped = 16384;
 constexpr int32_t kMaxBins = 1 << 16;
 constexpr int32_t kMinBins = 64;
@@ -108,12 +108,29 @@ __device__ __forceinline__ bool usable(const Comp<double>& r) {
     return r.a > 0.0 && r.a < kInf && fabs(r.mu) < kInf;
 }
 
-// grid (dense labels): range, a*, counts -> scan[y * kScanFields ...].
+// a record's mean mu' = m'/a' as k_bx_table's window search reads it
+__device__ __forceinline__ double rec_mu(const Comp<double>& r) { return r.a > 0.0 ? r.mu / r.a : -kInf; }
+
+// grid (dense labels): range, a*, counts, order -> scan[y * kScanFields ...].
 // The candidate range of a label without both bounds covers each sampling
 // component k to z_k sigma_k with w_k Q(z_k) <= kRangeTail (at most 8 sigma):
 // a candidate outside the bins is always listed and scored in fp64 (exact,
 // only slower), and at 2^24 candidates per round that happens ~1e-3 times per
 // label; a one-sided bound cuts the range on its side.
+//
+// Order: k_bx_table finds a wave's clipped components by a binary search
+// over the above records' means (wave_window), so they must not decrease
+// along the records -- the builds' mixtures are sorted by mu, but
+// tpe_set_posterior takes any order.  A pair of neighbours that decreases by
+// more than the rounding of mu' = m'/a' (1e-14 relative here; the windows
+// carry a 1e-12 margin), or a NaN, is flagged and the posterior gets no
+// index (bx_build).  The test is per pair: for means that are sorted up to
+// that rounding the tolerance does not add up, but it does not catch a
+// hand-made mixture that creeps downward by less than it at every record
+// (16k records: ~3e-10 relative in all, past the windows' margin; what such
+// a window loses sits at its 2^-T edge).  Every record counts, usable or not
+// (a <= 0 reads as -inf, so it passes only in front), as wave_window reads
+// them: stricter than an order among the usable ones alone.
 constexpr double kRangeTail = 1e-10;
 __global__ __launch_bounds__(kBlock) void k_bx_scan(const DLabel* __restrict__ labels,
                                                     const int32_t* __restrict__ grp,
@@ -147,18 +164,29 @@ __global__ __launch_bounds__(kBlock) void k_bx_scan(const DLabel* __restrict__ l
     // record left the 10k-record passes latency-bound)
     constexpr int kScanU = 8;
     double am = 0.0;
+    int unsorted = 0;
     for (int k0 = threadIdx.x; k0 < L.na; k0 += kBlock * kScanU) {
-        Comp<double> r[kScanU];
+        Comp<double> r[kScanU], nx[kScanU];   // (nx: the record after r, for the order)
 #pragma unroll
         for (int u = 0; u < kScanU; ++u) {
             const int k = k0 + u * kBlock;
             r[u] = k < L.na ? c[k] : Comp<double>{0.0, 0.0, 0.0, 0.0};
+            nx[u] = k + 1 < L.na ? c[k + 1] : Comp<double>{0.0, 0.0, 0.0, 0.0};
         }
 #pragma unroll
-        for (int u = 0; u < kScanU; ++u)
-            if (k0 + u * kBlock < L.na && usable(r[u])) am = fmax(am, r[u].a);
+        for (int u = 0; u < kScanU; ++u) {
+            const int k = k0 + u * kBlock;
+            if (k < L.na && usable(r[u])) am = fmax(am, r[u].a);
+            if (k + 1 < L.na) {
+                const double m0 = rec_mu(r[u]), m1 = rec_mu(nx[u]);
+                // (a NaN compares false: flagged)
+                const double tol = fabs(m0) < kInf && fabs(m1) < kInf ? 1e-14 * (fabs(m0) + fabs(m1)) : 0.0;
+                if (!(m1 >= m0 - tol)) unsorted = 1;
+            }
+        }
     }
     am = blk_max(am, shd);
+    unsorted = blk_sum(unsorted, shi);
     int nc = 0, ncl = 0;
     for (int k0 = threadIdx.x; k0 < L.na; k0 += kBlock * kScanU) {
         double a[kScanU];
@@ -184,7 +212,7 @@ __global__ __launch_bounds__(kBlock) void k_bx_scan(const DLabel* __restrict__ l
         o[2] = am;
         o[3] = (double)nc;
         o[4] = (double)ncl;
-        o[5] = 0.0;
+        o[5] = unsorted ? 1.0 : 0.0;
     }
 }
 
@@ -278,8 +306,6 @@ __constant__ double kInvFact[kBxP + 1] = {
     1.0 / 3628800, 1.0 / 39916800, 1.0 / 479001600, 1.0 / 6227020800.0, 1.0 / 87178291200.0,
     1.0 / 1307674368000.0};
 
-
-__device__ __forceinline__ double rec_mu(const Comp<double>& r) { return r.a > 0.0 ? r.mu / r.a : -kInf; }
 
 // The wave's first record index with mu' >= v0 (-> k0) and with mu' >= v1
 // (-> k1) over records [0, n) sorted by mu (mu' = m'/a'): lanes 0..31 search
@@ -913,8 +939,9 @@ int tpe_rt::bx_build(tpe_ctx* ctx) {
         const int32_t n_nc = (int32_t)s[3], n_cl = (int32_t)s[4];
         BxLabel B{};
         const double kap = am * am * kExpScaleInv;
+        // (s[5]: above records out of mu order -- k_bx_table's window search needs it)
         if (!(am > 0.0) || !(kap > 0.0 && kap < 1e300) || !(xhi > xlo) || !std::isfinite(xhi - xlo) ||
-            n_nc > kMaxUnclipped || n_cl < 1) {
+            n_nc > kMaxUnclipped || n_cl < 1 || s[5] != 0.0) {
             ok = false;
             break;
         }

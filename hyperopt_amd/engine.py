@@ -738,6 +738,19 @@ class Engine(object):
                                            _ptr(m)))
         return u, l, m
 
+    def bx_layout(self, label):
+        """The expansion index's bins of one dense resident label
+        (diagnostic, tpe_bx_layout): a dict of xlo, bw (recentred draw
+        space: x - centre, or log x - centre for LGMM1), nbins, n_nc, tcut
+        and centre."""
+        xlo, bw, tcut, centre = (ctypes.c_double() for _ in range(4))
+        nbins, n_nc = ctypes.c_int32(), ctypes.c_int32()
+        self._check(self.lib.tpe_bx_layout(self.h, int(label), ctypes.byref(xlo), ctypes.byref(bw),
+                                           ctypes.byref(nbins), ctypes.byref(n_nc), ctypes.byref(tcut),
+                                           ctypes.byref(centre)))
+        return {'xlo': xlo.value, 'bw': bw.value, 'nbins': nbins.value, 'n_nc': n_nc.value,
+                'tcut': tcut.value, 'centre': centre.value}
+
     # slot 0: dense GMM1 -- and, in sampled tile/packed rounds, the dense
     # LGMM1 labels too (one merged launch; slot 1 then stays 0)
     MODES = ('dense', 'dense_lgmm1', 'quant_gmm1', 'quant_lgmm1', 'categorical')

@@ -206,7 +206,10 @@ int tpe_categorical_sample(tpe_ctx *ctx, const double *p, int32_t upper,
 /* Upload the per-label posteriors (replaces the graph that
  * build_posterior/tpe_transform rebuild on every call, tpe.py:651-739,
  * 794-820).  Arrays are copied; the device copy stays resident until the
- * next call or tpe_ctx_destroy. */
+ * next call or tpe_ctx_destroy.  A mixture's components may come in any
+ * order; only a posterior whose above mixtures are ordered by mu (as
+ * adaptive_parzen_normal and the device builds leave them) gets the
+ * expansion index (TPE_OPT_EXPAND), any other takes the windowed screen. */
 int tpe_set_posterior(tpe_ctx *ctx, const tpe_label_desc *labels, int32_t n_labels,
                       const double *weights, const double *mus, const double *sigmas,
                       int64_t n_components);
@@ -646,6 +649,17 @@ int tpe_last_prepare(tpe_ctx *ctx, float *ms);
 int tpe_hot_probe(tpe_ctx *ctx, int32_t label, const double *cand, int64_t n,
                   double *upper, double *lower, double *mass);
 
+/* Diagnostic of the expansion index (tests): the layout of one dense
+ * resident label's bins, so that candidates can be aimed at bin and sub-bin
+ * edges.  In recentred draw space x' = x - centre (GMM1) or log x - centre
+ * (LGMM1), bin b covers [xlo + b bw, xlo + (b + 1) bw) and is cut into 16
+ * sub-bins of equal width; n_nc: the unclipped above components (each
+ * bin's list slot); tcut: the window's cut T.  Builds the index of the tile
+ * rounds if it is not there, and fails as tpe_hot_probe does when the
+ * posterior has none.  Any output pointer may be NULL. */
+int tpe_bx_layout(tpe_ctx *ctx, int32_t label, double *xlo, double *bw, int32_t *nbins,
+                  int32_t *n_nc, double *tcut, double *centre);
+
 /* Diagnostic of the screen (tests): for caller-supplied candidates of one
  * dense resident label, the fp32 score lpdf_below - lpdf_above the screen
  * computes and its rigorous error bound (x 1.25, as used by the round):
@@ -670,7 +684,10 @@ int tpe_screen_probe(tpe_ctx *ctx, int32_t label, const double *cand, int64_t n,
  *   TPE_OPT_EXPAND  expansion screen of large tile rounds (taken before the
  *                   windowed one when every dense label qualifies): the
  *                   above mixture's equal-sigma components as a per-bin
- *                   Taylor polynomial in fp64, bounds ~1e-12, no sort   [1]
+ *                   Taylor polynomial in fp64, bounds ~1e-12, no sort.
+ *                   Mixtures need not be ordered, but only above mixtures
+ *                   ordered by mu get this index; others qualify for the
+ *                   windowed screen only                                [1]
  *   TPE_OPT_HOT     hot-bin prefilter of the expansion screen: every
  *                   candidate is drawn and bounded by its sub-bin's score
  *                   interval; only those that can still win are scored

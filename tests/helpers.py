@@ -81,3 +81,9 @@ def assert_lpdf_close(got, ref, quantized=False, rtol=1e-9, atol=1e-9, w_sum=1.0
         raise AssertionError('lpdf mismatch at %s: got %s ref %s' % (
             bad.tolist(), got[bad].tolist(), ref[bad].tolist()))
     return abs_only
+
+
+def _assert_same(a, b):
+    """Two rounds' results agree on all six fields (NaN equal to NaN)."""
+    for f in ('index', 'value', 'score', 'lpdf_below', 'lpdf_above', 'label'):
+        assert np.array_equal(a[f], b[f], equal_nan=f != 'index' and f != 'label'), f

@@ -13,6 +13,8 @@ round's largest lower bound are re-scored in fp64.
 import numpy as np
 import pytest
 
+from tests.helpers import _assert_same
+
 pytestmark = pytest.mark.gpu
 
 
@@ -93,11 +95,6 @@ def _suggest_both(eng, C, rnd, seed):
     assert eng.last_screen() == (0, 0)
     eng.set_option('screen', 1)
     return a, b, screened, rescored
-
-
-def _assert_same(a, b):
-    for f in ('index', 'value', 'score', 'lpdf_below', 'lpdf_above', 'label'):
-        assert np.array_equal(a[f], b[f], equal_nan=f != 'index' and f != 'label'), f
 
 
 def test_screened_round_is_the_fp64_round_at_2_24(eng):
