@@ -147,6 +147,9 @@ SIGNATURES = {
     'tpe_resident_labels': (ctypes.c_int32, [_P]),
     'tpe_history_reset': (ctypes.c_int, [_P, _P, _I32, _P, _I64]),
     'tpe_history_append': (ctypes.c_int, [_P, _P, _P, _P]),
+    # diagnostic (tests): one label's pool region and sorted view
+    'tpe_history_get': (ctypes.c_int, [_P, _I32, _I32, _P, _P, _P, _P, _I64, ctypes.POINTER(_I64),
+                                       ctypes.POINTER(_I64), ctypes.POINTER(_I64)]),
     'tpe_build_posterior_resident': (ctypes.c_int, [_P, _P, _I64, _I64, _D, _D, _I32, _P]),
     'tpe_build_posterior_resident_ordered': (ctypes.c_int, [_P, _P, _I64, _I64, _D, _D, _I32, _P, _P, _P,
                                                             _P, _P]),

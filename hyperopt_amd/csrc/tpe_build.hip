@@ -2153,6 +2153,44 @@ TPE_DEV int tpe1_get_mixture(tpe_ctx* ctx, int32_t label, int32_t side, double* 
     return TPE_OK;
 }
 
+// Diagnostic readback of one label's pool region (tests): the live prefix in
+// observation order and, for a non-categorical label, its value-sorted view.
+TPE_DEV int tpe1_history_get(tpe_ctx* ctx, int32_t label, int32_t* trial, double* val, double* key,
+                             int32_t* idx, int64_t cap, int64_t* n, int64_t* region_cap, int64_t* region_off) {
+    if (!ctx) return TPE_ERR_ARG;
+    TPE_SETTLE(ctx);
+    auto& B = ctx->build;
+    if (!B.hist_ready) return ctx->fail(TPE_ERR_ARG, "tpe_history_get: no resident history (tpe_history_reset)");
+    if (label < 0 || label >= (int32_t)B.specs_h.size())
+        return ctx->fail(TPE_ERR_ARG, "tpe_history_get: label out of range");
+    const int64_t c = B.cnt_h[label], off = B.off_h[label];
+    if (n) *n = c;
+    if (region_cap) *region_cap = B.cap_h[label];
+    if (region_off) *region_off = off;
+    const int64_t m = std::min(c, std::max<int64_t>(cap, 0));
+    if (m <= 0 || (!trial && !val && !key && !idx)) return TPE_OK;
+    HIPCHK(ctx, hipSetDevice(ctx->device));
+    HIPCHK(ctx, hipStreamSynchronize(ctx->stream));   // (the appends are queued, not waited for)
+    if (trial) HIPCHK(ctx, hipMemcpy(trial, B.p_trial.p + off, m * sizeof(int32_t), hipMemcpyDeviceToHost));
+    if (val) HIPCHK(ctx, hipMemcpy(val, B.p_val.p + off, m * sizeof(double), hipMemcpyDeviceToHost));
+    if (B.specs_h[label].kind != TPE_CATEGORICAL) {   // (a categorical label has no sorted view)
+        if (key) HIPCHK(ctx, hipMemcpy(key, B.s_key.p + off, m * sizeof(double), hipMemcpyDeviceToHost));
+        if (idx) HIPCHK(ctx, hipMemcpy(idx, B.s_idx.p + off, m * sizeof(int32_t), hipMemcpyDeviceToHost));
+    }
+    return TPE_OK;
+}
+
+// A label-sharded rebuild skipped this device (none of the subset's labels is
+// its own): its labels' tie flags read 0 in the next report, as the other
+// labels' of a one-device subset rebuild do.
+TPE_DEV int tpe1_report_skipped(tpe_ctx* ctx) {
+    if (!ctx) return TPE_ERR_ARG;
+    TPE_SETTLE(ctx);
+    auto& t = ctx->build.last_ties;
+    std::fill(t.begin(), t.end(), 0);
+    return TPE_OK;
+}
+
 TPE_DEV int32_t tpe1_resident_labels(const tpe_ctx* ctx) { return ctx ? ctx->resident.n_labels : 0; }
 
 TPE_DEV int tpe1_last_build_ms(const tpe_ctx* ctx, float* ms) {

@@ -736,6 +736,9 @@ TPE_DEV int tpe1_build_posterior(tpe_ctx* ctx, const tpe_label_spec* specs, int3
 TPE_DEV void tpe1_ctx_destroy(tpe_ctx* ctx);
 TPE_DEV int tpe1_get_mixture(tpe_ctx* ctx, int32_t label, int32_t side, double* weights, double* mus,
                              double* sigmas, int32_t cap, int32_t* n);
+TPE_DEV int tpe1_history_get(tpe_ctx* ctx, int32_t label, int32_t* trial, double* val, double* key,
+                             int32_t* idx, int64_t cap, int64_t* n, int64_t* region_cap, int64_t* region_off);
+TPE_DEV int tpe1_report_skipped(tpe_ctx* ctx);
 TPE_DEV int32_t tpe1_resident_labels(const tpe_ctx* ctx);
 TPE_DEV int tpe1_last_build_ms(const tpe_ctx* ctx, float* ms);
 TPE_DEV int tpe1_build_report(tpe_ctx* ctx, int32_t* n_below, int32_t* ties);

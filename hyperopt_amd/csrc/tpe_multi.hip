@@ -592,7 +592,9 @@ int tpe_rebuild_labels(tpe_ctx* ctx, const double* losses, int64_t n_trials, int
             if (g < 0 || g >= L) return x->fail(TPE_ERR_ARG, "tpe_rebuild_labels: label out of range");
             if (ctx->lsh_dev[g] == d) mine.push_back(ctx->lsh_local[g]);
         }
-        if (mine.empty()) return TPE_OK;   // (its labels keep their build)
+        // (its labels keep their build; their tie flags read 0 from now on,
+        // as the labels outside a one-device subset rebuild's do)
+        if (mine.empty()) return tpe1_report_skipped(x);
         std::vector<int64_t> off;
         std::vector<int32_t> ord;
         lsh_orders(ids, order_off, order, off, ord);
@@ -644,6 +646,26 @@ int tpe_get_mixture(tpe_ctx* ctx, int32_t label, int32_t side, double* weights, 
     HIPCHK(ctx, hipSetDevice(x->device));
     const int rc = tpe1_get_mixture(x, ctx->lsh_local[label], side, weights, mus, sigmas, cap, n);
     if (rc) ctx->err = x->err;
+    return rc;
+}
+
+int tpe_history_get(tpe_ctx* ctx, int32_t label, int32_t device, int32_t* trial, double* val, double* key,
+                    int32_t* idx, int64_t cap, int64_t* n, int64_t* region_cap, int64_t* region_off) {
+    if (!ctx) return TPE_ERR_ARG;
+    if (ctx->peers.empty())   // (one device: `device` is not looked at)
+        return tpe1_history_get(ctx, label, trial, val, key, idx, cap, n, region_cap, region_off);
+    tpe_ctx* x;
+    int32_t local = label;
+    if (lsharded(ctx)) {   // (the owning device and its local label number, as tpe_get_mixture)
+        if (label < 0 || label >= ctx->lsh_L) return ctx->fail(TPE_ERR_ARG, "tpe_history_get: label out of range");
+        x = dev(ctx, ctx->lsh_dev[label]);
+        local = ctx->lsh_local[label];
+    } else {               // (replicated: every device holds every label)
+        if (device < 0 || device >= ndev(ctx)) return ctx->fail(TPE_ERR_ARG, "tpe_history_get: no such device");
+        x = dev(ctx, device);
+    }
+    const int rc = tpe1_history_get(x, local, trial, val, key, idx, cap, n, region_cap, region_off);
+    if (rc && x != ctx) ctx->err = x->err;
     return rc;
 }
 

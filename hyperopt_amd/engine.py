@@ -179,6 +179,7 @@ class Engine(object):
             _ptr(obs_off), _ptr(obs_trial), _ptr(obs_val), float(gamma), float(prior_weight),
             int(lf), ctypes.byref(nb)))
         self.n_labels = self.hist_labels = len(specs)
+        self.hist_kinds = specs['kind'].copy()
         return nb.value
 
     # -- device-resident history -----------------------------------------------
@@ -189,6 +190,7 @@ class Engine(object):
         self._check(self.lib.tpe_history_reset(self.h, _ptr(specs), len(specs), _ptr(cat_p),
                                                len(cat_p)))
         self.hist_labels = len(specs)
+        self.hist_kinds = specs['kind'].copy()
 
     def history_append(self, n_new, obs_trial, obs_val):
         """n_new[l] new observations of label l (concatenated label-major):
@@ -198,6 +200,26 @@ class Engine(object):
         obs_val = _f64(obs_val)
         self._check(self.lib.tpe_history_append(self.h, _ptr(n_new), _ptr(obs_trial),
                                                 _ptr(obs_val)))
+
+    def history_get(self, label, device=0):
+        """One label's region of the resident history as the appends left it
+        (diagnostic, tpe_history_get): (trial int32, val f64, key f64, idx
+        int32, region_cap, region_off) -- trial and val in observation order,
+        key / idx the value-sorted view (empty for a categorical label).
+        `device` picks the replica of a replicated multi-device context; a
+        label-sharded one reads the owning device."""
+        n, cap, off = ctypes.c_int64(), ctypes.c_int64(), ctypes.c_int64()
+        self._check(self.lib.tpe_history_get(self.h, int(label), int(device), None, None, None, None, 0,
+                                             ctypes.byref(n), ctypes.byref(cap), ctypes.byref(off)))
+        m = n.value
+        trial, val = np.zeros(m, dtype=np.int32), np.zeros(m)
+        key, idx = np.full(m, np.nan), np.full(m, -1, dtype=np.int32)
+        self._check(self.lib.tpe_history_get(self.h, int(label), int(device), _ptr(trial), _ptr(val),
+                                             _ptr(key), _ptr(idx), m, ctypes.byref(n), ctypes.byref(cap),
+                                             ctypes.byref(off)))
+        if self.hist_kinds[int(label)] == L.TPE_CATEGORICAL:   # (no sorted view)
+            key, idx = key[:0], idx[:0]
+        return trial, val, key, idx, cap.value, off.value
 
     def build_posterior_resident(self, losses, n_valid, gamma, prior_weight, lf=25):
         """Rebuild the posterior from the resident history; losses per trial

@@ -261,6 +261,24 @@ int tpe_build_posterior_resident(tpe_ctx *ctx, const double *losses, int64_t n_t
                                  int64_t n_valid, double gamma, double prior_weight,
                                  int32_t lf, int32_t *n_below_out);
 
+/* Diagnostic readback of the resident history (tests): label `label`'s pool
+ * region as the appends left it.  *n receives its observation count, and the
+ * first min(cap, *n) entries of each non-NULL array are written: trial and val
+ * in observation order (what tpe_history_append was given), and for a
+ * non-categorical label its value-sorted view -- key ascending, idx the
+ * observation index of each key, equal keys in observation order (key and idx
+ * are left untouched for a categorical label, which has none).  region_cap /
+ * region_off: the capacity and the offset of the label's region in the pool
+ * (a label never observed owns a region of capacity 0).  With every array
+ * NULL only the three numbers are returned.  Waits for the context's stream
+ * (the appends are queued) before it reads; changes nothing.  A label-sharded
+ * multi-device context reads the owning device (as tpe_get_mixture does); a
+ * replicated one reads replica `device` (0 .. devices - 1); a one-device
+ * context ignores `device`.  TPE_ERR_ARG before tpe_history_reset. */
+int tpe_history_get(tpe_ctx *ctx, int32_t label, int32_t device, int32_t *trial, double *val,
+                    double *key, int32_t *idx, int64_t cap, int64_t *n, int64_t *region_cap,
+                    int64_t *region_off);
+
 /* tpe_build_posterior_resident with the reference's tie order (ap_filter_trials
  * tpe.py:637 `l_order = np.argsort(l_vals)` and adaptive_parzen_normal
  * tpe.py:433 `order = np.argsort(mus)`: numpy's unstable sort, whose order of
@@ -315,7 +333,10 @@ int tpe_last_build_ms(const tpe_ctx *ctx, float *ms);
 
 /* The last build's report, applied first if it was deferred
  * (TPE_OPT_DEFER_REPORT): n_below and the tie report tpe_rebuild_labels
- * returns (ties: n_labels + 1 entries, NULL to skip).  Replaces nothing in
+ * returns (ties: n_labels + 1 entries, NULL to skip).  After a
+ * tpe_rebuild_labels the flags of the labels outside its subset read 0 --
+ * on a label-sharded multi-device context also those of a device that holds
+ * none of the subset's labels, as on one device.  Replaces nothing in
  * the reference: the deferral is this library's (posterior.py
  * _build_reference_order reads it after the round). */
 int tpe_build_report(tpe_ctx *ctx, int32_t *n_below, int32_t *ties);

@@ -13,59 +13,9 @@ mixtures uploaded with tpe_set_posterior (host fold)."""
 import numpy as np
 import pytest
 
-from oracle import tpe_oracle as O
+from tests.helpers import ALL_KINDS, _check_bit_exact, make_history, oracle_mixtures
 
 pytestmark = pytest.mark.gpu
-
-ALL_KINDS = [
-    ('u', 'uniform', dict(low=-5.0, high=5.0)),
-    ('qu', 'quniform', dict(low=0.0, high=20.0, q=1.0)),
-    ('lu', 'loguniform', dict(low=-5.0, high=2.0)),
-    ('qlu', 'qloguniform', dict(low=0.0, high=4.0, q=1.0)),
-    ('n', 'normal', dict(mu=0.0, sigma=3.0)),
-    ('qn', 'qnormal', dict(mu=0.0, sigma=3.0, q=0.5)),
-    ('ln', 'lognormal', dict(mu=0.0, sigma=1.0)),
-    ('qln', 'qlognormal', dict(mu=1.0, sigma=1.0, q=1.0)),
-    ('ri', 'randint', dict(upper=7)),
-    ('pc', 'categorical', dict(upper=4, p=[0.1, 0.2, 0.3, 0.4])),
-]
-
-
-def make_history(labels, n_trials, seed, active_frac=1.0, loss_round=None, orphan=0):
-    """Synthetic history: prior draws, each label active in a random subset,
-    losses optionally rounded (ties), `orphan` observations whose tid has no
-    loss entry (the reference drops them)."""
-    from hyperopt_amd.workloads import History, prior_draw
-    rng = np.random.RandomState(seed)
-    tids = np.arange(n_trials, dtype=np.int64) * 3 + 5          # sparse, sorted tids
-    losses = rng.normal(size=n_trials)
-    if loss_round is not None:
-        losses = np.round(losses, loss_round)
-    obs = {}
-    for name, kind, args in labels:
-        act = tids[rng.uniform(size=n_trials) < active_frac] if active_frac < 1 else tids
-        v = prior_draw(kind, args, rng, len(act))
-        if orphan:
-            extra = np.arange(orphan, dtype=np.int64) * 3 + 6        # never a trial tid
-            act = np.concatenate([act, extra])
-            v = np.concatenate([v, prior_draw(kind, args, rng, orphan)])
-            o = np.argsort(act, kind='stable')
-            act, v = act[o], v[o]
-        obs[name] = (act, v)
-    return History(labels, tids, losses, obs)
-
-
-def oracle_mixtures(hist, gamma=0.25, pw=1.0, sort_kind=None):
-    out = []
-    for name, kind, args in hist.labels:
-        oi, ov = hist.obs[name]
-        r = O.label_posteriors(kind, args, oi, ov, hist.tids, hist.losses, gamma, pw,
-                               sort_kind=sort_kind)
-        if r[0] == 'CAT':
-            out.append(((r[1],), (r[2],)))
-        else:
-            out.append((r[0][1:4], r[1][1:4]))
-    return out
 
 
 @pytest.fixture(scope='module')
@@ -78,22 +28,6 @@ def eng():
 
 def _build(eng, hist, gamma=0.25, pw=1.0, tie_order='reference'):
     return eng.build_posterior(*hist.device_inputs(), gamma=gamma, prior_weight=pw, tie_order=tie_order)
-
-
-def _check_bit_exact(eng, hist, want):
-    for li, (name, kind, _) in enumerate(hist.labels):
-        for side in (0, 1):
-            w, m, s = eng.get_mixture(li, side)
-            ref = want[li][side]
-            if kind in ('randint', 'categorical'):
-                assert np.array_equal(w, ref[0]), (name, side, w, ref[0])
-            else:
-                rw, rm, rs = ref
-                assert len(w) == len(rw), (name, side, len(w), len(rw))
-                assert np.array_equal(m, rm), (name, side, 'mus')
-                assert np.array_equal(s, rs), (name, side, 'sigmas')
-                assert np.array_equal(w, rw), (name, side, 'weights',
-                                               np.max(np.abs(w - rw)))
 
 
 @pytest.mark.parametrize('n_trials', [1, 2, 3, 25, 26, 27, 200, 3000])
