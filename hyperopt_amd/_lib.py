@@ -15,7 +15,7 @@ HERE = os.path.dirname(os.path.abspath(__file__))
 LIB_PATH = os.path.join(HERE, 'libhyperopt_tpe.so')
 HEADER = os.path.join(os.path.dirname(HERE), 'include', 'hyperopt_tpe.h')
 
-ABI_VERSION = 4
+ABI_VERSION = 5
 
 TPE_OK = 0
 TPE_ERR_VALUE = -1
@@ -172,14 +172,8 @@ SIGNATURES = {
     'tpe_screen_probe': (ctypes.c_int, [_P, _I32, _P, _I64, _P, _P]),
     'tpe_export_posterior': (ctypes.c_int, [_P, _P, _I64, _P]),
     'tpe_import_posterior': (ctypes.c_int, [_P, _P, _I64, _P, _I32, _P, _P]),
-    'tpe_joint_set_posterior': (ctypes.c_int, [_P, _P, _I32, _I32, _P, _P, _P, _I32, _P, _P, _P]),
-    'tpe_joint_draw': (ctypes.c_int, [_P, _U64, _U32, _I64, _I64, _P, _P]),
-    'tpe_joint_score': (ctypes.c_int, [_P, _P, _I64, _P, _P]),
-    'tpe_joint_suggest': (ctypes.c_int, [_P, _U64, _U32, _I64, _P, _P, _PD, _PD]),
-    'tpe_joint_set_group': (ctypes.c_int, [_P, _I32, _U32, _P, _I32, _I32, _P, _P, _P, _I32, _P, _P, _P]),
-    'tpe_joint_set_group_q': (ctypes.c_int, [_P, _I32, _U32, _P, _P, _I32, _I32, _P, _P, _P, _I32, _P, _P, _P]),
-    'tpe_joint_set_group_c': (ctypes.c_int, [_P, _I32, _U32, _P, _P, _P, _P, _D, _I32, _I32, _P, _P, _P, _I32, _P,
-                                             _P, _P]),
+    'tpe_joint_set_group': (ctypes.c_int, [_P, _I32, _U32, _P, _P, _P, _P, _D, _I32, _I32, _P, _P, _P, _I32, _P, _P,
+                                           _P]),
     'tpe_joint_clear_groups': (ctypes.c_int, [_P]),
     'tpe_joint_build_groups': (ctypes.c_int, [_P, _I32, _P, _P, _P, _P, _P, _P, _P, _P, _D, _P]),
     'tpe_joint_get_group': (ctypes.c_int, [_P, _I32, _I32, _P, _P, _P, _I32, _P, _P]),

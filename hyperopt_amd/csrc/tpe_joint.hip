@@ -22,7 +22,7 @@
 //                                     same arithmetic: the same bits
 //   k_joint_best                      the round's winner; its D values are
 //                                     drawn again from Philox by index
-//   k_joint_draw                      candidates and their components (tpe_joint_draw)
+//   k_joint_draw                      candidates and their components (tpe_joint_draw_group)
 //   k_joint_best_cells                packed rounds (tpe_joint_suggest_batch): the
 //                                     lanes of k_joint_round run over the flat
 //                                     index f = r n + g of R rounds of n
@@ -44,7 +44,7 @@
 // y' in registers up to kJReg dimensions, beyond in LDS (dimension-major:
 // consecutive lanes read consecutive words).
 //
-// Quantized dimensions (tpe_joint_set_group_q, q_d > 0): the mixtures, m_kd,
+// Quantized dimensions (tpe_joint_set_group, q_d > 0): the mixtures, m_kd,
 // A_S, the pick and the draw of y are the dense group's; the drawn value is
 // x_d = rint(v / q_d) q_d (v = exp(y) for a log kind), and the factor of the
 // dimension is the component's mass on the value's interval,
@@ -63,7 +63,7 @@
 // dimension), ~100 times the two LDS reads they share among kJU components.
 // Dense-only groups launch the instantiations they always did.
 //
-// Categorical dimensions (tpe_joint_set_group_c, upper_d = C_d > 0, prior p_d):
+// Categorical dimensions (tpe_joint_set_group, upper_d = C_d > 0, prior p_d):
 // with a_Sd = C_d prior_weight / K_S the factor of category x in component k is
 //   r_0d[x] = p_d[x],   r_td[x] = ([x == o_td] + a_Sd p_d[x]) / (1 + a_Sd)
 // (o_td: the category trial t observed); m_kd = 1, so A_S and the pick are
@@ -954,12 +954,11 @@ int read_err(tpe_ctx* ctx, JointGroups* G) {
     return TPE_OK;
 }
 
-// upload and fold one slot's posterior; `only`: the other slots are cleared
-// once the arguments are accepted (tpe_joint_set_posterior)
-int joint_set(tpe_ctx* ctx, int32_t slot, uint32_t pick_stream, bool only, const tpe_joint_dim* dims,
-              const double* q, int32_t n_dims, int32_t n_below, const double* wb, const double* mub, const double* sigb,
-              int32_t n_above, const double* wa, const double* mua, const double* siga,
-              const int32_t* upper = nullptr, const double* cat_p = nullptr, double prior_weight = 0.0) {
+// upload and fold one slot's posterior (tpe_joint_set_group)
+int joint_set(tpe_ctx* ctx, int32_t slot, uint32_t pick_stream, const tpe_joint_dim* dims, const double* q,
+              const int32_t* upper, const double* cat_p, double prior_weight, int32_t n_dims, int32_t n_below,
+              const double* wb, const double* mub, const double* sigb, int32_t n_above, const double* wa,
+              const double* mua, const double* siga) {
     if (!ctx) return TPE_ERR_ARG;
     if (slot < 0 || slot >= kJMaxGroups)
         return ctx->fail(TPE_ERR_ARG, "a joint slot is in [0, " + std::to_string(kJMaxGroups) + ")");
@@ -1050,9 +1049,6 @@ int joint_set(tpe_ctx* ctx, int32_t slot, uint32_t pick_stream, bool only, const
     }
     HIPCHK(ctx, hipSetDevice(ctx->device));
     JointGroups* G = jgroups(ctx, true);
-    if (only)   // (an unset slot keeps its buffers for the next posterior: no hipFree per call)
-        for (int j = 0; j < kJMaxGroups; ++j)
-            if (j != slot && G->slot[j]) G->slot[j]->ready = false;
     if (!G->slot[slot]) G->slot[slot].reset(new JointState());
     JointState* J = G->slot[slot].get();
     J->ready = false;
@@ -1398,32 +1394,12 @@ int joint_build_groups(tpe_ctx* ctx, int32_t n_groups, const int32_t* slots, con
 
 extern "C" {
 
-int tpe_joint_set_posterior(tpe_ctx* ctx, const tpe_joint_dim* dims, int32_t n_dims, int32_t n_below,
-                            const double* wb, const double* mub, const double* sigb, int32_t n_above,
-                            const double* wa, const double* mua, const double* siga) {
-    return joint_set(ctx, 0, TPE_JOINT_STREAM, true, dims, nullptr, n_dims, n_below, wb, mub, sigb, n_above, wa, mua, siga);
-}
-
-int tpe_joint_set_group(tpe_ctx* ctx, int32_t slot, uint32_t pick_stream, const tpe_joint_dim* dims, int32_t n_dims,
-                        int32_t n_below, const double* wb, const double* mub, const double* sigb, int32_t n_above,
-                        const double* wa, const double* mua, const double* siga) {
-    return joint_set(ctx, slot, pick_stream, false, dims, nullptr, n_dims, n_below, wb, mub, sigb, n_above, wa, mua,
-                     siga);
-}
-
-int tpe_joint_set_group_q(tpe_ctx* ctx, int32_t slot, uint32_t pick_stream, const tpe_joint_dim* dims,
-                          const double* q, int32_t n_dims, int32_t n_below, const double* wb, const double* mub,
-                          const double* sigb, int32_t n_above, const double* wa, const double* mua,
-                          const double* siga) {
-    return joint_set(ctx, slot, pick_stream, false, dims, q, n_dims, n_below, wb, mub, sigb, n_above, wa, mua, siga);
-}
-
-int tpe_joint_set_group_c(tpe_ctx* ctx, int32_t slot, uint32_t pick_stream, const tpe_joint_dim* dims,
-                          const double* q, const int32_t* upper, const double* cat_p, double prior_weight,
-                          int32_t n_dims, int32_t n_below, const double* wb, const double* mub, const double* sigb,
-                          int32_t n_above, const double* wa, const double* mua, const double* siga) {
-    return joint_set(ctx, slot, pick_stream, false, dims, q, n_dims, n_below, wb, mub, sigb, n_above, wa, mua, siga,
-                     upper, cat_p, prior_weight);
+int tpe_joint_set_group(tpe_ctx* ctx, int32_t slot, uint32_t pick_stream, const tpe_joint_dim* dims,
+                        const double* q, const int32_t* upper, const double* cat_p, double prior_weight,
+                        int32_t n_dims, int32_t n_below, const double* wb, const double* mub, const double* sigb,
+                        int32_t n_above, const double* wa, const double* mua, const double* siga) {
+    return joint_set(ctx, slot, pick_stream, dims, q, upper, cat_p, prior_weight, n_dims, n_below, wb, mub, sigb,
+                     n_above, wa, mua, siga);
 }
 
 int tpe_joint_clear_groups(tpe_ctx* ctx) {
@@ -1431,7 +1407,7 @@ int tpe_joint_clear_groups(tpe_ctx* ctx) {
     JointGroups* G = jgroups(ctx, false);
     if (!G) return TPE_OK;
     for (int j = 0; j < kJMaxGroups; ++j)
-        if (G->slot[j]) G->slot[j]->ready = false;   // (buffers kept, as above)
+        if (G->slot[j]) G->slot[j]->ready = false;   // (buffers kept for the next posterior: no hipFree per call)
     return TPE_OK;
 }
 
@@ -1471,7 +1447,7 @@ int tpe_joint_draw_group(tpe_ctx* ctx, int32_t slot, uint64_t seed, uint32_t rou
     if (!ctx) return TPE_ERR_ARG;
     JointGroups* G = nullptr;
     JointState* J = nullptr;
-    int rc = joint_ready(ctx, slot, &G, &J, "tpe_joint_draw");
+    int rc = joint_ready(ctx, slot, &G, &J, "tpe_joint_draw_group");
     if (rc) return rc;
     if (!values || !comp) return ctx->fail(TPE_ERR_ARG, "null pointer");
     if ((rc = check_range(ctx, n, cand_offset))) return rc;
@@ -1488,16 +1464,11 @@ int tpe_joint_draw_group(tpe_ctx* ctx, int32_t slot, uint64_t seed, uint32_t rou
     return read_err(ctx, G);
 }
 
-int tpe_joint_draw(tpe_ctx* ctx, uint64_t seed, uint32_t round, int64_t n, int64_t cand_offset, double* values,
-                   int32_t* comp) {
-    return tpe_joint_draw_group(ctx, 0, seed, round, n, cand_offset, values, comp);
-}
-
 int tpe_joint_score_group(tpe_ctx* ctx, int32_t slot, const double* values, int64_t n, double* ll, double* lg) {
     if (!ctx) return TPE_ERR_ARG;
     JointGroups* G = nullptr;
     JointState* J = nullptr;
-    int rc = joint_ready(ctx, slot, &G, &J, "tpe_joint_score");
+    int rc = joint_ready(ctx, slot, &G, &J, "tpe_joint_score_group");
     if (rc) return rc;
     if (!values || !ll || !lg) return ctx->fail(TPE_ERR_ARG, "null pointer");
     if ((rc = check_range(ctx, n, 0))) return rc;
@@ -1513,16 +1484,12 @@ int tpe_joint_score_group(tpe_ctx* ctx, int32_t slot, const double* values, int6
     return TPE_OK;
 }
 
-int tpe_joint_score(tpe_ctx* ctx, const double* values, int64_t n, double* ll, double* lg) {
-    return tpe_joint_score_group(ctx, 0, values, n, ll, lg);
-}
-
 int tpe_joint_suggest_group(tpe_ctx* ctx, int32_t slot, uint64_t seed, uint32_t round, int64_t n_candidates,
                             double* values, int64_t* index, double* ll, double* lg) {
     if (!ctx) return TPE_ERR_ARG;
     JointGroups* G = nullptr;
     JointState* J = nullptr;
-    int rc = joint_ready(ctx, slot, &G, &J, "tpe_joint_suggest");
+    int rc = joint_ready(ctx, slot, &G, &J, "tpe_joint_suggest_group");
     if (rc) return rc;
     if (!values || !index || !ll || !lg) return ctx->fail(TPE_ERR_ARG, "null pointer");
     if ((rc = check_range(ctx, n_candidates, 0))) return rc;
@@ -1550,15 +1517,10 @@ int tpe_joint_suggest_group(tpe_ctx* ctx, int32_t slot, uint64_t seed, uint32_t 
     return TPE_OK;
 }
 
-int tpe_joint_suggest(tpe_ctx* ctx, uint64_t seed, uint32_t round, int64_t n_candidates, double* values,
-                      int64_t* index, double* ll, double* lg) {
-    return tpe_joint_suggest_group(ctx, 0, seed, round, n_candidates, values, index, ll, lg);
-}
-
 // Every set slot's rounds in packed launches: per slot, chunks of whole
 // rounds whose flat candidate count stays within the cap -- one k_joint_round
 // (+ k_joint_merge) and one k_joint_best_cells each; a round beyond the cap
-// runs alone as tpe_joint_suggest runs it.  The result rows of all slots and,
+// runs alone as tpe_joint_suggest_group runs it.  The result rows of all slots and,
 // in front of them, the error word are one device buffer: one copy back, one
 // synchronisation.
 int tpe_joint_suggest_batch(tpe_ctx* ctx, uint64_t seed, const uint32_t* rounds, int32_t n_rounds,

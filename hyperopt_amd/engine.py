@@ -426,26 +426,15 @@ class Engine(object):
     # -- joint (multivariate) posterior ---------------------------------------
     def set_joint_posterior(self, dims, wb, mub, sigb, wa, mua, siga, q=None, upper=None, cat_p=None,
                             prior_weight=None):
-        """The joint mixtures of a group of D dense labels
-        (posterior.joint_mixture): dims a JOINT_DIM_DTYPE array, weights [K],
-        means and sigmas [K, D], component 0 the prior
-        (tpe_joint_set_posterior).  q: the quantization step per dimension, 0
-        for a dense one (posterior.joint_mixture(quantized=True)); with a
-        step set the group is slot 0 of tpe_joint_set_group_q, the other
-        slots cleared.  upper, cat_p, prior_weight: the categorical dimensions
-        (set_joint_group), slot 0 likewise."""
-        if (q is not None and np.any(_f64(q) != 0.0)) or (upper is not None and np.any(np.asarray(upper) != 0)):
-            self.clear_joint_groups()
-            return self.set_joint_group(0, L.TPE_JOINT_STREAM, dims, wb, mub, sigb, wa, mua, siga, q=q,
-                                        upper=upper, cat_p=cat_p, prior_weight=prior_weight)
-        args = self._joint_args(dims, wb, mub, sigb, wa, mua, siga)
-        rc = self.lib.tpe_joint_set_posterior(self.h, *args)
-        # (a box without below mass is set, and every draw reports it again)
-        self.joint_slots = {0: args[1]} if rc in (L.TPE_OK, L.TPE_ERR_SAMPLE) else {}
-        self._check(rc)
+        """set_joint_group for slot 0 with the pick stream L.TPE_JOINT_STREAM,
+        every other slot cleared (also when the posterior is refused)."""
+        self.clear_joint_groups()
+        self.set_joint_group(0, L.TPE_JOINT_STREAM, dims, wb, mub, sigb, wa, mua, siga, q=q, upper=upper,
+                             cat_p=cat_p, prior_weight=prior_weight)
 
     @staticmethod
-    def _joint_args(dims, wb, mub, sigb, wa, mua, siga):
+    def _joint_args(dims, wb, mub, sigb, wa, mua, siga, q=None, upper=None, cat_p=None, prior_weight=None):
+        """tpe_joint_set_group's arguments after the pick stream."""
         dims = np.ascontiguousarray(dims, dtype=JOINT_DIM_DTYPE)
         D = len(dims)
         arrs = []
@@ -455,52 +444,47 @@ class Engine(object):
                 raise ValueError('joint means and sigmas must be [components, dimensions]')
             arrs.append((w, m, s))
         (wb, mub, sigb), (wa, mua, siga) = arrs
+        if q is not None:
+            q = _f64(q).ravel()
+            if len(q) != D:
+                raise ValueError('q holds one step per joint dimension')
+        if upper is not None:
+            upper = np.ascontiguousarray(upper, dtype=np.int32).ravel()
+            if len(upper) != D:
+                raise ValueError('upper holds one entry per joint dimension')
+            cat_p = _f64(cat_p if cat_p is not None else []).ravel()
+            ncat = int(np.maximum(upper, 0).sum())
+            if len(cat_p) != ncat:
+                raise ValueError('cat_p holds the priors of the categorical dimensions, concatenated')
+            if ncat and prior_weight is None:
+                raise ValueError('categorical joint dimensions need prior_weight')
+        if upper is None or not len(cat_p):
+            cat_p = None
         # (data_as pointers hold their arrays)
-        return (_ptr(dims), D, len(wb), _ptr(wb), _ptr(mub), _ptr(sigb), len(wa), _ptr(wa), _ptr(mua),
-                _ptr(siga))
+        return (_ptr(dims), _ptr(q), _ptr(upper), _ptr(cat_p),
+                float(prior_weight if prior_weight is not None else 0.0), D, len(wb), _ptr(wb), _ptr(mub),
+                _ptr(sigb), len(wa), _ptr(wa), _ptr(mua), _ptr(siga))
 
     def set_joint_group(self, slot, pick_stream, dims, wb, mub, sigb, wa, mua, siga, q=None, upper=None,
                         cat_p=None, prior_weight=None):
-        """set_joint_posterior for one of the context's L.TPE_JOINT_MAX_GROUPS
-        slots, the other slots left as they are; pick_stream: the Philox
-        stream of the slot's component pick (tpe_joint_set_group).  q [D]: the
-        quantization steps, 0 for a dense dimension (tpe_joint_set_group_q:
-        D plus the number of quantized dimensions is at most 128).  upper [D]:
-        the number of categories of a categorical dimension, 0 for any other;
-        cat_p: those dimensions' priors, concatenated; prior_weight: the
-        pseudocount weight of their kernels (tpe_joint_set_group_c; the
-        observed categories travel in the means, posterior.joint_mixture(
-        categorical=True))."""
-        args = self._joint_args(dims, wb, mub, sigb, wa, mua, siga)
-        if upper is not None:
-            upper = np.ascontiguousarray(upper, dtype=np.int32).ravel()
-            if len(upper) != args[1]:
-                raise ValueError('upper holds one entry per joint dimension')
-            if q is not None:
-                q = _f64(q).ravel()
-                if len(q) != args[1]:
-                    raise ValueError('q holds one step per joint dimension')
-            cat_p = _f64(cat_p if cat_p is not None else []).ravel()
-            if len(cat_p) != int(np.sum(np.maximum(upper, 0))):
-                raise ValueError('cat_p holds the priors of the categorical dimensions, concatenated')
-            if np.any(upper > 0) and prior_weight is None:
-                raise ValueError('categorical joint dimensions need prior_weight')
-            rc = self.lib.tpe_joint_set_group_c(self.h, int(slot), int(pick_stream) & 0xFFFFFFFF, args[0],
-                                                _ptr(q) if q is not None else None, _ptr(upper),
-                                                _ptr(cat_p) if len(cat_p) else None,
-                                                float(prior_weight if prior_weight is not None else 0.0),
-                                                *args[1:])
-        elif q is None:
-            rc = self.lib.tpe_joint_set_group(self.h, int(slot), int(pick_stream) & 0xFFFFFFFF, *args)
-        else:
-            q = _f64(q).ravel()
-            if len(q) != args[1]:
-                raise ValueError('q holds one step per joint dimension')
-            rc = self.lib.tpe_joint_set_group_q(self.h, int(slot), int(pick_stream) & 0xFFFFFFFF, args[0],
-                                                _ptr(q), *args[1:])
+        """The joint mixtures of a group of D labels in one of the context's
+        L.TPE_JOINT_MAX_GROUPS slots, the other slots left as they are
+        (tpe_joint_set_group): the fields of a posterior.JointMixture, so
+        set_joint_group(slot, pick_stream, *mix, prior_weight=pw).  dims a
+        JOINT_DIM_DTYPE array, weights [K], means and sigmas [K, D], component
+        0 the prior; pick_stream: the Philox stream of the slot's component
+        pick.  q [D]: the quantization steps, 0 for a dimension that is not
+        quantized (D plus the number of quantized dimensions is at most 128).
+        upper [D]: the number of categories of a categorical dimension, 0 for
+        any other; cat_p: those dimensions' priors, concatenated;
+        prior_weight: the pseudocount weight of their kernels (the observed
+        categories travel in the means).  None: no such dimension."""
+        args = self._joint_args(dims, wb, mub, sigb, wa, mua, siga, q, upper, cat_p, prior_weight)
+        rc = self.lib.tpe_joint_set_group(self.h, int(slot), int(pick_stream) & 0xFFFFFFFF, *args)
+        # (a box without below mass is set, and every draw reports it again)
         slots = self.__dict__.setdefault('joint_slots', {})
         if rc in (L.TPE_OK, L.TPE_ERR_SAMPLE):
-            slots[int(slot)] = args[1]
+            slots[int(slot)] = len(dims)
         elif 0 <= int(slot) < L.TPE_JOINT_MAX_GROUPS:
             slots.pop(int(slot), None)
         self._check(rc)

@@ -14,6 +14,7 @@ same order, including the default, non-stable np.argsort tie order):
   categorical   pseudocount posteriors        tpe.py:581-617
 It is vectorised over the history (no per-trial Python loops).
 """
+import collections
 import threading
 import time
 import weakref
@@ -232,44 +233,53 @@ def _parzen_positions(mus, prior_mu):
     return pos, where
 
 
+# A joint-group label's prior: the prior mapping label_posterior uses (tpe
+# kind is log or not, bounds, prior mu and sigma in the working space), the
+# quantization step q (0.0: not quantized), the number of categories upper (0:
+# not categorical) and the categorical prior p (None).  A categorical label's
+# first six fields are placeholders (False, False, 0, 0, 0, 1).
+JointPrior = collections.namedtuple('JointPrior', 'log bounded low high mu sigma q upper p')
+
+# A joint group's mixtures (joint_mixture): the positional arguments of
+# Engine.set_joint_group after the slot and its pick stream.
+JointMixture = collections.namedtuple('JointMixture', 'dims wb mub sigb wa mua siga q upper cat_p')
+
+
 def joint_prior(kind, args, quantized=False, categorical=False):
-    """(tpe kind, bounded, low, high, prior_mu, prior_sigma, transform) of a
-    joint-group label: the prior mapping label_posterior uses.
-    quantized=True accepts JOINT_QUANT_KINDS too (the prior of the kind
-    without its q) and returns the step as a seventh element, 0.0 for a
-    dense kind.  categorical=True accepts JOINT_CAT_KINDS too and returns
-    two more, last elements: the number of categories (0 for any other kind)
-    and the prior p (None); a categorical label's first six elements are
-    placeholders (False, False, 0, 0, 0, 1), its p must be positive."""
+    """The JointPrior of a joint-group label.  The flags say which kinds may
+    join besides JOINT_KINDS: quantized=True the JOINT_QUANT_KINDS (the prior
+    of the kind without its q, and the step), categorical=True the
+    JOINT_CAT_KINDS (their p must be positive); any other kind is a
+    ValueError."""
     if categorical and kind in JOINT_CAT_KINDS:
         upper, p = joint_cat_prior(kind, args)
         if upper < 1 or len(p) != upper or not np.all((p > 0.0) & np.isfinite(p)):
             raise ValueError('a categorical joint label needs upper >= 1 positive finite probabilities')
-        return (False, False, 0.0, 0.0, 0.0, 1.0) + ((0.0,) if quantized else ()) + (upper, p)
+        return JointPrior(False, False, 0.0, 0.0, 0.0, 1.0, 0.0, upper, p)
     if kind not in JOINT_KINDS and not (quantized and kind in JOINT_QUANT_KINDS):
         raise ValueError('%r labels cannot join a joint group' % (kind,))
-    if categorical:
-        return joint_prior(kind, args, quantized) + (0, None)
-    step = ()
-    if quantized:
-        step = (float(args['q']) if kind in JOINT_QUANT_KINDS else 0.0,)
-        if kind in JOINT_QUANT_KINDS and not (0.0 < step[0] < np.inf):
+    q = 0.0
+    if kind in JOINT_QUANT_KINDS:
+        q = float(args['q'])
+        if not (0.0 < q < np.inf):
             raise ValueError('label kind %r needs a positive finite q' % (kind,))
-        kind = kind[1:] if kind in JOINT_QUANT_KINDS else kind
+        kind = kind[1:]
     log = kind in ('loguniform', 'lognormal')
     if kind in ('uniform', 'loguniform'):
         low, high = float(args['low']), float(args['high'])
-        return (log, True, low, high, 0.5 * (high + low), 1.0 * (high - low)) + step
-    return (log, False, 0.0, 0.0, float(args['mu']), float(args['sigma'])) + step
+        return JointPrior(log, True, low, high, 0.5 * (high + low), 1.0 * (high - low), q, 0, None)
+    return JointPrior(log, False, 0.0, 0.0, float(args['mu']), float(args['sigma']), q, 0, None)
 
 
 def joint_mixture(group_specs, obs, splitter, prior_weight, streams=None, quantized=False, categorical=False):
-    """The joint (multivariate) mixtures of a group of dense continuous
-    labels whose observations belong to the same trials.
+    """The joint (multivariate) mixtures of a group of labels whose
+    observations belong to the same trials, as a JointMixture.
 
     group_specs: the group's LabelSpecs (or (label, kind, args) tuples);
     obs[label] = (idxs, vals); splitter: the history's Splitter; streams: each
-    label's Philox stream (default its position in the group).
+    label's Philox stream (default its position in the group).  quantized and
+    categorical say which kinds may join (joint_prior); what is returned for a
+    group does not depend on them.
 
     Per side and label d the unchanged univariate build
     adaptive_parzen_normal(o[:, d], ...) supplies sigma and weight of every
@@ -280,70 +290,37 @@ def joint_mixture(group_specs, obs, splitter, prior_weight, streams=None, quanti
     with them to rounding (each label normalises by a sum of the same terms
     taken in its own sorted order, so the last bits can differ).
 
-    Returns (dims, wb, mub, sigb, wa, mua, siga): dims a JOINT_DIM_DTYPE
-    array, weights [K], means and sigmas [K, D] in the labels' working space
-    (log space for the log kinds).
+    dims is a JOINT_DIM_DTYPE array; the weights are [K], means and sigmas
+    [K, D] in the labels' working space (log space for the log kinds); q
+    (float64 [D]) holds the steps, 0 for a label that is not quantized; upper
+    (int32 [D]) the number of categories, 0 for a label that is not
+    categorical; cat_p the categorical labels' priors concatenated (uniform
+    for 'randint'; empty without such a label).
 
-    quantized=True accepts the quantized kinds (JOINT_QUANT_KINDS) too and
-    returns the steps q [D] (0 for a dense label) as one more, last element.
     A quantized log kind's observations enter through the univariate
     transform of label_spec -- qloguniform: log(max(o, max(EPS, exp(low)))),
     qlognormal: log(max(o, EPS)) -- so an observed 0 builds.
 
-    categorical=True accepts the categorical kinds (JOINT_CAT_KINDS) too and
-    returns, as two further last elements, upper [D] (int32: the number of
-    categories, 0 for any other label) and the categorical labels' priors p
-    concatenated (uniform for 'randint').  A categorical label's column of
-    the means holds the observed categories (row 0: 0), its column of the
-    sigmas ones, its dims entry kind TPE_CATEGORICAL and the stream.  The
-    weights are those of the group's first non-categorical label; a group of
-    categorical labels alone has W = w / w.sum() with w = concatenate([
-    prior_weight], linear_forgetting_weights(n, 25)) in Splitter.split order
-    -- what every continuous label's weights are up to rounding, which is
-    asserted where the group has one."""
+    A categorical label's column of the means holds the observed categories
+    (row 0: 0), its column of the sigmas ones, its dims entry kind
+    TPE_CATEGORICAL and the stream.  The weights are those of the group's
+    first non-categorical label; a group of categorical labels alone has
+    W = w / w.sum() with w = concatenate([prior_weight],
+    linear_forgetting_weights(n, 25)) in Splitter.split order -- what every
+    continuous label's weights are up to rounding, which is asserted where the
+    group has one."""
     from .engine import JOINT_DIM_DTYPE
     group = [(g.label, g.kind, g.args) if hasattr(g, 'kind') else tuple(g) for g in group_specs]
     D = len(group)
     pw = float(prior_weight)
     dims = np.zeros(D, dtype=JOINT_DIM_DTYPE)
     sides = [[], []]
-    steps = []
-    uppers, cat_p = [], []
+    steps, uppers, cat_p = [], [], []
     ids0 = None
     for d, (label, kind, args) in enumerate(group):
-        if categorical and kind in JOINT_CAT_KINDS:
-            upper, p = joint_prior(kind, args, quantized, True)[-2:]
-            uppers.append(upper)
-            cat_p.append(p)
-            if quantized:
-                steps.append(0.0)
-            dims[d]['kind'] = L.TPE_CATEGORICAL
-            dims[d]['stream'] = d if streams is None else int(streams[d])
-            oi, ov = obs[label]
-            oi = np.asarray(oi)
-            if ids0 is None:
-                ids0 = oi
-            elif not np.array_equal(ids0, oi):
-                raise ValueError('joint group: label %r is not observed in the same trials as %r'
-                                 % (label, group[0][0]))
-            for side, o in enumerate(splitter.split(oi, ov)):
-                o = np.asarray(o, dtype=float)
-                if len(o) and not np.all((o >= 0) & (o < upper) & (o == np.floor(o))):
-                    raise ValueError('joint group: label %r has an observation outside its categories' % (label,))
-                sides[side].append((None, np.concatenate([[0.0], o]), np.ones(len(o) + 1)))
-            continue
-        uppers.append(0)
-        log, bounded, low, high, pmu, psig = joint_prior(kind, args, quantized)[:6]
-        floor = None
-        if quantized:
-            steps.append(joint_prior(kind, args, True)[6])
-            if kind == 'qloguniform':
-                floor = np.maximum(EPS, np.exp(low))
-            elif kind == 'qlognormal':
-                floor = EPS
-        dims[d]['kind'] = L.TPE_LGMM1 if log else L.TPE_GMM1
-        dims[d]['flags'] = (L.TPE_HAS_LOW | L.TPE_HAS_HIGH) if bounded else 0
-        dims[d]['low'], dims[d]['high'] = low, high
+        pri = joint_prior(kind, args, quantized, categorical)
+        steps.append(pri.q)
+        uppers.append(pri.upper)
         dims[d]['stream'] = d if streams is None else int(streams[d])
         oi, ov = obs[label]
         oi = np.asarray(oi)
@@ -352,17 +329,34 @@ def joint_mixture(group_specs, obs, splitter, prior_weight, streams=None, quanti
         elif not np.array_equal(ids0, oi):
             raise ValueError('joint group: label %r is not observed in the same trials as %r'
                              % (label, group[0][0]))
+        if pri.upper:
+            cat_p.append(pri.p)
+            dims[d]['kind'] = L.TPE_CATEGORICAL
+            for side, o in enumerate(splitter.split(oi, ov)):
+                o = np.asarray(o, dtype=float)
+                if len(o) and not np.all((o >= 0) & (o < pri.upper) & (o == np.floor(o))):
+                    raise ValueError('joint group: label %r has an observation outside its categories' % (label,))
+                sides[side].append((None, np.concatenate([[0.0], o]), np.ones(len(o) + 1)))
+            continue
+        floor = None
+        if kind == 'qloguniform':
+            floor = np.maximum(EPS, np.exp(pri.low))
+        elif kind == 'qlognormal':
+            floor = EPS
+        dims[d]['kind'] = L.TPE_LGMM1 if pri.log else L.TPE_GMM1
+        dims[d]['flags'] = (L.TPE_HAS_LOW | L.TPE_HAS_HIGH) if pri.bounded else 0
+        dims[d]['low'], dims[d]['high'] = pri.low, pri.high
         for side, o in enumerate(splitter.split(oi, ov)):
             o = np.asarray(o, dtype=float)
             if floor is not None:
                 o = np.log(np.maximum(o, floor))
-            elif log:
+            elif pri.log:
                 o = np.log(o)
-            w, mu, sigma = adaptive_parzen_normal(o, pw, pmu, psig)
-            p, where = _parzen_positions(o, pmu)
-            assert mu[p] == pmu and np.array_equal(mu[where], o)
+            w, mu, sigma = adaptive_parzen_normal(o, pw, pri.mu, pri.sigma)
+            p, where = _parzen_positions(o, pri.mu)
+            assert mu[p] == pri.mu and np.array_equal(mu[where], o)
             at = np.concatenate([[p], where]).astype(np.int64)
-            sides[side].append((w[at], np.concatenate([[pmu], o]), sigma[at]))
+            sides[side].append((w[at], np.concatenate([[pri.mu], o]), sigma[at]))
     out = [dims]
     for cols in sides:
         ws = [c[0] for c in cols if c[0] is not None]
@@ -376,12 +370,8 @@ def joint_mixture(group_specs, obs, splitter, prior_weight, streams=None, quanti
                 'joint group: weights differ between labels'
         out += [np.ascontiguousarray(W), np.ascontiguousarray(np.stack([c[1] for c in cols], axis=1)),
                 np.ascontiguousarray(np.stack([c[2] for c in cols], axis=1))]
-    if quantized:
-        out.append(np.asarray(steps, dtype=np.float64))
-    if categorical:
-        out.append(np.asarray(uppers, dtype=np.int32))
-        out.append(np.concatenate(cat_p).astype(np.float64) if cat_p else np.zeros(0))
-    return tuple(out)
+    return JointMixture(*out, np.asarray(steps, dtype=np.float64), np.asarray(uppers, dtype=np.int32),
+                        np.concatenate(cat_p).astype(np.float64) if cat_p else np.zeros(0))
 
 
 def label_spec(kind, args):

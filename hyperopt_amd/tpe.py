@@ -305,9 +305,9 @@ def _view_columns(view):
 
 def _joint_device_args(specs, labels, groups, quantized, categorical, prior_weight):
     """Arguments of Engine.build_joint_groups for [(slot, [label names])]:
-    label indices and streams are positions in the space (the resident
-    history holds the labels in that order), slot j's pick stream
-    TPE_JOINT_STREAM - j; steps and categorical priors from the same
+    (groups, keywords).  Label indices and streams are positions in the space
+    (the resident history holds the labels in that order), slot j's pick
+    stream TPE_JOINT_STREAM - j; steps and categorical priors from the same
     joint_prior the host build asks (it raises what that raises)."""
     at = {k: i for i, k in enumerate(labels)}
     args, qs, uppers, cat_ps = [], [], [], []
@@ -315,16 +315,13 @@ def _joint_device_args(specs, labels, groups, quantized, categorical, prior_weig
         ids = [at[k] for k in g]
         args.append((slot, _engine.L.TPE_JOINT_STREAM - slot, ids, ids))
         pri = [_post.joint_prior(specs[k].kind, specs[k].args, quantized, categorical) for k in g]
-        if quantized:
-            qs.append([p[6] for p in pri])
-        if categorical:
-            uppers.append([p[-2] for p in pri])
-            ps = [p[-1] for p in pri if p[-2] > 0]
-            cat_ps.append(np.concatenate(ps) if ps else np.zeros(0))
-    kw = dict(q=qs if quantized else None)
-    if categorical:
-        kw.update(upper=uppers, cat_p=cat_ps, prior_weight=prior_weight)
-    return args, kw
+        qs.append([p.q for p in pri])
+        uppers.append([p.upper for p in pri])
+        ps = [p.p for p in pri if p.upper > 0]
+        cat_ps.append(np.concatenate(ps) if ps else np.zeros(0))
+    # (None where the call's kinds hold no such label: Engine.build_joint_groups' defaults)
+    return args, dict(q=qs if quantized else None, upper=uppers if categorical else None,
+                      cat_p=cat_ps if categorical else None, prior_weight=prior_weight if categorical else None)
 
 
 def _joint_rounds(eng, domain, trials, specs, gathered, gamma, prior_weight, seed, ids, n_candidates,
@@ -386,9 +383,7 @@ def _joint_rounds(eng, domain, trials, specs, gathered, gamma, prior_weight, see
             mix = _post.joint_mixture([specs[k] for k in g], obs, splitter, prior_weight,
                                       streams=[labels.index(k) for k in g], quantized=quantized,
                                       categorical=categorical)
-            cat = dict(upper=mix[-2], cat_p=mix[-1], prior_weight=prior_weight) if categorical else {}
-            eng.set_joint_group(slot, _engine.L.TPE_JOINT_STREAM - slot, *mix[:7],
-                                q=mix[7] if quantized else None, **cat)
+            eng.set_joint_group(slot, _engine.L.TPE_JOINT_STREAM - slot, *mix, prior_weight=prior_weight)
     won = eng.joint_suggest_batch(seed, ids, n_candidates)
     out = [{} for _ in ids]
     for slot, g in groups:

@@ -24,7 +24,7 @@
 extern "C" {
 #endif
 
-#define TPE_ABI_VERSION 4
+#define TPE_ABI_VERSION 5
 
 /* error codes; the Python layer maps them to the reference's exception types */
 #define TPE_OK 0
@@ -420,49 +420,32 @@ int tpe_import_posterior(tpe_ctx *ctx, const void *d_blobs, int64_t blob_bytes, 
 #define TPE_JOINT_STREAM 0x7FFFFFFF
 
 typedef struct {
-    int32_t kind;        /* TPE_GMM1 | TPE_LGMM1 */
+    int32_t kind;        /* TPE_GMM1 | TPE_LGMM1 (not read for a categorical dimension) */
     int32_t flags;       /* TPE_HAS_LOW | TPE_HAS_HIGH */
     double low, high;
     int32_t stream;      /* the label's Philox stream */
 } tpe_joint_dim;         /* 32 bytes */
 
-/* Upload and fold both mixtures: weights w[k], means and sigmas row-major
- * [k][d], k = 0 the prior.  TPE_ERR_SAMPLE when the box holds none of the
- * below mixture's mass (the draw and suggest calls then return it too). */
-int tpe_joint_set_posterior(tpe_ctx *ctx, const tpe_joint_dim *dims, int32_t n_dims,
-                            int32_t n_below, const double *wb, const double *mub, const double *sigb,
-                            int32_t n_above, const double *wa, const double *mua, const double *siga);
-/* Candidates cand_offset .. cand_offset + n - 1 of (seed, round): values[n D]
- * row-major and the below component each was drawn from. */
-int tpe_joint_draw(tpe_ctx *ctx, uint64_t seed, uint32_t round, int64_t n, int64_t cand_offset,
-                   double *values, int32_t *comp);
-/* Joint lpdfs of supplied configurations values[n D]: ll below, lg above. */
-int tpe_joint_score(tpe_ctx *ctx, const double *values, int64_t n, double *ll, double *lg);
-/* One fused round: draw n_candidates, score both sides, broadcast_best's
- * winner (NaN greatest, lowest index on ties): its D values, index and lpdfs.
- * The three calls above return TPE_ERR_ARG before a joint posterior is set. */
-int tpe_joint_suggest(tpe_ctx *ctx, uint64_t seed, uint32_t round, int64_t n_candidates,
-                      double *values, int64_t *index, double *ll, double *lg);
-
-/* Several joint groups at once: a context holds up to TPE_JOINT_MAX_GROUPS
- * joint posteriors, one per slot, each with the Philox stream of its
- * component pick (tpe.suggest(group=True) gives slot j TPE_JOINT_STREAM - j).
- * tpe_joint_set_group is tpe_joint_set_posterior (same validation, same fold)
- * for one slot and leaves the others; tpe_joint_set_posterior is slot 0 with
- * TPE_JOINT_STREAM and clears every other slot.  The _group calls are the
- * three calls above on a slot (those are slot 0); a slot outside [0,
- * TPE_JOINT_MAX_GROUPS) or not set: TPE_ERR_ARG. */
+/* A context holds up to TPE_JOINT_MAX_GROUPS joint posteriors, one per slot,
+ * each with the Philox stream of its component pick (tpe.suggest(group=True)
+ * gives slot j TPE_JOINT_STREAM - j; a single group is slot 0 with
+ * TPE_JOINT_STREAM).  A slot outside [0, TPE_JOINT_MAX_GROUPS), or one that is
+ * not set where a call reads it: TPE_ERR_ARG. */
 #define TPE_JOINT_MAX_GROUPS 64
-int tpe_joint_set_group(tpe_ctx *ctx, int32_t slot, uint32_t pick_stream, const tpe_joint_dim *dims,
-                        int32_t n_dims, int32_t n_below, const double *wb, const double *mub,
-                        const double *sigb, int32_t n_above, const double *wa, const double *mua,
-                        const double *siga);
-/* Quantized dimensions in a joint group.  q[d] > 0 makes dimension d
- * quantized with that step (q NULL or all zeros: tpe_joint_set_group, the
- * same instantiations and bits).  W_k, mu_kd, s_kd, m_kd, A_S, the component
- * pick and the draw of y in the working space are those of the dense group;
- * the drawn value is x_d = rint(v / q_d) q_d with v = exp(y) for TPE_LGMM1,
- * and the factor of a quantized dimension is the component's mass on the
+
+/* tpe_joint_set_group: upload and fold both mixtures of one slot and leave the
+ * other slots as they are -- weights w[k], means and sigmas row-major [k][d],
+ * k = 0 the prior.  "This slot alone" is tpe_joint_clear_groups, then this
+ * call: a refused posterior then leaves every slot unset.  q, upper and cat_p
+ * may each be NULL (no dimension quantized / none categorical); an all-zero q
+ * or upper is its NULL, the same instantiations and bits.
+ *
+ * Dense dimension (q[d] = 0, upper[d] = 0): as described above.
+ *
+ * Quantized dimension, q[d] > 0 its step.  W_k, mu_kd, s_kd, m_kd, A_S, the
+ * component pick and the draw of y in the working space are those of the dense
+ * dimension; the drawn value is x_d = rint(v / q_d) q_d with v = exp(y) for
+ * TPE_LGMM1, and the factor of the dimension is the component's mass on the
  * value's interval,
  *   g_kd(x_d) = Phi((ub - mu_kd)/s_kd) - Phi((lb - mu_kd)/s_kd),
  *   ub = x_d + q_d/2, lb = x_d - q_d/2, clipped to [low, high] by the flags
@@ -475,23 +458,14 @@ int tpe_joint_set_group(tpe_ctx *ctx, int32_t slot, uint32_t pick_stream, const 
  * probability of the value).  A configuration no component reaches has lpdf
  * -inf.  Equal configurations get equal lpdf bits, so among them the lowest
  * index wins.
- * Accepted groups: n_dims + (number of quantized dimensions) <= 128 -- a
- * candidate keeps one value per dense and two (ub, lb) per quantized dimension
- * in LDS; a larger group, or a q[d] that is negative, NaN or infinite:
- * TPE_ERR_ARG.  The draw, score, suggest and batch calls serve such slots. */
-int tpe_joint_set_group_q(tpe_ctx *ctx, int32_t slot, uint32_t pick_stream, const tpe_joint_dim *dims,
-                          const double *q /* [n_dims], 0 = dense */, int32_t n_dims, int32_t n_below,
-                          const double *wb, const double *mub, const double *sigb, int32_t n_above,
-                          const double *wa, const double *mua, const double *siga);
-/* Categorical dimensions in a joint group.  upper[d] = C_d > 0 makes dimension
- * d categorical with categories 0 .. C_d - 1 and prior p_d, the next C_d
- * entries of cat_p (upper NULL or all zeros: tpe_joint_set_group_q, the same
- * instantiations and bits; cat_p and prior_weight are then not read).  With
- * K_S = n_S the side's components and a_Sd = C_d prior_weight / K_S the factor
- * of category x in component k is
+ *
+ * Categorical dimension, upper[d] = C_d > 0 its categories 0 .. C_d - 1, with
+ * prior p_d, the next C_d entries of cat_p (cat_p and prior_weight are read
+ * only when a dimension is categorical).  With K_S = n_S the side's components
+ * and a_Sd = C_d prior_weight / K_S the factor of category x in component k is
  *   r_0d[x] = p_d[x]                                        (the prior),
  *   r_td[x] = ([x == o_td] + a_Sd p_d[x]) / (1 + a_Sd)      (trial t observed o_td),
- *   f_S(x) = (1/A_S) sum_k W_k prod_d g_kd(x_d),  g_kd(x_d) = r_kd[x_d],  m_kd = 1:
+ *   g_kd(x_d) = r_kd[x_d],  m_kd = 1:
  * A_S, the pick thresholds and the pick stream are those of the group without
  * the dimension, and it has no Jacobian term.  The observed category of trial t
  * travels in mu*[k][d] (k >= 1), integer-valued; row 0 and sig*[.][d] of the
@@ -502,19 +476,31 @@ int tpe_joint_set_group_q(tpe_ctx *ctx, int32_t slot, uint32_t pick_stream, cons
  * round) -- the categorical layout of the independent round -- and the first
  * category c with ceil(cdf_kd[c] 2^32) above it, cdf_kd the running sum of
  * r_kd in category order over its total, the last entry 1.
- * TPE_ERR_ARG: upper[d] < 0; q[d] > 0 and upper[d] > 0; a p entry that is not
- * positive and finite; a p whose sum is not within 1e-9 of 1; an observed
- * category that is no integer in [0, upper[d]); prior_weight not positive and
- * finite; n_dims + (number of quantized dimensions) > 128 -- a categorical
- * dimension keeps one value per candidate in LDS, like a dense one.  A group
- * with a categorical dimension runs the quantized variant of the round. */
-int tpe_joint_set_group_c(tpe_ctx *ctx, int32_t slot, uint32_t pick_stream, const tpe_joint_dim *dims,
-                          const double *q /* [n_dims], 0 = dense; NULL */,
-                          const int32_t *upper /* [n_dims], 0 = not categorical */,
-                          const double *cat_p /* the categorical dimensions' priors, concatenated */,
-                          double prior_weight, int32_t n_dims, int32_t n_below, const double *wb,
-                          const double *mub, const double *sigb, int32_t n_above, const double *wa,
-                          const double *mua, const double *siga);
+ *
+ * Accepted groups: S = n_dims + (number of quantized dimensions) <= 128 -- a
+ * candidate keeps one value per dense or categorical and two (ub, lb) per
+ * quantized dimension in LDS.  A group with a quantized or categorical
+ * dimension runs the quantized variant of the round; the draw, score, suggest
+ * and batch calls serve every slot.
+ * TPE_ERR_ARG: a NULL dims or mixture pointer; n_dims outside [1, 128] or
+ * S > 128; n_below outside [1, 4096] or n_above < 1; a kind that is not
+ * TPE_GMM1 or TPE_LGMM1, or flags other than the two bounds; q[d] negative,
+ * NaN or infinite; upper[d] < 0; q[d] > 0 and upper[d] > 0; a categorical
+ * dimension with cat_p NULL, a p entry that is not positive and finite, a p
+ * whose sum is not within 1e-9 of 1, an observed category that is no integer
+ * in [0, upper[d]), or prior_weight not positive and finite; a label-sharded
+ * context.  TPE_ERR_VALUE: low >= high; a negative or NaN weight; a sigma that
+ * is not positive and finite.  TPE_ERR_SAMPLE when the box holds none of the
+ * below mixture's mass: the slot counts as set, and the draw, suggest and
+ * batch calls return it too. */
+int tpe_joint_set_group(tpe_ctx *ctx, int32_t slot, uint32_t pick_stream, const tpe_joint_dim *dims,
+                        const double *q /* [n_dims], 0 = dense; NULL */,
+                        const int32_t *upper /* [n_dims], 0 = not categorical; NULL */,
+                        const double *cat_p /* the categorical dimensions' priors, concatenated; NULL */,
+                        double prior_weight, int32_t n_dims, int32_t n_below, const double *wb,
+                        const double *mub, const double *sigb, int32_t n_above, const double *wa,
+                        const double *mua, const double *siga);
+/* Unset every slot (their buffers are kept for the next posterior). */
 int tpe_joint_clear_groups(tpe_ctx *ctx);
 /* Joint groups built on the device from the current build of the resident
  * history (tpe_build_posterior_resident and its kin) -- nothing is uploaded but
@@ -523,14 +509,14 @@ int tpe_joint_clear_groups(tpe_ctx *ctx);
  * observation of the side in observation order, each with the sigma and the
  * weight its own sorted position gave it; W is the first non-categorical
  * label's; a categorical label's rows hold the observed categories, sigma 1):
- * one launch un-permutes them into the arrays tpe_joint_set_group_c takes,
+ * one launch un-permutes them into the arrays tpe_joint_set_group takes,
  * then each slot is folded as that call folds it -- the same bits wherever the
  * univariate mixtures are the host's.  One stream synchronisation per call.
  * Group g is labels[group_off[g] .. group_off[g + 1]) -- indices of the
  * resident history's labels, whose tpe_label_spec supplies kind, bounds and
  * prior -- in slot slots[g] with pick stream pick_streams[g]; streams, q and
  * upper are parallel to labels (q, upper: NULL or 0 as in
- * tpe_joint_set_group_c; upper[i] must be the label's own), cat_p the
+ * tpe_joint_set_group; upper[i] must be the label's own), cat_p the
  * categorical labels' priors concatenated in that order.
  * flags[g] != 0: the group was not built and its slot is left unset (the other
  * groups are built) --
@@ -562,10 +548,15 @@ int tpe_joint_build_groups(tpe_ctx *ctx, int32_t n_groups, const int32_t *slots,
  * pointers may be NULL. */
 int tpe_joint_get_group(tpe_ctx *ctx, int32_t slot, int32_t side, double *w, double *mu, double *sigma,
                         int32_t cap, int32_t *n_components, int32_t *n_dims);
+/* Candidates cand_offset .. cand_offset + n - 1 of (seed, round) of a set
+ * slot: values[n D] row-major and the below component each was drawn from. */
 int tpe_joint_draw_group(tpe_ctx *ctx, int32_t slot, uint64_t seed, uint32_t round, int64_t n,
                          int64_t cand_offset, double *values, int32_t *comp);
+/* Joint lpdfs of supplied configurations values[n D]: ll below, lg above. */
 int tpe_joint_score_group(tpe_ctx *ctx, int32_t slot, const double *values, int64_t n, double *ll,
                           double *lg);
+/* One fused round: draw n_candidates, score both sides, broadcast_best's
+ * winner (NaN greatest, lowest index on ties): its D values, index and lpdfs. */
 int tpe_joint_suggest_group(tpe_ctx *ctx, int32_t slot, uint64_t seed, uint32_t round,
                             int64_t n_candidates, double *values, int64_t *index, double *ll, double *lg);
 /* tpe_joint_suggest_group for every set slot (ascending) and every round
@@ -574,7 +565,7 @@ int tpe_joint_suggest_group(tpe_ctx *ctx, int32_t slot, uint64_t seed, uint32_t 
  * synchronisation of a call do not grow with n_rounds.  values[n_rounds][sum
  * of D over the set slots] (the slots' values concatenated per round); index,
  * ll, lg [n_rounds][number of set slots].  TPE_ERR_ARG when no slot is set,
- * TPE_ERR_SAMPLE as tpe_joint_suggest. */
+ * TPE_ERR_SAMPLE as tpe_joint_suggest_group. */
 int tpe_joint_suggest_batch(tpe_ctx *ctx, uint64_t seed, const uint32_t *rounds, int32_t n_rounds,
                             int64_t n_candidates, double *values, int64_t *index, double *ll, double *lg);
 

@@ -117,10 +117,9 @@ def check(eng, up, specs, view, groups, quantized=False, categorical=False, want
             continue
         mix = P.joint_mixture([specs[k] for k in g], cols, splitter, PW, streams=[names.index(k) for k in g],
                               quantized=quantized, categorical=categorical)
-        cat = dict(upper=mix[-2], cat_p=mix[-1], prior_weight=PW) if categorical else {}
-        eng.set_joint_group(slot + HOST, L.TPE_JOINT_STREAM - slot, *mix[:7], q=mix[7] if quantized else None, **cat)
+        eng.set_joint_group(slot + HOST, L.TPE_JOINT_STREAM - slot, *mix, prior_weight=PW)
         for side in (0, 1):
-            ref = mix[1 + 3 * side:4 + 3 * side]
+            ref = (mix.wa, mix.mua, mix.siga) if side else (mix.wb, mix.mub, mix.sigb)
             for where in (slot, slot + HOST):
                 got = eng.joint_get_group(where, side)
                 for name, a, b in zip(('W', 'mu', 'sigma'), got, ref):

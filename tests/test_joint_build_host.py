@@ -129,7 +129,7 @@ def test_a_flagged_group_is_built_on_the_host(case):
     tids, losses, obs = history.gather(domain, trials, labels)
     mix = P.joint_mixture([specs['a'], specs['b']], obs, P.Splitter(tids, losses, 0.25), 1.0,
                           streams=[labels.index('a'), labels.index('b')])
-    for got, ref in zip(arrays, mix[1:7]):
+    for got, ref in zip(arrays, (mix.wb, mix.mub, mix.sigb, mix.wa, mix.mua, mix.siga)):
         assert np.array_equal(got, ref)
     assert set(out[0]) == {'ly', 'x', 'a', 'b'}
 

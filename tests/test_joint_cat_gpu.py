@@ -243,6 +243,17 @@ def test_zero_uppers_give_the_quantized_bits(eng):
     eng.set_joint_group(0, L.TPE_JOINT_STREAM, *dargs, upper=np.zeros(dense.D, dtype=np.int32))
     w2 = eng.joint_suggest(4, 300, round=2)
     assert np.array_equal(w1[0], w2[0]) and w1[1:] == w2[1:]
+    # all-zero steps together with all-zero uppers, as every dense group is set: the bits of neither
+    small = JC.group('d2')
+    sargs = JC.engine_args(small)
+    eng.clear_joint_groups()
+    eng.set_joint_group(0, L.TPE_JOINT_STREAM, *sargs)
+    w1 = eng.joint_suggest(4, 300, round=2)
+    eng.clear_joint_groups()
+    eng.set_joint_group(0, L.TPE_JOINT_STREAM, *sargs, q=np.zeros(small.D), upper=np.zeros(small.D, dtype=np.int32),
+                        cat_p=np.zeros(0), prior_weight=1.0)
+    w2 = eng.joint_suggest(4, 300, round=2)
+    assert np.array_equal(w1[0], w2[0]) and w1[1:] == w2[1:]
 
 
 def test_abi_errors():
@@ -258,12 +269,12 @@ def test_abi_errors():
             cat_p = None if cat_p is None else np.ascontiguousarray(cat_p, dtype=np.float64)
             keep = [np.ascontiguousarray(a, dtype=np.float64) for a in (wb, mub, sigb, wa, mua, siga)]
             p = [a.ctypes.data for a in keep]
-            return e.lib.tpe_joint_set_group_c(e.h, 0, L.TPE_JOINT_STREAM, dims.ctypes.data,
-                                               q.ctypes.data if q is not None else None,
-                                               upper.ctypes.data if upper is not None else None,
-                                               cat_p.ctypes.data if cat_p is not None and len(cat_p) else None,
-                                               float(pw), len(dims), len(wb), p[0], p[1], p[2], len(wa), p[3], p[4],
-                                               p[5])
+            return e.lib.tpe_joint_set_group(e.h, 0, L.TPE_JOINT_STREAM, dims.ctypes.data,
+                                             q.ctypes.data if q is not None else None,
+                                             upper.ctypes.data if upper is not None else None,
+                                             cat_p.ctypes.data if cat_p is not None and len(cat_p) else None,
+                                             float(pw), len(dims), len(wb), p[0], p[1], p[2], len(wa), p[3], p[4],
+                                             p[5])
         mix = (wb, mub, sigb, wa, mua, siga)
         up, p4 = [0, 4], [0.25] * 4
         assert rc(dims, None, up, p4, 1.0, *mix) == L.TPE_OK
@@ -382,7 +393,7 @@ def test_suggest_documents_given_the_same_history():
     eng = E.get_engine(0, 'f64')
     mix = P.joint_mixture([specs[k] for k in group], obs, P.Splitter(tids, losses, 0.25), 1.0,
                           streams=[labels.index(k) for k in group], quantized=True, categorical=True)
-    eng.set_joint_posterior(*mix[:7], q=mix[7], upper=mix[8], cat_p=mix[9], prior_weight=1.0)
+    eng.set_joint_posterior(*mix, prior_weight=1.0)
     values = eng.joint_suggest_batch(17, ids, 24)[0][0]
     for j in range(3):
         got, ref = cat[j]['misc']['vals'], indep[j]['misc']['vals']

@@ -89,21 +89,22 @@ def _history(n_trials, seed):
 
 @pytest.mark.parametrize('n_trials,gamma', [(200, 0.25), (200, 4.0), (30, 0.25), (1, 0.25), (0, 0.25)])
 def test_mixture_carries_the_categories_and_the_weight_rule(n_trials, gamma):
-    """Observed categories in the means, upper and p as last elements, and W:
+    """Observed categories in the means, upper and cat_p by name, and W:
     the first continuous label's in a mixed group, concatenate([pw], lfw) /
     sum in an all-categorical one -- the two within 4e-16 (K + 1) relative,
     with the ramp (the above side of 200 trials) and without."""
     group, tids, losses, obs = _history(n_trials, 300 + n_trials)
     sp = P.Splitter(tids, losses, gamma)
     mixed = P.joint_mixture(group[:3], obs, sp, 1.0, categorical=True)
-    assert len(mixed) == 9
-    dims, wb, mub, sigb, wa, mua, siga, upper, cat_p = mixed
+    assert len(mixed) == 10 and mixed.q.tolist() == [0.0] * 3
+    dims, wb, mub, wa, mua = mixed.dims, mixed.wb, mixed.mub, mixed.wa, mixed.mua
+    upper, cat_p = mixed.upper, mixed.cat_p
     assert upper.tolist() == [0, 4, 3] and upper.dtype == np.int32
     assert cat_p.tolist() == [0.25] * 4 + [0.5, 0.3, 0.2]
     assert dims['stream'].tolist() == [0, 1, 2]
     cats = P.joint_mixture(group[1:3], obs, sp, 1.0, categorical=True)
     dense = P.joint_mixture(group[:1], obs, sp, 1.0)
-    for side, (W, mu, Wc, Wd) in enumerate(((wb, mub, cats[1], dense[1]), (wa, mua, cats[4], dense[4]))):
+    for side, (W, mu, Wc, Wd) in enumerate(((wb, mub, cats.wb, dense.wb), (wa, mua, cats.wa, dense.wa))):
         n = len(W) - 1
         for d, label in ((1, 'r'), (2, 'c')):
             o = sp.split(*obs[label])[side]
@@ -115,10 +116,11 @@ def test_mixture_carries_the_categories_and_the_weight_rule(n_trials, gamma):
         if n_trials == 200 and side == 1:
             assert n > 25 and len(np.unique(w)) > 2          # the ramp
     allq = P.joint_mixture(group, obs, sp, 1.0, quantized=True, categorical=True)
-    assert len(allq) == 10 and allq[7].tolist() == [0.0, 0.0, 0.0, 2.0] and allq[8].tolist() == [0, 4, 3, 0]
-    assert np.array_equal(allq[0][:3], dims) and np.array_equal(allq[1], wb) and np.array_equal(allq[4], wa)
-    for i in (2, 3, 5, 6):
-        assert np.array_equal(allq[i][:, :3], mixed[i])
+    assert len(allq) == 10 and allq.q.tolist() == [0.0, 0.0, 0.0, 2.0] and allq.upper.tolist() == [0, 4, 3, 0]
+    assert np.array_equal(allq.dims[:3], dims) and np.array_equal(allq.wb, wb) and np.array_equal(allq.wa, wa)
+    assert np.array_equal(allq.cat_p, cat_p)
+    for name in ('mub', 'sigb', 'mua', 'siga'):
+        assert np.array_equal(getattr(allq, name)[:, :3], getattr(mixed, name))
 
 
 def test_default_call_is_unchanged():
@@ -133,13 +135,14 @@ def test_default_call_is_unchanged():
             P.joint_prior('categorical', dict(upper=2, p=[0.5, 0.5]), **kw)
     a = P.joint_mixture(group[:1], obs, sp, 1.0)
     b = P.joint_mixture(group[:1], obs, sp, 1.0, categorical=True)
-    assert len(a) == 7 and len(b) == 9 and b[7].tolist() == [0] and len(b[8]) == 0
+    assert len(a) == len(b) == 10 and b.upper.tolist() == [0] and len(b.cat_p) == 0
     for x, y in zip(a, b):
         assert np.array_equal(x, y)
-    assert P.joint_prior('uniform', dict(low=0.0, high=2.0), categorical=True) == \
-        (False, True, 0.0, 2.0, 1.0, 2.0, 0, None)
+    pri = P.joint_prior('uniform', dict(low=0.0, high=2.0), categorical=True)
+    assert (pri.log, pri.bounded, pri.low, pri.high, pri.mu, pri.sigma) == (False, True, 0.0, 2.0, 1.0, 2.0)
+    assert pri.q == 0.0 and pri.upper == 0 and pri.p is None
     got = P.joint_prior('randint', dict(upper=4), categorical=True)
-    assert got[6] == 4 and got[7].tolist() == [0.25] * 4
+    assert got.upper == 4 and got.p.tolist() == [0.25] * 4
     with pytest.raises(ValueError):
         P.joint_prior('categorical', dict(upper=3, p=[0.5, 0.5, 0.0]), categorical=True)
     assert P.JOINT_CAT_KINDS == ('randint', 'categorical')

@@ -176,11 +176,11 @@ def test_errors():
         buf = np.zeros(8)
         idx = ctypes.c_int64()
         a, b = ctypes.c_double(), ctypes.c_double()
-        assert lib.tpe_joint_suggest(h, 0, 0, 24, buf.ctypes.data, ctypes.byref(idx), ctypes.byref(a),
-                                     ctypes.byref(b)) == L.TPE_ERR_ARG
-        assert lib.tpe_joint_score(h, buf.ctypes.data, 1, buf.ctypes.data, buf.ctypes.data) == L.TPE_ERR_ARG
+        assert lib.tpe_joint_suggest_group(h, 0, 0, 0, 24, buf.ctypes.data, ctypes.byref(idx), ctypes.byref(a),
+                                           ctypes.byref(b)) == L.TPE_ERR_ARG
+        assert lib.tpe_joint_score_group(h, 0, buf.ctypes.data, 1, buf.ctypes.data, buf.ctypes.data) == L.TPE_ERR_ARG
         comp = np.zeros(8, dtype=np.int32)
-        assert lib.tpe_joint_draw(h, 0, 0, 1, 0, buf.ctypes.data, comp.ctypes.data) == L.TPE_ERR_ARG
+        assert lib.tpe_joint_draw_group(h, 0, 0, 0, 1, 0, buf.ctypes.data, comp.ctypes.data) == L.TPE_ERR_ARG
         # a box that holds none of the below mixture's mass: the sampler error
         ref = JC.group('d1_prior')
         dims, wb, mub, sigb, wa, mua, siga = JC.engine_args(ref)

@@ -81,7 +81,8 @@ def _check_group(group, obs, splitter, want_kb):
     label_posterior's, bit for bit; the weights by test_joint_host.py's rule:
     bit-identical for the first label and wherever a side has no ramp (n_S <=
     25), else equal to the rounding of two sums of K terms."""
-    dims, wb, mub, sigb, wa, mua, siga = P.joint_mixture(group, obs, splitter, 1.0)
+    m = P.joint_mixture(group, obs, splitter, 1.0)
+    wb, mub, sigb, wa, mua, siga = m.wb, m.mub, m.sigb, m.wa, m.mua, m.siga
     assert len(wb) == want_kb
     for d, (label, kind, args) in enumerate(group):
         b, a = splitter.split(*obs[label])

@@ -95,13 +95,14 @@ def test_marginals_equal_univariate_posteriors(n_trials, gamma):
     else:
         group, tids, losses, obs = _history(n_trials, kinds, 100 + n_trials, ties=False)
     splitter = P.Splitter(tids, losses, gamma)
-    dims, wb, mub, sigb, wa, mua, siga = P.joint_mixture(group, obs, splitter, 1.0)
-    assert list(dims['flags']) == [0, 0, 0]
+    mix = P.joint_mixture(group, obs, splitter, 1.0)
+    assert list(mix.dims['flags']) == [0, 0, 0]
     ramp = False
     for d, (label, kind, args) in enumerate(group):
         b, a = splitter.split(*obs[label])
         post = P.label_posterior(label, kind, args, b, a, 1.0)
-        for (W, mu, s), (w1, m1, s1) in (((wb, mub, sigb), post.below), ((wa, mua, siga), post.above)):
+        for (W, mu, s), (w1, m1, s1) in (((mix.wb, mix.mub, mix.sigb), post.below),
+                                         ((mix.wa, mix.mua, mix.siga), post.above)):
             assert len(W) == len(w1)
             gw, gm, gs = _sorted_rows(W, mu[:, d], s[:, d])
             ew, em, es = _sorted_rows(w1, m1, s1)
@@ -142,7 +143,7 @@ def test_joint_mixture_equals_reference(n_trials):
     group, tids, losses, obs = _history(n_trials, kinds, 31 + n_trials, ties=n_trials >= 20)
     splitter = P.Splitter(tids, losses, 0.25)
     out = P.joint_mixture(group, obs, splitter, 0.7, streams=[4, 9, 1, 6])
-    dims = out[0]
+    dims = out.dims
     assert list(dims['stream']) == [4, 9, 1, 6]
     for d, (label, kind, args) in enumerate(group):
         log, low, high, _, _ = JR.prior_of(kind, args)
@@ -158,10 +159,53 @@ def test_joint_mixture_equals_reference(n_trials):
             cols.append(np.log(o) if log else o)
             priors.append((pmu, psig))
         Ws, mu, s = JR.side_mixture(cols, priors, 0.7, P.adaptive_parzen_normal)
-        W, gm, gs = out[1 + 3 * side:4 + 3 * side]
+        W, gm, gs = (out.wa, out.mua, out.siga) if side else (out.wb, out.mub, out.sigb)
         assert np.array_equal(W, Ws[0])
         assert np.array_equal(gm, mu) and np.array_equal(gs, s)
         assert abs(W.sum() - 1.0) < 1e-12 and gm.shape == (len(W), 4)
+
+
+def _same_fields(a, b):
+    assert type(a) is type(b) and a._fields == b._fields
+    for name, x, y in zip(a._fields, a, b):
+        if name == 'dims':
+            assert x.dtype == y.dtype and x.tobytes() == y.tobytes()
+        elif isinstance(x, np.ndarray):
+            assert x.dtype == y.dtype and np.array_equal(x, y), name
+        else:
+            assert type(x) is type(y) and x == y, name
+
+
+def test_joint_records_do_not_depend_on_the_flags():
+    """The quantized / categorical flags say which kinds may join; the record
+    of a dense group, and of a kind of any family, is the same under every
+    flag that accepts it: ten and nine fields, bit for bit."""
+    D, _, _, kinds, gseed = JC.GROUPS['d5_k300']
+    group, tids, losses, obs = _history(40, [kinds[d % len(kinds)] for d in range(D)], gseed)
+    splitter = P.Splitter(tids, losses, 0.25)
+    plain = P.joint_mixture(group, obs, splitter, 1.0)
+    assert plain._fields == ('dims', 'wb', 'mub', 'sigb', 'wa', 'mua', 'siga', 'q', 'upper', 'cat_p')
+    assert plain.q.dtype == np.float64 and plain.q.tolist() == [0.0] * D
+    assert plain.upper.dtype == np.int32 and plain.upper.tolist() == [0] * D
+    assert plain.cat_p.dtype == np.float64 and plain.cat_p.shape == (0,)
+    assert plain.mub.shape == (len(plain.wb), D) and plain.siga.shape == (len(plain.wa), D)
+    _same_fields(plain, P.joint_mixture(group, obs, splitter, 1.0, quantized=True))
+    _same_fields(plain, P.joint_mixture(group, obs, splitter, 1.0, quantized=True, categorical=True))
+
+    fields = ('log', 'bounded', 'low', 'high', 'mu', 'sigma', 'q', 'upper', 'p')
+    every = (dict(), dict(quantized=True), dict(categorical=True), dict(quantized=True, categorical=True))
+    dense = P.joint_prior('loguniform', dict(low=-3.0, high=2.0))
+    assert dense._fields == fields and tuple(dense) == (True, True, -3.0, 2.0, -0.5, 5.0, 0.0, 0, None)
+    for kw in every[1:]:
+        _same_fields(dense, P.joint_prior('loguniform', dict(low=-3.0, high=2.0), **kw))
+    quant = P.joint_prior('qnormal', dict(mu=1.0, sigma=2.0, q=0.5), quantized=True)
+    assert quant._fields == fields and tuple(quant) == (False, False, 0.0, 0.0, 1.0, 2.0, 0.5, 0, None)
+    _same_fields(quant, P.joint_prior('qnormal', dict(mu=1.0, sigma=2.0, q=0.5), quantized=True, categorical=True))
+    cat = P.joint_prior('categorical', dict(upper=2, p=[0.25, 0.75]), categorical=True)
+    assert cat._fields == fields and tuple(cat)[:8] == (False, False, 0.0, 0.0, 0.0, 1.0, 0.0, 2)
+    assert cat.p.tolist() == [0.25, 0.75]
+    both = P.joint_prior('categorical', dict(upper=2, p=[0.25, 0.75]), quantized=True, categorical=True)
+    assert tuple(both)[:8] == tuple(cat)[:8] and np.array_equal(both.p, cat.p)
 
 
 def test_joint_mixture_refuses_mismatched_trials():

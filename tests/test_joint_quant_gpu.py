@@ -260,9 +260,9 @@ def test_abi_errors():
             q = None if q is None else np.ascontiguousarray(q, dtype=np.float64)
             keep = [np.ascontiguousarray(a, dtype=np.float64) for a in (wb, mub, sigb, wa, mua, siga)]
             p = [a.ctypes.data for a in keep]
-            return e.lib.tpe_joint_set_group_q(e.h, 0, L.TPE_JOINT_STREAM, dims.ctypes.data,
-                                               q.ctypes.data if q is not None else None, len(dims), len(wb),
-                                               p[0], p[1], p[2], len(wa), p[3], p[4], p[5])
+            return e.lib.tpe_joint_set_group(e.h, 0, L.TPE_JOINT_STREAM, dims.ctypes.data,
+                                             q.ctypes.data if q is not None else None, None, None, 0.0, len(dims),
+                                             len(wb), p[0], p[1], p[2], len(wa), p[3], p[4], p[5])
         assert rc(dims, q, wb, mub, sigb, wa, mua, siga) == L.TPE_OK
         assert rc(dims, None, wb, mub, sigb, wa, mua, siga) == L.TPE_OK
         for bad in (-1.0, np.nan, np.inf):
@@ -353,8 +353,8 @@ def test_suggest_documents_given_the_same_history():
     eng = E.get_engine(0, 'f64')
     mix = P.joint_mixture([specs[k] for k in group], obs, P.Splitter(tids, losses, 0.25), 1.0,
                           streams=[labels.index(k) for k in group], quantized=True)
-    assert mix[7].tolist() == [2.0, 2.0, 0.0]
-    eng.set_joint_posterior(*mix[:7], q=mix[7])
+    assert mix.q.tolist() == [2.0, 2.0, 0.0]
+    eng.set_joint_posterior(*mix)
     for j, new_id in enumerate(ids):
         got, ref = quant[j]['misc']['vals'], before[j]['misc']['vals']
         for k in ('r', 'c', 'u'):

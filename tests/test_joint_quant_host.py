@@ -134,8 +134,8 @@ def test_quantized_marginals_equal_univariate_posteriors(n_trials, gamma):
         assert len(np.unique(obs['h1'][1])) < n_trials // 2        # ties
     splitter = P.Splitter(tids, losses, gamma)
     out = P.joint_mixture(group, obs, splitter, 1.0, quantized=True)
-    assert len(out) == 8
-    dims, wb, mub, sigb, wa, mua, siga, q = out
+    assert len(out) == 10 and out.upper.tolist() == [0] * 6 and len(out.cat_p) == 0
+    dims, wb, mub, sigb, wa, mua, siga, q = out.dims, out.wb, out.mub, out.sigb, out.wa, out.mua, out.siga, out.q
     assert q.tolist() == [0.0, 2.0, 1.0, 0.5, 0.5, 0.0] and q.dtype == np.float64
     assert list(dims['flags']) == [3, 3, 3, 0, 0, 3]
     assert [bool(k) for k in dims['kind']] == [False, False, True, False, True, True]
@@ -170,12 +170,15 @@ def test_default_call_is_unchanged():
     dense = [g for g in group if g[1] in P.JOINT_KINDS]
     a = P.joint_mixture(dense, obs, splitter, 1.0)
     b = P.joint_mixture(dense, obs, splitter, 1.0, quantized=True)
-    assert len(a) == 7 and len(b) == 8 and b[7].tolist() == [0.0, 0.0]
+    assert len(a) == len(b) == 10 and a.q.tolist() == b.q.tolist() == [0.0, 0.0]
     for x, y in zip(a, b):
         assert np.array_equal(x, y)
-    assert P.joint_prior('uniform', dict(low=0.0, high=2.0)) == (False, True, 0.0, 2.0, 1.0, 2.0)
-    assert P.joint_prior('qlognormal', dict(mu=0.5, sigma=2.0, q=3.0), quantized=True) == \
-        (True, False, 0.0, 0.0, 0.5, 2.0, 3.0)
+    pri = P.joint_prior('uniform', dict(low=0.0, high=2.0))
+    assert (pri.log, pri.bounded, pri.low, pri.high, pri.mu, pri.sigma) == (False, True, 0.0, 2.0, 1.0, 2.0)
+    assert pri.q == 0.0 and pri.upper == 0 and pri.p is None
+    pri = P.joint_prior('qlognormal', dict(mu=0.5, sigma=2.0, q=3.0), quantized=True)
+    assert (pri.log, pri.bounded, pri.low, pri.high, pri.mu, pri.sigma) == (True, False, 0.0, 0.0, 0.5, 2.0)
+    assert pri.q == 3.0 and pri.upper == 0 and pri.p is None
     assert P.JOINT_KINDS == ('uniform', 'loguniform', 'normal', 'lognormal')
     assert P.JOINT_QUANT_KINDS == ('quniform', 'qloguniform', 'qnormal', 'qlognormal')
 

@@ -111,7 +111,7 @@ def timings(n_dims, n_trials, reps):
     res = dict(dims=n_dims, trials=n_trials, reps=reps)
     mix = P.joint_mixture(group, obs, splitter, 1.0)
     res['host_build_ms'] = median_ms(lambda: P.joint_mixture(group, obs, splitter, 1.0), max(3, reps // 4))
-    res['k_below'], res['k_above'] = len(mix[1]), len(mix[4])
+    res['k_below'], res['k_above'] = len(mix.wb), len(mix.wa)
     eng = Engine(0, 'f64')
     eng.set_joint_posterior(*mix)
     res['upload_fold_ms'] = median_ms(lambda: eng.set_joint_posterior(*mix), reps)
@@ -149,7 +149,7 @@ def timings(n_dims, n_trials, reps):
     for d, (label, kind, args) in enumerate(group):
         log, low, high, _, _ = JR.prior_of(kind, args)
         dims.append(JR.Dim(log, low, high, d))
-    ref = JR.JointRef(dims, mix[1:4], mix[4:7])
+    ref = JR.JointRef(dims, (mix.wb, mix.mub, mix.sigb), (mix.wa, mix.mua, mix.siga))
     eng.set_joint_posterior(*mix)
     vals, _ = eng.joint_draw(1, 24, round=1)
     t = time.perf_counter()
@@ -192,9 +192,9 @@ def groups_timings(reps, legs=('loop', 'batch'), rounds=(1, 24, 4096), n=24):
     eng = Engine(0, 'f64')
     out = {}
     for name, mixes in sorted(group_shapes().items()):
-        terms = sum((len(m[1]) + len(m[4])) * len(m[0]) for m in mixes)
-        res = out[name] = dict(groups=len(mixes), dims=[len(m[0]) for m in mixes],
-                               k_below=[len(m[1]) for m in mixes], k_above=[len(m[4]) for m in mixes])
+        terms = sum((len(m.wb) + len(m.wa)) * len(m.dims) for m in mixes)
+        res = out[name] = dict(groups=len(mixes), dims=[len(m.dims) for m in mixes],
+                               k_below=[len(m.wb) for m in mixes], k_above=[len(m.wa) for m in mixes])
         for R in rounds:
             ids = list(range(1000, 1000 + R))
 
@@ -286,18 +286,12 @@ def quantized_timings(reps, legs=('dense', 'quantized'), n_dims=32, n_trials=100
     eng = Engine(0, 'f64')
     out = {}
     for leg in legs:
-        if leg == 'dense':
-            group, tids, losses, obs = history(n_dims, n_trials)
-            mix = P.joint_mixture(group, obs, P.Splitter(tids, losses, 0.25), 1.0)
-            eng.clear_joint_groups()
-            eng.set_joint_group(0, L.TPE_JOINT_STREAM, *mix)
-        else:
-            group, tids, losses, obs = quantized_history(n_dims, n_trials)
-            mix = P.joint_mixture(group, obs, P.Splitter(tids, losses, 0.25), 1.0, quantized=True)
-            eng.clear_joint_groups()
-            eng.set_joint_group(0, L.TPE_JOINT_STREAM, *mix[:7], q=mix[7])
-        res = out[leg] = dict(dims=n_dims, k_below=len(mix[1]), k_above=len(mix[4]),
-                              quantized_dims=int(np.count_nonzero(mix[7])) if leg != 'dense' else 0)
+        group, tids, losses, obs = (history if leg == 'dense' else quantized_history)(n_dims, n_trials)
+        mix = P.joint_mixture(group, obs, P.Splitter(tids, losses, 0.25), 1.0, quantized=True)
+        eng.clear_joint_groups()
+        eng.set_joint_group(0, L.TPE_JOINT_STREAM, *mix)
+        res = out[leg] = dict(dims=n_dims, k_below=len(mix.wb), k_above=len(mix.wa),
+                              quantized_dims=int(np.count_nonzero(mix.q)))
         res.update(_round_shapes(eng, reps))
     if 'dense' in out and 'quantized' in out:
         for name in ('one_24', 'batch_4096x24', 'one_65536'):
@@ -323,27 +317,19 @@ def categorical_history(n_dims, n_trials, upper=8):
 
 def categorical_timings(reps, legs=('dense', 'categorical'), n_dims=32, n_trials=10000):
     """quantized_timings' shapes for the dense d32 group and the group with
-    every fourth label a randint(8) (`mixed`).  The dense leg uses the entry
-    points of a checkout without categorical groups, so it runs unchanged
-    there (--quantized --legs dense on that checkout is the same leg)."""
+    every fourth label a randint(8) (`mixed`)."""
     from hyperopt_amd import _lib as L
     from hyperopt_amd import posterior as P
     from hyperopt_amd.engine import Engine
     eng = Engine(0, 'f64')
     out = {}
     for leg in legs:
+        group, tids, losses, obs = (history if leg == 'dense' else categorical_history)(n_dims, n_trials)
+        mix = P.joint_mixture(group, obs, P.Splitter(tids, losses, 0.25), 1.0, categorical=True)
         eng.clear_joint_groups()
-        if leg == 'dense':
-            group, tids, losses, obs = history(n_dims, n_trials)
-            mix = P.joint_mixture(group, obs, P.Splitter(tids, losses, 0.25), 1.0)
-            eng.set_joint_group(0, L.TPE_JOINT_STREAM, *mix)
-            ncat = 0
-        else:
-            group, tids, losses, obs = categorical_history(n_dims, n_trials)
-            mix = P.joint_mixture(group, obs, P.Splitter(tids, losses, 0.25), 1.0, categorical=True)
-            eng.set_joint_group(0, L.TPE_JOINT_STREAM, *mix[:7], upper=mix[7], cat_p=mix[8], prior_weight=1.0)
-            ncat = int(np.count_nonzero(mix[7]))
-        res = out[leg] = dict(dims=n_dims, k_below=len(mix[1]), k_above=len(mix[4]), categorical_dims=ncat)
+        eng.set_joint_group(0, L.TPE_JOINT_STREAM, *mix, prior_weight=1.0)
+        res = out[leg] = dict(dims=n_dims, k_below=len(mix.wb), k_above=len(mix.wa),
+                              categorical_dims=int(np.count_nonzero(mix.upper)))
         res.update(_round_shapes(eng, reps))
     if 'dense' in out and 'categorical' in out:
         for name in ('one_24', 'batch_4096x24', 'one_65536'):
@@ -399,7 +385,7 @@ def build_timings(reps, n_dims=32, n_trials=10000):
             fn()
             out.append((time.perf_counter() - t) * 1e3)
         return dict(median_ms=float(np.median(out)), min_ms=float(np.min(out)), max_ms=float(np.max(out)), reps=n)
-    res = dict(dims=n_dims, trials=n_trials, k_below=len(mix[1]), k_above=len(mix[4]))
+    res = dict(dims=n_dims, trials=n_trials, k_below=len(mix.wb), k_above=len(mix.wa))
     res['device_build'] = spread(lambda: eng.build_joint_groups(args), reps)
     res['host_build'] = spread(lambda: P.joint_mixture(group, obs, splitter, 1.0), reps)
     res['upload_fold'] = spread(lambda: eng.set_joint_posterior(*mix), reps)
