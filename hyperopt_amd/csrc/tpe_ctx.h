@@ -613,6 +613,9 @@ struct tpe_ctx {
     // the joint (multivariate) posterior and its scratch (tpe_joint.hip)
     std::shared_ptr<void> joint;
     int64_t joint_flat_cap = 0;          // TPE_OPT_JOINT_CAP (0: tpe_joint.hip's kJFlatCap)
+    // the last joint round's split (tpe_joint_last_shards): 0 the primary
+    // alone, 1 candidate shards, 2 round shards; the devices that ran one
+    int32_t joint_shard_mode = 0, joint_shard_devs = 1;
 
     int fail(int code, const std::string& m) {
         err = m;
@@ -744,7 +747,46 @@ TPE_DEV int tpe1_last_build_ms(const tpe_ctx* ctx, float* ms);
 TPE_DEV int tpe1_build_report(tpe_ctx* ctx, int32_t* n_below, int32_t* ties);
 TPE_DEV int tpe1_score(tpe_ctx* ctx, int32_t label, const double* cand, int64_t n, double* lpdf_below,
                        double* lpdf_above, tpe_label_result* out);
+// the joint posteriors of one device (tpe_joint.hip); the suggest calls run
+// candidates [cand_offset, cand_offset + n_candidates) and return global indices
+TPE_DEV int tpe1_joint_set_group(tpe_ctx* ctx, int32_t slot, uint32_t pick_stream, const tpe_joint_dim* dims,
+                                 const double* q, const int32_t* upper, const double* cat_p, double prior_weight,
+                                 int32_t n_dims, int32_t n_below, const double* wb, const double* mub,
+                                 const double* sigb, int32_t n_above, const double* wa, const double* mua,
+                                 const double* siga);
+TPE_DEV int tpe1_joint_clear_groups(tpe_ctx* ctx);
+TPE_DEV int tpe1_joint_build_groups(tpe_ctx* ctx, int32_t n_groups, const int32_t* slots,
+                                    const uint32_t* pick_streams, const int64_t* group_off, const int32_t* labels,
+                                    const int32_t* streams, const double* q, const int32_t* upper,
+                                    const double* cat_p, double prior_weight, int32_t* flags);
+TPE_DEV int tpe1_joint_get_group(tpe_ctx* ctx, int32_t slot, int32_t side, double* w, double* mu, double* sigma,
+                                 int32_t cap, int32_t* n_components, int32_t* n_dims);
+TPE_DEV int tpe1_joint_draw_group(tpe_ctx* ctx, int32_t slot, uint64_t seed, uint32_t round, int64_t n,
+                                  int64_t cand_offset, double* values, int32_t* comp);
+TPE_DEV int tpe1_joint_score_group(tpe_ctx* ctx, int32_t slot, const double* values, int64_t n, double* ll,
+                                   double* lg);
+TPE_DEV int tpe1_joint_suggest_group(tpe_ctx* ctx, int32_t slot, uint64_t seed, uint32_t round,
+                                     int64_t n_candidates, int64_t cand_offset, double* values, int64_t* index,
+                                     double* ll, double* lg);
+TPE_DEV int tpe1_joint_suggest_batch(tpe_ctx* ctx, uint64_t seed, const uint32_t* rounds, int32_t n_rounds,
+                                     int64_t n_candidates, int64_t cand_offset, double* values, int64_t* index,
+                                     double* ll, double* lg);
 }
+// the set slots of a context, ascending (only >= 0: that slot alone): their
+// dimensions into D[TPE_JOINT_MAX_GROUPS], their number back
+TPE_DEV int32_t tpe1_joint_set_slots(tpe_ctx* ctx, int32_t only, int32_t* D);
+// tpe_joint_build_groups on a label-sharded context, in the order its caller
+// runs them: the check on every device, the plan on the caller's thread
+// (the one-device validation against the owners' records), the gather on
+// every device, the flags OR-ed on the caller's thread, the fold on every device
+TPE_DEV int tpe1_joint_lsh_check(tpe_ctx* x);
+TPE_DEV int tpe1_joint_lsh_plan(tpe_ctx* ctx, int32_t n_groups, const int32_t* slots, const uint32_t* pick_streams,
+                                const int64_t* group_off, const int32_t* labels, const int32_t* streams,
+                                const double* q, const int32_t* upper, const double* cat_p, double prior_weight,
+                                int32_t* flags, std::shared_ptr<void>* plan);
+TPE_DEV int tpe1_joint_lsh_gather(tpe_ctx* x, int d, void* plan);
+TPE_DEV void tpe1_joint_lsh_flags(void* plan, int32_t* flags);
+TPE_DEV int tpe1_joint_lsh_fold(tpe_ctx* x, int d, void* plan);
 
 // entry points that read the primary context's posterior alone refuse a
 // label-sharded multi-device context (its labels are spread over devices)

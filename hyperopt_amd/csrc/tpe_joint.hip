@@ -32,6 +32,12 @@
 //   k_joint_gather                    tpe_joint_build_groups: W, mu, sigma of every
 //                                     group un-permuted out of the resident
 //                                     univariate build (tpe_build.hip), one launch
+//   k_joint_interleave                that build under label shards: the slot's
+//                                     [K][D] arrays from per-label columns
+//
+// The extern "C" functions here are the per-device bodies tpe1_joint_*; the
+// public tpe_joint_* names are tpe_multi.hip's, which replicates the groups
+// over the devices of a multi-device context and shards the rounds.
 //
 // A context holds up to TPE_JOINT_MAX_GROUPS folded posteriors (slots), each
 // with the Philox stream of its component pick; the scratch is shared.
@@ -521,8 +527,8 @@ __device__ __forceinline__ void jblock_best(uint64_t key, int64_t idx, double ll
 // per workgroup, its (max, sum) to part[slice][i] and the candidate's ylog to
 // aux[i] (k_joint_merge finishes).  SAMPLE: candidate i is drawn (index
 // cand_offset + i), else read from vals[i][d].  Packed (rounds != nullptr): i
-// is the flat index over rounds of ncell candidates each -- candidate i %
-// ncell of round rounds[i / ncell]; every candidate's lpdfs are stored, and
+// is the flat index over rounds of ncell candidates each -- candidate
+// cand_offset + i % ncell of round rounds[i / ncell]; every candidate's lpdfs are stored, and
 // without `partials` no workgroup best is formed.
 // Q: a group with quantized dimensions -- the LDS layout of slice_ms_q (DR = 0);
 // C: that layout with categorical dimensions.
@@ -546,7 +552,7 @@ __global__ __launch_bounds__(DR > 0 ? kJBlock : kJLdsLanes) void k_joint_round(
     uint32_t g = (uint32_t)(cand_offset + i);
     if (rounds && valid) {   // (n < 2^31 in packed launches)
         const uint32_t r = (uint32_t)i / ncell;
-        g = (uint32_t)i - r * ncell;
+        g = (uint32_t)cand_offset + ((uint32_t)i - r * ncell);
         round = rounds[r];
     }
     int kc = 0;
@@ -715,7 +721,8 @@ __global__ __launch_bounds__(kJBlock) void k_joint_merge(JP p, int64_t n, const 
                 partials + blockIdx.x, scr);
 }
 
-// res: lpdf_below, lpdf_above, index, then (SAMPLE rounds) the winner's D values
+// res: lpdf_below, lpdf_above, global index (cand_offset + the winner's
+// position in the launch), then (SAMPLE rounds) the winner's D values
 __global__ __launch_bounds__(kJBlock) void k_joint_best(JP p, const Partial* __restrict__ partials, int32_t nparts,
                                                         int64_t cand_offset, uint64_t seed, uint32_t round,
                                                         int32_t sample, double* __restrict__ res) {
@@ -739,7 +746,7 @@ __global__ __launch_bounds__(kJBlock) void k_joint_best(JP p, const Partial* __r
     if (threadIdx.x == 0) {
         res[0] = w.lb;
         res[1] = w.la;
-        res[2] = (double)w.idx;
+        res[2] = w.idx == INT64_MAX ? (double)w.idx : (double)(cand_offset + w.idx);
     }
     if (!sample || w.idx == INT64_MAX) return;
     const uint32_t k0 = (uint32_t)seed, k1 = (uint32_t)(seed >> 32), g = (uint32_t)(cand_offset + w.idx);
@@ -749,11 +756,13 @@ __global__ __launch_bounds__(kJBlock) void k_joint_best(JP p, const Partial* __r
 
 // packed rounds: workgroup b reduces the ncell (ll, lg) pairs of round slot b
 // with k_joint_round's key and order, and writes the slot's row like
-// k_joint_best: lpdf_below, lpdf_above, index, the winner's D values
+// k_joint_best: lpdf_below, lpdf_above, global index, the winner's D values
+// (candidate j of a cell is cand_offset + j of its round)
 __global__ __launch_bounds__(kJBlock) void k_joint_best_cells(JP p, const double* __restrict__ ll,
                                                               const double* __restrict__ lg,
                                                               const uint32_t* __restrict__ rounds, uint32_t ncell,
-                                                              uint64_t seed, double* __restrict__ res) {
+                                                              int64_t cand_offset, uint64_t seed,
+                                                              double* __restrict__ res) {
     const size_t base = (size_t)blockIdx.x * ncell;
     uint64_t bk = 0;
     int64_t bi = INT64_MAX;
@@ -777,10 +786,11 @@ __global__ __launch_bounds__(kJBlock) void k_joint_best_cells(JP p, const double
     if (threadIdx.x == 0) {
         row[0] = w.lb;
         row[1] = w.la;
-        row[2] = (double)w.idx;
+        row[2] = w.idx == INT64_MAX ? (double)w.idx : (double)(cand_offset + w.idx);
     }
     if (w.idx == INT64_MAX) return;
-    const uint32_t k0 = (uint32_t)seed, k1 = (uint32_t)(seed >> 32), g = (uint32_t)w.idx, round = rounds[blockIdx.x];
+    const uint32_t k0 = (uint32_t)seed, k1 = (uint32_t)(seed >> 32), g = (uint32_t)(cand_offset + w.idx),
+                   round = rounds[blockIdx.x];
     const int kc = jpick(p, k0, k1, g, round);
     for (int d = threadIdx.x; d < p.D; d += kJBlock) row[3 + d] = jdraw<true>(p, p.dims[d], d, kc, k0, k1, g, round);
 }
@@ -834,6 +844,7 @@ struct JointGroups {   // a context's slots and the scratch they share (one stre
     DevBuf<double2> part;
     DevBuf<int32_t> err, comp, berr;
     DevBuf<JBDim> btask;
+    DevBuf<double> bcols;   // the build under label shards: the call's columns
     DevBuf<Partial> partials;
     DevBuf<uint32_t> rounds;
     std::vector<double> hres;
@@ -968,7 +979,6 @@ int joint_set(tpe_ctx* ctx, int32_t slot, uint32_t pick_stream, const tpe_joint_
     if (n_below < 1 || n_below > kJMaxBelow || n_above < 1)
         return ctx->fail(TPE_ERR_ARG, "each side needs its prior component (below: at most " +
                                           std::to_string(kJMaxBelow) + ")");
-    TPE_NOT_LSHARD(ctx);
     const int D = n_dims, Kb = n_below, Ka = n_above, K = Kb + Ka;
     std::vector<JDim> hd(D);
     int S = 0;
@@ -1201,28 +1211,47 @@ __global__ __launch_bounds__(kJBlock) void k_joint_gather(
     put((int64_t)r + 1, w[o + j], v, sigma[o + j]);
 }
 
-int joint_build_groups(tpe_ctx* ctx, int32_t n_groups, const int32_t* slots, const uint32_t* pick_streams,
-                       const int64_t* group_off, const int32_t* labels, const int32_t* streams, const double* q,
-                       const int32_t* upper, const double* cat_p, double prior_weight, int32_t* flags) {
-    auto& B = ctx->build;
+struct GInfo {   // one validated group of a tpe_joint_build_groups call
+    int32_t D, S, Kb, Ka, ncat;
+    bool quant, cat;
+    std::vector<JDim> hd;
+    std::vector<double> ctab;
+};
+
+struct JLabelInfo {   // what the validation reads of a resident label: its spec, its side counts
+    const tpe_label_spec* spec;
+    int32_t nb, na;
+};
+
+int joint_build_args(tpe_ctx* ctx, int32_t n_groups, const int32_t* slots, const uint32_t* pick_streams,
+                     const int64_t* group_off, const int32_t* labels, const int32_t* streams, const int32_t* flags) {
     if (n_groups < 1 || n_groups > kJMaxGroups)
         return ctx->fail(TPE_ERR_ARG, "tpe_joint_build_groups: 1 to " + std::to_string(kJMaxGroups) + " groups");
     if (!slots || !pick_streams || !group_off || !labels || !streams || !flags)
         return ctx->fail(TPE_ERR_ARG, "null pointer");
-    TPE_NOT_LSHARD(ctx);
+    return TPE_OK;
+}
+
+// the device's univariate build is the current one of its resident history
+int joint_build_current(tpe_ctx* ctx) {
+    auto& B = ctx->build;
     const int32_t L = B.n_labels;
     if (!B.hist_ready || !B.built_ok || B.built_gen != B.hist_gen || L < 1 || (int32_t)B.specs_h.size() != L ||
         (int32_t)ctx->resident.h_labels.size() != L || ctx->resident.n_labels != L ||
         (int32_t)B.ord_cur.size() != L)
         return ctx->fail(TPE_ERR_ARG, "tpe_joint_build_groups: no current build of the resident history");
+    return TPE_OK;
+}
+
+// The groups of a build call against the L resident labels, info(l) the
+// record of label l (one device: its own build; label shards: the owner's).
+template <typename Info>
+int joint_plan_groups(tpe_ctx* ctx, int32_t L, Info&& info, int32_t n_groups, const int32_t* slots,
+                      const int64_t* group_off, const int32_t* labels, const int32_t* streams, const double* q,
+                      const int32_t* upper, const double* cat_p, double prior_weight, std::vector<GInfo>& gi,
+                      int32_t* maxK_out) {
     if (group_off[0] != 0) return ctx->fail(TPE_ERR_ARG, "group offsets start at 0");
-    struct GInfo {
-        int32_t D, S, Kb, Ka, ncat;
-        bool quant, cat;
-        std::vector<JDim> hd;
-        std::vector<double> ctab;
-    };
-    std::vector<GInfo> gi(n_groups);
+    gi.assign(n_groups, GInfo{});
     std::vector<uint8_t> seen(L, 0), slot_seen(kJMaxGroups, 0);
     size_t cat_at = 0;
     int32_t maxK = 1;
@@ -1243,7 +1272,7 @@ int joint_build_groups(tpe_ctx* ctx, int32_t n_groups, const int32_t* slots, con
             if (l < 0 || l >= L) return ctx->fail(TPE_ERR_ARG, "tpe_joint_build_groups: label index out of range");
             if (seen[l]) return ctx->fail(TPE_ERR_ARG, "tpe_joint_build_groups: a label is listed twice");
             seen[l] = 1;
-            const tpe_label_spec& s = B.specs_h[l];
+            const tpe_label_spec& s = *info(l).spec;
             const double qd = q ? q[a + d] : 0.0;
             const int32_t C = upper ? upper[a + d] : 0;
             if (!(qd >= 0.0 && qd < __builtin_inf()))
@@ -1265,7 +1294,7 @@ int joint_build_groups(tpe_ctx* ctx, int32_t n_groups, const int32_t* slots, con
         I.quant = S > D;
         I.cat = ncat > 0;
         I.ncat = (int32_t)ncat;
-        const DLabel& f = ctx->resident.h_labels[labels[a + first]];
+        const JLabelInfo f = info(labels[a + first]);
         I.Kb = f.nb;
         I.Ka = f.na;
         if (I.Kb < 1 || I.Kb > kJMaxBelow || I.Ka < 1)
@@ -1280,7 +1309,7 @@ int joint_build_groups(tpe_ctx* ctx, int32_t n_groups, const int32_t* slots, con
         }
         size_t at = 0;
         for (int d = 0, vs = 0, coff = 0; d < D; ++d) {
-            const tpe_label_spec& s = B.specs_h[labels[a + d]];
+            const tpe_label_spec& s = *info(labels[a + d]).spec;
             const int32_t C = upper ? upper[a + d] : 0;
             if (C > 0) {   // tables: p, its running sums in category order, log p (joint_set)
                 double run = 0.0;
@@ -1310,27 +1339,88 @@ int joint_build_groups(tpe_ctx* ctx, int32_t n_groups, const int32_t* slots, con
             vs += qd > 0.0 ? 2 : 1;
         }
     }
+    *maxK_out = maxK;
+    return TPE_OK;
+}
+
+// the slot of a group about to be built: unset, its buffers at the group's size
+int joint_reserve_slot(tpe_ctx* ctx, JointGroups* G, int32_t slot, const GInfo& I, JointState** out) {
+    if (!G->slot[slot]) G->slot[slot].reset(new JointState());
+    JointState* J = G->slot[slot].get();
+    J->ready = false;
+    const int D = I.D, Kb = I.Kb, K = I.Kb + I.Ka;
+    HIPCHK(ctx, J->dims.reserve(D));
+    HIPCHK(ctx, J->W.reserve(K));
+    HIPCHK(ctx, J->mu.reserve((size_t)K * D));
+    HIPCHK(ctx, J->sig.reserve((size_t)K * D));
+    HIPCHK(ctx, J->rec.reserve((size_t)K * D));
+    HIPCHK(ctx, J->cst.reserve(K));
+    HIPCHK(ctx, J->P.reserve(K));
+    HIPCHK(ctx, J->logA.reserve(2));
+    HIPCHK(ctx, J->draw.reserve((size_t)Kb * D));
+    HIPCHK(ctx, J->thr.reserve(Kb));
+    if (I.cat) HIPCHK(ctx, J->ctab.reserve(I.ctab.size()));
+    *out = J;
+    return TPE_OK;
+}
+
+// fold a gathered group as joint_set folds an uploaded one; its error word: *err
+int joint_fold_group(tpe_ctx* ctx, JointState* J, const GInfo& I, double prior_weight, int32_t* err) {
+    hipStream_t st = ctx->stream;
+    if (I.cat)
+        HIPCHK(ctx, hipMemcpyAsync(J->ctab.p, I.ctab.data(), I.ctab.size() * sizeof(double), hipMemcpyHostToDevice,
+                                   st));
+    HIPCHK(ctx, hipMemcpyAsync(J->dims.p, I.hd.data(), I.D * sizeof(JDim), hipMemcpyHostToDevice, st));
+    const int K = I.Kb + I.Ka;
+    hipLaunchKernelGGL(k_joint_fold, dim3((K + kJBlock - 1) / kJBlock), dim3(kJBlock), 0, st, J->dims.p, I.D, I.Kb,
+                       I.Ka, J->W.p, J->mu.p, J->sig.p, J->rec.p, J->cst.p, J->P.p, J->draw.p, prior_weight,
+                       I.cat ? J->ctab.p : nullptr);
+    HIPCHK(ctx, hipGetLastError());
+    hipLaunchKernelGGL(k_joint_fold_sum, dim3(2), dim3(kJBlock), 0, st, J->P.p, I.Kb, I.Ka, J->logA.p, J->thr.p, err);
+    HIPCHK(ctx, hipGetLastError());
+    return TPE_OK;
+}
+
+// the slot's record after the call's synchronisation (a flagged group is the host build's)
+void joint_commit(JointState* J, const GInfo& I, uint32_t pick_stream, int32_t flag, int32_t fold_err) {
+    J->D = I.D;
+    J->S = I.S;
+    J->quant = I.quant;
+    J->cat = I.cat;
+    J->ncat = I.ncat;
+    J->Kb = I.Kb;
+    J->Ka = I.Ka;
+    J->stream = pick_stream;
+    J->zero = (fold_err & 1) != 0;
+    J->ready = flag == 0;
+}
+
+int joint_build_groups(tpe_ctx* ctx, int32_t n_groups, const int32_t* slots, const uint32_t* pick_streams,
+                       const int64_t* group_off, const int32_t* labels, const int32_t* streams, const double* q,
+                       const int32_t* upper, const double* cat_p, double prior_weight, int32_t* flags) {
+    auto& B = ctx->build;
+    int rc = joint_build_args(ctx, n_groups, slots, pick_streams, group_off, labels, streams, flags);
+    if (rc) return rc;
+    if ((rc = joint_build_current(ctx))) return rc;
+    std::vector<GInfo> gi;
+    int32_t maxK = 1;
+    rc = joint_plan_groups(
+        ctx, B.n_labels,
+        [&](int32_t l) {
+            const DLabel& f = ctx->resident.h_labels[l];
+            return JLabelInfo{&B.specs_h[l], f.nb, f.na};
+        },
+        n_groups, slots, group_off, labels, streams, q, upper, cat_p, prior_weight, gi, &maxK);
+    if (rc) return rc;
     HIPCHK(ctx, hipSetDevice(ctx->device));
     JointGroups* G = jgroups(ctx, true);
     hipStream_t st = ctx->stream;
     std::vector<JBDim> tasks;
     for (int32_t g = 0; g < n_groups; ++g) {
         const GInfo& I = gi[g];
-        if (!G->slot[slots[g]]) G->slot[slots[g]].reset(new JointState());
-        JointState* J = G->slot[slots[g]].get();
-        J->ready = false;
-        const int D = I.D, Kb = I.Kb, K = I.Kb + I.Ka;
-        HIPCHK(ctx, J->dims.reserve(D));
-        HIPCHK(ctx, J->W.reserve(K));
-        HIPCHK(ctx, J->mu.reserve((size_t)K * D));
-        HIPCHK(ctx, J->sig.reserve((size_t)K * D));
-        HIPCHK(ctx, J->rec.reserve((size_t)K * D));
-        HIPCHK(ctx, J->cst.reserve(K));
-        HIPCHK(ctx, J->P.reserve(K));
-        HIPCHK(ctx, J->logA.reserve(2));
-        HIPCHK(ctx, J->draw.reserve((size_t)Kb * D));
-        HIPCHK(ctx, J->thr.reserve(Kb));
-        if (I.cat) HIPCHK(ctx, J->ctab.reserve(I.ctab.size()));
+        JointState* J = nullptr;
+        if ((rc = joint_reserve_slot(ctx, G, slots[g], I, &J))) return rc;
+        const int D = I.D;
         bool first = true;
         for (int d = 0; d < D; ++d) {
             const int32_t l = labels[group_off[g] + d], C = I.hd[d].upper;
@@ -1351,58 +1441,246 @@ int joint_build_groups(tpe_ctx* ctx, int32_t n_groups, const int32_t* slots, con
                        dim3(kJBlock), 0, st, G->btask.p, B.specs.p, B.p_off.p, B.counts.p, B.below_val.p, B.keys.p,
                        B.idx.p, B.order_off.p, B.order.p, B.mix_off.p, B.w.p, B.sigma.p, G->berr.p);
     HIPCHK(ctx, hipGetLastError());
-    for (int32_t g = 0; g < n_groups; ++g) {
-        const GInfo& I = gi[g];
-        JointState* J = G->slot[slots[g]].get();
-        if (I.cat)
-            HIPCHK(ctx, hipMemcpyAsync(J->ctab.p, I.ctab.data(), I.ctab.size() * sizeof(double), hipMemcpyHostToDevice,
-                                       st));
-        HIPCHK(ctx, hipMemcpyAsync(J->dims.p, I.hd.data(), I.D * sizeof(JDim), hipMemcpyHostToDevice, st));
-        const int K = I.Kb + I.Ka;
-        hipLaunchKernelGGL(k_joint_fold, dim3((K + kJBlock - 1) / kJBlock), dim3(kJBlock), 0, st, J->dims.p, I.D, I.Kb,
-                           I.Ka, J->W.p, J->mu.p, J->sig.p, J->rec.p, J->cst.p, J->P.p, J->draw.p, prior_weight,
-                           I.cat ? J->ctab.p : nullptr);
-        HIPCHK(ctx, hipGetLastError());
-        hipLaunchKernelGGL(k_joint_fold_sum, dim3(2), dim3(kJBlock), 0, st, J->P.p, I.Kb, I.Ka, J->logA.p, J->thr.p,
-                           G->berr.p + n_groups + g);
-        HIPCHK(ctx, hipGetLastError());
-    }
+    for (int32_t g = 0; g < n_groups; ++g)
+        if ((rc = joint_fold_group(ctx, G->slot[slots[g]].get(), gi[g], prior_weight, G->berr.p + n_groups + g)))
+            return rc;
     std::vector<int32_t> eh(2 * (size_t)n_groups);
     HIPCHK(ctx, hipMemcpyAsync(eh.data(), G->berr.p, eh.size() * sizeof(int32_t), hipMemcpyDeviceToHost, st));
     HIPCHK(ctx, hipStreamSynchronize(st));   // the call's one synchronisation
     bool zero = false;
     for (int32_t g = 0; g < n_groups; ++g) {
-        const GInfo& I = gi[g];
         JointState* J = G->slot[slots[g]].get();
         flags[g] = eh[g];
-        J->D = I.D;
-        J->S = I.S;
-        J->quant = I.quant;
-        J->cat = I.cat;
-        J->ncat = I.ncat;
-        J->Kb = I.Kb;
-        J->Ka = I.Ka;
-        J->stream = pick_streams[g];
-        J->zero = (eh[n_groups + g] & 1) != 0;
-        J->ready = eh[g] == 0;   // a flagged group is the host build's
+        joint_commit(J, gi[g], pick_streams[g], eh[g], eh[n_groups + g]);
         zero |= J->ready && J->zero;
     }
     if (zero) return zero_mass(ctx);
     return TPE_OK;
 }
+
+// ------------------------------------------ the build under label shards ----
+// A group's labels live on different devices of a label-sharded context.  The
+// columns of a call -- per group W [K], then per dimension mu [K] and sig [K],
+// K = Kb + Ka -- have the same place in every device's column buffer: the
+// owner of a label gathers its columns (k_joint_gather on a one-dimension
+// task), every device copies in the columns it does not own, device to
+// device, and k_joint_interleave writes the slot's [K][D] arrays from them.
+__global__ __launch_bounds__(kJBlock) void k_joint_interleave(const double* __restrict__ cols, int32_t D, int32_t K,
+                                                              double* __restrict__ W, double* __restrict__ mu,
+                                                              double* __restrict__ sig) {
+    const int64_t e = (int64_t)blockIdx.x * kJBlock + threadIdx.x;
+    if (e >= (int64_t)K * D) return;
+    const int64_t k = e / D, d = e - k * D;
+    mu[e] = cols[(size_t)K * (1 + 2 * d) + k];
+    sig[e] = cols[(size_t)K * (2 + 2 * d) + k];
+    if (d == 0) W[k] = cols[k];
+}
+
+struct JLshPlan {
+    int32_t n_groups = 0, maxK = 1;
+    double prior_weight = 0.0;
+    std::vector<int32_t> slots, labels;   // labels: global indices, flat over the groups
+    std::vector<uint32_t> picks;
+    std::vector<int64_t> goff;
+    std::vector<GInfo> gi;
+    std::vector<int32_t> owner, local;    // per flat label: its device and its index there
+    std::vector<int32_t> wdim;            // per group: the dimension that supplies W
+    std::vector<size_t> base;             // per group: its first column in the buffer (doubles)
+    size_t total = 0;
+    std::vector<int> device;              // per context: its HIP ordinal
+    std::vector<double*> cols;            // per context: its column buffer (set by the gather phase)
+    std::vector<std::vector<int32_t>> dflags;   // per context: the flags its gather raised
+    std::vector<int32_t> flags;           // OR over the contexts (between the phases)
+};
+
+tpe_ctx* jdev(tpe_ctx* c, int d) { return d == 0 ? c : c->peers[d - 1]; }
+
+size_t jcol_mu(const JLshPlan& P, int32_t g, int d) {
+    return P.base[g] + (size_t)(P.gi[g].Kb + P.gi[g].Ka) * (1 + 2 * (size_t)d);
+}
 }  // namespace
+
+int tpe1_joint_lsh_check(tpe_ctx* x) {
+    TPE_SETTLE(x);   // (a deferred rebuild's report: its buffers are read here)
+    return joint_build_current(x);
+}
+
+int tpe1_joint_lsh_plan(tpe_ctx* ctx, int32_t n_groups, const int32_t* slots, const uint32_t* pick_streams,
+                        const int64_t* group_off, const int32_t* labels, const int32_t* streams, const double* q,
+                        const int32_t* upper, const double* cat_p, double prior_weight, int32_t* flags,
+                        std::shared_ptr<void>* out) {
+    int rc = joint_build_args(ctx, n_groups, slots, pick_streams, group_off, labels, streams, flags);
+    if (rc) return rc;
+    const int nd = 1 + (int)ctx->peers.size();
+    const int32_t L = ctx->lsh_L;
+    for (int d = 0; d < nd; ++d)
+        if (jdev(ctx, d)->build.n_labels != (int32_t)ctx->lsh_ids[d].size())
+            return ctx->fail(TPE_ERR_ARG, "tpe_joint_build_groups: no current build of the resident history");
+    auto P = std::make_shared<JLshPlan>();
+    rc = joint_plan_groups(
+        ctx, L,
+        [&](int32_t l) {
+            tpe_ctx* x = jdev(ctx, ctx->lsh_dev[l]);
+            const int32_t j = ctx->lsh_local[l];
+            const DLabel& f = x->resident.h_labels[j];
+            return JLabelInfo{&x->build.specs_h[j], f.nb, f.na};
+        },
+        n_groups, slots, group_off, labels, streams, q, upper, cat_p, prior_weight, P->gi, &P->maxK);
+    if (rc) return rc;
+    P->n_groups = n_groups;
+    P->prior_weight = prior_weight;
+    P->slots.assign(slots, slots + n_groups);
+    P->picks.assign(pick_streams, pick_streams + n_groups);
+    P->goff.assign(group_off, group_off + n_groups + 1);
+    P->labels.assign(labels, labels + group_off[n_groups]);
+    for (int32_t l : P->labels) {
+        P->owner.push_back(ctx->lsh_dev[l]);
+        P->local.push_back(ctx->lsh_local[l]);
+    }
+    for (int32_t g = 0; g < n_groups; ++g) {
+        const GInfo& I = P->gi[g];
+        int w = 0;
+        while (I.hd[w].upper > 0) ++w;   // (validated: a group holds a label that is not categorical)
+        P->wdim.push_back(w);
+        P->base.push_back(P->total);
+        P->total += (size_t)(I.Kb + I.Ka) * (1 + 2 * (size_t)I.D);
+    }
+    for (int d = 0; d < nd; ++d) P->device.push_back(jdev(ctx, d)->device);
+    P->cols.assign(nd, nullptr);
+    P->dflags.assign(nd, std::vector<int32_t>(n_groups, 0));
+    P->flags.assign(n_groups, 0);
+    *out = std::static_pointer_cast<void>(P);
+    return TPE_OK;
+}
+
+// phase 1 on device d: its labels' columns, its flag words, one synchronisation
+int tpe1_joint_lsh_gather(tpe_ctx* x, int d, void* plan) {
+    JLshPlan& P = *static_cast<JLshPlan*>(plan);
+    auto& B = x->build;
+    HIPCHK(x, hipSetDevice(x->device));
+    JointGroups* G = jgroups(x, true);
+    hipStream_t st = x->stream;
+    HIPCHK(x, G->bcols.reserve(P.total));
+    P.cols[d] = G->bcols.p;
+    std::vector<JBDim> tasks;
+    int rc;
+    for (int32_t g = 0; g < P.n_groups; ++g) {
+        const GInfo& I = P.gi[g];
+        JointState* J = nullptr;
+        if ((rc = joint_reserve_slot(x, G, P.slots[g], I, &J))) return rc;
+        const int32_t K = I.Kb + I.Ka;
+        for (int dd = 0; dd < I.D; ++dd) {
+            const size_t at = (size_t)P.goff[g] + dd;
+            if (P.owner[at] != d) continue;
+            const int32_t l = P.local[at];
+            const int32_t fl = (B.ord_cur[l] ? 1 : 0) | (dd == P.wdim[g] ? 2 : 0);
+            double* mu = G->bcols.p + jcol_mu(P, g, dd);
+            tasks.push_back(JBDim{G->bcols.p + P.base[g], mu, mu + K, l, g, 0, 1, I.Kb, I.Ka, I.hd[dd].upper, fl});
+        }
+    }
+    HIPCHK(x, G->err.reserve(1));
+    HIPCHK(x, G->berr.reserve(2 * (size_t)P.n_groups));   // flags | fold errors, per group
+    HIPCHK(x, hipMemsetAsync(G->berr.p, 0, 2 * (size_t)P.n_groups * sizeof(int32_t), st));
+    if (!tasks.empty()) {
+        HIPCHK(x, G->btask.reserve(tasks.size()));
+        HIPCHK(x, hipMemcpyAsync(G->btask.p, tasks.data(), tasks.size() * sizeof(JBDim), hipMemcpyHostToDevice, st));
+        hipLaunchKernelGGL(k_joint_gather,
+                           dim3((unsigned)((P.maxK + kJBlock - 1) / kJBlock), (unsigned)tasks.size(), 2), dim3(kJBlock),
+                           0, st, G->btask.p, B.specs.p, B.p_off.p, B.counts.p, B.below_val.p, B.keys.p, B.idx.p,
+                           B.order_off.p, B.order.p, B.mix_off.p, B.w.p, B.sigma.p, G->berr.p);
+        HIPCHK(x, hipGetLastError());
+        HIPCHK(x, hipMemcpyAsync(P.dflags[d].data(), G->berr.p, P.n_groups * sizeof(int32_t), hipMemcpyDeviceToHost,
+                                 st));
+    }
+    HIPCHK(x, hipStreamSynchronize(st));   // (the other devices read these columns in phase 2)
+    return TPE_OK;
+}
+
+// between the phases, on the caller's thread: a group flagged anywhere is flagged
+void tpe1_joint_lsh_flags(void* plan, int32_t* flags) {
+    JLshPlan& P = *static_cast<JLshPlan*>(plan);
+    for (int32_t g = 0; g < P.n_groups; ++g) {
+        int32_t f = 0;
+        for (const auto& df : P.dflags) f |= df[g];
+        P.flags[g] = f;
+        flags[g] = f;
+    }
+}
+
+// phase 2 on device d: the columns of the other devices, the [K][D] arrays,
+// the folds; a flagged group stays unset
+int tpe1_joint_lsh_fold(tpe_ctx* x, int d, void* plan) {
+    JLshPlan& P = *static_cast<JLshPlan*>(plan);
+    HIPCHK(x, hipSetDevice(x->device));
+    JointGroups* G = jgroups(x, true);
+    hipStream_t st = x->stream;
+    int rc;
+    auto fetch = [&](int from, size_t off, size_t count) -> int {
+        double* dst = G->bcols.p + off;
+        const double* src = P.cols[from] + off;
+        if (P.device[from] == x->device)
+            HIPCHK(x, hipMemcpyAsync(dst, src, count * sizeof(double), hipMemcpyDeviceToDevice, st));
+        else
+            HIPCHK(x, hipMemcpyPeerAsync(dst, x->device, src, P.device[from], count * sizeof(double), st));
+        return TPE_OK;
+    };
+    for (int32_t g = 0; g < P.n_groups; ++g) {
+        if (P.flags[g]) continue;
+        const GInfo& I = P.gi[g];
+        JointState* J = G->slot[P.slots[g]].get();
+        const size_t K = (size_t)(I.Kb + I.Ka);
+        const int wo = P.owner[(size_t)P.goff[g] + P.wdim[g]];
+        if (wo != d && (rc = fetch(wo, P.base[g], K))) return rc;
+        for (int dd = 0; dd < I.D;) {   // runs of dimensions of one owner: one copy each
+            const int o = P.owner[(size_t)P.goff[g] + dd];
+            int e = dd + 1;
+            while (e < I.D && P.owner[(size_t)P.goff[g] + e] == o) ++e;
+            if (o != d && (rc = fetch(o, jcol_mu(P, g, dd), 2 * K * (size_t)(e - dd)))) return rc;
+            dd = e;
+        }
+        hipLaunchKernelGGL(k_joint_interleave, dim3((unsigned)((K * I.D + kJBlock - 1) / kJBlock)), dim3(kJBlock), 0,
+                           st, G->bcols.p + P.base[g], I.D, (int32_t)K, J->W.p, J->mu.p, J->sig.p);
+        HIPCHK(x, hipGetLastError());
+        if ((rc = joint_fold_group(x, J, I, P.prior_weight, G->berr.p + P.n_groups + g))) return rc;
+    }
+    std::vector<int32_t> eh(P.n_groups);
+    HIPCHK(x, hipMemcpyAsync(eh.data(), G->berr.p + P.n_groups, eh.size() * sizeof(int32_t), hipMemcpyDeviceToHost,
+                             st));
+    HIPCHK(x, hipStreamSynchronize(st));
+    bool zero = false;
+    for (int32_t g = 0; g < P.n_groups; ++g) {
+        JointState* J = G->slot[P.slots[g]].get();
+        joint_commit(J, P.gi[g], P.picks[g], P.flags[g], eh[g]);
+        zero |= J->ready && J->zero;
+    }
+    if (zero) return zero_mass(x);
+    return TPE_OK;
+}
+
+// the set slots of a context in ascending order: their dimensions into D[], their number back
+int32_t tpe1_joint_set_slots(tpe_ctx* ctx, int32_t only, int32_t* D) {
+    JointGroups* G = jgroups(ctx, false);
+    int32_t n = 0;
+    if (!G) return 0;
+    for (int j = 0; j < kJMaxGroups; ++j) {
+        if (only >= 0 && j != only) continue;
+        if (G->slot[j] && G->slot[j]->ready) D[n++] = G->slot[j]->D;
+    }
+    return n;
+}
 
 extern "C" {
 
-int tpe_joint_set_group(tpe_ctx* ctx, int32_t slot, uint32_t pick_stream, const tpe_joint_dim* dims,
-                        const double* q, const int32_t* upper, const double* cat_p, double prior_weight,
-                        int32_t n_dims, int32_t n_below, const double* wb, const double* mub, const double* sigb,
-                        int32_t n_above, const double* wa, const double* mua, const double* siga) {
+// (the per-device bodies; tpe_multi.hip exports the public tpe_joint_* names)
+int tpe1_joint_set_group(tpe_ctx* ctx, int32_t slot, uint32_t pick_stream, const tpe_joint_dim* dims,
+                         const double* q, const int32_t* upper, const double* cat_p, double prior_weight,
+                         int32_t n_dims, int32_t n_below, const double* wb, const double* mub, const double* sigb,
+                         int32_t n_above, const double* wa, const double* mua, const double* siga) {
     return joint_set(ctx, slot, pick_stream, dims, q, upper, cat_p, prior_weight, n_dims, n_below, wb, mub, sigb,
                      n_above, wa, mua, siga);
 }
 
-int tpe_joint_clear_groups(tpe_ctx* ctx) {
+int tpe1_joint_clear_groups(tpe_ctx* ctx) {
     if (!ctx) return TPE_ERR_ARG;
     JointGroups* G = jgroups(ctx, false);
     if (!G) return TPE_OK;
@@ -1411,17 +1689,17 @@ int tpe_joint_clear_groups(tpe_ctx* ctx) {
     return TPE_OK;
 }
 
-int tpe_joint_build_groups(tpe_ctx* ctx, int32_t n_groups, const int32_t* slots, const uint32_t* pick_streams,
-                           const int64_t* group_off, const int32_t* labels, const int32_t* streams, const double* q,
-                           const int32_t* upper, const double* cat_p, double prior_weight, int32_t* flags) {
+int tpe1_joint_build_groups(tpe_ctx* ctx, int32_t n_groups, const int32_t* slots, const uint32_t* pick_streams,
+                            const int64_t* group_off, const int32_t* labels, const int32_t* streams, const double* q,
+                            const int32_t* upper, const double* cat_p, double prior_weight, int32_t* flags) {
     if (!ctx) return TPE_ERR_ARG;
     TPE_SETTLE(ctx);   // (a deferred rebuild's report: its buffers are read here)
     return joint_build_groups(ctx, n_groups, slots, pick_streams, group_off, labels, streams, q, upper, cat_p,
                               prior_weight, flags);
 }
 
-int tpe_joint_get_group(tpe_ctx* ctx, int32_t slot, int32_t side, double* w, double* mu, double* sigma, int32_t cap,
-                        int32_t* n_components, int32_t* n_dims) {
+int tpe1_joint_get_group(tpe_ctx* ctx, int32_t slot, int32_t side, double* w, double* mu, double* sigma, int32_t cap,
+                         int32_t* n_components, int32_t* n_dims) {
     if (!ctx) return TPE_ERR_ARG;
     if (slot < 0 || slot >= kJMaxGroups || side < 0 || side > 1)
         return ctx->fail(TPE_ERR_ARG, "tpe_joint_get_group: slot in [0, " + std::to_string(kJMaxGroups) +
@@ -1442,8 +1720,8 @@ int tpe_joint_get_group(tpe_ctx* ctx, int32_t slot, int32_t side, double* w, dou
     return TPE_OK;
 }
 
-int tpe_joint_draw_group(tpe_ctx* ctx, int32_t slot, uint64_t seed, uint32_t round, int64_t n, int64_t cand_offset,
-                         double* values, int32_t* comp) {
+int tpe1_joint_draw_group(tpe_ctx* ctx, int32_t slot, uint64_t seed, uint32_t round, int64_t n, int64_t cand_offset,
+                          double* values, int32_t* comp) {
     if (!ctx) return TPE_ERR_ARG;
     JointGroups* G = nullptr;
     JointState* J = nullptr;
@@ -1464,7 +1742,7 @@ int tpe_joint_draw_group(tpe_ctx* ctx, int32_t slot, uint64_t seed, uint32_t rou
     return read_err(ctx, G);
 }
 
-int tpe_joint_score_group(tpe_ctx* ctx, int32_t slot, const double* values, int64_t n, double* ll, double* lg) {
+int tpe1_joint_score_group(tpe_ctx* ctx, int32_t slot, const double* values, int64_t n, double* ll, double* lg) {
     if (!ctx) return TPE_ERR_ARG;
     JointGroups* G = nullptr;
     JointState* J = nullptr;
@@ -1484,23 +1762,26 @@ int tpe_joint_score_group(tpe_ctx* ctx, int32_t slot, const double* values, int6
     return TPE_OK;
 }
 
-int tpe_joint_suggest_group(tpe_ctx* ctx, int32_t slot, uint64_t seed, uint32_t round, int64_t n_candidates,
-                            double* values, int64_t* index, double* ll, double* lg) {
+// candidates [cand_offset, cand_offset + n_candidates) of the round (a shard
+// of a multi-device round; the whole round: offset 0); *index is global
+int tpe1_joint_suggest_group(tpe_ctx* ctx, int32_t slot, uint64_t seed, uint32_t round, int64_t n_candidates,
+                             int64_t cand_offset, double* values, int64_t* index, double* ll, double* lg) {
     if (!ctx) return TPE_ERR_ARG;
     JointGroups* G = nullptr;
     JointState* J = nullptr;
     int rc = joint_ready(ctx, slot, &G, &J, "tpe_joint_suggest_group");
     if (rc) return rc;
     if (!values || !index || !ll || !lg) return ctx->fail(TPE_ERR_ARG, "null pointer");
-    if ((rc = check_range(ctx, n_candidates, 0))) return rc;
+    if ((rc = check_range(ctx, n_candidates, cand_offset))) return rc;
     HIPCHK(ctx, hipSetDevice(ctx->device));
     HIPCHK(ctx, G->res.reserve(3 + J->D));
     HIPCHK(ctx, hipMemsetAsync(G->err.p, 0, sizeof(int32_t), ctx->stream));
     int32_t nparts = 0;
     if (ctx->timing) HIPCHK(ctx, hipEventRecord(ctx->ev0, ctx->stream));
-    if ((rc = launch_round(ctx, G, J, true, n_candidates, 0, seed, round, false, &nparts, G->err.p))) return rc;
+    if ((rc = launch_round(ctx, G, J, true, n_candidates, cand_offset, seed, round, false, &nparts, G->err.p)))
+        return rc;
     hipLaunchKernelGGL(k_joint_best, dim3(1), dim3(kJBlock), 0, ctx->stream, J->jp(), G->partials.p, nparts,
-                       (int64_t)0, seed, round, 1, G->res.p);
+                       cand_offset, seed, round, 1, G->res.p);
     HIPCHK(ctx, hipGetLastError());
     if (ctx->timing) HIPCHK(ctx, hipEventRecord(ctx->ev1, ctx->stream));
     std::vector<double> h(3 + J->D);
@@ -1522,13 +1803,16 @@ int tpe_joint_suggest_group(tpe_ctx* ctx, int32_t slot, uint64_t seed, uint32_t 
 // (+ k_joint_merge) and one k_joint_best_cells each; a round beyond the cap
 // runs alone as tpe_joint_suggest_group runs it.  The result rows of all slots and,
 // in front of them, the error word are one device buffer: one copy back, one
-// synchronisation.
-int tpe_joint_suggest_batch(tpe_ctx* ctx, uint64_t seed, const uint32_t* rounds, int32_t n_rounds,
-                            int64_t n_candidates, double* values, int64_t* index, double* ll, double* lg) {
+// synchronisation.  Candidates [cand_offset, cand_offset + n_candidates) of
+// every round (a shard of a multi-device call; the whole rounds: offset 0);
+// the indices are global.
+int tpe1_joint_suggest_batch(tpe_ctx* ctx, uint64_t seed, const uint32_t* rounds, int32_t n_rounds,
+                             int64_t n_candidates, int64_t cand_offset, double* values, int64_t* index, double* ll,
+                             double* lg) {
     if (!ctx) return TPE_ERR_ARG;
     if (!rounds || !values || !index || !ll || !lg) return ctx->fail(TPE_ERR_ARG, "null pointer");
     if (n_rounds < 1) return ctx->fail(TPE_ERR_ARG, "the number of rounds must be positive");
-    int rc = check_range(ctx, n_candidates, 0);
+    int rc = check_range(ctx, n_candidates, cand_offset);
     if (rc) return rc;
     JointGroups* G = jgroups(ctx, false);
     std::vector<JointState*> set;
@@ -1565,18 +1849,19 @@ int tpe_joint_suggest_batch(tpe_ctx* ctx, uint64_t seed, const uint32_t* rounds,
         if (per) {
             for (int64_t r0 = 0; r0 < R; r0 += per) {
                 const int64_t rc_n = std::min(per, R - r0);
-                if ((rc = launch_round(ctx, G, J, true, rc_n * n, 0, seed, 0, true, &nparts, err, G->rounds.p + r0,
-                                       (uint32_t)n)))
+                if ((rc = launch_round(ctx, G, J, true, rc_n * n, cand_offset, seed, 0, true, &nparts, err,
+                                       G->rounds.p + r0, (uint32_t)n)))
                     return rc;
                 hipLaunchKernelGGL(k_joint_best_cells, dim3((unsigned)rc_n), dim3(kJBlock), 0, st, J->jp(), G->ll.p,
-                                   G->lg.p, G->rounds.p + r0, (uint32_t)n, seed, row0 + r0 * w);
+                                   G->lg.p, G->rounds.p + r0, (uint32_t)n, cand_offset, seed, row0 + r0 * w);
                 HIPCHK(ctx, hipGetLastError());
             }
         } else {
             for (int64_t r = 0; r < R; ++r) {
-                if ((rc = launch_round(ctx, G, J, true, n, 0, seed, rounds[r], false, &nparts, err))) return rc;
+                if ((rc = launch_round(ctx, G, J, true, n, cand_offset, seed, rounds[r], false, &nparts, err)))
+                    return rc;
                 hipLaunchKernelGGL(k_joint_best, dim3(1), dim3(kJBlock), 0, st, J->jp(), G->partials.p, nparts,
-                                   (int64_t)0, seed, rounds[r], 1, row0 + r * w);
+                                   cand_offset, seed, rounds[r], 1, row0 + r * w);
                 HIPCHK(ctx, hipGetLastError());
             }
         }

@@ -34,6 +34,14 @@
 // devices with the candidates, where the candidate split repeats it on
 // every device.  Spaces with fewer labels than devices, tpe_set_posterior
 // and the one-shot tpe_build_posterior keep the candidate / round split.
+//
+// Joint posteriors (tpe_joint.hip) are replicated on every device of either
+// kind of context: tpe_joint_set_group folds the same arrays everywhere, and
+// tpe_joint_build_groups builds them from the univariate build -- on a
+// label-sharded context in two for_all phases (the owners gather their
+// labels' columns; every device copies in the others', device to device,
+// interleaves and folds).  The joint rounds split like the univariate ones
+// (joint_sharded); tpe_joint_last_shards tells how the last one ran.
 #include <hip/hip_runtime.h>
 
 #include <condition_variable>
@@ -400,6 +408,102 @@ int lsh_round(tpe_ctx* c, uint64_t seed, const uint32_t* rounds, int32_t n_round
     return TPE_OK;
 }
 
+// ---------------------------------------------------------- joint rounds ----
+// One joint call -- rounds[0 .. n_rounds) of n candidates for `ns` slots of
+// dimensions D[] -- split like sharded_round: candidate shards from kMinShard
+// candidates per device, else whole rounds, else the primary alone.  The
+// joint posterior is replicated (tpe_joint_set_group), so every device draws
+// and scores its range [lo, lo + m) of the global candidate indices; the
+// shards' winners merge with tpe_merge_results, the one broadcast_best order.
+// run(x, shard, values, index, ll, lg) is the device's call on its rows.
+using JointRun = std::function<int(tpe_ctx*, const Shard&, double*, int64_t*, double*, double*)>;
+
+void joint_timing(tpe_ctx* c) {   // (the slowest device's, as aggregate_stats)
+    float score_ms = 0.f, round_ms = 0.f;
+    for (int d = 0; d < ndev(c); ++d) {
+        score_ms = std::max(score_ms, dev(c, d)->score_ms);
+        round_ms = std::max(round_ms, dev(c, d)->round_ms);
+    }
+    c->score_ms = score_ms;
+    c->round_ms = round_ms;
+}
+
+int joint_sharded(tpe_ctx* c, int32_t n_rounds, int64_t n, int32_t ns, const int32_t* D, const JointRun& run,
+                  double* values, int64_t* index, double* ll, double* lg) {
+    const int nd = ndev(c);
+    const bool by_cand = n >= (int64_t)nd * kMinShard;
+    const bool by_round = !by_cand && n_rounds >= nd && n > 0;
+    c->joint_shard_mode = by_cand ? 1 : (by_round ? 2 : 0);
+    c->joint_shard_devs = by_cand || by_round ? nd : 1;
+    Shard whole;
+    whole.n_cand = n;
+    whole.n_rounds = n_rounds;
+    if (!by_cand && !by_round) return run(c, whole, values, index, ll, lg);
+    size_t sumD = 0;
+    for (int32_t s = 0; s < ns; ++s) sumD += (size_t)D[s];
+    std::vector<Shard> sh(nd);
+    for (int d = 0; d < nd; ++d) {
+        if (by_cand) {
+            const int64_t q = n / nd, r = n % nd;
+            sh[d].n_cand = q + (d < r ? 1 : 0);
+            sh[d].cand_lo = d * q + std::min<int64_t>(d, r);
+            sh[d].round_lo = 0;
+            sh[d].n_rounds = n_rounds;
+        } else {
+            const int32_t q = n_rounds / nd, r = n_rounds % nd;
+            sh[d].n_rounds = q + (d < r ? 1 : 0);
+            sh[d].round_lo = d * q + std::min<int32_t>(d, r);
+            sh[d].cand_lo = 0;
+            sh[d].n_cand = n;
+        }
+    }
+    if (by_round) {   // each device writes its own rows: nothing to merge
+        const int rc = for_all(c, [&](tpe_ctx* x, int d) {
+            const size_t r0 = (size_t)sh[d].round_lo;
+            return run(x, sh[d], values + r0 * sumD, index + r0 * ns, ll + r0 * ns, lg + r0 * ns);
+        });
+        if (rc) return rc;
+        joint_timing(c);
+        return TPE_OK;
+    }
+    const size_t cells = (size_t)n_rounds * ns, nv = (size_t)n_rounds * sumD;
+    std::vector<double> pv(nd * nv), pl(nd * cells), pg(nd * cells);
+    std::vector<int64_t> pi(nd * cells);
+    int rc = for_all(c, [&](tpe_ctx* x, int d) {
+        return run(x, sh[d], pv.data() + d * nv, pi.data() + d * cells, pl.data() + d * cells, pg.data() + d * cells);
+    });
+    if (rc) return rc;
+    std::vector<tpe_label_result> parts(nd * cells), best(cells);
+    for (size_t j = 0; j < nd * cells; ++j) {
+        tpe_label_result& p = parts[j];
+        p.value = 0.0;
+        p.score = pl[j] - pg[j];   // (the round's own key: lpdf_below - lpdf_above)
+        p.lpdf_below = pl[j];
+        p.lpdf_above = pg[j];
+        p.index = pi[j];
+        p.label = 0;
+        p.status = 0;
+    }
+    rc = tpe_merge_results(parts.data(), nd, (int32_t)cells, best.data());
+    if (rc) return c->fail(rc, "merging the shards' joint winners failed");
+    for (int32_t r = 0; r < n_rounds; ++r) {
+        size_t doff = 0;
+        for (int32_t s = 0; s < ns; ++s) {
+            const size_t j = (size_t)r * ns + s;
+            int d = 0;   // the shard whose range holds the winner
+            while (d + 1 < nd && best[j].index >= sh[d + 1].cand_lo) ++d;
+            ll[j] = best[j].lpdf_below;
+            lg[j] = best[j].lpdf_above;
+            index[j] = best[j].index;
+            const double* v = pv.data() + d * nv + (size_t)r * sumD + doff;
+            std::copy(v, v + D[s], values + (size_t)r * sumD + doff);
+            doff += (size_t)D[s];
+        }
+    }
+    joint_timing(c);
+    return TPE_OK;
+}
+
 }  // namespace
 
 extern "C" {
@@ -736,6 +840,118 @@ int tpe_suggest_batch(tpe_ctx* ctx, uint64_t seed, const uint32_t* rounds, int32
     if (n_rounds <= 0) return ctx->fail(TPE_ERR_ARG, "bad candidate/round count");
     if (lsharded(ctx)) return lsh_round(ctx, seed, rounds, n_rounds, n_candidates, cand_offset, out);
     return sharded_round(ctx, seed, rounds, n_rounds, n_candidates, cand_offset, out);
+}
+
+// ---- joint (multivariate) posteriors: replicated on every device, also on a
+// label-sharded context (a joint group is a posterior of its own) ----
+int tpe_joint_set_group(tpe_ctx* ctx, int32_t slot, uint32_t pick_stream, const tpe_joint_dim* dims,
+                        const double* q, const int32_t* upper, const double* cat_p, double prior_weight,
+                        int32_t n_dims, int32_t n_below, const double* wb, const double* mub, const double* sigb,
+                        int32_t n_above, const double* wa, const double* mua, const double* siga) {
+    if (!ctx) return TPE_ERR_ARG;
+    return for_all(ctx, [&](tpe_ctx* x, int) {
+        return tpe1_joint_set_group(x, slot, pick_stream, dims, q, upper, cat_p, prior_weight, n_dims, n_below, wb,
+                                    mub, sigb, n_above, wa, mua, siga);
+    });
+}
+
+int tpe_joint_clear_groups(tpe_ctx* ctx) {
+    if (!ctx) return TPE_ERR_ARG;
+    return for_all(ctx, [&](tpe_ctx* x, int) { return tpe1_joint_clear_groups(x); });
+}
+
+int tpe_joint_build_groups(tpe_ctx* ctx, int32_t n_groups, const int32_t* slots, const uint32_t* pick_streams,
+                           const int64_t* group_off, const int32_t* labels, const int32_t* streams, const double* q,
+                           const int32_t* upper, const double* cat_p, double prior_weight, int32_t* flags) {
+    if (!ctx) return TPE_ERR_ARG;
+    const int nd = ndev(ctx);
+    if (nd == 1)
+        return tpe1_joint_build_groups(ctx, n_groups, slots, pick_streams, group_off, labels, streams, q, upper, cat_p,
+                                       prior_weight, flags);
+    if (!lsharded(ctx)) {   // replicated: every device holds the whole univariate build
+        std::vector<std::vector<int32_t>> fd(nd, std::vector<int32_t>(std::max(n_groups, 1), 0));
+        const int rc = for_all(ctx, [&](tpe_ctx* x, int d) {
+            return tpe1_joint_build_groups(x, n_groups, slots, pick_streams, group_off, labels, streams, q, upper,
+                                           cat_p, prior_weight, d == 0 ? flags : fd[d].data());
+        });
+#ifndef NDEBUG
+        if (flags && n_groups > 0 && (rc == TPE_OK || rc == TPE_ERR_SAMPLE))
+            for (int d = 1; d < nd; ++d)
+                for (int32_t g = 0; g < n_groups; ++g)
+                    if (fd[d][g] != flags[g]) return ctx->fail(TPE_ERR_ARG, "joint build: devices disagree on flags");
+#endif
+        return rc;
+    }
+    int rc = for_all(ctx, [&](tpe_ctx* x, int) { return tpe1_joint_lsh_check(x); });
+    if (rc) return rc;
+    std::shared_ptr<void> plan;
+    if ((rc = tpe1_joint_lsh_plan(ctx, n_groups, slots, pick_streams, group_off, labels, streams, q, upper, cat_p,
+                                  prior_weight, flags, &plan)))
+        return rc;
+    // two phases with the host barrier of for_all between them: every
+    // device's columns are complete (its stream synchronised) before another
+    // device copies them
+    if ((rc = for_all(ctx, [&](tpe_ctx* x, int d) { return tpe1_joint_lsh_gather(x, d, plan.get()); }))) return rc;
+    tpe1_joint_lsh_flags(plan.get(), flags);
+    return for_all(ctx, [&](tpe_ctx* x, int d) { return tpe1_joint_lsh_fold(x, d, plan.get()); });
+}
+
+// (the primary's replica answers these three)
+int tpe_joint_get_group(tpe_ctx* ctx, int32_t slot, int32_t side, double* w, double* mu, double* sigma, int32_t cap,
+                        int32_t* n_components, int32_t* n_dims) {
+    return tpe1_joint_get_group(ctx, slot, side, w, mu, sigma, cap, n_components, n_dims);
+}
+
+int tpe_joint_draw_group(tpe_ctx* ctx, int32_t slot, uint64_t seed, uint32_t round, int64_t n, int64_t cand_offset,
+                         double* values, int32_t* comp) {
+    return tpe1_joint_draw_group(ctx, slot, seed, round, n, cand_offset, values, comp);
+}
+
+int tpe_joint_score_group(tpe_ctx* ctx, int32_t slot, const double* values, int64_t n, double* ll, double* lg) {
+    return tpe1_joint_score_group(ctx, slot, values, n, ll, lg);
+}
+
+int tpe_joint_suggest_group(tpe_ctx* ctx, int32_t slot, uint64_t seed, uint32_t round, int64_t n_candidates,
+                            double* values, int64_t* index, double* ll, double* lg) {
+    if (!ctx) return TPE_ERR_ARG;
+    ctx->joint_shard_mode = 0;
+    ctx->joint_shard_devs = 1;
+    int32_t D[TPE_JOINT_MAX_GROUPS];
+    // (an unset slot, a bad argument: the primary's own refusal)
+    if (ctx->peers.empty() || !values || !index || !ll || !lg || slot < 0 ||
+        tpe1_joint_set_slots(ctx, slot, D) != 1)
+        return tpe1_joint_suggest_group(ctx, slot, seed, round, n_candidates, 0, values, index, ll, lg);
+    return joint_sharded(
+        ctx, 1, n_candidates, 1, D,
+        [&](tpe_ctx* x, const Shard& s, double* v, int64_t* i, double* l, double* g) {
+            return tpe1_joint_suggest_group(x, slot, seed, round, s.n_cand, s.cand_lo, v, i, l, g);
+        },
+        values, index, ll, lg);
+}
+
+int tpe_joint_suggest_batch(tpe_ctx* ctx, uint64_t seed, const uint32_t* rounds, int32_t n_rounds,
+                            int64_t n_candidates, double* values, int64_t* index, double* ll, double* lg) {
+    if (!ctx) return TPE_ERR_ARG;
+    ctx->joint_shard_mode = 0;
+    ctx->joint_shard_devs = 1;
+    int32_t D[TPE_JOINT_MAX_GROUPS];
+    int32_t ns = 0;
+    if (ctx->peers.empty() || !rounds || !values || !index || !ll || !lg || n_rounds < 1 ||
+        (ns = tpe1_joint_set_slots(ctx, -1, D)) < 1)
+        return tpe1_joint_suggest_batch(ctx, seed, rounds, n_rounds, n_candidates, 0, values, index, ll, lg);
+    return joint_sharded(
+        ctx, n_rounds, n_candidates, ns, D,
+        [&](tpe_ctx* x, const Shard& s, double* v, int64_t* i, double* l, double* g) {
+            return tpe1_joint_suggest_batch(x, seed, rounds + s.round_lo, s.n_rounds, s.n_cand, s.cand_lo, v, i, l, g);
+        },
+        values, index, ll, lg);
+}
+
+int tpe_joint_last_shards(const tpe_ctx* ctx, int32_t* mode, int32_t* n_devices) {
+    if (!ctx) return TPE_ERR_ARG;
+    if (mode) *mode = ctx->joint_shard_mode;
+    if (n_devices) *n_devices = ctx->joint_shard_devs;
+    return TPE_OK;
 }
 
 }  // extern "C"

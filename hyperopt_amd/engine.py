@@ -627,6 +627,17 @@ class Engine(object):
             at += D
         return out
 
+    def joint_last_shards(self):
+        """(mode, devices) of the last joint_suggest / joint_suggest_batch
+        (tpe_joint_last_shards): mode 0 -- the primary device ran it alone
+        (always so with one device), 1 -- every device ran a contiguous range
+        of each round's candidates and the winners were merged, 2 -- every
+        device ran a contiguous range of whole rounds; devices: how many ran
+        a shard.  The results are the one-device engine's bit for bit."""
+        mode, nd = ctypes.c_int32(), ctypes.c_int32()
+        self._check(self.lib.tpe_joint_last_shards(self.h, ctypes.byref(mode), ctypes.byref(nd)))
+        return int(mode.value), int(nd.value)
+
     def score(self, label, cand, want_lpdf=True):
         cand = _f64(cand).ravel()
         lb = np.empty(len(cand)) if want_lpdf else None
@@ -869,6 +880,14 @@ def merge_results(parts):
 
 
 _tls = threading.local()
+
+
+def missing_devices(devices):
+    """The ordinals of `devices` this process sees no GPU for (torch's count
+    of the visible devices; no context is created)."""
+    import torch
+    n = torch.cuda.device_count()
+    return [int(d) for d in devices if not 0 <= int(d) < n]
 
 
 def get_engine(device=0, precision='f64', role='main'):

@@ -427,7 +427,13 @@ def suggest(new_ids, domain, trials, seed,
     ("Multivariate TPE"; Engine.joint_suggest).  Every other label
     keeps its independent round, bit for bit.  The call is the independent
     one when the group has fewer than two labels or its labels are not
-    observed in the same trials; more than one device is not supported.
+    observed in the same trials.  With `devices` the joint posteriors are
+    replicated on every device and each joint round is split over them --
+    by candidate ranges from 1024 candidates per device, else by whole
+    rounds of a batch -- with the one-device documents bit for bit
+    (Engine.joint_last_shards tells how the last round ran).  Such a call
+    raises ValueError when a listed device is not on the machine (before it
+    was supported the combination always raised it).
 
     group=True (with multivariate=True) models the labels inside hp.choice
     branches too: every set of at least two such labels that are active in
@@ -465,10 +471,13 @@ def suggest(new_ids, domain, trials, seed,
     default every call returns the documents it always did.
 
     Where the call's posterior is built on the device from the resident
-    history (posterior_builder 'device', or 'auto' past its threshold; one
-    device), the joint groups are built there too, from that build
+    history (posterior_builder 'device', or 'auto' past its threshold), the
+    joint groups are built there too, from that build
     (Engine.build_joint_groups: no gather, no upload, one synchronisation
     for all groups) -- the same mixtures bit for bit, so the same documents.
+    With several devices each one builds its replica; under label shards
+    (the default of `devices` on a resident history) the owners of a group's
+    labels gather their columns and the devices exchange them directly.
     A group in which a label's side holds two equal observations whose
     np.argsort order the univariate build did not need (common for quantized
     labels), one with an out-of-range category and one of categorical labels
@@ -495,7 +504,12 @@ def suggest(new_ids, domain, trials, seed,
     if joint_categorical and not multivariate:
         raise ValueError('joint_categorical=True needs multivariate=True')
     if multivariate and devices and len(list(devices)) > 1:
-        raise ValueError('multivariate=True runs on one device')
+        # every device holds a replica of every joint group and runs a shard
+        # of every joint round: the call needs all of them, startup phase or not
+        missing = _engine.missing_devices(devices)
+        if missing:
+            raise ValueError('multivariate=True with devices=%r: no GPU %r on this machine'
+                             % (list(devices), missing))
     kw = dict(prior_weight=prior_weight, n_startup_jobs=n_startup_jobs,
               n_EI_candidates=n_EI_candidates, gamma=gamma, linear_forgetting=linear_forgetting,
               precision=precision, device=device, posterior_builder=posterior_builder,
@@ -551,10 +565,10 @@ def suggest(new_ids, domain, trials, seed,
                                  round_call=round_call, info=info)
     if res is None:
         res = round_call()
-    # the joint groups are built on the device when this call's univariate
-    # posterior was: from the resident history, on one device
-    jview = view if (JOINT_DEVICE_BUILD and info.get('resident') and
-                     len(getattr(eng, 'devices', (0,))) == 1) else None
+    # the joint groups are built on the device(s) when this call's univariate
+    # posterior was: from the resident history (on several devices, label
+    # shards or not, every device builds its replica of every group)
+    jview = view if (JOINT_DEVICE_BUILD and info.get('resident')) else None
     joint = _joint_rounds(eng, domain, trials, specs, gathered, gamma, prior_weight, seed, ids,
                           n_EI_candidates, group=group, quantized=bool(joint_quantized),
                           categorical=bool(joint_categorical), view=jview) if multivariate else None

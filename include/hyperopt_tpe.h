@@ -416,7 +416,23 @@ int tpe_import_posterior(tpe_ctx *ctx, const void *d_blobs, int64_t blob_bytes, 
  * reserved Philox stream TPE_JOINT_STREAM (cumulative W_k prod_d m_kd / A) and
  * draws dimension d from that component's normal truncated to [low_d, high_d)
  * with the two words of the dimension's own stream.  The joint posterior is
- * separate from the resident per-label posterior; single-device contexts. */
+ * separate from the resident per-label posterior.
+ *
+ * Multi-device contexts (tpe_ctx_create_multi), label-sharded or not, hold
+ * every joint posterior on every device: tpe_joint_set_group and
+ * tpe_joint_clear_groups run on all of them (the fold is deterministic, so
+ * the replicas are the same bits; an error on any device, TPE_ERR_SAMPLE
+ * included, is the call's), and tpe_joint_build_groups builds every replica
+ * from the univariate build.  tpe_joint_get_group, tpe_joint_draw_group and
+ * tpe_joint_score_group answer from the primary device's replica.
+ * tpe_joint_suggest_group and tpe_joint_suggest_batch split over the nd
+ * devices like tpe_suggest: contiguous near-equal candidate ranges when
+ * n_candidates >= 1024 nd (every (slot, round) cell runs on every device over
+ * its range and the shards' winners merge in broadcast_best's order: larger
+ * lpdf_below - lpdf_above, NaN greatest, lowest global index), else
+ * contiguous near-equal ranges of whole rounds when n_rounds >= nd, else the
+ * primary device alone -- the one-device results bit for bit either way;
+ * tpe_last_timing then reports the slowest device. */
 #define TPE_JOINT_STREAM 0x7FFFFFFF
 
 typedef struct {
@@ -488,8 +504,8 @@ typedef struct {
  * NaN or infinite; upper[d] < 0; q[d] > 0 and upper[d] > 0; a categorical
  * dimension with cat_p NULL, a p entry that is not positive and finite, a p
  * whose sum is not within 1e-9 of 1, an observed category that is no integer
- * in [0, upper[d]), or prior_weight not positive and finite; a label-sharded
- * context.  TPE_ERR_VALUE: low >= high; a negative or NaN weight; a sigma that
+ * in [0, upper[d]), or prior_weight not positive and finite.
+ * TPE_ERR_VALUE: low >= high; a negative or NaN weight; a sigma that
  * is not positive and finite.  TPE_ERR_SAMPLE when the box holds none of the
  * below mixture's mass: the slot counts as set, and the draw, suggest and
  * batch calls return it too. */
@@ -533,7 +549,17 @@ int tpe_joint_clear_groups(tpe_ctx *ctx);
  * listed twice; a slot out of range or used twice; a group without a
  * non-categorical label; upper[i] not the label's; more than 128 dimensions
  * (plus quantized dimensions), 4096 below components or TPE_JOINT_MAX_GROUPS
- * groups; a label-sharded context.  TPE_ERR_SAMPLE as tpe_joint_set_group. */
+ * groups.  TPE_ERR_SAMPLE as tpe_joint_set_group.
+ * Multi-device contexts: a replicated one (label shards off) runs the call
+ * on every device, the flags are the primary's.  On a label-sharded one a
+ * group's labels live on different devices: each device gathers the columns
+ * (W, mu, sigma per label) of the labels it owns and synchronises, then
+ * every device copies in the columns it does not own, device to device --
+ * (16 D + 8) K bytes per group and further device, K both sides' components,
+ * nothing through host memory -- interleaves them into the [K][D] arrays and
+ * folds.  The flags are OR-ed over the devices, a flagged group is left
+ * unset on every device, and the validation is the one above against the
+ * owners' records. */
 #define TPE_JOINT_FLAG_TIE 1
 #define TPE_JOINT_FLAG_CATEGORY 2
 #define TPE_JOINT_FLAG_COUNT 4
@@ -568,6 +594,11 @@ int tpe_joint_suggest_group(tpe_ctx *ctx, int32_t slot, uint64_t seed, uint32_t 
  * TPE_ERR_SAMPLE as tpe_joint_suggest_group. */
 int tpe_joint_suggest_batch(tpe_ctx *ctx, uint64_t seed, const uint32_t *rounds, int32_t n_rounds,
                             int64_t n_candidates, double *values, int64_t *index, double *ll, double *lg);
+/* How the last tpe_joint_suggest_group / tpe_joint_suggest_batch call was
+ * split: mode 0 the primary device alone (always so on a one-device context),
+ * 1 candidate shards, 2 round shards; n_devices the devices that ran a shard.
+ * Either pointer may be NULL. */
+int tpe_joint_last_shards(const tpe_ctx *ctx, int32_t *mode, int32_t *n_devices);
 
 /* Score a caller-supplied candidate set for one resident label (the parity
  * entry point: identical candidates in, both lpdf vectors and the winner

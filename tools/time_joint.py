@@ -5,6 +5,7 @@
     python tools/time_joint.py --quantized | --categorical [--legs dense,...] [--reps 20] [--out FILE]
     python tools/time_joint.py --no-timings --quality-quantized | --quality-categorical [--out FILE]
     python tools/time_joint.py --build [--dims 32] [--trials 10000] [--reps 20] [--out FILE]
+    python tools/time_joint.py --devices 0,0 --quantized --legs dense | --build [--out FILE]
 
 On a synthetic history of `--trials` trials over `--dims` dense continuous
 labels (kinds cycled over uniform / loguniform / normal / lognormal):
@@ -55,6 +56,14 @@ posterior.joint_mixture + Engine.set_joint_posterior, and a whole
 tpe.suggest(multivariate=True) call with posterior_builder='device' against
 'host' (build_timings); medians of --reps calls after a warm-up call.
 
+--devices 0,0 (or 0,1 on a machine with two GPUs): the legs of --quantized,
+--categorical and --build on a multi-device engine, Engine([0, 0]) -- the
+joint rounds sharded over the devices (each leg records how:
+Engine.joint_last_shards), the joint build behind a label-sharded univariate
+build; the tpe.suggest legs of --build get devices=[...] too.  Two contexts on
+one GPU show what the fork, the merge and the duplicated launches cost, not a
+speed-up.
+
 Prints one JSON document (and writes it to --out).
 """
 import argparse
@@ -70,6 +79,12 @@ sys.path.insert(0, os.path.dirname(os.path.dirname(os.path.abspath(__file__))))
 
 FP64_VECTOR_PEAK = 78.6e12   # MI355X data sheet, fp64 vector FLOP/s
 KINDS = ('uniform', 'loguniform', 'normal', 'lognormal')
+DEVICES = None   # --devices: the ordinals of a multi-device engine
+
+
+def make_engine():
+    from hyperopt_amd.engine import Engine
+    return Engine(list(DEVICES) if DEVICES else 0, 'f64')
 
 
 def history(n_dims, n_trials, seed=0):
@@ -271,6 +286,8 @@ def _round_shapes(eng, reps):
         res[name] = dict(device_ms=float(np.median(dev)), device_min_ms=float(np.min(dev)),
                          device_max_ms=float(np.max(dev)), wall_ms=float(np.median(wall)),
                          wall_min_ms=float(np.min(wall)), wall_max_ms=float(np.max(wall)))
+        if hasattr(eng, 'joint_last_shards'):   # (mode, devices): how the leg's rounds were split
+            res[name]['shards'] = list(eng.joint_last_shards())
     return res
 
 
@@ -282,8 +299,7 @@ def quantized_timings(reps, legs=('dense', 'quantized'), n_dims=32, n_trials=100
     quantized."""
     from hyperopt_amd import _lib as L
     from hyperopt_amd import posterior as P
-    from hyperopt_amd.engine import Engine
-    eng = Engine(0, 'f64')
+    eng = make_engine()
     out = {}
     for leg in legs:
         group, tids, losses, obs = (history if leg == 'dense' else quantized_history)(n_dims, n_trials)
@@ -320,8 +336,7 @@ def categorical_timings(reps, legs=('dense', 'categorical'), n_dims=32, n_trials
     every fourth label a randint(8) (`mixed`)."""
     from hyperopt_amd import _lib as L
     from hyperopt_amd import posterior as P
-    from hyperopt_amd.engine import Engine
-    eng = Engine(0, 'f64')
+    eng = make_engine()
     out = {}
     for leg in legs:
         group, tids, losses, obs = (history if leg == 'dense' else categorical_history)(n_dims, n_trials)
@@ -359,14 +374,14 @@ def build_timings(reps, n_dims=32, n_trials=10000):
     from hyperopt_amd import _lib as L
     from hyperopt_amd import posterior as P, tpe, workloads
     from hyperopt_amd.base import Domain
-    from hyperopt_amd.engine import Engine
     group, tids, losses, obs = history(n_dims, n_trials)
     splitter = P.Splitter(tids, losses, 0.25)
+    dev_kw = dict(devices=list(DEVICES)) if DEVICES else {}
 
     class Owner(object):
         pass
     view = (tids, losses, n_trials, obs, Owner())
-    eng = Engine(0, 'f64')
+    eng = make_engine()
     P.DeviceHistoryUploader().build(eng, group, view, 0.25, 1.0)
     ids = list(range(n_dims))
     args = [(0, L.TPE_JOINT_STREAM, ids, ids)]
@@ -386,6 +401,9 @@ def build_timings(reps, n_dims=32, n_trials=10000):
             out.append((time.perf_counter() - t) * 1e3)
         return dict(median_ms=float(np.median(out)), min_ms=float(np.min(out)), max_ms=float(np.max(out)), reps=n)
     res = dict(dims=n_dims, trials=n_trials, k_below=len(mix.wb), k_above=len(mix.wa))
+    if DEVICES:   # where the group's labels live: -1 everywhere on a replicated context
+        res['devices'] = list(DEVICES)
+        res['label_devices'] = [int(eng.lib.tpe_label_device(eng.h, i)) for i in ids]
     res['device_build'] = spread(lambda: eng.build_joint_groups(args), reps)
     res['host_build'] = spread(lambda: P.joint_mixture(group, obs, splitter, 1.0), reps)
     res['upload_fold'] = spread(lambda: eng.set_joint_posterior(*mix), reps)
@@ -397,19 +415,29 @@ def build_timings(reps, n_dims=32, n_trials=10000):
     trials = workloads.history_trials(hist)
     space = workloads.hp_space(group)
     domain = Domain(lambda d: 0.0, space)
+
+    def leg_trials():
+        # --devices: every leg starts from trials of its own (a first upload, taken by the warm-up call).
+        # A posterior set from the host (posterior_builder='host') leaves a multi-device context
+        # replicated, and a resident history sharded before it is only re-partitioned by an upload.
+        return workloads.history_trials(hist) if DEVICES else trials
     for builder in ('device', 'host'):
+        trials = leg_trials()
         res['suggest_' + builder] = spread(
-            lambda: tpe.suggest([n_trials], domain, trials, 3, multivariate=True, posterior_builder=builder), reps)
+            lambda: tpe.suggest([n_trials], domain, trials, 3, multivariate=True, posterior_builder=builder, **dev_kw), reps)
     # the device univariate build with the joint groups built on the host: what
     # posterior_builder='device' did before the joint build moved to the device
     tpe.JOINT_DEVICE_BUILD = False
+    trials = leg_trials()
     try:
         res['suggest_device_joint_on_host'] = spread(
-            lambda: tpe.suggest([n_trials], domain, trials, 3, multivariate=True, posterior_builder='device'), reps)
+            lambda: tpe.suggest([n_trials], domain, trials, 3, multivariate=True, posterior_builder='device', **dev_kw),
+            reps)
     finally:
         tpe.JOINT_DEVICE_BUILD = True
+    trials = leg_trials()
     res['suggest_independent_device'] = spread(
-        lambda: tpe.suggest([n_trials], domain, trials, 3, posterior_builder='device'), reps)
+        lambda: tpe.suggest([n_trials], domain, trials, 3, posterior_builder='device', **dev_kw), reps)
     res['suggest_host_over_device'] = res['suggest_host']['median_ms'] / res['suggest_device']['median_ms']
     return res
 
@@ -497,8 +525,13 @@ def main(argv):
     ap.add_argument('--build', action='store_true', help='the device joint build against the host build')
     ap.add_argument('--legs', default=None,
                     help='--groups: loop,batch; --quantized: dense,quantized; --categorical: dense,categorical')
+    ap.add_argument('--devices', default=None, help='ordinals of a multi-device engine, e.g. 0,0 (--quantized, '
+                                                    '--categorical, --build)')
     ap.add_argument('--out')
     a = ap.parse_args(argv)
+    if a.devices:
+        global DEVICES
+        DEVICES = [int(d) for d in a.devices.split(',')]
     res = {}
     if a.groups:
         res['groups'] = groups_timings(a.reps, legs=tuple((a.legs or 'loop,batch').split(',')))
