@@ -68,6 +68,8 @@ TPE_JOINT_MAX_GROUPS = 64
 TPE_JOINT_FLAG_TIE = 1
 TPE_JOINT_FLAG_CATEGORY = 2
 TPE_JOINT_FLAG_COUNT = 4
+TPE_JOINT_BW_NEIGHBOUR = 0
+TPE_JOINT_BW_SCOTT = 1
 
 TPE_OBS_IDENTITY = 0
 TPE_OBS_LOG = 1
@@ -176,6 +178,8 @@ SIGNATURES = {
                                            _P]),
     'tpe_joint_clear_groups': (ctypes.c_int, [_P]),
     'tpe_joint_build_groups': (ctypes.c_int, [_P, _I32, _P, _P, _P, _P, _P, _P, _P, _P, _D, _P]),
+    'tpe_joint_build_groups_bw': (ctypes.c_int, [_P, _I32, _P, _P, _P, _P, _P, _P, _P, _P, _D, _I32, _P]),
+    'tpe_joint_bandwidth_factor': (ctypes.c_double, [_I32, _I32]),
     'tpe_joint_get_group': (ctypes.c_int, [_P, _I32, _I32, _P, _P, _P, _I32, _P, _P]),
     'tpe_joint_draw_group': (ctypes.c_int, [_P, _I32, _U64, _U32, _I64, _I64, _P, _P]),
     'tpe_joint_score_group': (ctypes.c_int, [_P, _I32, _P, _I64, _P, _P]),

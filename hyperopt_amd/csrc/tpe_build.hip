@@ -1381,7 +1381,33 @@ __global__ __launch_bounds__(kUpBlock) void k_build_report(const uint32_t* __res
     for (int32_t i = threadIdx.x; i < n_ties; i += kUpBlock) out[dl_words + 4 + i] = (uint32_t)ties[i];
 }
 
+// The weights of a joint group's side under the Scott-rule bandwidth
+// (posterior.joint_mixture(bandwidth='scott')): w = (prior_weight,
+// linear_forgetting_weights(n, lf)) in trial order, W = w / np.sum(w) -- the
+// ramp and the sum of k_parzen, without its sorted position.  One workgroup
+// per (task, side).
+__global__ __launch_bounds__(kParzenBlock) void k_joint_weights(const JointWTask* __restrict__ tasks, double pw,
+                                                                int32_t lf, double* __restrict__ leaf) {
+#pragma clang fp contract(off)
+    const JointWTask t = tasks[blockIdx.x];
+    const int side = blockIdx.y;
+    const int64_t K = side ? t.Ka : t.Kb, n = K - 1;
+    double* __restrict__ w = t.W + (side ? t.Kb : 0);
+    const LFRamp ramp = lf_ramp(n, lf);
+    for (int64_t j = threadIdx.x; j < K; j += kParzenBlock) w[j] = j == 0 ? pw : lf_weight(j - 1, ramp);
+    const double tot = block_np_sum(w, K, leaf + t.leaf[side]);
+    for (int64_t j = threadIdx.x; j < K; j += kParzenBlock) w[j] = w[j] / tot;
+}
+
 }  // namespace
+
+int tpe_rt::joint_weights_launch(tpe_ctx* ctx, hipStream_t st, const JointWTask* d_tasks, int32_t n_tasks, double pw,
+                                 int32_t lf, double* leaf) {
+    if (n_tasks < 1) return TPE_OK;
+    hipLaunchKernelGGL(k_joint_weights, dim3((unsigned)n_tasks, 2), dim3(kParzenBlock), 0, st, d_tasks, pw, lf, leaf);
+    HIPCHK(ctx, hipGetLastError());
+    return TPE_OK;
+}
 
 int tpe_rt::copy_batch(tpe_ctx* ctx, hipStream_t st, const CopySpec* specs, int n) {
     for (int i0 = 0; i0 < n; i0 += kCopyBatch) {

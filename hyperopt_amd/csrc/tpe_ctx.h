@@ -690,6 +690,20 @@ int bx_prescan(tpe_ctx* ctx, hipStream_t st, bool* queued);
 // when not ready; the subset rebuild beside the expansion index queues it on
 // the aux stream, off the round's path.
 int qc_launch(tpe_ctx* ctx, hipStream_t st);
+// The weights of joint groups under the Scott-rule bandwidth (tpe_joint.hip,
+// TPE_JOINT_BW_SCOTT): per task and side the column W[0 .. K) = w / np.sum(w),
+// w = (prior_weight, linear_forgetting_weights(K - 1, lf)) in trial order --
+// the ramp and the pairwise sum the univariate build restates (tpe_build.hip
+// k_joint_weights, one workgroup per (task, side)).  d_tasks and leaf are
+// device pointers; leaf[side] of a task: its private scratch in `leaf`, K / 56
+// + 1 doubles.
+struct JointWTask {
+    double* W;         // the group's weights: below [Kb], then above [Ka]
+    int64_t leaf[2];
+    int32_t Kb, Ka;
+};
+int joint_weights_launch(tpe_ctx* ctx, hipStream_t st, const JointWTask* d_tasks, int32_t n_tasks, double pw,
+                         int32_t lf, double* leaf);
 }  // namespace tpe_rt
 
 // per-device implementations of the entry points a multi-device context
@@ -758,7 +772,7 @@ TPE_DEV int tpe1_joint_clear_groups(tpe_ctx* ctx);
 TPE_DEV int tpe1_joint_build_groups(tpe_ctx* ctx, int32_t n_groups, const int32_t* slots,
                                     const uint32_t* pick_streams, const int64_t* group_off, const int32_t* labels,
                                     const int32_t* streams, const double* q, const int32_t* upper,
-                                    const double* cat_p, double prior_weight, int32_t* flags);
+                                    const double* cat_p, double prior_weight, int32_t bandwidth, int32_t* flags);
 TPE_DEV int tpe1_joint_get_group(tpe_ctx* ctx, int32_t slot, int32_t side, double* w, double* mu, double* sigma,
                                  int32_t cap, int32_t* n_components, int32_t* n_dims);
 TPE_DEV int tpe1_joint_draw_group(tpe_ctx* ctx, int32_t slot, uint64_t seed, uint32_t round, int64_t n,
@@ -783,7 +797,7 @@ TPE_DEV int tpe1_joint_lsh_check(tpe_ctx* x);
 TPE_DEV int tpe1_joint_lsh_plan(tpe_ctx* ctx, int32_t n_groups, const int32_t* slots, const uint32_t* pick_streams,
                                 const int64_t* group_off, const int32_t* labels, const int32_t* streams,
                                 const double* q, const int32_t* upper, const double* cat_p, double prior_weight,
-                                int32_t* flags, std::shared_ptr<void>* plan);
+                                int32_t bandwidth, int32_t* flags, std::shared_ptr<void>* plan);
 TPE_DEV int tpe1_joint_lsh_gather(tpe_ctx* x, int d, void* plan);
 TPE_DEV void tpe1_joint_lsh_flags(void* plan, int32_t* flags);
 TPE_DEV int tpe1_joint_lsh_fold(tpe_ctx* x, int d, void* plan);

@@ -32,6 +32,10 @@
 //   k_joint_gather                    tpe_joint_build_groups: W, mu, sigma of every
 //                                     group un-permuted out of the resident
 //                                     univariate build (tpe_build.hip), one launch
+//   k_joint_gather_scott              tpe_joint_build_groups_bw, TPE_JOINT_BW_SCOTT: mu
+//                                     un-permuted the same way, one sigma per
+//                                     (side, dimension) from the host's factor; W is
+//                                     k_joint_weights' (tpe_build.hip)
 //   k_joint_interleave                that build under label shards: the slot's
 //                                     [K][D] arrays from per-label columns
 //
@@ -838,12 +842,23 @@ struct JBDim {   // one dimension of one group of a tpe_joint_build_groups call 
     int32_t flags;          // 1: the build holds this label's above order; 2: this dimension supplies W
 };
 
+struct JSDim {   // that dimension under TPE_JOINT_BW_SCOTT (k_joint_gather_scott)
+    double *mu, *sig;       // the slot's arrays
+    double fb, fa;          // the bandwidth factor of the group's below / above side
+    int32_t label, group, d, D, Kb, Ka;
+    int32_t upper;          // > 0: categorical
+    int32_t flags;          // 1: the build holds this label's above order
+};
+
 struct JointGroups {   // a context's slots and the scratch they share (one stream: one user at a time)
     std::unique_ptr<JointState> slot[kJMaxGroups];
     DevBuf<double> vals, ll, lg, aux, res, bres;
     DevBuf<double2> part;
     DevBuf<int32_t> err, comp, berr;
     DevBuf<JBDim> btask;
+    DevBuf<JSDim> stask;                  // the build under TPE_JOINT_BW_SCOTT: its gather's tasks,
+    DevBuf<tpe_rt::JointWTask> wtask;     //   its weight columns
+    DevBuf<double> bleaf;                 //   and their sums' scratch
     DevBuf<double> bcols;   // the build under label shards: the call's columns
     DevBuf<Partial> partials;
     DevBuf<uint32_t> rounds;
@@ -1211,6 +1226,75 @@ __global__ __launch_bounds__(kJBlock) void k_joint_gather(
     put((int64_t)r + 1, w[o + j], v, sigma[o + j]);
 }
 
+// tpe_joint_build_groups_bw, TPE_JOINT_BW_SCOTT: every trial row of dimension
+// d has the sigma clip(f psig_d, psig_d / min(100, 1 + K), psig_d), f = 0.2
+// n^(-1/(D+4)) of the side's n = K - 1 trials (computed on the host:
+// tpe_joint_bandwidth_factor; the product and the quotient are single IEEE
+// operations here), row 0 the prior's psig_d.  No sorted position enters: a
+// thread per (dimension, side, row) stores the below value of its trial or the
+// sorted key of its slot, the latter in the row of the build's rank map -- tied
+// observations get equal rows whichever way the map orders them, so no tie
+// flag.  The univariate w / sigma are not read; W is k_joint_weights'
+// (tpe_build.hip), launched beside this kernel.
+constexpr int32_t kJointLF = 25;   // linear_forgetting_weights(n, 25): posterior.DEFAULT_LF
+
+__global__ __launch_bounds__(kJBlock) void k_joint_gather_scott(
+    const JSDim* __restrict__ tasks, const tpe_label_spec* __restrict__ specs, const int64_t* __restrict__ p_off,
+    const int32_t* __restrict__ counts, const double* __restrict__ below_val, const double* __restrict__ keys,
+    const int32_t* __restrict__ idx, const int64_t* __restrict__ order_off, const int32_t* __restrict__ order,
+    int32_t* __restrict__ flags) {
+#pragma clang fp contract(off)
+    const JSDim t = tasks[blockIdx.y];
+    const int side = blockIdx.z, Ks = side ? t.Ka : t.Kb;
+    const int p = blockIdx.x * kJBlock + threadIdx.x;   // row 0: the prior; above: sorted slot p - 1; else trial p - 1
+    if (p >= Ks) return;
+    const int l = t.label;
+    const int64_t n = counts[2 * l + side];
+    const size_t row0 = side ? (size_t)t.Kb : 0;
+    auto put = [&](int64_t row, double m, double s) {
+        const size_t k = row0 + (size_t)row;
+        t.mu[k * t.D + t.d] = m;
+        t.sig[k * t.D + t.d] = s;
+    };
+    const double pmu = specs[l].prior_mu, psig = specs[l].prior_sigma;
+    if (n != Ks - 1 || (side == 0 && n > tpe_rt::kBuildMaxLF)) {   // not the group's trials: rows that fold, flagged
+        atomicOr(flags + t.group, kJFlagCount);
+        put(p, t.upper > 0 ? 0.0 : pmu, 1.0);
+        return;
+    }
+    const int64_t off = p_off[l];
+    const double* __restrict__ bv = below_val + (size_t)l * tpe_rt::kBuildMaxLF;
+    if (t.upper > 0) {   // the observed category, in observation order on both sides
+        double c = 0.0;
+        if (p > 0) {
+            c = side ? keys[off + p - 1] : bv[p - 1];
+            if (!(c >= 0.0 && c < (double)t.upper && c == floor(c))) {
+                atomicOr(flags + t.group, kJFlagCat);
+                c = 0.0;   // (k_joint_fold indexes the prior with it)
+            }
+        }
+        put(p, c, 1.0);
+        return;
+    }
+    if (p == 0) {
+        put(0, pmu, psig);
+        return;
+    }
+    const double lo = psig / fmin(100.0, 1.0 + (double)Ks);
+    const double s = fmin(fmax((side ? t.fa : t.fb) * psig, lo), psig);   // np.clip (finite terms)
+    if (side == 0) {
+        put(p, bv[p - 1], s);
+        return;
+    }
+    const int64_t q = p - 1;   // sorted slot q: the above list's trial r
+    const int32_t r = (t.flags & 1) ? order[order_off[l] + q] : idx[off + q];
+    if (r < 0 || r >= n) {
+        atomicOr(flags + t.group, kJFlagCount);
+        return;
+    }
+    put((int64_t)r + 1, keys[off + q], s);
+}
+
 struct GInfo {   // one validated group of a tpe_joint_build_groups call
     int32_t D, S, Kb, Ka, ncat;
     bool quant, cat;
@@ -1395,12 +1479,61 @@ void joint_commit(JointState* J, const GInfo& I, uint32_t pick_stream, int32_t f
     J->ready = flag == 0;
 }
 
+// the bandwidth mode of a build call; TPE_JOINT_BW_SCOTT forms W from the prior weight
+int joint_build_mode(tpe_ctx* ctx, int32_t bw, double prior_weight) {
+    if (bw != TPE_JOINT_BW_NEIGHBOUR && bw != TPE_JOINT_BW_SCOTT)
+        return ctx->fail(TPE_ERR_ARG, "tpe_joint_build_groups_bw: bandwidth is TPE_JOINT_BW_NEIGHBOUR or "
+                                      "TPE_JOINT_BW_SCOTT");
+    if (bw == TPE_JOINT_BW_SCOTT && !(prior_weight > 0.0 && prior_weight < __builtin_inf()))
+        return ctx->fail(TPE_ERR_ARG, "TPE_JOINT_BW_SCOTT needs a positive finite prior weight");
+    return TPE_OK;
+}
+
+// the Scott-rule task of dimension dd of group g (label l of this device):
+// column d of D at mu / sig (the factor's D is the group's, whatever the layout)
+JSDim joint_scott_task(const GInfo& I, int dd, double* mu, double* sig, int32_t l, int32_t g, int32_t d, int32_t D,
+                       bool ordered) {
+    return JSDim{mu, sig, tpe_joint_bandwidth_factor(I.Kb - 1, I.D), tpe_joint_bandwidth_factor(I.Ka - 1, I.D),
+                 l, g, d, D, I.Kb, I.Ka, I.hd[dd].upper, ordered ? 1 : 0};
+}
+
+// queue the Scott-rule gather of `tasks` and the weight columns of `wts` (their
+// scratch is placed here) on the context's stream; G->berr holds the flags
+int joint_launch_scott(tpe_ctx* ctx, JointGroups* G, const std::vector<JSDim>& tasks,
+                       std::vector<tpe_rt::JointWTask>& wts, int32_t maxK, double prior_weight) {
+    auto& B = ctx->build;
+    hipStream_t st = ctx->stream;
+    if (!tasks.empty()) {
+        HIPCHK(ctx, G->stask.reserve(tasks.size()));
+        HIPCHK(ctx, hipMemcpyAsync(G->stask.p, tasks.data(), tasks.size() * sizeof(JSDim), hipMemcpyHostToDevice, st));
+        hipLaunchKernelGGL(k_joint_gather_scott,
+                           dim3((unsigned)((maxK + kJBlock - 1) / kJBlock), (unsigned)tasks.size(), 2), dim3(kJBlock),
+                           0, st, G->stask.p, B.specs.p, B.p_off.p, B.counts.p, B.below_val.p, B.keys.p, B.idx.p,
+                           B.order_off.p, B.order.p, G->berr.p);
+        HIPCHK(ctx, hipGetLastError());
+    }
+    if (wts.empty()) return TPE_OK;
+    int64_t leaf = 0;
+    for (auto& w : wts)
+        for (int side = 0; side < 2; ++side) {
+            w.leaf[side] = leaf;
+            leaf += (side ? w.Ka : w.Kb) / 56 + 1;
+        }
+    HIPCHK(ctx, G->bleaf.reserve((size_t)leaf));
+    HIPCHK(ctx, G->wtask.reserve(wts.size()));
+    HIPCHK(ctx, hipMemcpyAsync(G->wtask.p, wts.data(), wts.size() * sizeof(tpe_rt::JointWTask),
+                               hipMemcpyHostToDevice, st));
+    return tpe_rt::joint_weights_launch(ctx, st, G->wtask.p, (int32_t)wts.size(), prior_weight, kJointLF,
+                                        G->bleaf.p);
+}
+
 int joint_build_groups(tpe_ctx* ctx, int32_t n_groups, const int32_t* slots, const uint32_t* pick_streams,
                        const int64_t* group_off, const int32_t* labels, const int32_t* streams, const double* q,
-                       const int32_t* upper, const double* cat_p, double prior_weight, int32_t* flags) {
+                       const int32_t* upper, const double* cat_p, double prior_weight, int32_t bw, int32_t* flags) {
     auto& B = ctx->build;
     int rc = joint_build_args(ctx, n_groups, slots, pick_streams, group_off, labels, streams, flags);
     if (rc) return rc;
+    if ((rc = joint_build_mode(ctx, bw, prior_weight))) return rc;
     if ((rc = joint_build_current(ctx))) return rc;
     std::vector<GInfo> gi;
     int32_t maxK = 1;
@@ -1415,15 +1548,23 @@ int joint_build_groups(tpe_ctx* ctx, int32_t n_groups, const int32_t* slots, con
     HIPCHK(ctx, hipSetDevice(ctx->device));
     JointGroups* G = jgroups(ctx, true);
     hipStream_t st = ctx->stream;
+    const bool scott = bw == TPE_JOINT_BW_SCOTT;
     std::vector<JBDim> tasks;
+    std::vector<JSDim> stasks;              // scott: the gather's tasks and
+    std::vector<tpe_rt::JointWTask> wts;    //   one weight column per group
     for (int32_t g = 0; g < n_groups; ++g) {
         const GInfo& I = gi[g];
         JointState* J = nullptr;
         if ((rc = joint_reserve_slot(ctx, G, slots[g], I, &J))) return rc;
         const int D = I.D;
+        if (scott) wts.push_back(tpe_rt::JointWTask{J->W.p, {0, 0}, I.Kb, I.Ka});
         bool first = true;
         for (int d = 0; d < D; ++d) {
             const int32_t l = labels[group_off[g] + d], C = I.hd[d].upper;
+            if (scott) {
+                stasks.push_back(joint_scott_task(I, d, J->mu.p, J->sig.p, l, g, d, D, B.ord_cur[l] != 0));
+                continue;
+            }
             int32_t fl = B.ord_cur[l] ? 1 : 0;
             if (C == 0 && first) {
                 fl |= 2;
@@ -1433,14 +1574,18 @@ int joint_build_groups(tpe_ctx* ctx, int32_t n_groups, const int32_t* slots, con
         }
     }
     HIPCHK(ctx, G->err.reserve(1));
-    HIPCHK(ctx, G->btask.reserve(tasks.size()));
     HIPCHK(ctx, G->berr.reserve(2 * (size_t)n_groups));   // flags | fold errors, per group
-    HIPCHK(ctx, hipMemcpyAsync(G->btask.p, tasks.data(), tasks.size() * sizeof(JBDim), hipMemcpyHostToDevice, st));
     HIPCHK(ctx, hipMemsetAsync(G->berr.p, 0, 2 * (size_t)n_groups * sizeof(int32_t), st));
-    hipLaunchKernelGGL(k_joint_gather, dim3((unsigned)((maxK + kJBlock - 1) / kJBlock), (unsigned)tasks.size(), 2),
-                       dim3(kJBlock), 0, st, G->btask.p, B.specs.p, B.p_off.p, B.counts.p, B.below_val.p, B.keys.p,
-                       B.idx.p, B.order_off.p, B.order.p, B.mix_off.p, B.w.p, B.sigma.p, G->berr.p);
-    HIPCHK(ctx, hipGetLastError());
+    if (scott) {
+        if ((rc = joint_launch_scott(ctx, G, stasks, wts, maxK, prior_weight))) return rc;
+    } else {
+        HIPCHK(ctx, G->btask.reserve(tasks.size()));
+        HIPCHK(ctx, hipMemcpyAsync(G->btask.p, tasks.data(), tasks.size() * sizeof(JBDim), hipMemcpyHostToDevice, st));
+        hipLaunchKernelGGL(k_joint_gather, dim3((unsigned)((maxK + kJBlock - 1) / kJBlock), (unsigned)tasks.size(), 2),
+                           dim3(kJBlock), 0, st, G->btask.p, B.specs.p, B.p_off.p, B.counts.p, B.below_val.p,
+                           B.keys.p, B.idx.p, B.order_off.p, B.order.p, B.mix_off.p, B.w.p, B.sigma.p, G->berr.p);
+        HIPCHK(ctx, hipGetLastError());
+    }
     for (int32_t g = 0; g < n_groups; ++g)
         if ((rc = joint_fold_group(ctx, G->slot[slots[g]].get(), gi[g], prior_weight, G->berr.p + n_groups + g)))
             return rc;
@@ -1478,6 +1623,7 @@ __global__ __launch_bounds__(kJBlock) void k_joint_interleave(const double* __re
 
 struct JLshPlan {
     int32_t n_groups = 0, maxK = 1;
+    int32_t bw = TPE_JOINT_BW_NEIGHBOUR;
     double prior_weight = 0.0;
     std::vector<int32_t> slots, labels;   // labels: global indices, flat over the groups
     std::vector<uint32_t> picks;
@@ -1507,10 +1653,11 @@ int tpe1_joint_lsh_check(tpe_ctx* x) {
 
 int tpe1_joint_lsh_plan(tpe_ctx* ctx, int32_t n_groups, const int32_t* slots, const uint32_t* pick_streams,
                         const int64_t* group_off, const int32_t* labels, const int32_t* streams, const double* q,
-                        const int32_t* upper, const double* cat_p, double prior_weight, int32_t* flags,
+                        const int32_t* upper, const double* cat_p, double prior_weight, int32_t bw, int32_t* flags,
                         std::shared_ptr<void>* out) {
     int rc = joint_build_args(ctx, n_groups, slots, pick_streams, group_off, labels, streams, flags);
     if (rc) return rc;
+    if ((rc = joint_build_mode(ctx, bw, prior_weight))) return rc;
     const int nd = 1 + (int)ctx->peers.size();
     const int32_t L = ctx->lsh_L;
     for (int d = 0; d < nd; ++d)
@@ -1529,6 +1676,7 @@ int tpe1_joint_lsh_plan(tpe_ctx* ctx, int32_t n_groups, const int32_t* slots, co
     if (rc) return rc;
     P->n_groups = n_groups;
     P->prior_weight = prior_weight;
+    P->bw = bw;
     P->slots.assign(slots, slots + n_groups);
     P->picks.assign(pick_streams, pick_streams + n_groups);
     P->goff.assign(group_off, group_off + n_groups + 1);
@@ -1562,7 +1710,10 @@ int tpe1_joint_lsh_gather(tpe_ctx* x, int d, void* plan) {
     hipStream_t st = x->stream;
     HIPCHK(x, G->bcols.reserve(P.total));
     P.cols[d] = G->bcols.p;
+    const bool scott = P.bw == TPE_JOINT_BW_SCOTT;
     std::vector<JBDim> tasks;
+    std::vector<JSDim> stasks;              // scott: this device's columns, and the weight
+    std::vector<tpe_rt::JointWTask> wts;    //   columns of the groups whose W dimension it owns
     int rc;
     for (int32_t g = 0; g < P.n_groups; ++g) {
         const GInfo& I = P.gi[g];
@@ -1573,14 +1724,24 @@ int tpe1_joint_lsh_gather(tpe_ctx* x, int d, void* plan) {
             const size_t at = (size_t)P.goff[g] + dd;
             if (P.owner[at] != d) continue;
             const int32_t l = P.local[at];
-            const int32_t fl = (B.ord_cur[l] ? 1 : 0) | (dd == P.wdim[g] ? 2 : 0);
             double* mu = G->bcols.p + jcol_mu(P, g, dd);
+            if (scott) {
+                stasks.push_back(joint_scott_task(I, dd, mu, mu + K, l, g, 0, 1, B.ord_cur[l] != 0));
+                if (dd == P.wdim[g]) wts.push_back(tpe_rt::JointWTask{G->bcols.p + P.base[g], {0, 0}, I.Kb, I.Ka});
+                continue;
+            }
+            const int32_t fl = (B.ord_cur[l] ? 1 : 0) | (dd == P.wdim[g] ? 2 : 0);
             tasks.push_back(JBDim{G->bcols.p + P.base[g], mu, mu + K, l, g, 0, 1, I.Kb, I.Ka, I.hd[dd].upper, fl});
         }
     }
     HIPCHK(x, G->err.reserve(1));
     HIPCHK(x, G->berr.reserve(2 * (size_t)P.n_groups));   // flags | fold errors, per group
     HIPCHK(x, hipMemsetAsync(G->berr.p, 0, 2 * (size_t)P.n_groups * sizeof(int32_t), st));
+    if (scott && !stasks.empty()) {
+        if ((rc = joint_launch_scott(x, G, stasks, wts, P.maxK, P.prior_weight))) return rc;
+        HIPCHK(x, hipMemcpyAsync(P.dflags[d].data(), G->berr.p, P.n_groups * sizeof(int32_t), hipMemcpyDeviceToHost,
+                                 st));
+    }
     if (!tasks.empty()) {
         HIPCHK(x, G->btask.reserve(tasks.size()));
         HIPCHK(x, hipMemcpyAsync(G->btask.p, tasks.data(), tasks.size() * sizeof(JBDim), hipMemcpyHostToDevice, st));
@@ -1691,11 +1852,18 @@ int tpe1_joint_clear_groups(tpe_ctx* ctx) {
 
 int tpe1_joint_build_groups(tpe_ctx* ctx, int32_t n_groups, const int32_t* slots, const uint32_t* pick_streams,
                             const int64_t* group_off, const int32_t* labels, const int32_t* streams, const double* q,
-                            const int32_t* upper, const double* cat_p, double prior_weight, int32_t* flags) {
+                            const int32_t* upper, const double* cat_p, double prior_weight, int32_t bandwidth,
+                            int32_t* flags) {
     if (!ctx) return TPE_ERR_ARG;
     TPE_SETTLE(ctx);   // (a deferred rebuild's report: its buffers are read here)
     return joint_build_groups(ctx, n_groups, slots, pick_streams, group_off, labels, streams, q, upper, cat_p,
-                              prior_weight, flags);
+                              prior_weight, bandwidth, flags);
+}
+
+// (host arithmetic only: posterior.joint_bandwidth_factor is the same operations in the same order)
+double tpe_joint_bandwidth_factor(int32_t n, int32_t D) {
+    if (n <= 1) return 0.2;
+    return 0.2 * std::pow((double)n, -1.0 / (double)(D + 4));
 }
 
 int tpe1_joint_get_group(tpe_ctx* ctx, int32_t slot, int32_t side, double* w, double* mu, double* sigma, int32_t cap,

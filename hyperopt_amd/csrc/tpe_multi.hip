@@ -863,16 +863,24 @@ int tpe_joint_clear_groups(tpe_ctx* ctx) {
 int tpe_joint_build_groups(tpe_ctx* ctx, int32_t n_groups, const int32_t* slots, const uint32_t* pick_streams,
                            const int64_t* group_off, const int32_t* labels, const int32_t* streams, const double* q,
                            const int32_t* upper, const double* cat_p, double prior_weight, int32_t* flags) {
+    return tpe_joint_build_groups_bw(ctx, n_groups, slots, pick_streams, group_off, labels, streams, q, upper, cat_p,
+                                     prior_weight, TPE_JOINT_BW_NEIGHBOUR, flags);
+}
+
+int tpe_joint_build_groups_bw(tpe_ctx* ctx, int32_t n_groups, const int32_t* slots, const uint32_t* pick_streams,
+                              const int64_t* group_off, const int32_t* labels, const int32_t* streams,
+                              const double* q, const int32_t* upper, const double* cat_p, double prior_weight,
+                              int32_t bandwidth, int32_t* flags) {
     if (!ctx) return TPE_ERR_ARG;
     const int nd = ndev(ctx);
     if (nd == 1)
         return tpe1_joint_build_groups(ctx, n_groups, slots, pick_streams, group_off, labels, streams, q, upper, cat_p,
-                                       prior_weight, flags);
+                                       prior_weight, bandwidth, flags);
     if (!lsharded(ctx)) {   // replicated: every device holds the whole univariate build
         std::vector<std::vector<int32_t>> fd(nd, std::vector<int32_t>(std::max(n_groups, 1), 0));
         const int rc = for_all(ctx, [&](tpe_ctx* x, int d) {
             return tpe1_joint_build_groups(x, n_groups, slots, pick_streams, group_off, labels, streams, q, upper,
-                                           cat_p, prior_weight, d == 0 ? flags : fd[d].data());
+                                           cat_p, prior_weight, bandwidth, d == 0 ? flags : fd[d].data());
         });
 #ifndef NDEBUG
         if (flags && n_groups > 0 && (rc == TPE_OK || rc == TPE_ERR_SAMPLE))
@@ -886,7 +894,7 @@ int tpe_joint_build_groups(tpe_ctx* ctx, int32_t n_groups, const int32_t* slots,
     if (rc) return rc;
     std::shared_ptr<void> plan;
     if ((rc = tpe1_joint_lsh_plan(ctx, n_groups, slots, pick_streams, group_off, labels, streams, q, upper, cat_p,
-                                  prior_weight, flags, &plan)))
+                                  prior_weight, bandwidth, flags, &plan)))
         return rc;
     // two phases with the host barrier of for_all between them: every
     // device's columns are complete (its stream synchronised) before another

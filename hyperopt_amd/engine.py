@@ -494,7 +494,7 @@ class Engine(object):
         self.joint_slots = {}
         self._check(self.lib.tpe_joint_clear_groups(self.h))
 
-    def build_joint_groups(self, groups, q=None, upper=None, cat_p=None, prior_weight=None):
+    def build_joint_groups(self, groups, q=None, upper=None, cat_p=None, prior_weight=None, bandwidth='neighbour'):
         """Joint groups built on the device from the current build of the
         resident history (tpe_joint_build_groups): groups = [(slot,
         pick_stream, label indices, streams)], the indices those of the
@@ -505,7 +505,15 @@ class Engine(object):
         as there.  The mixtures are posterior.joint_mixture's, bit for bit,
         without its arrays crossing the bus.  Returns the int32 flags, one
         per group: 0 -- the slot is set; else (L.TPE_JOINT_FLAG_TIE |
-        _CATEGORY | _COUNT) the group is left unset for the host build."""
+        _CATEGORY | _COUNT) the group is left unset for the host build.
+        bandwidth: 'neighbour' or 'scott', the rule of joint_mixture's keyword
+        (tpe_joint_build_groups_bw); 'scott' needs prior_weight whatever the
+        labels and never flags a tie."""
+        from .posterior import JOINT_BANDWIDTHS
+        if bandwidth not in JOINT_BANDWIDTHS:
+            raise ValueError('bandwidth must be one of %r' % (JOINT_BANDWIDTHS,))
+        if bandwidth == 'scott' and prior_weight is None:
+            raise ValueError("bandwidth='scott' needs prior_weight")
         groups = [(int(s), int(ps) & 0xFFFFFFFF, [int(l) for l in ls], [int(t) for t in ts])
                   for s, ps, ls, ts in groups]
         n = len(groups)
@@ -539,9 +547,10 @@ class Engine(object):
             if len(cp) != int(np.sum(np.maximum(uf, 0))):
                 raise ValueError('cat_p holds the priors of the categorical dimensions, concatenated')
         flags = np.zeros(max(n, 1), dtype=np.int32)
-        rc = self.lib.tpe_joint_build_groups(self.h, n, _ptr(slots), _ptr(picks), _ptr(off), _ptr(labels),
-                                             _ptr(streams), _ptr(qf), _ptr(uf), _ptr(cp),
-                                             float(prior_weight if prior_weight is not None else 0.0), _ptr(flags))
+        rc = self.lib.tpe_joint_build_groups_bw(self.h, n, _ptr(slots), _ptr(picks), _ptr(off), _ptr(labels),
+                                                _ptr(streams), _ptr(qf), _ptr(uf), _ptr(cp),
+                                                float(prior_weight if prior_weight is not None else 0.0),
+                                                JOINT_BANDWIDTHS.index(bandwidth), _ptr(flags))
         known = self.__dict__.setdefault('joint_slots', {})
         for (slot, _, ls, _), f in zip(groups, flags):
             if 0 <= slot < L.TPE_JOINT_MAX_GROUPS:

@@ -15,6 +15,7 @@ same order, including the default, non-stable np.argsort tie order):
 It is vectorised over the history (no per-trial Python loops).
 """
 import collections
+import math
 import threading
 import time
 import weakref
@@ -271,7 +272,26 @@ def joint_prior(kind, args, quantized=False, categorical=False):
     return JointPrior(log, False, 0.0, 0.0, float(args['mu']), float(args['sigma']), q, 0, None)
 
 
-def joint_mixture(group_specs, obs, splitter, prior_weight, streams=None, quantized=False, categorical=False):
+# the bandwidth rules of a joint group's kernels (joint_mixture)
+JOINT_BANDWIDTHS = ('neighbour', 'scott')
+
+
+def joint_bandwidth_factor(n, D):
+    """0.2 n^(-1/(D+4)), the Scott-rule factor of a side of n trials in a
+    group of D labels (0.2 for n <= 1) -- the operations, in the order, of
+    the library's tpe_joint_bandwidth_factor: the same bits."""
+    if n <= 1:
+        return 0.2
+    return 0.2 * math.pow(float(n), -1.0 / (D + 4))
+
+
+def _trial_weights(n, pw):
+    w = np.concatenate([[pw], linear_forgetting_weights(n, DEFAULT_LF)])
+    return w / w.sum()
+
+
+def joint_mixture(group_specs, obs, splitter, prior_weight, streams=None, quantized=False, categorical=False,
+                  bandwidth='neighbour'):
     """The joint (multivariate) mixtures of a group of labels whose
     observations belong to the same trials, as a JointMixture.
 
@@ -308,11 +328,28 @@ def joint_mixture(group_specs, obs, splitter, prior_weight, streams=None, quanti
     W = w / w.sum() with w = concatenate([prior_weight],
     linear_forgetting_weights(n, 25)) in Splitter.split order -- what every
     continuous label's weights are up to rounding, which is asserted where the
-    group has one."""
+    group has one.
+
+    bandwidth='scott' (default 'neighbour': everything above) takes the
+    sigmas from the number of trials and the dimension instead of the
+    univariate build, whose neighbour gaps are those of a different trial in
+    every dimension of a product kernel: with n trials on the side, K = n + 1
+    and D labels in the group (categorical ones counted), every trial row of
+    a non-categorical dimension d has
+        s_d = clip(f prior_sigma_d, prior_sigma_d / min(100, 1 + K), prior_sigma_d),
+        f = joint_bandwidth_factor(n, D) = 0.2 n^(-1/(D+4))
+    (Optuna's multivariate bandwidth with the reference's lower clip), row 0
+    prior_sigma_d; a quantized kind the same with its unquantized prior; the
+    means and the categorical columns as above; W the all-categorical rule
+    above for every group.  No sorted position enters, so tied observations
+    need no order."""
     from .engine import JOINT_DIM_DTYPE
     group = [(g.label, g.kind, g.args) if hasattr(g, 'kind') else tuple(g) for g in group_specs]
     D = len(group)
     pw = float(prior_weight)
+    if bandwidth not in JOINT_BANDWIDTHS:
+        raise ValueError('bandwidth must be one of %r' % (JOINT_BANDWIDTHS,))
+    scott = bandwidth == 'scott'
     dims = np.zeros(D, dtype=JOINT_DIM_DTYPE)
     sides = [[], []]
     steps, uppers, cat_p = [], [], []
@@ -352,6 +389,13 @@ def joint_mixture(group_specs, obs, splitter, prior_weight, streams=None, quanti
                 o = np.log(np.maximum(o, floor))
             elif pri.log:
                 o = np.log(o)
+            if scott:   # one sigma per (side, dimension); the weights by their rule below
+                n = len(o)
+                s = np.clip(joint_bandwidth_factor(n, D) * pri.sigma, pri.sigma / min(100.0, 1.0 + (n + 1)),
+                            pri.sigma)
+                sides[side].append((None, np.concatenate([[pri.mu], o]),
+                                    np.concatenate([[pri.sigma], np.full(n, s)])))
+                continue
             w, mu, sigma = adaptive_parzen_normal(o, pw, pri.mu, pri.sigma)
             p, where = _parzen_positions(o, pri.mu)
             assert mu[p] == pri.mu and np.array_equal(mu[where], o)
@@ -360,9 +404,8 @@ def joint_mixture(group_specs, obs, splitter, prior_weight, streams=None, quanti
     out = [dims]
     for cols in sides:
         ws = [c[0] for c in cols if c[0] is not None]
-        if len(ws) < len(cols):   # a categorical label: the weights by their rule
-            w = np.concatenate([[pw], linear_forgetting_weights(len(cols[0][1]) - 1, DEFAULT_LF)])
-            ws.append(w / w.sum())
+        if len(ws) < len(cols):   # a categorical label, or every label under 'scott': the weights by their rule
+            ws.append(_trial_weights(len(cols[0][1]) - 1, pw))
         W = ws[0]
         for w in ws[1:]:
             # equal up to the rounding of each label's own normalising sum

@@ -21,7 +21,8 @@
 Extra keyword arguments (not in the reference): `multivariate` (True: the
 unconditional dense continuous labels are modelled jointly, see `suggest`
 (joint_quantized=True: the quantized continuous ones with them,
-joint_categorical=True: the categorical ones too);
+joint_categorical=True: the categorical ones too; joint_bandwidth='scott':
+the joint kernels' sigmas from the number of trials and the dimension);
 with `group=True` also those that share an hp.choice branch, one joint group
 per branch),
 `precision` ('f64'; 'f32'
@@ -303,12 +304,14 @@ def _view_columns(view):
     return out
 
 
-def _joint_device_args(specs, labels, groups, quantized, categorical, prior_weight):
+def _joint_device_args(specs, labels, groups, quantized, categorical, prior_weight, bandwidth='neighbour'):
     """Arguments of Engine.build_joint_groups for [(slot, [label names])]:
     (groups, keywords).  Label indices and streams are positions in the space
     (the resident history holds the labels in that order), slot j's pick
     stream TPE_JOINT_STREAM - j; steps and categorical priors from the same
-    joint_prior the host build asks (it raises what that raises)."""
+    joint_prior the host build asks (it raises what that raises).  A
+    bandwidth other than the default travels as a keyword, with the prior
+    weight its W needs."""
     at = {k: i for i, k in enumerate(labels)}
     args, qs, uppers, cat_ps = [], [], [], []
     for slot, g in groups:
@@ -320,12 +323,15 @@ def _joint_device_args(specs, labels, groups, quantized, categorical, prior_weig
         ps = [p.p for p in pri if p.upper > 0]
         cat_ps.append(np.concatenate(ps) if ps else np.zeros(0))
     # (None where the call's kinds hold no such label: Engine.build_joint_groups' defaults)
-    return args, dict(q=qs if quantized else None, upper=uppers if categorical else None,
-                      cat_p=cat_ps if categorical else None, prior_weight=prior_weight if categorical else None)
+    kw = dict(q=qs if quantized else None, upper=uppers if categorical else None,
+              cat_p=cat_ps if categorical else None, prior_weight=prior_weight if categorical else None)
+    if bandwidth != 'neighbour':
+        kw.update(bandwidth=bandwidth, prior_weight=prior_weight)
+    return args, kw
 
 
 def _joint_rounds(eng, domain, trials, specs, gathered, gamma, prior_weight, seed, ids, n_candidates,
-                  group=False, quantized=False, categorical=False, view=None):
+                  group=False, quantized=False, categorical=False, view=None, bandwidth='neighbour'):
     """One joint round per id and joint group: [label -> value] per id, or
     None when the call falls back to the independent path.  group=False: the
     unconditional group alone (joint_group), slot 0; group=True: every group
@@ -348,7 +354,13 @@ def _joint_rounds(eng, domain, trials, specs, gathered, gamma, prior_weight, see
     (posterior.JOINT_QUANT_KINDS), their values rounded to the label's grid;
     categorical=True: and the categorical kinds (posterior.JOINT_CAT_KINDS; a
     label with a zero prior probability stays out), their values category
-    indices; every group value enters the document through labels.coerce."""
+    indices; every group value enters the document through labels.coerce.
+
+    bandwidth: the rule of the groups' sigmas (posterior.JOINT_BANDWIDTHS),
+    handed to both builders.  Under 'scott' no sorted position enters a
+    mixture, so the device flags no tie: the groups with tied observations
+    (the rule for quantized labels) stay on the device."""
+    bw = {} if bandwidth == 'neighbour' else {'bandwidth': bandwidth}
     kinds = _post.JOINT_KINDS + (_post.JOINT_QUANT_KINDS if quantized else ()) + \
         (_post.JOINT_CAT_KINDS if categorical else ())
     labels = list(specs)
@@ -369,20 +381,20 @@ def _joint_rounds(eng, domain, trials, specs, gathered, gamma, prior_weight, see
                  if view is not None and any(specs[k].kind not in _post.JOINT_CAT_KINDS for k in g)]
     flagged = []
     if on_device:
-        args, kw = _joint_device_args(specs, labels, on_device, quantized, categorical, prior_weight)
+        args, kw = _joint_device_args(specs, labels, on_device, quantized, categorical, prior_weight, bandwidth)
         flags = eng.build_joint_groups(args, **kw)
         flagged = [sg for sg, f in zip(on_device, flags) if f]
     built = [sg for sg in on_device if sg not in flagged]
     on_host = [sg for sg in groups if sg not in built]
-    logger.info('multivariate TPE: %d group(s) built on the device, %d on the host (%d flagged by the device)'
-                % (len(built), len(on_host), len(flagged)))
+    logger.info('multivariate TPE: %d group(s) built on the device, %d on the host (%d flagged by the device), '
+                '%s bandwidth' % (len(built), len(on_host), len(flagged), bandwidth))
     if on_host:
         tids, losses, obs = gathered or _history.gather(domain, trials, labels)
         splitter = _post.Splitter(tids, losses, gamma)
         for slot, g in on_host:
             mix = _post.joint_mixture([specs[k] for k in g], obs, splitter, prior_weight,
                                       streams=[labels.index(k) for k in g], quantized=quantized,
-                                      categorical=categorical)
+                                      categorical=categorical, **bw)
             eng.set_joint_group(slot, _engine.L.TPE_JOINT_STREAM - slot, *mix, prior_weight=prior_weight)
     won = eng.joint_suggest_batch(seed, ids, n_candidates)
     out = [{} for _ in ids]
@@ -400,7 +412,8 @@ def suggest(new_ids, domain, trials, seed,
             gamma=_default_gamma,
             linear_forgetting=_default_linear_forgetting,
             precision='f64', device=0, batch=False, posterior_builder='auto', devices=None,
-            multivariate=False, group=False, joint_quantized=False, joint_categorical=False):
+            multivariate=False, group=False, joint_quantized=False, joint_categorical=False,
+            joint_bandwidth='neighbour'):
     """tpe.py:823-916.  Past the startup phase one document for new_ids[0],
     like the reference; `batch` (not in the reference) asks for one document
     per new_id:
@@ -484,6 +497,20 @@ def suggest(new_ids, domain, trials, seed,
     alone are built on the host as before (_joint_rounds; one logger.info
     line per call names the path).
 
+    joint_bandwidth='scott' (with multivariate=True; default 'neighbour')
+    takes the sigmas of the joint kernels from the number of trials and the
+    dimension -- s_d = clip(0.2 n^(-1/(D+4)) prior_sigma_d, prior_sigma_d /
+    min(100, 2 + n), prior_sigma_d) for every trial of a side of n trials in
+    a group of D labels -- instead of the univariate build's neighbour gaps,
+    which in a product over D dimensions collapse to the lower clip
+    (posterior.joint_mixture, DESIGN.md section 6b, "Bandwidth of joint
+    groups").  It composes with group, joint_quantized, joint_categorical,
+    batch and devices, and both builders give the same documents.  The rule
+    needs no sorted position, so groups with tied observations (quantized
+    labels) are built on the device too; a group of categorical labels alone
+    still goes to the host.  With the default every call returns the
+    documents it always did.
+
     precision='f32' runs the exact fp64 path: a round draws every candidate
     and proves all but ~0.5 % of them out of the race from per-sub-bin score
     bounds before any lpdf is summed, so scoring the rest in fp32 would save
@@ -503,6 +530,10 @@ def suggest(new_ids, domain, trials, seed,
         raise ValueError('joint_quantized=True needs multivariate=True')
     if joint_categorical and not multivariate:
         raise ValueError('joint_categorical=True needs multivariate=True')
+    if joint_bandwidth not in _post.JOINT_BANDWIDTHS:
+        raise ValueError('joint_bandwidth must be one of %r' % (_post.JOINT_BANDWIDTHS,))
+    if joint_bandwidth != 'neighbour' and not multivariate:
+        raise ValueError('joint_bandwidth=%r needs multivariate=True' % (joint_bandwidth,))
     if multivariate and devices and len(list(devices)) > 1:
         # every device holds a replica of every joint group and runs a shard
         # of every joint round: the call needs all of them, startup phase or not
@@ -514,7 +545,7 @@ def suggest(new_ids, domain, trials, seed,
               n_EI_candidates=n_EI_candidates, gamma=gamma, linear_forgetting=linear_forgetting,
               precision=precision, device=device, posterior_builder=posterior_builder,
               devices=devices, multivariate=multivariate, group=group, joint_quantized=joint_quantized,
-              joint_categorical=joint_categorical)
+              joint_categorical=joint_categorical, joint_bandwidth=joint_bandwidth)
     specs = specs_of(domain)
     labels = list(specs)
     # the device-resident history's view of the trials (None when the fast
@@ -571,7 +602,9 @@ def suggest(new_ids, domain, trials, seed,
     jview = view if (JOINT_DEVICE_BUILD and info.get('resident')) else None
     joint = _joint_rounds(eng, domain, trials, specs, gathered, gamma, prior_weight, seed, ids,
                           n_EI_candidates, group=group, quantized=bool(joint_quantized),
-                          categorical=bool(joint_categorical), view=jview) if multivariate else None
+                          categorical=bool(joint_categorical), view=jview,
+                          **({} if joint_bandwidth == 'neighbour' else {'bandwidth': joint_bandwidth})
+                          ) if multivariate else None
     rval = []
     for j, new_id in enumerate(ids):
         values = {s.label: _labels.coerce(s.kind, res[j][i]['value'])

@@ -568,6 +568,40 @@ int tpe_joint_build_groups(tpe_ctx *ctx, int32_t n_groups, const int32_t *slots,
                            const int32_t *labels, const int32_t *streams, const double *q,
                            const int32_t *upper, const double *cat_p, double prior_weight,
                            int32_t *flags /* [n_groups] */);
+/* tpe_joint_build_groups with the bandwidth rule of the groups' kernels;
+ * tpe_joint_build_groups is this call with TPE_JOINT_BW_NEIGHBOUR.
+ *   TPE_JOINT_BW_NEIGHBOUR  the rule above: each trial's sigma in dimension d
+ *                           is the one the univariate build gave it (the gap
+ *                           to its neighbours in the sorted values of label d),
+ *   TPE_JOINT_BW_SCOTT      one sigma per (side, dimension) from the number of
+ *                           trials and the dimension: with n trials on the
+ *                           side, K = n + 1 components and D labels in the
+ *                           group (categorical ones counted),
+ *                             s_d = clip(f psig_d, psig_d / min(100, 1 + K), psig_d),
+ *                             f = tpe_joint_bandwidth_factor(n, D) = 0.2 n^(-1/(D+4)),
+ *                           psig_d the label's prior sigma (tpe_label_spec);
+ *                           row 0 keeps psig_d; categorical rows as above.  W
+ *                           = w / sum(w), w = (prior_weight, the linear-
+ *                           forgetting weights of n trials, lf = 25) in trial
+ *                           order, the sum in numpy's pairwise order; means
+ *                           as above.  prior_weight must be positive and
+ *                           finite whatever the labels (TPE_ERR_ARG).
+ * The Scott rule reads neither the univariate weights and sigmas nor a sorted
+ * position -- two equal observations get equal rows -- so it never raises
+ * TPE_JOINT_FLAG_TIE; _CATEGORY and _COUNT are raised as above.  The factor is
+ * computed on the host (0.2 * pow((double)n, -1.0 / (double)(D + 4)), 0.2 for
+ * n <= 1) and handed to the kernel, so a host build that evaluates the same
+ * expression gets the same bits.  Any other bandwidth: TPE_ERR_ARG.
+ * Multi-device contexts as tpe_joint_build_groups; under label shards the
+ * owner of a group's first non-categorical label forms its W column. */
+#define TPE_JOINT_BW_NEIGHBOUR 0
+#define TPE_JOINT_BW_SCOTT 1
+int tpe_joint_build_groups_bw(tpe_ctx *ctx, int32_t n_groups, const int32_t *slots,
+                              const uint32_t *pick_streams, const int64_t *group_off /* [n_groups + 1] */,
+                              const int32_t *labels, const int32_t *streams, const double *q,
+                              const int32_t *upper, const double *cat_p, double prior_weight,
+                              int32_t bandwidth, int32_t *flags /* [n_groups] */);
+double tpe_joint_bandwidth_factor(int32_t n, int32_t D);
 /* A set slot's unfolded arrays, however it was set (tests, diagnostics): the
  * first min(cap, K) components of side 0 (below) or 1 (above) -- w[k], mu and
  * sigma [k][D] row-major; K and D through n_components and n_dims.  Output

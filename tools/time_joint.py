@@ -4,7 +4,8 @@
     python tools/time_joint.py --groups [--legs loop,batch] [--reps 20] [--out FILE]
     python tools/time_joint.py --quantized | --categorical [--legs dense,...] [--reps 20] [--out FILE]
     python tools/time_joint.py --no-timings --quality-quantized | --quality-categorical [--out FILE]
-    python tools/time_joint.py --build [--dims 32] [--trials 10000] [--reps 20] [--out FILE]
+    python tools/time_joint.py --build [--legs device_build,...] [--dims 32] [--trials 10000] [--reps 20] [--out FILE]
+    python tools/time_joint.py --no-timings --quality-bandwidth [--out FILE]
     python tools/time_joint.py --devices 0,0 --quantized --legs dense | --build [--out FILE]
 
 On a synthetic history of `--trials` trials over `--dims` dense continuous
@@ -54,7 +55,13 @@ joint_categorical=True.  A record, not a gate.
 Engine.build_joint_groups on the resident history against
 posterior.joint_mixture + Engine.set_joint_posterior, and a whole
 tpe.suggest(multivariate=True) call with posterior_builder='device' against
-'host' (build_timings); medians of --reps calls after a warm-up call.
+'host' (build_timings); medians of --reps calls after a warm-up call.  Both
+builders are timed under joint_bandwidth 'neighbour' and 'scott'; --legs
+device_build,device_build_scott times the two device builds alone.
+
+--quality-bandwidth: the three quality objectives above, fmin for 100
+evaluations over seeds 0..9, with joint_bandwidth='neighbour' and 'scott' (and
+the independent call).  A record, not a gate.
 
 --devices 0,0 (or 0,1 on a machine with two GPUs): the legs of --quantized,
 --categorical and --build on a multi-device engine, Engine([0, 0]) -- the
@@ -354,14 +361,20 @@ def categorical_timings(reps, legs=('dense', 'categorical'), n_dims=32, n_trials
     return out
 
 
-def build_timings(reps, n_dims=32, n_trials=10000):
+BUILD_LEGS = ('device_build', 'device_build_scott', 'host_build', 'host_build_scott', 'upload_fold',
+              'host_build_plus_upload', 'suggest')
+
+
+def build_timings(reps, n_dims=32, n_trials=10000, legs=BUILD_LEGS):
     """The joint build on the device against the host's, on the d32 shape,
     medians (and the range) of the wall time over `reps` calls after one
-    warm-up call each:
+    warm-up call each (`legs` selects):
 
     * device_build: Engine.build_joint_groups on the resident history, its
       univariate posterior built once before (gather launch + fold + the
       call's one synchronisation);
+    * device_build_scott / host_build_scott: that call and
+      posterior.joint_mixture with bandwidth='scott';
     * host_build + upload_fold: posterior.joint_mixture, then
       Engine.set_joint_posterior with its arrays -- what the same call costs
       without the device build (the expectation to report against);
@@ -391,6 +404,12 @@ def build_timings(reps, n_dims=32, n_trials=10000):
     eng.set_joint_posterior(*mix)
     won_host = eng.joint_suggest(1, 24, round=5)
     assert np.array_equal(won_dev[0], won_host[0]) and won_dev[1:] == won_host[1:]
+    scott = dict(bandwidth='scott', prior_weight=1.0)
+    assert not eng.build_joint_groups(args, **scott)[0]
+    won_dev = eng.joint_suggest(1, 24, round=5)
+    eng.set_joint_posterior(*P.joint_mixture(group, obs, splitter, 1.0, bandwidth='scott'))
+    won_host = eng.joint_suggest(1, 24, round=5)
+    assert np.array_equal(won_dev[0], won_host[0]) and won_dev[1:] == won_host[1:]
 
     def spread(fn, n):
         fn()
@@ -404,13 +423,22 @@ def build_timings(reps, n_dims=32, n_trials=10000):
     if DEVICES:   # where the group's labels live: -1 everywhere on a replicated context
         res['devices'] = list(DEVICES)
         res['label_devices'] = [int(eng.lib.tpe_label_device(eng.h, i)) for i in ids]
-    res['device_build'] = spread(lambda: eng.build_joint_groups(args), reps)
-    res['host_build'] = spread(lambda: P.joint_mixture(group, obs, splitter, 1.0), reps)
-    res['upload_fold'] = spread(lambda: eng.set_joint_posterior(*mix), reps)
-    res['host_build_plus_upload'] = spread(lambda: eng.set_joint_posterior(*P.joint_mixture(group, obs, splitter, 1.0)),
-                                           reps)
-    res['host_over_device'] = res['host_build_plus_upload']['median_ms'] / res['device_build']['median_ms']
+    timed = (('device_build', lambda: eng.build_joint_groups(args)),
+             ('device_build_scott', lambda: eng.build_joint_groups(args, **scott)),
+             ('host_build', lambda: P.joint_mixture(group, obs, splitter, 1.0)),
+             ('host_build_scott', lambda: P.joint_mixture(group, obs, splitter, 1.0, bandwidth='scott')),
+             ('upload_fold', lambda: eng.set_joint_posterior(*mix)),
+             ('host_build_plus_upload', lambda: eng.set_joint_posterior(*P.joint_mixture(group, obs, splitter, 1.0))))
+    for leg, fn in timed:
+        if leg in legs:
+            res[leg] = spread(fn, reps)
+    if 'host_build_plus_upload' in res and 'device_build' in res:
+        res['host_over_device'] = res['host_build_plus_upload']['median_ms'] / res['device_build']['median_ms']
+    if 'device_build_scott' in res and 'device_build' in res:
+        res['scott_over_neighbour_device'] = res['device_build_scott']['median_ms'] / res['device_build']['median_ms']
     eng.close()
+    if 'suggest' not in legs:
+        return res
     hist = workloads.History(group, tids, losses, obs)
     trials = workloads.history_trials(hist)
     space = workloads.hp_space(group)
@@ -438,8 +466,46 @@ def build_timings(reps, n_dims=32, n_trials=10000):
     trials = leg_trials()
     res['suggest_independent_device'] = spread(
         lambda: tpe.suggest([n_trials], domain, trials, 3, posterior_builder='device', **dev_kw), reps)
+    trials = leg_trials()
+    res['suggest_device_scott'] = spread(
+        lambda: tpe.suggest([n_trials], domain, trials, 3, multivariate=True, posterior_builder='device',
+                            joint_bandwidth='scott', **dev_kw), reps)
     res['suggest_host_over_device'] = res['suggest_host']['median_ms'] / res['suggest_device']['median_ms']
     return res
+
+
+def quality_bandwidth(evals=100, seeds=10):
+    """The three quality objectives above with joint_bandwidth 'neighbour' and
+    'scott' (each with the joint keyword its space needs), and the independent
+    call beside them: the best losses of `seeds` runs and their medians."""
+    import hyperopt_amd as H
+    from hyperopt_amd import hp, tpe
+    centre = (-3.0, 0.0, 3.0)
+    objectives = (
+        ('coupled', '(x-y)^2 + 0.01 (x+y)^2 on uniform(-5,5)^2',
+         {'x': hp.uniform('x', -5, 5), 'y': hp.uniform('y', -5, 5)},
+         lambda d: (d['x'] - d['y']) ** 2 + 0.01 * (d['x'] + d['y']) ** 2, {}),
+        ('quantized', '(x-n)^2 + 0.01 (x+n)^2, x uniform(-5,5), n quniform(-5,5,1)',
+         {'x': hp.uniform('x', -5, 5), 'n': hp.quniform('n', -5, 5, 1)},
+         lambda d: (d['x'] - d['n']) ** 2 + 0.01 * (d['x'] + d['n']) ** 2, dict(joint_quantized=True)),
+        ('categorical', '(x - [-3,0,3][k])^2 + 0.1 k, x uniform(-5,5), k choice(3)',
+         {'x': hp.uniform('x', -5, 5), 'k': hp.choice('k', [0, 1, 2])},
+         lambda d: (d['x'] - centre[d['k']]) ** 2 + 0.1 * d['k'], dict(joint_categorical=True)))
+    out = dict(evals=evals, seeds=seeds)
+    for name, text, space, loss, joint_kw in objectives:
+        rec = out[name] = dict(objective=text)
+        modes = (('independent', {}),
+                 ('neighbour', dict(multivariate=True, joint_bandwidth='neighbour', **joint_kw)),
+                 ('scott', dict(multivariate=True, joint_bandwidth='scott', **joint_kw)))
+        for mode, kw in modes:
+            best = []
+            for seed in range(seeds):
+                trials = H.Trials()
+                H.fmin(loss, space, algo=partial(tpe.suggest, **kw), max_evals=evals, trials=trials,
+                       rstate=np.random.RandomState(seed))
+                best.append(float(min(trials.losses())))
+            rec[mode] = dict(best=best, median=float(np.median(best)))
+    return out
 
 
 def quality_categorical(evals=100, seeds=10):
@@ -523,8 +589,11 @@ def main(argv):
     ap.add_argument('--categorical', action='store_true', help='the dense and categorical d32 legs')
     ap.add_argument('--quality-categorical', action='store_true')
     ap.add_argument('--build', action='store_true', help='the device joint build against the host build')
+    ap.add_argument('--quality-bandwidth', action='store_true',
+                    help="the three quality objectives with joint_bandwidth 'neighbour' and 'scott'")
     ap.add_argument('--legs', default=None,
-                    help='--groups: loop,batch; --quantized: dense,quantized; --categorical: dense,categorical')
+                    help='--groups: loop,batch; --quantized: dense,quantized; --categorical: dense,categorical; '
+                         '--build: ' + ','.join(BUILD_LEGS))
     ap.add_argument('--devices', default=None, help='ordinals of a multi-device engine, e.g. 0,0 (--quantized, '
                                                     '--categorical, --build)')
     ap.add_argument('--out')
@@ -540,7 +609,7 @@ def main(argv):
     elif a.categorical:
         res['categorical'] = categorical_timings(a.reps, legs=tuple((a.legs or 'dense,categorical').split(',')))
     elif a.build:
-        res['build'] = build_timings(a.reps, a.dims, a.trials)
+        res['build'] = build_timings(a.reps, a.dims, a.trials, legs=tuple(a.legs.split(',')) if a.legs else BUILD_LEGS)
     elif not a.no_timings:
         res['timings'] = timings(a.dims, a.trials, a.reps)
     if a.quality:
@@ -549,6 +618,8 @@ def main(argv):
         res['quality_quantized'] = quality_quantized()
     if a.quality_categorical:
         res['quality_categorical'] = quality_categorical()
+    if a.quality_bandwidth:
+        res['quality_bandwidth'] = quality_bandwidth()
     txt = json.dumps(res, indent=1, sort_keys=True)
     print(txt)
     if a.out:
