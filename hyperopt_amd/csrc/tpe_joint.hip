@@ -29,13 +29,13 @@
 //                                     candidates and store every candidate's
 //                                     lpdfs; one workgroup per round slot r
 //                                     reduces its n pairs and draws the winner
-//   k_joint_gather                    tpe_joint_build_groups: W, mu, sigma of every
+//   k_joint_gather<SCOTT>             tpe_joint_build_groups[_bw]: W, mu, sigma of every
 //                                     group un-permuted out of the resident
-//                                     univariate build (tpe_build.hip), one launch
-//   k_joint_gather_scott              tpe_joint_build_groups_bw, TPE_JOINT_BW_SCOTT: mu
-//                                     un-permuted the same way, one sigma per
-//                                     (side, dimension) from the host's factor; W is
-//                                     k_joint_weights' (tpe_build.hip)
+//                                     univariate build (tpe_build.hip), one launch;
+//                                     SCOTT (TPE_JOINT_BW_SCOTT): mu un-permuted the
+//                                     same way, one sigma per (side, dimension) from
+//                                     the host's factor; W is k_joint_weights'
+//                                     (tpe_build.hip)
 //   k_joint_interleave                that build under label shards: the slot's
 //                                     [K][D] arrays from per-label columns
 //
@@ -45,6 +45,16 @@
 //
 // A context holds up to TPE_JOINT_MAX_GROUPS folded posteriors (slots), each
 // with the Philox stream of its component pick; the scratch is shared.
+//
+// A posterior reaches a slot by one sequence, whoever supplies W / mu / sig:
+// joint_layout (a group's checks, JDim records and categorical tables, from
+// its per-dimension description), joint_reserve_slot, joint_upload_layout and
+// the fill, joint_fold_group, one synchronisation, joint_commit.  The fill is the upload
+// of joint_set (tpe_joint_set_group), or the gather of a device build: one
+// plan (JBuildPlan: joint_build_plan) and one driver (joint_build_gather, then
+// joint_build_fold) for one device, for every device of a replicated context,
+// and -- with a column buffer as the tasks' destination and the caller's
+// barrier between the two -- for the devices of a label-sharded one.
 //
 // Arithmetic: component records are recentred and pre-scaled like the dense
 // labels' (tpe_device.h, Comp): (m' = (mu - centre_d) a, a = sqrt(K/2)/s) with
@@ -835,19 +845,12 @@ struct JointState {   // one slot's folded posterior
     }
 };
 
-struct JBDim {   // one dimension of one group of a tpe_joint_build_groups call (k_joint_gather)
-    double *W, *mu, *sig;   // the slot's arrays
+struct JGDim {   // one dimension of one group of a device build (k_joint_gather)
+    double *W, *mu, *sig;   // its destination: column d of D (the slot's arrays, or a column buffer's: 0 of 1)
+    double fb, fa;          // TPE_JOINT_BW_SCOTT: the bandwidth factor of the group's below / above side
     int32_t label, group, d, D, Kb, Ka;
     int32_t upper;          // > 0: categorical
     int32_t flags;          // 1: the build holds this label's above order; 2: this dimension supplies W
-};
-
-struct JSDim {   // that dimension under TPE_JOINT_BW_SCOTT (k_joint_gather_scott)
-    double *mu, *sig;       // the slot's arrays
-    double fb, fa;          // the bandwidth factor of the group's below / above side
-    int32_t label, group, d, D, Kb, Ka;
-    int32_t upper;          // > 0: categorical
-    int32_t flags;          // 1: the build holds this label's above order
 };
 
 struct JointGroups {   // a context's slots and the scratch they share (one stream: one user at a time)
@@ -855,9 +858,8 @@ struct JointGroups {   // a context's slots and the scratch they share (one stre
     DevBuf<double> vals, ll, lg, aux, res, bres;
     DevBuf<double2> part;
     DevBuf<int32_t> err, comp, berr;
-    DevBuf<JBDim> btask;
-    DevBuf<JSDim> stask;                  // the build under TPE_JOINT_BW_SCOTT: its gather's tasks,
-    DevBuf<tpe_rt::JointWTask> wtask;     //   its weight columns
+    DevBuf<JGDim> gtask;                  // a device build: its gather's tasks
+    DevBuf<tpe_rt::JointWTask> wtask;     // under TPE_JOINT_BW_SCOTT: its weight columns
     DevBuf<double> bleaf;                 //   and their sums' scratch
     DevBuf<double> bcols;   // the build under label shards: the call's columns
     DevBuf<Partial> partials;
@@ -980,6 +982,149 @@ int read_err(tpe_ctx* ctx, JointGroups* G) {
     return TPE_OK;
 }
 
+// ------------------------------------------------------ one group's slot ----
+// Every path that puts a posterior into a slot -- the upload and the device
+// builds -- lays the group out (joint_layout), reserves the slot's buffers
+// (joint_reserve_slot), fills W / mu / sig, folds (joint_fold_group) and, after
+// its synchronisation, records the slot (joint_commit).
+struct JDimSpec {   // one dimension of a group as its caller describes it
+    double low, high;   // bounds and their flags as the dimension's JDim holds them
+    double prior_mu;    // the prior's mu: the dimension's centre
+    double q;           // step of a quantized dimension, 0: dense
+    int32_t flags;      // TPE_HAS_LOW | TPE_HAS_HIGH
+    int32_t log;        // 1: a log kind
+    int32_t C;          // categories, 0: not categorical (a categorical dimension's fields above are not read)
+    int32_t stream;     // the label's Philox stream
+};
+
+struct GInfo {   // one validated group: its layout, and its side counts from the caller
+    int32_t D, S, Kb, Ka, ncat;
+    bool quant, cat;
+    std::vector<JDim> hd;
+    std::vector<double> ctab;   // categorical tables: p, its running sums in category order, log p (ncat each)
+};
+
+// the layout of the group of dimensions ds into I (all but Kb, Ka); cat_p: the
+// group's categorical priors, one after the other
+int joint_layout(tpe_ctx* ctx, const std::vector<JDimSpec>& ds, const double* cat_p, double prior_weight,
+                 GInfo& I) {
+    const int D = I.D = (int32_t)ds.size();
+    int S = 0;
+    size_t ncat = 0;   // categories of all categorical dimensions
+    for (const JDimSpec& s : ds) {
+        if (!(s.q >= 0.0 && s.q < __builtin_inf()))
+            return ctx->fail(TPE_ERR_ARG, "a quantization step is finite and not negative (0: dense)");
+        S += s.q > 0.0 ? 2 : 1;
+        if (s.C < 0) return ctx->fail(TPE_ERR_ARG, "upper is the number of categories, 0: not categorical");
+        if (s.C > 0 && s.q > 0.0)
+            return ctx->fail(TPE_ERR_ARG, "a joint dimension is quantized or categorical, not both");
+        ncat += (size_t)s.C;
+    }
+    if (S > kJMaxD)
+        return ctx->fail(TPE_ERR_ARG, "a joint group holds at most " + std::to_string(kJMaxD) +
+                                          " per-candidate values: dimensions plus quantized dimensions");
+    if (ncat > (size_t)INT32_MAX / 4) return ctx->fail(TPE_ERR_ARG, "too many categories");
+    I.S = S;
+    I.quant = S > D;
+    I.cat = ncat > 0;
+    I.ncat = (int32_t)ncat;
+    I.ctab.assign(3 * ncat, 0.0);
+    if (I.cat) {
+        if (!cat_p) return ctx->fail(TPE_ERR_ARG, "null pointer");
+        if (!(prior_weight > 0.0 && prior_weight < __builtin_inf()))
+            return ctx->fail(TPE_ERR_ARG, "a categorical dimension needs a positive finite prior weight");
+    }
+    size_t at = 0;
+    for (const JDimSpec& s : ds) {
+        double run = 0.0;
+        for (int32_t c = 0; c < s.C; ++c, ++at) {
+            const double pc = cat_p[at];
+            if (!(pc > 0.0 && pc < __builtin_inf()))
+                return ctx->fail(TPE_ERR_ARG, "a categorical prior's entries are positive and finite");
+            run += pc;
+            I.ctab[at] = pc;
+            I.ctab[ncat + at] = run;
+            I.ctab[2 * ncat + at] = std::log(pc);
+        }
+        if (s.C > 0 && !(std::fabs(run - 1.0) <= 1e-9)) return ctx->fail(TPE_ERR_ARG, "a categorical prior sums to 1");
+    }
+    I.hd.resize(D);
+    for (int d = 0, vs = 0, coff = 0; d < D; ++d) {   // vs: the dimension's first per-candidate value
+        const JDimSpec& s = ds[d];
+        if (s.C > 0) {
+            I.hd[d] = JDim{0.0, 0.0, 0.0, 0.0, 0.0, 0.0, 0, s.stream, 0, vs, s.C, coff};
+            vs += 1;
+            coff += s.C;
+            continue;
+        }
+        if ((s.flags & 3) == 3 && !(s.low < s.high)) return ctx->fail(TPE_ERR_VALUE, "low >= high");
+        I.hd[d] = JDim{s.low, s.high, s.prior_mu, s.q, s.log ? std::exp(s.low) : 0.0, s.log ? std::exp(s.high) : 0.0,
+                       s.flags, s.stream, s.log, (I.quant || I.cat) ? vs : d, 0, 0};
+        vs += s.q > 0.0 ? 2 : 1;
+    }
+    return TPE_OK;
+}
+
+// the slot of a group about to be filled: unset, its buffers at the group's size
+int joint_reserve_slot(tpe_ctx* ctx, JointGroups* G, int32_t slot, const GInfo& I, JointState** out) {
+    if (!G->slot[slot]) G->slot[slot].reset(new JointState());
+    JointState* J = G->slot[slot].get();
+    J->ready = false;
+    const int D = I.D, Kb = I.Kb, K = I.Kb + I.Ka;
+    HIPCHK(ctx, J->dims.reserve(D));
+    HIPCHK(ctx, J->W.reserve(K));
+    HIPCHK(ctx, J->mu.reserve((size_t)K * D));
+    HIPCHK(ctx, J->sig.reserve((size_t)K * D));
+    HIPCHK(ctx, J->rec.reserve((size_t)K * D));
+    HIPCHK(ctx, J->cst.reserve(K));
+    HIPCHK(ctx, J->P.reserve(K));
+    HIPCHK(ctx, J->logA.reserve(2));
+    HIPCHK(ctx, J->draw.reserve((size_t)Kb * D));
+    HIPCHK(ctx, J->thr.reserve(Kb));
+    if (I.cat) HIPCHK(ctx, J->ctab.reserve(I.ctab.size()));
+    *out = J;
+    return TPE_OK;
+}
+
+// queue the upload of the group's tables and records (the setter's go ahead of
+// its large copies: a small copy behind them waits for them)
+int joint_upload_layout(tpe_ctx* ctx, JointState* J, const GInfo& I) {
+    hipStream_t st = ctx->stream;
+    if (I.cat)
+        HIPCHK(ctx, hipMemcpyAsync(J->ctab.p, I.ctab.data(), I.ctab.size() * sizeof(double), hipMemcpyHostToDevice,
+                                   st));
+    HIPCHK(ctx, hipMemcpyAsync(J->dims.p, I.hd.data(), I.D * sizeof(JDim), hipMemcpyHostToDevice, st));
+    return TPE_OK;
+}
+
+// queue the fold of the slot's W / mu / sig under its uploaded layout; its error word: *err
+int joint_fold_group(tpe_ctx* ctx, JointState* J, const GInfo& I, double prior_weight, int32_t* err) {
+    hipStream_t st = ctx->stream;
+    const int K = I.Kb + I.Ka;
+    hipLaunchKernelGGL(k_joint_fold, dim3((K + kJBlock - 1) / kJBlock), dim3(kJBlock), 0, st, J->dims.p, I.D, I.Kb,
+                       I.Ka, J->W.p, J->mu.p, J->sig.p, J->rec.p, J->cst.p, J->P.p, J->draw.p, prior_weight,
+                       I.cat ? J->ctab.p : nullptr);
+    HIPCHK(ctx, hipGetLastError());
+    hipLaunchKernelGGL(k_joint_fold_sum, dim3(2), dim3(kJBlock), 0, st, J->P.p, I.Kb, I.Ka, J->logA.p, J->thr.p, err);
+    HIPCHK(ctx, hipGetLastError());
+    return TPE_OK;
+}
+
+// the slot's record after the caller's synchronisation (a group the device
+// build flagged stays unset: it is the host build's)
+void joint_commit(JointState* J, const GInfo& I, uint32_t pick_stream, int32_t flag, int32_t fold_err) {
+    J->D = I.D;
+    J->S = I.S;
+    J->quant = I.quant;
+    J->cat = I.cat;
+    J->ncat = I.ncat;
+    J->Kb = I.Kb;
+    J->Ka = I.Ka;
+    J->stream = pick_stream;
+    J->zero = (fold_err & 1) != 0;
+    J->ready = flag == 0;
+}
+
 // upload and fold one slot's posterior (tpe_joint_set_group)
 int joint_set(tpe_ctx* ctx, int32_t slot, uint32_t pick_stream, const tpe_joint_dim* dims, const double* q,
               const int32_t* upper, const double* cat_p, double prior_weight, int32_t n_dims, int32_t n_below,
@@ -994,47 +1139,16 @@ int joint_set(tpe_ctx* ctx, int32_t slot, uint32_t pick_stream, const tpe_joint_
     if (n_below < 1 || n_below > kJMaxBelow || n_above < 1)
         return ctx->fail(TPE_ERR_ARG, "each side needs its prior component (below: at most " +
                                           std::to_string(kJMaxBelow) + ")");
-    const int D = n_dims, Kb = n_below, Ka = n_above, K = Kb + Ka;
-    std::vector<JDim> hd(D);
-    int S = 0;
-    size_t ncat = 0;   // categories of all categorical dimensions
+    const int D = n_dims, Kb = n_below, Ka = n_above;
+    GInfo I{};
+    I.Kb = Kb;
+    I.Ka = Ka;
+    std::vector<JDimSpec> ds(D);
     for (int d = 0; d < D; ++d) {
-        const double qd = q ? q[d] : 0.0;
-        if (!(qd >= 0.0 && qd < __builtin_inf()))
-            return ctx->fail(TPE_ERR_ARG, "a quantization step is finite and not negative (0: dense)");
-        S += qd > 0.0 ? 2 : 1;
+        const tpe_joint_dim& s = dims[d];
         const int32_t C = upper ? upper[d] : 0;
-        if (C < 0) return ctx->fail(TPE_ERR_ARG, "upper is the number of categories, 0: not categorical");
-        if (C > 0 && qd > 0.0) return ctx->fail(TPE_ERR_ARG, "a joint dimension is quantized or categorical, not both");
-        ncat += (size_t)C;
-    }
-    if (S > kJMaxD)
-        return ctx->fail(TPE_ERR_ARG, "a joint group holds at most " + std::to_string(kJMaxD) +
-                                          " per-candidate values: dimensions plus quantized dimensions");
-    const bool quant = S > D, cat = ncat > 0;
-    if (ncat > (size_t)INT32_MAX / 4) return ctx->fail(TPE_ERR_ARG, "too many categories");
-    // categorical tables: p, its running sums in category order, log p
-    std::vector<double> ctab(3 * ncat);
-    if (cat) {
-        if (!cat_p) return ctx->fail(TPE_ERR_ARG, "null pointer");
-        if (!(prior_weight > 0.0 && prior_weight < __builtin_inf()))
-            return ctx->fail(TPE_ERR_ARG, "a categorical dimension needs a positive finite prior weight");
-        size_t at = 0;
-        for (int d = 0; d < D; ++d) {
-            const int32_t C = upper[d];
-            double run = 0.0;
-            for (int32_t c = 0; c < C; ++c, ++at) {
-                const double pc = cat_p[at];
-                if (!(pc > 0.0 && pc < __builtin_inf()))
-                    return ctx->fail(TPE_ERR_ARG, "a categorical prior's entries are positive and finite");
-                run += pc;
-                ctab[at] = pc;
-                ctab[ncat + at] = run;
-                ctab[2 * ncat + at] = std::log(pc);
-            }
-            if (C > 0 && !(std::fabs(run - 1.0) <= 1e-9))
-                return ctx->fail(TPE_ERR_ARG, "a categorical prior sums to 1");
-            if (!C) continue;
+        ds[d] = JDimSpec{s.low, s.high, mub[d], q ? q[d] : 0.0, s.flags, s.kind == TPE_LGMM1 ? 1 : 0, C, s.stream};
+        if (C > 0) {   // (kind, flags and bounds of a categorical dimension are not read)
             for (int side = 0; side < 2; ++side) {   // the observed categories (row 0, the prior's, is ignored)
                 const double* m = side ? mua : mub;
                 for (int k = 1; k < (side ? Ka : Kb); ++k) {
@@ -1043,58 +1157,31 @@ int joint_set(tpe_ctx* ctx, int32_t slot, uint32_t pick_stream, const tpe_joint_
                         return ctx->fail(TPE_ERR_ARG, "an observed category is an integer in [0, upper)");
                 }
             }
-        }
-    }
-    for (int d = 0, slot = 0, coff = 0; d < D; ++d) {
-        const tpe_joint_dim& s = dims[d];
-        if (upper && upper[d] > 0) {   // (kind, flags and bounds of a categorical dimension are not read)
-            hd[d] = JDim{0.0, 0.0, 0.0, 0.0, 0.0, 0.0, 0, s.stream, 0, (quant || cat) ? slot : d, upper[d], coff};
-            slot += 1;
-            coff += upper[d];
             continue;
         }
         if (s.kind != TPE_GMM1 && s.kind != TPE_LGMM1)
             return ctx->fail(TPE_ERR_ARG, "a joint dimension is TPE_GMM1 or TPE_LGMM1");
         if (s.flags & ~(TPE_HAS_LOW | TPE_HAS_HIGH)) return ctx->fail(TPE_ERR_ARG, "joint dimensions are not quantized");
-        if ((s.flags & 3) == 3 && !(s.low < s.high)) return ctx->fail(TPE_ERR_VALUE, "low >= high");
-        const double qd = q ? q[d] : 0.0;
-        const bool lg = s.kind == TPE_LGMM1;
-        hd[d] = JDim{s.low, s.high, mub[d], qd, lg ? std::exp(s.low) : 0.0, lg ? std::exp(s.high) : 0.0,
-                     s.flags, s.stream, lg ? 1 : 0, (quant || cat) ? slot : d, 0, 0};
-        slot += qd > 0.0 ? 2 : 1;
     }
+    int rc = joint_layout(ctx, ds, cat_p, prior_weight, I);
+    if (rc) return rc;
     for (int side = 0; side < 2; ++side) {
         const double *w = side ? wa : wb, *sg = side ? siga : sigb;
         const int Ks = side ? Ka : Kb;
         for (int k = 0; k < Ks; ++k)
             if (!(w[k] >= 0.0)) return ctx->fail(TPE_ERR_VALUE, "negative or NaN weight");
         for (size_t o = 0; o < (size_t)Ks * D; ++o)
-            if (!(cat && upper[o % D] > 0) && !(sg[o] > 0.0 && sg[o] < __builtin_inf()))
+            if (!(I.cat && ds[o % D].C > 0) && !(sg[o] > 0.0 && sg[o] < __builtin_inf()))
                 return ctx->fail(TPE_ERR_VALUE, "sigma must be positive");
     }
     HIPCHK(ctx, hipSetDevice(ctx->device));
     JointGroups* G = jgroups(ctx, true);
-    if (!G->slot[slot]) G->slot[slot].reset(new JointState());
-    JointState* J = G->slot[slot].get();
-    J->ready = false;
-    HIPCHK(ctx, J->dims.reserve(D));
-    HIPCHK(ctx, J->W.reserve(K));
-    HIPCHK(ctx, J->mu.reserve((size_t)K * D));
-    HIPCHK(ctx, J->sig.reserve((size_t)K * D));
-    HIPCHK(ctx, J->rec.reserve((size_t)K * D));
-    HIPCHK(ctx, J->cst.reserve(K));
-    HIPCHK(ctx, J->P.reserve(K));
-    HIPCHK(ctx, J->logA.reserve(2));
-    HIPCHK(ctx, J->draw.reserve((size_t)Kb * D));
-    HIPCHK(ctx, J->thr.reserve(Kb));
+    JointState* J = nullptr;
+    if ((rc = joint_reserve_slot(ctx, G, slot, I, &J))) return rc;
     HIPCHK(ctx, G->err.reserve(1));
     hipStream_t st = ctx->stream;
-    if (cat) {
-        HIPCHK(ctx, J->ctab.reserve(ctab.size()));
-        HIPCHK(ctx, hipMemcpyAsync(J->ctab.p, ctab.data(), ctab.size() * sizeof(double), hipMemcpyHostToDevice, st));
-    }
+    if ((rc = joint_upload_layout(ctx, J, I))) return rc;
     const size_t nb = (size_t)Kb * D, na = (size_t)Ka * D;
-    HIPCHK(ctx, hipMemcpyAsync(J->dims.p, hd.data(), D * sizeof(JDim), hipMemcpyHostToDevice, st));
     HIPCHK(ctx, hipMemcpyAsync(J->W.p, wb, Kb * sizeof(double), hipMemcpyHostToDevice, st));
     HIPCHK(ctx, hipMemcpyAsync(J->W.p + Kb, wa, Ka * sizeof(double), hipMemcpyHostToDevice, st));
     HIPCHK(ctx, hipMemcpyAsync(J->mu.p, mub, nb * sizeof(double), hipMemcpyHostToDevice, st));
@@ -1102,26 +1189,11 @@ int joint_set(tpe_ctx* ctx, int32_t slot, uint32_t pick_stream, const tpe_joint_
     HIPCHK(ctx, hipMemcpyAsync(J->sig.p, sigb, nb * sizeof(double), hipMemcpyHostToDevice, st));
     HIPCHK(ctx, hipMemcpyAsync(J->sig.p + nb, siga, na * sizeof(double), hipMemcpyHostToDevice, st));
     HIPCHK(ctx, hipMemsetAsync(G->err.p, 0, sizeof(int32_t), st));
-    hipLaunchKernelGGL(k_joint_fold, dim3((K + kJBlock - 1) / kJBlock), dim3(kJBlock), 0, st, J->dims.p, D, Kb, Ka,
-                       J->W.p, J->mu.p, J->sig.p, J->rec.p, J->cst.p, J->P.p, J->draw.p, prior_weight,
-                       cat ? J->ctab.p : nullptr);
-    HIPCHK(ctx, hipGetLastError());
-    hipLaunchKernelGGL(k_joint_fold_sum, dim3(2), dim3(kJBlock), 0, st, J->P.p, Kb, Ka, J->logA.p, J->thr.p,
-                       G->err.p);
-    HIPCHK(ctx, hipGetLastError());
+    if ((rc = joint_fold_group(ctx, J, I, prior_weight, G->err.p))) return rc;
     int32_t e = 0;
     HIPCHK(ctx, hipMemcpyAsync(&e, G->err.p, sizeof(int32_t), hipMemcpyDeviceToHost, st));
-    HIPCHK(ctx, hipStreamSynchronize(st));
-    J->D = D;
-    J->S = S;
-    J->quant = quant;
-    J->cat = cat;
-    J->ncat = (int32_t)ncat;
-    J->Kb = Kb;
-    J->Ka = Ka;
-    J->stream = pick_stream;
-    J->zero = (e & 1) != 0;
-    J->ready = true;
+    HIPCHK(ctx, hipStreamSynchronize(st));   // the call's one synchronisation
+    joint_commit(J, I, pick_stream, 0, e);   // (set also when the box holds no below mass: the rounds refuse it)
     if (J->zero) return zero_mass(ctx);
     return TPE_OK;
 }
@@ -1136,23 +1208,40 @@ int joint_set(tpe_ctx* ctx, int32_t slot, uint32_t pick_stream, const tpe_joint_
 // above list's rank beside the sorted keys, or the supplied np.argsort order;
 // the <= kBuildMaxLF below values are ranked in place, as k_parzen ranks them)
 // and stores the slot's (w, mu, sigma) in the trial's row.
+//
+// SCOTT (tpe_joint_build_groups_bw, TPE_JOINT_BW_SCOTT): every trial row of
+// dimension d has the sigma clip(f psig_d, psig_d / min(100, 1 + K), psig_d),
+// f = 0.2 n^(-1/(D+4)) of the side's n = K - 1 trials (computed on the host:
+// tpe_joint_bandwidth_factor; the product and the quotient are single IEEE
+// operations here), row 0 the prior's psig_d.  No sorted position enters: a
+// thread stores the below value of its trial or the sorted key of its slot,
+// the latter in the row of the build's rank map -- tied observations get equal
+// rows whichever way the map orders them, so no tie flag.  The univariate
+// w / sigma are not read (their pointers are null); W is k_joint_weights'
+// (tpe_build.hip), launched beside this kernel.
+//
+// (fp contract(off) covers both instantiations: the neighbour rule's only
+// floating-point operation is the 1.0 / Ks of a flagged row)
 constexpr int32_t kJFlagTie = TPE_JOINT_FLAG_TIE, kJFlagCat = TPE_JOINT_FLAG_CATEGORY,
                   kJFlagCount = TPE_JOINT_FLAG_COUNT;
+constexpr int32_t kJointLF = 25;   // linear_forgetting_weights(n, 25): posterior.DEFAULT_LF
 
+template <bool SCOTT>
 __global__ __launch_bounds__(kJBlock) void k_joint_gather(
-    const JBDim* __restrict__ tasks, const tpe_label_spec* __restrict__ specs, const int64_t* __restrict__ p_off,
+    const JGDim* __restrict__ tasks, const tpe_label_spec* __restrict__ specs, const int64_t* __restrict__ p_off,
     const int32_t* __restrict__ counts, const double* __restrict__ below_val, const double* __restrict__ keys,
     const int32_t* __restrict__ idx, const int64_t* __restrict__ order_off, const int32_t* __restrict__ order,
     const int64_t* __restrict__ mix_off, const double* __restrict__ w, const double* __restrict__ sigma,
     int32_t* __restrict__ flags) {
-    const JBDim t = tasks[blockIdx.y];
+#pragma clang fp contract(off)
+    const JGDim t = tasks[blockIdx.y];
     const int side = blockIdx.z, Ks = side ? t.Ka : t.Kb;
     const int p = blockIdx.x * kJBlock + threadIdx.x;   // row 0: the prior; above: sorted slot p - 1; else trial p - 1
     if (p >= Ks) return;
     const int l = t.label;
     const int64_t n = counts[2 * l + side];
     const size_t row0 = side ? (size_t)t.Kb : 0;
-    auto put = [&](int64_t row, double wv, double m, double s) {
+    auto put = [&](int64_t row, double wv, double m, double s) {   // (SCOTT: no task supplies W)
         const size_t k = row0 + (size_t)row;
         t.mu[k * t.D + t.d] = m;
         t.sig[k * t.D + t.d] = s;
@@ -1178,436 +1267,79 @@ __global__ __launch_bounds__(kJBlock) void k_joint_gather(
         put(p, 0.0, c, 1.0);
         return;
     }
-    const int64_t o = mix_off[2 * l + side];
     const double* __restrict__ sk = keys + off;
-    // the prior's slot: np.searchsorted(sorted, prior_mu), side='left' (k_parzen)
-    int64_t pos = 0;
-    if (n == 1) {
-        pos = pmu < (side ? sk[0] : bv[0]) ? 0 : 1;
-    } else if (side == 0) {
-        for (int64_t j = 0; j < n; ++j) pos += bv[j] < pmu ? 1 : 0;
-    } else {
-        int64_t lo = 0, hi = n;
-        while (lo < hi) {
-            const int64_t mid = (lo + hi) >> 1;
-            if (sk[mid] < pmu) lo = mid + 1; else hi = mid;
-        }
-        pos = lo;
-    }
-    if (p == 0) {
-        put(0, w[o + pos], pmu, sigma[o + pos]);
-        return;
-    }
-    if (side == 0) {   // trial p - 1: its rank among the below values, ties by position
-        const int64_t ti = p - 1;
-        const double v = bv[ti];
-        int64_t rank = 0;
-        bool tie = v != v;
-        for (int64_t j = 0; j < n; ++j) {
-            const double vj = bv[j];
-            rank += (vj < v || (vj == v && j < ti)) ? 1 : 0;
-            tie |= j != ti && vj == v;
-        }
-        if (tie) atomicOr(flags + t.group, kJFlagTie);
-        const int64_t j = rank < pos ? rank : rank + 1;
-        put(p, w[o + j], v, sigma[o + j]);
-        return;
-    }
-    const int64_t q = p - 1;   // sorted slot q: the above list's trial r
-    const double v = sk[q];
     const bool sup = (t.flags & 1) != 0;
-    const int32_t r = sup ? order[order_off[l] + q] : idx[off + q];
-    if (v != v || (!sup && q > 0 && sk[q - 1] == v)) atomicOr(flags + t.group, kJFlagTie);
-    if (r < 0 || r >= n) {
-        atomicOr(flags + t.group, kJFlagCount);
-        return;
-    }
-    const int64_t j = q < pos ? q : q + 1;
-    put((int64_t)r + 1, w[o + j], v, sigma[o + j]);
-}
-
-// tpe_joint_build_groups_bw, TPE_JOINT_BW_SCOTT: every trial row of dimension
-// d has the sigma clip(f psig_d, psig_d / min(100, 1 + K), psig_d), f = 0.2
-// n^(-1/(D+4)) of the side's n = K - 1 trials (computed on the host:
-// tpe_joint_bandwidth_factor; the product and the quotient are single IEEE
-// operations here), row 0 the prior's psig_d.  No sorted position enters: a
-// thread per (dimension, side, row) stores the below value of its trial or the
-// sorted key of its slot, the latter in the row of the build's rank map -- tied
-// observations get equal rows whichever way the map orders them, so no tie
-// flag.  The univariate w / sigma are not read; W is k_joint_weights'
-// (tpe_build.hip), launched beside this kernel.
-constexpr int32_t kJointLF = 25;   // linear_forgetting_weights(n, 25): posterior.DEFAULT_LF
-
-__global__ __launch_bounds__(kJBlock) void k_joint_gather_scott(
-    const JSDim* __restrict__ tasks, const tpe_label_spec* __restrict__ specs, const int64_t* __restrict__ p_off,
-    const int32_t* __restrict__ counts, const double* __restrict__ below_val, const double* __restrict__ keys,
-    const int32_t* __restrict__ idx, const int64_t* __restrict__ order_off, const int32_t* __restrict__ order,
-    int32_t* __restrict__ flags) {
-#pragma clang fp contract(off)
-    const JSDim t = tasks[blockIdx.y];
-    const int side = blockIdx.z, Ks = side ? t.Ka : t.Kb;
-    const int p = blockIdx.x * kJBlock + threadIdx.x;   // row 0: the prior; above: sorted slot p - 1; else trial p - 1
-    if (p >= Ks) return;
-    const int l = t.label;
-    const int64_t n = counts[2 * l + side];
-    const size_t row0 = side ? (size_t)t.Kb : 0;
-    auto put = [&](int64_t row, double m, double s) {
-        const size_t k = row0 + (size_t)row;
-        t.mu[k * t.D + t.d] = m;
-        t.sig[k * t.D + t.d] = s;
+    // the row of sorted slot q of the above list: its trial r, from the supplied order or the build's rank map
+    auto above_row = [&](int64_t q) -> int64_t {
+        const int32_t r = sup ? order[order_off[l] + q] : idx[off + q];
+        if (r < 0 || r >= n) {
+            atomicOr(flags + t.group, kJFlagCount);
+            return -1;
+        }
+        return (int64_t)r + 1;
     };
-    const double pmu = specs[l].prior_mu, psig = specs[l].prior_sigma;
-    if (n != Ks - 1 || (side == 0 && n > tpe_rt::kBuildMaxLF)) {   // not the group's trials: rows that fold, flagged
-        atomicOr(flags + t.group, kJFlagCount);
-        put(p, t.upper > 0 ? 0.0 : pmu, 1.0);
-        return;
-    }
-    const int64_t off = p_off[l];
-    const double* __restrict__ bv = below_val + (size_t)l * tpe_rt::kBuildMaxLF;
-    if (t.upper > 0) {   // the observed category, in observation order on both sides
-        double c = 0.0;
-        if (p > 0) {
-            c = side ? keys[off + p - 1] : bv[p - 1];
-            if (!(c >= 0.0 && c < (double)t.upper && c == floor(c))) {
-                atomicOr(flags + t.group, kJFlagCat);
-                c = 0.0;   // (k_joint_fold indexes the prior with it)
-            }
+    if constexpr (SCOTT) {
+        const double psig = specs[l].prior_sigma;
+        if (p == 0) {
+            put(0, 0.0, pmu, psig);
+            return;
         }
-        put(p, c, 1.0);
-        return;
-    }
-    if (p == 0) {
-        put(0, pmu, psig);
-        return;
-    }
-    const double lo = psig / fmin(100.0, 1.0 + (double)Ks);
-    const double s = fmin(fmax((side ? t.fa : t.fb) * psig, lo), psig);   // np.clip (finite terms)
-    if (side == 0) {
-        put(p, bv[p - 1], s);
-        return;
-    }
-    const int64_t q = p - 1;   // sorted slot q: the above list's trial r
-    const int32_t r = (t.flags & 1) ? order[order_off[l] + q] : idx[off + q];
-    if (r < 0 || r >= n) {
-        atomicOr(flags + t.group, kJFlagCount);
-        return;
-    }
-    put((int64_t)r + 1, keys[off + q], s);
-}
-
-struct GInfo {   // one validated group of a tpe_joint_build_groups call
-    int32_t D, S, Kb, Ka, ncat;
-    bool quant, cat;
-    std::vector<JDim> hd;
-    std::vector<double> ctab;
-};
-
-struct JLabelInfo {   // what the validation reads of a resident label: its spec, its side counts
-    const tpe_label_spec* spec;
-    int32_t nb, na;
-};
-
-int joint_build_args(tpe_ctx* ctx, int32_t n_groups, const int32_t* slots, const uint32_t* pick_streams,
-                     const int64_t* group_off, const int32_t* labels, const int32_t* streams, const int32_t* flags) {
-    if (n_groups < 1 || n_groups > kJMaxGroups)
-        return ctx->fail(TPE_ERR_ARG, "tpe_joint_build_groups: 1 to " + std::to_string(kJMaxGroups) + " groups");
-    if (!slots || !pick_streams || !group_off || !labels || !streams || !flags)
-        return ctx->fail(TPE_ERR_ARG, "null pointer");
-    return TPE_OK;
-}
-
-// the device's univariate build is the current one of its resident history
-int joint_build_current(tpe_ctx* ctx) {
-    auto& B = ctx->build;
-    const int32_t L = B.n_labels;
-    if (!B.hist_ready || !B.built_ok || B.built_gen != B.hist_gen || L < 1 || (int32_t)B.specs_h.size() != L ||
-        (int32_t)ctx->resident.h_labels.size() != L || ctx->resident.n_labels != L ||
-        (int32_t)B.ord_cur.size() != L)
-        return ctx->fail(TPE_ERR_ARG, "tpe_joint_build_groups: no current build of the resident history");
-    return TPE_OK;
-}
-
-// The groups of a build call against the L resident labels, info(l) the
-// record of label l (one device: its own build; label shards: the owner's).
-template <typename Info>
-int joint_plan_groups(tpe_ctx* ctx, int32_t L, Info&& info, int32_t n_groups, const int32_t* slots,
-                      const int64_t* group_off, const int32_t* labels, const int32_t* streams, const double* q,
-                      const int32_t* upper, const double* cat_p, double prior_weight, std::vector<GInfo>& gi,
-                      int32_t* maxK_out) {
-    if (group_off[0] != 0) return ctx->fail(TPE_ERR_ARG, "group offsets start at 0");
-    gi.assign(n_groups, GInfo{});
-    std::vector<uint8_t> seen(L, 0), slot_seen(kJMaxGroups, 0);
-    size_t cat_at = 0;
-    int32_t maxK = 1;
-    for (int32_t g = 0; g < n_groups; ++g) {
-        GInfo& I = gi[g];
-        if (slots[g] < 0 || slots[g] >= kJMaxGroups || slot_seen[slots[g]])
-            return ctx->fail(TPE_ERR_ARG, "joint slots are distinct and in [0, " + std::to_string(kJMaxGroups) + ")");
-        slot_seen[slots[g]] = 1;
-        const int64_t a = group_off[g], b = group_off[g + 1];
-        if (b - a < 1 || b - a > kJMaxD)
-            return ctx->fail(TPE_ERR_ARG, "a joint group holds 1 to " + std::to_string(kJMaxD) + " dimensions");
-        const int D = I.D = (int32_t)(b - a);
-        I.hd.resize(D);
-        int S = 0, first = -1;
-        size_t ncat = 0;
-        for (int d = 0; d < D; ++d) {
-            const int32_t l = labels[a + d];
-            if (l < 0 || l >= L) return ctx->fail(TPE_ERR_ARG, "tpe_joint_build_groups: label index out of range");
-            if (seen[l]) return ctx->fail(TPE_ERR_ARG, "tpe_joint_build_groups: a label is listed twice");
-            seen[l] = 1;
-            const tpe_label_spec& s = *info(l).spec;
-            const double qd = q ? q[a + d] : 0.0;
-            const int32_t C = upper ? upper[a + d] : 0;
-            if (!(qd >= 0.0 && qd < __builtin_inf()))
-                return ctx->fail(TPE_ERR_ARG, "a quantization step is finite and not negative (0: dense)");
-            if (C < 0) return ctx->fail(TPE_ERR_ARG, "upper is the number of categories, 0: not categorical");
-            if (C > 0 && qd > 0.0) return ctx->fail(TPE_ERR_ARG, "a joint dimension is quantized or categorical, not both");
-            if ((C > 0) != (s.kind == TPE_CATEGORICAL) || (C > 0 && C != s.upper))
-                return ctx->fail(TPE_ERR_ARG, "upper must be the resident label's categories, 0 for a continuous label");
-            if (C == 0 && first < 0) first = d;
-            S += qd > 0.0 ? 2 : 1;
-            ncat += (size_t)C;
+        const double lo = psig / fmin(100.0, 1.0 + (double)Ks);
+        const double s = fmin(fmax((side ? t.fa : t.fb) * psig, lo), psig);   // np.clip (finite terms)
+        if (side == 0) {
+            put(p, 0.0, bv[p - 1], s);
+            return;
         }
-        if (first < 0) return ctx->fail(TPE_ERR_ARG, "a device-built joint group needs a label that is not categorical");
-        if (S > kJMaxD)
-            return ctx->fail(TPE_ERR_ARG, "a joint group holds at most " + std::to_string(kJMaxD) +
-                                              " per-candidate values: dimensions plus quantized dimensions");
-        if (ncat > (size_t)INT32_MAX / 4) return ctx->fail(TPE_ERR_ARG, "too many categories");
-        I.S = S;
-        I.quant = S > D;
-        I.cat = ncat > 0;
-        I.ncat = (int32_t)ncat;
-        const JLabelInfo f = info(labels[a + first]);
-        I.Kb = f.nb;
-        I.Ka = f.na;
-        if (I.Kb < 1 || I.Kb > kJMaxBelow || I.Ka < 1)
-            return ctx->fail(TPE_ERR_ARG, "each side needs its prior component (below: at most " +
-                                              std::to_string(kJMaxBelow) + ")");
-        maxK = std::max(maxK, std::max(I.Kb, I.Ka));
-        I.ctab.resize(3 * ncat);
-        if (I.cat) {
-            if (!cat_p) return ctx->fail(TPE_ERR_ARG, "null pointer");
-            if (!(prior_weight > 0.0 && prior_weight < __builtin_inf()))
-                return ctx->fail(TPE_ERR_ARG, "a categorical dimension needs a positive finite prior weight");
-        }
-        size_t at = 0;
-        for (int d = 0, vs = 0, coff = 0; d < D; ++d) {
-            const tpe_label_spec& s = *info(labels[a + d]).spec;
-            const int32_t C = upper ? upper[a + d] : 0;
-            if (C > 0) {   // tables: p, its running sums in category order, log p (joint_set)
-                double run = 0.0;
-                for (int32_t c = 0; c < C; ++c, ++at, ++cat_at) {
-                    const double pc = cat_p[cat_at];
-                    if (!(pc > 0.0 && pc < __builtin_inf()))
-                        return ctx->fail(TPE_ERR_ARG, "a categorical prior's entries are positive and finite");
-                    run += pc;
-                    I.ctab[at] = pc;
-                    I.ctab[ncat + at] = run;
-                    I.ctab[2 * ncat + at] = std::log(pc);
-                }
-                if (!(std::fabs(run - 1.0) <= 1e-9)) return ctx->fail(TPE_ERR_ARG, "a categorical prior sums to 1");
-                I.hd[d] = JDim{0.0, 0.0, 0.0, 0.0, 0.0, 0.0, 0, streams[a + d], 0, vs, C, coff};
-                vs += 1;
-                coff += C;
-                continue;
-            }
-            const int32_t fl = s.flags & (TPE_HAS_LOW | TPE_HAS_HIGH);
-            if (fl == 3 && !(s.low < s.high)) return ctx->fail(TPE_ERR_VALUE, "low >= high");
-            const double qd = q ? q[a + d] : 0.0;
-            const bool lg = s.kind == TPE_LGMM1;
-            // (an unbounded label's low and high are 0, as joint_prior's)
-            const double lo = fl ? s.low : 0.0, hi = fl ? s.high : 0.0;
-            I.hd[d] = JDim{lo, hi, s.prior_mu, qd, lg ? std::exp(lo) : 0.0, lg ? std::exp(hi) : 0.0,
-                           fl, streams[a + d], lg ? 1 : 0, (I.quant || I.cat) ? vs : d, 0, 0};
-            vs += qd > 0.0 ? 2 : 1;
-        }
-    }
-    *maxK_out = maxK;
-    return TPE_OK;
-}
-
-// the slot of a group about to be built: unset, its buffers at the group's size
-int joint_reserve_slot(tpe_ctx* ctx, JointGroups* G, int32_t slot, const GInfo& I, JointState** out) {
-    if (!G->slot[slot]) G->slot[slot].reset(new JointState());
-    JointState* J = G->slot[slot].get();
-    J->ready = false;
-    const int D = I.D, Kb = I.Kb, K = I.Kb + I.Ka;
-    HIPCHK(ctx, J->dims.reserve(D));
-    HIPCHK(ctx, J->W.reserve(K));
-    HIPCHK(ctx, J->mu.reserve((size_t)K * D));
-    HIPCHK(ctx, J->sig.reserve((size_t)K * D));
-    HIPCHK(ctx, J->rec.reserve((size_t)K * D));
-    HIPCHK(ctx, J->cst.reserve(K));
-    HIPCHK(ctx, J->P.reserve(K));
-    HIPCHK(ctx, J->logA.reserve(2));
-    HIPCHK(ctx, J->draw.reserve((size_t)Kb * D));
-    HIPCHK(ctx, J->thr.reserve(Kb));
-    if (I.cat) HIPCHK(ctx, J->ctab.reserve(I.ctab.size()));
-    *out = J;
-    return TPE_OK;
-}
-
-// fold a gathered group as joint_set folds an uploaded one; its error word: *err
-int joint_fold_group(tpe_ctx* ctx, JointState* J, const GInfo& I, double prior_weight, int32_t* err) {
-    hipStream_t st = ctx->stream;
-    if (I.cat)
-        HIPCHK(ctx, hipMemcpyAsync(J->ctab.p, I.ctab.data(), I.ctab.size() * sizeof(double), hipMemcpyHostToDevice,
-                                   st));
-    HIPCHK(ctx, hipMemcpyAsync(J->dims.p, I.hd.data(), I.D * sizeof(JDim), hipMemcpyHostToDevice, st));
-    const int K = I.Kb + I.Ka;
-    hipLaunchKernelGGL(k_joint_fold, dim3((K + kJBlock - 1) / kJBlock), dim3(kJBlock), 0, st, J->dims.p, I.D, I.Kb,
-                       I.Ka, J->W.p, J->mu.p, J->sig.p, J->rec.p, J->cst.p, J->P.p, J->draw.p, prior_weight,
-                       I.cat ? J->ctab.p : nullptr);
-    HIPCHK(ctx, hipGetLastError());
-    hipLaunchKernelGGL(k_joint_fold_sum, dim3(2), dim3(kJBlock), 0, st, J->P.p, I.Kb, I.Ka, J->logA.p, J->thr.p, err);
-    HIPCHK(ctx, hipGetLastError());
-    return TPE_OK;
-}
-
-// the slot's record after the call's synchronisation (a flagged group is the host build's)
-void joint_commit(JointState* J, const GInfo& I, uint32_t pick_stream, int32_t flag, int32_t fold_err) {
-    J->D = I.D;
-    J->S = I.S;
-    J->quant = I.quant;
-    J->cat = I.cat;
-    J->ncat = I.ncat;
-    J->Kb = I.Kb;
-    J->Ka = I.Ka;
-    J->stream = pick_stream;
-    J->zero = (fold_err & 1) != 0;
-    J->ready = flag == 0;
-}
-
-// the bandwidth mode of a build call; TPE_JOINT_BW_SCOTT forms W from the prior weight
-int joint_build_mode(tpe_ctx* ctx, int32_t bw, double prior_weight) {
-    if (bw != TPE_JOINT_BW_NEIGHBOUR && bw != TPE_JOINT_BW_SCOTT)
-        return ctx->fail(TPE_ERR_ARG, "tpe_joint_build_groups_bw: bandwidth is TPE_JOINT_BW_NEIGHBOUR or "
-                                      "TPE_JOINT_BW_SCOTT");
-    if (bw == TPE_JOINT_BW_SCOTT && !(prior_weight > 0.0 && prior_weight < __builtin_inf()))
-        return ctx->fail(TPE_ERR_ARG, "TPE_JOINT_BW_SCOTT needs a positive finite prior weight");
-    return TPE_OK;
-}
-
-// the Scott-rule task of dimension dd of group g (label l of this device):
-// column d of D at mu / sig (the factor's D is the group's, whatever the layout)
-JSDim joint_scott_task(const GInfo& I, int dd, double* mu, double* sig, int32_t l, int32_t g, int32_t d, int32_t D,
-                       bool ordered) {
-    return JSDim{mu, sig, tpe_joint_bandwidth_factor(I.Kb - 1, I.D), tpe_joint_bandwidth_factor(I.Ka - 1, I.D),
-                 l, g, d, D, I.Kb, I.Ka, I.hd[dd].upper, ordered ? 1 : 0};
-}
-
-// queue the Scott-rule gather of `tasks` and the weight columns of `wts` (their
-// scratch is placed here) on the context's stream; G->berr holds the flags
-int joint_launch_scott(tpe_ctx* ctx, JointGroups* G, const std::vector<JSDim>& tasks,
-                       std::vector<tpe_rt::JointWTask>& wts, int32_t maxK, double prior_weight) {
-    auto& B = ctx->build;
-    hipStream_t st = ctx->stream;
-    if (!tasks.empty()) {
-        HIPCHK(ctx, G->stask.reserve(tasks.size()));
-        HIPCHK(ctx, hipMemcpyAsync(G->stask.p, tasks.data(), tasks.size() * sizeof(JSDim), hipMemcpyHostToDevice, st));
-        hipLaunchKernelGGL(k_joint_gather_scott,
-                           dim3((unsigned)((maxK + kJBlock - 1) / kJBlock), (unsigned)tasks.size(), 2), dim3(kJBlock),
-                           0, st, G->stask.p, B.specs.p, B.p_off.p, B.counts.p, B.below_val.p, B.keys.p, B.idx.p,
-                           B.order_off.p, B.order.p, G->berr.p);
-        HIPCHK(ctx, hipGetLastError());
-    }
-    if (wts.empty()) return TPE_OK;
-    int64_t leaf = 0;
-    for (auto& w : wts)
-        for (int side = 0; side < 2; ++side) {
-            w.leaf[side] = leaf;
-            leaf += (side ? w.Ka : w.Kb) / 56 + 1;
-        }
-    HIPCHK(ctx, G->bleaf.reserve((size_t)leaf));
-    HIPCHK(ctx, G->wtask.reserve(wts.size()));
-    HIPCHK(ctx, hipMemcpyAsync(G->wtask.p, wts.data(), wts.size() * sizeof(tpe_rt::JointWTask),
-                               hipMemcpyHostToDevice, st));
-    return tpe_rt::joint_weights_launch(ctx, st, G->wtask.p, (int32_t)wts.size(), prior_weight, kJointLF,
-                                        G->bleaf.p);
-}
-
-int joint_build_groups(tpe_ctx* ctx, int32_t n_groups, const int32_t* slots, const uint32_t* pick_streams,
-                       const int64_t* group_off, const int32_t* labels, const int32_t* streams, const double* q,
-                       const int32_t* upper, const double* cat_p, double prior_weight, int32_t bw, int32_t* flags) {
-    auto& B = ctx->build;
-    int rc = joint_build_args(ctx, n_groups, slots, pick_streams, group_off, labels, streams, flags);
-    if (rc) return rc;
-    if ((rc = joint_build_mode(ctx, bw, prior_weight))) return rc;
-    if ((rc = joint_build_current(ctx))) return rc;
-    std::vector<GInfo> gi;
-    int32_t maxK = 1;
-    rc = joint_plan_groups(
-        ctx, B.n_labels,
-        [&](int32_t l) {
-            const DLabel& f = ctx->resident.h_labels[l];
-            return JLabelInfo{&B.specs_h[l], f.nb, f.na};
-        },
-        n_groups, slots, group_off, labels, streams, q, upper, cat_p, prior_weight, gi, &maxK);
-    if (rc) return rc;
-    HIPCHK(ctx, hipSetDevice(ctx->device));
-    JointGroups* G = jgroups(ctx, true);
-    hipStream_t st = ctx->stream;
-    const bool scott = bw == TPE_JOINT_BW_SCOTT;
-    std::vector<JBDim> tasks;
-    std::vector<JSDim> stasks;              // scott: the gather's tasks and
-    std::vector<tpe_rt::JointWTask> wts;    //   one weight column per group
-    for (int32_t g = 0; g < n_groups; ++g) {
-        const GInfo& I = gi[g];
-        JointState* J = nullptr;
-        if ((rc = joint_reserve_slot(ctx, G, slots[g], I, &J))) return rc;
-        const int D = I.D;
-        if (scott) wts.push_back(tpe_rt::JointWTask{J->W.p, {0, 0}, I.Kb, I.Ka});
-        bool first = true;
-        for (int d = 0; d < D; ++d) {
-            const int32_t l = labels[group_off[g] + d], C = I.hd[d].upper;
-            if (scott) {
-                stasks.push_back(joint_scott_task(I, d, J->mu.p, J->sig.p, l, g, d, D, B.ord_cur[l] != 0));
-                continue;
-            }
-            int32_t fl = B.ord_cur[l] ? 1 : 0;
-            if (C == 0 && first) {
-                fl |= 2;
-                first = false;
-            }
-            tasks.push_back(JBDim{J->W.p, J->mu.p, J->sig.p, l, g, d, D, I.Kb, I.Ka, C, fl});
-        }
-    }
-    HIPCHK(ctx, G->err.reserve(1));
-    HIPCHK(ctx, G->berr.reserve(2 * (size_t)n_groups));   // flags | fold errors, per group
-    HIPCHK(ctx, hipMemsetAsync(G->berr.p, 0, 2 * (size_t)n_groups * sizeof(int32_t), st));
-    if (scott) {
-        if ((rc = joint_launch_scott(ctx, G, stasks, wts, maxK, prior_weight))) return rc;
+        const int64_t row = above_row(p - 1);
+        if (row >= 0) put(row, 0.0, sk[p - 1], s);
     } else {
-        HIPCHK(ctx, G->btask.reserve(tasks.size()));
-        HIPCHK(ctx, hipMemcpyAsync(G->btask.p, tasks.data(), tasks.size() * sizeof(JBDim), hipMemcpyHostToDevice, st));
-        hipLaunchKernelGGL(k_joint_gather, dim3((unsigned)((maxK + kJBlock - 1) / kJBlock), (unsigned)tasks.size(), 2),
-                           dim3(kJBlock), 0, st, G->btask.p, B.specs.p, B.p_off.p, B.counts.p, B.below_val.p,
-                           B.keys.p, B.idx.p, B.order_off.p, B.order.p, B.mix_off.p, B.w.p, B.sigma.p, G->berr.p);
-        HIPCHK(ctx, hipGetLastError());
+        const int64_t o = mix_off[2 * l + side];
+        // the prior's slot: np.searchsorted(sorted, prior_mu), side='left' (k_parzen)
+        int64_t pos = 0;
+        if (n == 1) {
+            pos = pmu < (side ? sk[0] : bv[0]) ? 0 : 1;
+        } else if (side == 0) {
+            for (int64_t j = 0; j < n; ++j) pos += bv[j] < pmu ? 1 : 0;
+        } else {
+            int64_t lo = 0, hi = n;
+            while (lo < hi) {
+                const int64_t mid = (lo + hi) >> 1;
+                if (sk[mid] < pmu) lo = mid + 1; else hi = mid;
+            }
+            pos = lo;
+        }
+        if (p == 0) {
+            put(0, w[o + pos], pmu, sigma[o + pos]);
+            return;
+        }
+        if (side == 0) {   // trial p - 1: its rank among the below values, ties by position
+            const int64_t ti = p - 1;
+            const double v = bv[ti];
+            int64_t rank = 0;
+            bool tie = v != v;
+            for (int64_t j = 0; j < n; ++j) {
+                const double vj = bv[j];
+                rank += (vj < v || (vj == v && j < ti)) ? 1 : 0;
+                tie |= j != ti && vj == v;
+            }
+            if (tie) atomicOr(flags + t.group, kJFlagTie);
+            const int64_t j = rank < pos ? rank : rank + 1;
+            put(p, w[o + j], v, sigma[o + j]);
+            return;
+        }
+        const int64_t q = p - 1;   // sorted slot q
+        const double v = sk[q];
+        if (v != v || (!sup && q > 0 && sk[q - 1] == v)) atomicOr(flags + t.group, kJFlagTie);
+        const int64_t row = above_row(q);
+        const int64_t j = q < pos ? q : q + 1;
+        if (row >= 0) put(row, w[o + j], v, sigma[o + j]);
     }
-    for (int32_t g = 0; g < n_groups; ++g)
-        if ((rc = joint_fold_group(ctx, G->slot[slots[g]].get(), gi[g], prior_weight, G->berr.p + n_groups + g)))
-            return rc;
-    std::vector<int32_t> eh(2 * (size_t)n_groups);
-    HIPCHK(ctx, hipMemcpyAsync(eh.data(), G->berr.p, eh.size() * sizeof(int32_t), hipMemcpyDeviceToHost, st));
-    HIPCHK(ctx, hipStreamSynchronize(st));   // the call's one synchronisation
-    bool zero = false;
-    for (int32_t g = 0; g < n_groups; ++g) {
-        JointState* J = G->slot[slots[g]].get();
-        flags[g] = eh[g];
-        joint_commit(J, gi[g], pick_streams[g], eh[g], eh[n_groups + g]);
-        zero |= J->ready && J->zero;
-    }
-    if (zero) return zero_mass(ctx);
-    return TPE_OK;
 }
 
-// ------------------------------------------ the build under label shards ----
-// A group's labels live on different devices of a label-sharded context.  The
-// columns of a call -- per group W [K], then per dimension mu [K] and sig [K],
-// K = Kb + Ka -- have the same place in every device's column buffer: the
-// owner of a label gathers its columns (k_joint_gather on a one-dimension
+// The build under label shards: a group's labels live on different devices.
+// The columns of a call -- per group W [K], then per dimension mu [K] and
+// sig [K], K = Kb + Ka -- have the same place in every device's column buffer:
+// the owner of a label gathers its columns (k_joint_gather on a one-dimension
 // task), every device copies in the columns it does not own, device to
 // device, and k_joint_interleave writes the slot's [K][D] arrays from them.
 __global__ __launch_bounds__(kJBlock) void k_joint_interleave(const double* __restrict__ cols, int32_t D, int32_t K,
@@ -1621,160 +1353,236 @@ __global__ __launch_bounds__(kJBlock) void k_joint_interleave(const double* __re
     if (d == 0) W[k] = cols[k];
 }
 
-struct JLshPlan {
+// The plan of a device build call.  One device (and each device of a
+// replicated context) owns every dimension, and a task's destination is the
+// slot's own [K][D] arrays: one phase, one synchronisation.  Under label
+// shards a device owns the dimensions whose labels it holds and a task's
+// destination is its column buffer: the gather phase on every device, the
+// caller's barrier, then the fold phase.
+struct JBuildPlan {
+    bool sharded = false;
     int32_t n_groups = 0, maxK = 1;
     int32_t bw = TPE_JOINT_BW_NEIGHBOUR;
     double prior_weight = 0.0;
-    std::vector<int32_t> slots, labels;   // labels: global indices, flat over the groups
+    std::vector<int32_t> slots;
     std::vector<uint32_t> picks;
     std::vector<int64_t> goff;
     std::vector<GInfo> gi;
-    std::vector<int32_t> owner, local;    // per flat label: its device and its index there
+    std::vector<int32_t> owner, local;    // per dimension, flat over the groups: its label's device and index there
     std::vector<int32_t> wdim;            // per group: the dimension that supplies W
+    std::vector<int32_t> flags;           // per group: one device, read back with the fold errors; label shards,
+                                          //   the OR over the devices (between the phases)
+    // label shards only
     std::vector<size_t> base;             // per group: its first column in the buffer (doubles)
     size_t total = 0;
     std::vector<int> device;              // per context: its HIP ordinal
     std::vector<double*> cols;            // per context: its column buffer (set by the gather phase)
     std::vector<std::vector<int32_t>> dflags;   // per context: the flags its gather raised
-    std::vector<int32_t> flags;           // OR over the contexts (between the phases)
 };
 
 tpe_ctx* jdev(tpe_ctx* c, int d) { return d == 0 ? c : c->peers[d - 1]; }
 
-size_t jcol_mu(const JLshPlan& P, int32_t g, int d) {
+size_t jcol_mu(const JBuildPlan& P, int32_t g, int d) {
     return P.base[g] + (size_t)(P.gi[g].Kb + P.gi[g].Ka) * (1 + 2 * (size_t)d);
 }
-}  // namespace
 
-int tpe1_joint_lsh_check(tpe_ctx* x) {
-    TPE_SETTLE(x);   // (a deferred rebuild's report: its buffers are read here)
-    return joint_build_current(x);
-}
-
-int tpe1_joint_lsh_plan(tpe_ctx* ctx, int32_t n_groups, const int32_t* slots, const uint32_t* pick_streams,
-                        const int64_t* group_off, const int32_t* labels, const int32_t* streams, const double* q,
-                        const int32_t* upper, const double* cat_p, double prior_weight, int32_t bw, int32_t* flags,
-                        std::shared_ptr<void>* out) {
-    int rc = joint_build_args(ctx, n_groups, slots, pick_streams, group_off, labels, streams, flags);
-    if (rc) return rc;
-    if ((rc = joint_build_mode(ctx, bw, prior_weight))) return rc;
-    const int nd = 1 + (int)ctx->peers.size();
-    const int32_t L = ctx->lsh_L;
-    for (int d = 0; d < nd; ++d)
-        if (jdev(ctx, d)->build.n_labels != (int32_t)ctx->lsh_ids[d].size())
-            return ctx->fail(TPE_ERR_ARG, "tpe_joint_build_groups: no current build of the resident history");
-    auto P = std::make_shared<JLshPlan>();
-    rc = joint_plan_groups(
-        ctx, L,
-        [&](int32_t l) {
-            tpe_ctx* x = jdev(ctx, ctx->lsh_dev[l]);
-            const int32_t j = ctx->lsh_local[l];
-            const DLabel& f = x->resident.h_labels[j];
-            return JLabelInfo{&x->build.specs_h[j], f.nb, f.na};
-        },
-        n_groups, slots, group_off, labels, streams, q, upper, cat_p, prior_weight, P->gi, &P->maxK);
-    if (rc) return rc;
-    P->n_groups = n_groups;
-    P->prior_weight = prior_weight;
-    P->bw = bw;
-    P->slots.assign(slots, slots + n_groups);
-    P->picks.assign(pick_streams, pick_streams + n_groups);
-    P->goff.assign(group_off, group_off + n_groups + 1);
-    P->labels.assign(labels, labels + group_off[n_groups]);
-    for (int32_t l : P->labels) {
-        P->owner.push_back(ctx->lsh_dev[l]);
-        P->local.push_back(ctx->lsh_local[l]);
-    }
-    for (int32_t g = 0; g < n_groups; ++g) {
-        const GInfo& I = P->gi[g];
-        int w = 0;
-        while (I.hd[w].upper > 0) ++w;   // (validated: a group holds a label that is not categorical)
-        P->wdim.push_back(w);
-        P->base.push_back(P->total);
-        P->total += (size_t)(I.Kb + I.Ka) * (1 + 2 * (size_t)I.D);
-    }
-    for (int d = 0; d < nd; ++d) P->device.push_back(jdev(ctx, d)->device);
-    P->cols.assign(nd, nullptr);
-    P->dflags.assign(nd, std::vector<int32_t>(n_groups, 0));
-    P->flags.assign(n_groups, 0);
-    *out = std::static_pointer_cast<void>(P);
+// the device's univariate build is the current one of its resident history
+int joint_build_current(tpe_ctx* ctx) {
+    auto& B = ctx->build;
+    const int32_t L = B.n_labels;
+    if (!B.hist_ready || !B.built_ok || B.built_gen != B.hist_gen || L < 1 || (int32_t)B.specs_h.size() != L ||
+        (int32_t)ctx->resident.h_labels.size() != L || ctx->resident.n_labels != L ||
+        (int32_t)B.ord_cur.size() != L)
+        return ctx->fail(TPE_ERR_ARG, "tpe_joint_build_groups: no current build of the resident history");
     return TPE_OK;
 }
 
-// phase 1 on device d: its labels' columns, its flag words, one synchronisation
-int tpe1_joint_lsh_gather(tpe_ctx* x, int d, void* plan) {
-    JLshPlan& P = *static_cast<JLshPlan*>(plan);
+// Validate a build call into its plan.  sharded: ctx is the primary of a
+// label-sharded context and a label's record is its owner's; else ctx's own.
+int joint_build_plan(tpe_ctx* ctx, bool sharded, int32_t n_groups, const int32_t* slots, const uint32_t* pick_streams,
+                     const int64_t* group_off, const int32_t* labels, const int32_t* streams, const double* q,
+                     const int32_t* upper, const double* cat_p, double prior_weight, int32_t bw, const int32_t* flags,
+                     JBuildPlan& P) {
+    if (n_groups < 1 || n_groups > kJMaxGroups)
+        return ctx->fail(TPE_ERR_ARG, "tpe_joint_build_groups: 1 to " + std::to_string(kJMaxGroups) + " groups");
+    if (!slots || !pick_streams || !group_off || !labels || !streams || !flags)
+        return ctx->fail(TPE_ERR_ARG, "null pointer");
+    if (bw != TPE_JOINT_BW_NEIGHBOUR && bw != TPE_JOINT_BW_SCOTT)
+        return ctx->fail(TPE_ERR_ARG, "tpe_joint_build_groups_bw: bandwidth is TPE_JOINT_BW_NEIGHBOUR or "
+                                      "TPE_JOINT_BW_SCOTT");
+    if (bw == TPE_JOINT_BW_SCOTT && !(prior_weight > 0.0 && prior_weight < __builtin_inf()))
+        return ctx->fail(TPE_ERR_ARG, "TPE_JOINT_BW_SCOTT needs a positive finite prior weight");
+    const int nd = sharded ? 1 + (int)ctx->peers.size() : 1;
+    int rc;
+    if (!sharded) {
+        if ((rc = joint_build_current(ctx))) return rc;
+    } else {   // (every device's own check ran before: tpe1_joint_lsh_check)
+        for (int d = 0; d < nd; ++d)
+            if (jdev(ctx, d)->build.n_labels != (int32_t)ctx->lsh_ids[d].size())
+                return ctx->fail(TPE_ERR_ARG, "tpe_joint_build_groups: no current build of the resident history");
+    }
+    const int32_t L = sharded ? ctx->lsh_L : ctx->build.n_labels;
+    if (group_off[0] != 0) return ctx->fail(TPE_ERR_ARG, "group offsets start at 0");
+    P.sharded = sharded;
+    P.n_groups = n_groups;
+    P.bw = bw;
+    P.prior_weight = prior_weight;
+    P.gi.assign(n_groups, GInfo{});
+    std::vector<uint8_t> seen(L, 0), slot_seen(kJMaxGroups, 0);
+    std::vector<JDimSpec> ds;
+    size_t cat_at = 0;
+    for (int32_t g = 0; g < n_groups; ++g) {
+        GInfo& I = P.gi[g];
+        if (slots[g] < 0 || slots[g] >= kJMaxGroups || slot_seen[slots[g]])
+            return ctx->fail(TPE_ERR_ARG, "joint slots are distinct and in [0, " + std::to_string(kJMaxGroups) + ")");
+        slot_seen[slots[g]] = 1;
+        const int64_t a = group_off[g], b = group_off[g + 1];
+        if (b - a < 1 || b - a > kJMaxD)
+            return ctx->fail(TPE_ERR_ARG, "a joint group holds 1 to " + std::to_string(kJMaxD) + " dimensions");
+        const int D = (int32_t)(b - a);
+        ds.resize(D);
+        int first = -1;   // the first dimension that is not categorical: it supplies W and the side counts
+        for (int d = 0; d < D; ++d) {
+            const int32_t l = labels[a + d];
+            if (l < 0 || l >= L) return ctx->fail(TPE_ERR_ARG, "tpe_joint_build_groups: label index out of range");
+            if (seen[l]) return ctx->fail(TPE_ERR_ARG, "tpe_joint_build_groups: a label is listed twice");
+            seen[l] = 1;
+            const int32_t o = sharded ? ctx->lsh_dev[l] : 0, j = sharded ? ctx->lsh_local[l] : l;
+            P.owner.push_back(o);
+            P.local.push_back(j);
+            const tpe_ctx* x = jdev(ctx, o);
+            const tpe_label_spec& s = x->build.specs_h[j];
+            const int32_t C = upper ? upper[a + d] : 0;
+            if ((C > 0) != (s.kind == TPE_CATEGORICAL) || (C > 0 && C != s.upper))
+                return ctx->fail(TPE_ERR_ARG, "upper must be the resident label's categories, 0 for a continuous label");
+            if (C <= 0 && first < 0) {   // (C < 0: the layout refuses it)
+                first = d;
+                I.Kb = x->resident.h_labels[j].nb;
+                I.Ka = x->resident.h_labels[j].na;
+            }
+            // (an unbounded label's low and high are 0, as joint_prior's)
+            const int32_t fl = s.flags & (TPE_HAS_LOW | TPE_HAS_HIGH);
+            ds[d] = JDimSpec{fl ? s.low : 0.0, fl ? s.high : 0.0, s.prior_mu, q ? q[a + d] : 0.0,
+                             fl, s.kind == TPE_LGMM1 ? 1 : 0, C, streams[a + d]};
+        }
+        if (first < 0) return ctx->fail(TPE_ERR_ARG, "a device-built joint group needs a label that is not categorical");
+        if (I.Kb < 1 || I.Kb > kJMaxBelow || I.Ka < 1)
+            return ctx->fail(TPE_ERR_ARG, "each side needs its prior component (below: at most " +
+                                              std::to_string(kJMaxBelow) + ")");
+        if ((rc = joint_layout(ctx, ds, cat_p ? cat_p + cat_at : nullptr, prior_weight, I))) return rc;
+        cat_at += (size_t)I.ncat;
+        P.maxK = std::max(P.maxK, std::max(I.Kb, I.Ka));
+        P.wdim.push_back(first);
+        P.base.push_back(P.total);
+        P.total += (size_t)(I.Kb + I.Ka) * (1 + 2 * (size_t)D);
+    }
+    P.slots.assign(slots, slots + n_groups);
+    P.picks.assign(pick_streams, pick_streams + n_groups);
+    P.goff.assign(group_off, group_off + n_groups + 1);
+    P.flags.assign(n_groups, 0);
+    if (sharded) {
+        for (int d = 0; d < nd; ++d) P.device.push_back(jdev(ctx, d)->device);
+        P.cols.assign(nd, nullptr);
+        P.dflags.assign(nd, std::vector<int32_t>(n_groups, 0));
+    }
+    return TPE_OK;
+}
+
+// The gather phase on device d: the slots reserved, one task per dimension
+// the device owns, the gather and (TPE_JOINT_BW_SCOTT) the weight columns
+// queued; G->berr holds the groups' flags, then their fold errors.  Under
+// label shards the device's flags are read back and the stream synchronised:
+// the other devices read these columns in the fold phase.
+int joint_build_gather(tpe_ctx* x, int d, JBuildPlan& P) {
     auto& B = x->build;
     HIPCHK(x, hipSetDevice(x->device));
     JointGroups* G = jgroups(x, true);
     hipStream_t st = x->stream;
-    HIPCHK(x, G->bcols.reserve(P.total));
-    P.cols[d] = G->bcols.p;
+    if (P.sharded) {
+        HIPCHK(x, G->bcols.reserve(P.total));
+        P.cols[d] = G->bcols.p;
+    }
     const bool scott = P.bw == TPE_JOINT_BW_SCOTT;
-    std::vector<JBDim> tasks;
-    std::vector<JSDim> stasks;              // scott: this device's columns, and the weight
-    std::vector<tpe_rt::JointWTask> wts;    //   columns of the groups whose W dimension it owns
+    std::vector<JGDim> tasks;
+    std::vector<tpe_rt::JointWTask> wts;   // scott: the weight columns of the groups whose W dimension is here
     int rc;
     for (int32_t g = 0; g < P.n_groups; ++g) {
         const GInfo& I = P.gi[g];
         JointState* J = nullptr;
         if ((rc = joint_reserve_slot(x, G, P.slots[g], I, &J))) return rc;
         const int32_t K = I.Kb + I.Ka;
+        const double fb = scott ? tpe_joint_bandwidth_factor(I.Kb - 1, I.D) : 0.0,
+                     fa = scott ? tpe_joint_bandwidth_factor(I.Ka - 1, I.D) : 0.0;
         for (int dd = 0; dd < I.D; ++dd) {
             const size_t at = (size_t)P.goff[g] + dd;
             if (P.owner[at] != d) continue;
             const int32_t l = P.local[at];
-            double* mu = G->bcols.p + jcol_mu(P, g, dd);
-            if (scott) {
-                stasks.push_back(joint_scott_task(I, dd, mu, mu + K, l, g, 0, 1, B.ord_cur[l] != 0));
-                if (dd == P.wdim[g]) wts.push_back(tpe_rt::JointWTask{G->bcols.p + P.base[g], {0, 0}, I.Kb, I.Ka});
-                continue;
+            JGDim t{J->W.p, J->mu.p, J->sig.p, fb, fa, l, g, dd, I.D, I.Kb, I.Ka, I.hd[dd].upper, B.ord_cur[l] ? 1 : 0};
+            if (P.sharded) {   // its columns: column 0 of 1
+                t.W = G->bcols.p + P.base[g];
+                t.mu = G->bcols.p + jcol_mu(P, g, dd);
+                t.sig = t.mu + K;
+                t.d = 0;
+                t.D = 1;
             }
-            const int32_t fl = (B.ord_cur[l] ? 1 : 0) | (dd == P.wdim[g] ? 2 : 0);
-            tasks.push_back(JBDim{G->bcols.p + P.base[g], mu, mu + K, l, g, 0, 1, I.Kb, I.Ka, I.hd[dd].upper, fl});
+            if (dd == P.wdim[g]) {
+                if (scott) wts.push_back(tpe_rt::JointWTask{t.W, {0, 0}, I.Kb, I.Ka});
+                else t.flags |= 2;
+            }
+            tasks.push_back(t);
         }
     }
     HIPCHK(x, G->err.reserve(1));
     HIPCHK(x, G->berr.reserve(2 * (size_t)P.n_groups));   // flags | fold errors, per group
     HIPCHK(x, hipMemsetAsync(G->berr.p, 0, 2 * (size_t)P.n_groups * sizeof(int32_t), st));
-    if (scott && !stasks.empty()) {
-        if ((rc = joint_launch_scott(x, G, stasks, wts, P.maxK, P.prior_weight))) return rc;
-        HIPCHK(x, hipMemcpyAsync(P.dflags[d].data(), G->berr.p, P.n_groups * sizeof(int32_t), hipMemcpyDeviceToHost,
-                                 st));
-    }
     if (!tasks.empty()) {
-        HIPCHK(x, G->btask.reserve(tasks.size()));
-        HIPCHK(x, hipMemcpyAsync(G->btask.p, tasks.data(), tasks.size() * sizeof(JBDim), hipMemcpyHostToDevice, st));
-        hipLaunchKernelGGL(k_joint_gather,
-                           dim3((unsigned)((P.maxK + kJBlock - 1) / kJBlock), (unsigned)tasks.size(), 2), dim3(kJBlock),
-                           0, st, G->btask.p, B.specs.p, B.p_off.p, B.counts.p, B.below_val.p, B.keys.p, B.idx.p,
-                           B.order_off.p, B.order.p, B.mix_off.p, B.w.p, B.sigma.p, G->berr.p);
+        HIPCHK(x, G->gtask.reserve(tasks.size()));
+        HIPCHK(x, hipMemcpyAsync(G->gtask.p, tasks.data(), tasks.size() * sizeof(JGDim), hipMemcpyHostToDevice, st));
+        const dim3 grid((unsigned)((P.maxK + kJBlock - 1) / kJBlock), (unsigned)tasks.size(), 2);
+        if (scott)
+            hipLaunchKernelGGL(k_joint_gather<true>, grid, dim3(kJBlock), 0, st, G->gtask.p, B.specs.p, B.p_off.p,
+                               B.counts.p, B.below_val.p, B.keys.p, B.idx.p, B.order_off.p, B.order.p, nullptr,
+                               nullptr, nullptr, G->berr.p);
+        else
+            hipLaunchKernelGGL(k_joint_gather<false>, grid, dim3(kJBlock), 0, st, G->gtask.p, B.specs.p, B.p_off.p,
+                               B.counts.p, B.below_val.p, B.keys.p, B.idx.p, B.order_off.p, B.order.p, B.mix_off.p,
+                               B.w.p, B.sigma.p, G->berr.p);
         HIPCHK(x, hipGetLastError());
+    }
+    if (!wts.empty()) {   // their sums' scratch is placed here
+        int64_t leaf = 0;
+        for (auto& w : wts)
+            for (int side = 0; side < 2; ++side) {
+                w.leaf[side] = leaf;
+                leaf += (side ? w.Ka : w.Kb) / 56 + 1;
+            }
+        HIPCHK(x, G->bleaf.reserve((size_t)leaf));
+        HIPCHK(x, G->wtask.reserve(wts.size()));
+        HIPCHK(x, hipMemcpyAsync(G->wtask.p, wts.data(), wts.size() * sizeof(tpe_rt::JointWTask),
+                                 hipMemcpyHostToDevice, st));
+        if ((rc = tpe_rt::joint_weights_launch(x, st, G->wtask.p, (int32_t)wts.size(), P.prior_weight, kJointLF,
+                                               G->bleaf.p)))
+            return rc;
+    }
+    if (!P.sharded) return TPE_OK;
+    if (!tasks.empty())
         HIPCHK(x, hipMemcpyAsync(P.dflags[d].data(), G->berr.p, P.n_groups * sizeof(int32_t), hipMemcpyDeviceToHost,
                                  st));
-    }
-    HIPCHK(x, hipStreamSynchronize(st));   // (the other devices read these columns in phase 2)
+    HIPCHK(x, hipStreamSynchronize(st));
     return TPE_OK;
 }
 
-// between the phases, on the caller's thread: a group flagged anywhere is flagged
-void tpe1_joint_lsh_flags(void* plan, int32_t* flags) {
-    JLshPlan& P = *static_cast<JLshPlan*>(plan);
-    for (int32_t g = 0; g < P.n_groups; ++g) {
-        int32_t f = 0;
-        for (const auto& df : P.dflags) f |= df[g];
-        P.flags[g] = f;
-        flags[g] = f;
-    }
-}
-
-// phase 2 on device d: the columns of the other devices, the [K][D] arrays,
-// the folds; a flagged group stays unset
-int tpe1_joint_lsh_fold(tpe_ctx* x, int d, void* plan) {
-    JLshPlan& P = *static_cast<JLshPlan*>(plan);
+// The fold phase on device d.  Under label shards first the columns of the
+// other devices (runs of dimensions of one owner: one copy each) and the
+// slot's [K][D] arrays from them, for the groups no device flagged.  Then the
+// folds, the read-back of the error words and the call's synchronisation; on
+// one device the flags come back with them, so a flagged group is folded and
+// left unset, and they go to `flags` (label shards: null, the caller has them).
+int joint_build_fold(tpe_ctx* x, int d, JBuildPlan& P, int32_t* flags) {
     HIPCHK(x, hipSetDevice(x->device));
     JointGroups* G = jgroups(x, true);
     hipStream_t st = x->stream;
+    const int32_t n_groups = P.n_groups;
     int rc;
     auto fetch = [&](int from, size_t off, size_t count) -> int {
         double* dst = G->bcols.p + off;
@@ -1785,37 +1593,80 @@ int tpe1_joint_lsh_fold(tpe_ctx* x, int d, void* plan) {
             HIPCHK(x, hipMemcpyPeerAsync(dst, x->device, src, P.device[from], count * sizeof(double), st));
         return TPE_OK;
     };
-    for (int32_t g = 0; g < P.n_groups; ++g) {
-        if (P.flags[g]) continue;
+    for (int32_t g = 0; g < n_groups; ++g) {
+        if (P.flags[g]) continue;   // (label shards; one device knows no flag yet)
         const GInfo& I = P.gi[g];
         JointState* J = G->slot[P.slots[g]].get();
-        const size_t K = (size_t)(I.Kb + I.Ka);
-        const int wo = P.owner[(size_t)P.goff[g] + P.wdim[g]];
-        if (wo != d && (rc = fetch(wo, P.base[g], K))) return rc;
-        for (int dd = 0; dd < I.D;) {   // runs of dimensions of one owner: one copy each
-            const int o = P.owner[(size_t)P.goff[g] + dd];
-            int e = dd + 1;
-            while (e < I.D && P.owner[(size_t)P.goff[g] + e] == o) ++e;
-            if (o != d && (rc = fetch(o, jcol_mu(P, g, dd), 2 * K * (size_t)(e - dd)))) return rc;
-            dd = e;
+        if (P.sharded) {
+            const size_t K = (size_t)(I.Kb + I.Ka), at = (size_t)P.goff[g];
+            const int wo = P.owner[at + P.wdim[g]];
+            if (wo != d && (rc = fetch(wo, P.base[g], K))) return rc;
+            for (int dd = 0; dd < I.D;) {
+                const int o = P.owner[at + dd];
+                int e = dd + 1;
+                while (e < I.D && P.owner[at + e] == o) ++e;
+                if (o != d && (rc = fetch(o, jcol_mu(P, g, dd), 2 * K * (size_t)(e - dd)))) return rc;
+                dd = e;
+            }
+            hipLaunchKernelGGL(k_joint_interleave, dim3((unsigned)((K * I.D + kJBlock - 1) / kJBlock)), dim3(kJBlock),
+                               0, st, G->bcols.p + P.base[g], I.D, (int32_t)K, J->W.p, J->mu.p, J->sig.p);
+            HIPCHK(x, hipGetLastError());
         }
-        hipLaunchKernelGGL(k_joint_interleave, dim3((unsigned)((K * I.D + kJBlock - 1) / kJBlock)), dim3(kJBlock), 0,
-                           st, G->bcols.p + P.base[g], I.D, (int32_t)K, J->W.p, J->mu.p, J->sig.p);
-        HIPCHK(x, hipGetLastError());
-        if ((rc = joint_fold_group(x, J, I, P.prior_weight, G->berr.p + P.n_groups + g))) return rc;
+        if ((rc = joint_upload_layout(x, J, I))) return rc;
+        if ((rc = joint_fold_group(x, J, I, P.prior_weight, G->berr.p + n_groups + g))) return rc;
     }
-    std::vector<int32_t> eh(P.n_groups);
-    HIPCHK(x, hipMemcpyAsync(eh.data(), G->berr.p + P.n_groups, eh.size() * sizeof(int32_t), hipMemcpyDeviceToHost,
-                             st));
+    std::vector<int32_t> eh(2 * (size_t)n_groups);
+    HIPCHK(x, hipMemcpyAsync(eh.data(), G->berr.p, eh.size() * sizeof(int32_t), hipMemcpyDeviceToHost, st));
     HIPCHK(x, hipStreamSynchronize(st));
+    if (!P.sharded)
+        for (int32_t g = 0; g < n_groups; ++g) P.flags[g] = flags[g] = eh[g];
     bool zero = false;
-    for (int32_t g = 0; g < P.n_groups; ++g) {
+    for (int32_t g = 0; g < n_groups; ++g) {
         JointState* J = G->slot[P.slots[g]].get();
-        joint_commit(J, P.gi[g], P.picks[g], P.flags[g], eh[g]);
+        joint_commit(J, P.gi[g], P.picks[g], P.flags[g], eh[n_groups + g]);
         zero |= J->ready && J->zero;
     }
     if (zero) return zero_mass(x);
     return TPE_OK;
+}
+}  // namespace
+
+// tpe_joint_build_groups on a label-sharded context, in the order its caller
+// runs them (tpe_ctx.h)
+int tpe1_joint_lsh_check(tpe_ctx* x) {
+    TPE_SETTLE(x);   // (a deferred rebuild's report: its buffers are read here)
+    return joint_build_current(x);
+}
+
+int tpe1_joint_lsh_plan(tpe_ctx* ctx, int32_t n_groups, const int32_t* slots, const uint32_t* pick_streams,
+                        const int64_t* group_off, const int32_t* labels, const int32_t* streams, const double* q,
+                        const int32_t* upper, const double* cat_p, double prior_weight, int32_t bw, int32_t* flags,
+                        std::shared_ptr<void>* out) {
+    auto P = std::make_shared<JBuildPlan>();
+    const int rc = joint_build_plan(ctx, true, n_groups, slots, pick_streams, group_off, labels, streams, q, upper,
+                                    cat_p, prior_weight, bw, flags, *P);
+    if (rc) return rc;
+    *out = std::static_pointer_cast<void>(P);
+    return TPE_OK;
+}
+
+int tpe1_joint_lsh_gather(tpe_ctx* x, int d, void* plan) {
+    return joint_build_gather(x, d, *static_cast<JBuildPlan*>(plan));
+}
+
+// between the phases, on the caller's thread: a group flagged anywhere is flagged
+void tpe1_joint_lsh_flags(void* plan, int32_t* flags) {
+    JBuildPlan& P = *static_cast<JBuildPlan*>(plan);
+    for (int32_t g = 0; g < P.n_groups; ++g) {
+        int32_t f = 0;
+        for (const auto& df : P.dflags) f |= df[g];
+        P.flags[g] = f;
+        flags[g] = f;
+    }
+}
+
+int tpe1_joint_lsh_fold(tpe_ctx* x, int d, void* plan) {
+    return joint_build_fold(x, d, *static_cast<JBuildPlan*>(plan), nullptr);
 }
 
 // the set slots of a context in ascending order: their dimensions into D[], their number back
@@ -1856,8 +1707,12 @@ int tpe1_joint_build_groups(tpe_ctx* ctx, int32_t n_groups, const int32_t* slots
                             int32_t* flags) {
     if (!ctx) return TPE_ERR_ARG;
     TPE_SETTLE(ctx);   // (a deferred rebuild's report: its buffers are read here)
-    return joint_build_groups(ctx, n_groups, slots, pick_streams, group_off, labels, streams, q, upper, cat_p,
-                              prior_weight, bandwidth, flags);
+    JBuildPlan P;
+    int rc = joint_build_plan(ctx, false, n_groups, slots, pick_streams, group_off, labels, streams, q, upper, cat_p,
+                              prior_weight, bandwidth, flags, P);
+    if (rc) return rc;
+    if ((rc = joint_build_gather(ctx, 0, P))) return rc;
+    return joint_build_fold(ctx, 0, P, flags);
 }
 
 // (host arithmetic only: posterior.joint_bandwidth_factor is the same operations in the same order)

@@ -360,7 +360,6 @@ def _joint_rounds(eng, domain, trials, specs, gathered, gamma, prior_weight, see
     handed to both builders.  Under 'scott' no sorted position enters a
     mixture, so the device flags no tie: the groups with tied observations
     (the rule for quantized labels) stay on the device."""
-    bw = {} if bandwidth == 'neighbour' else {'bandwidth': bandwidth}
     kinds = _post.JOINT_KINDS + (_post.JOINT_QUANT_KINDS if quantized else ()) + \
         (_post.JOINT_CAT_KINDS if categorical else ())
     labels = list(specs)
@@ -394,7 +393,7 @@ def _joint_rounds(eng, domain, trials, specs, gathered, gamma, prior_weight, see
         for slot, g in on_host:
             mix = _post.joint_mixture([specs[k] for k in g], obs, splitter, prior_weight,
                                       streams=[labels.index(k) for k in g], quantized=quantized,
-                                      categorical=categorical, **bw)
+                                      categorical=categorical, bandwidth=bandwidth)
             eng.set_joint_group(slot, _engine.L.TPE_JOINT_STREAM - slot, *mix, prior_weight=prior_weight)
     won = eng.joint_suggest_batch(seed, ids, n_candidates)
     out = [{} for _ in ids]
@@ -603,8 +602,7 @@ def suggest(new_ids, domain, trials, seed,
     joint = _joint_rounds(eng, domain, trials, specs, gathered, gamma, prior_weight, seed, ids,
                           n_EI_candidates, group=group, quantized=bool(joint_quantized),
                           categorical=bool(joint_categorical), view=jview,
-                          **({} if joint_bandwidth == 'neighbour' else {'bandwidth': joint_bandwidth})
-                          ) if multivariate else None
+                          bandwidth=joint_bandwidth) if multivariate else None
     rval = []
     for j, new_id in enumerate(ids):
         values = {s.label: _labels.coerce(s.kind, res[j][i]['value'])

@@ -214,14 +214,14 @@ BUILD_ROUNDS = [3, 0, 4294967295]
 BUILD_ENGINES = ['two', 'three', 'two_replicated', real2]
 
 
-def build_on(eng, specs, view, groups, quantized=False, categorical=False):
+def build_on(eng, specs, view, groups, quantized=False, categorical=False, bandwidth='neighbour'):
     """The univariate posterior of `view` built on the engine's device(s),
-    the joint groups from it: (flags, {slot: both sides' unfolded arrays},
-    the 4096-candidate rounds of the built slots)."""
+    the joint groups from it under `bandwidth`: (flags, {slot: both sides'
+    unfolded arrays}, the 4096-candidate rounds of the built slots)."""
     names = list(specs)
     table = [(s.label, s.kind, s.args) for s in specs.values()]
     P.DeviceHistoryUploader().build(eng, table, view, BG.GAMMA, BG.PW)
-    args, kw = tpe._joint_device_args(specs, names, groups, quantized, categorical, BG.PW)
+    args, kw = tpe._joint_device_args(specs, names, groups, quantized, categorical, BG.PW, bandwidth)
     eng.clear_joint_groups()
     flags = [int(f) for f in eng.build_joint_groups(args, **kw)]
     built = [slot for (slot, _), f in zip(groups, flags) if not f]
@@ -290,6 +290,19 @@ def test_build_conditional_groups(engs, key):
     groups = tpe.joint_groups(domain, specs, view[3])
     assert groups == GC.GROUPS and len(groups) >= 2
     check_build(engs, key, specs, view, groups)
+
+
+@pytest.mark.parametrize('bandwidth', ['neighbour', 'scott'])
+def test_build_on_a_device_that_owns_no_dimension(engs, bandwidth):
+    """Three labels on three devices and one group of the first two: the
+    third device gathers nothing -- an empty task list, no gather launch -- and
+    still fetches, interleaves, folds and commits its replica, which scores a
+    third of every round's candidates."""
+    specs = BG.dense_specs(['uniform', 'normal', 'lognormal'])
+    check_build(engs, 'three', specs, BG.make_view(specs, 40, 47), [(0, ['h0', 'h1'])], bandwidth=bandwidth)
+    e = engs('three')
+    where = [e.lib.tpe_label_device(e.h, li) for li in range(3)]
+    assert where[2] not in where[:2], where
 
 
 FOUR = ['uniform', 'normal', 'lognormal', 'uniform']
