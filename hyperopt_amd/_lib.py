@@ -176,6 +176,7 @@ SIGNATURES = {
     'tpe_import_posterior': (ctypes.c_int, [_P, _P, _I64, _P, _I32, _P, _P]),
     'tpe_joint_set_group': (ctypes.c_int, [_P, _I32, _U32, _P, _P, _P, _P, _D, _I32, _I32, _P, _P, _P, _I32, _P, _P,
                                            _P]),
+    'tpe_joint_condition_group': (ctypes.c_int, [_P, _I32, _I32, _I32, _P, _P]),
     'tpe_joint_clear_groups': (ctypes.c_int, [_P]),
     'tpe_joint_build_groups': (ctypes.c_int, [_P, _I32, _P, _P, _P, _P, _P, _P, _P, _P, _D, _P]),
     'tpe_joint_build_groups_bw': (ctypes.c_int, [_P, _I32, _P, _P, _P, _P, _P, _P, _P, _P, _D, _I32, _P]),

@@ -768,6 +768,8 @@ TPE_DEV int tpe1_joint_set_group(tpe_ctx* ctx, int32_t slot, uint32_t pick_strea
                                  int32_t n_dims, int32_t n_below, const double* wb, const double* mub,
                                  const double* sigb, int32_t n_above, const double* wa, const double* mua,
                                  const double* siga);
+TPE_DEV int tpe1_joint_condition_group(tpe_ctx* ctx, int32_t src_slot, int32_t dst_slot, int32_t n_fixed,
+                                       const int32_t* dims, const double* values);
 TPE_DEV int tpe1_joint_clear_groups(tpe_ctx* ctx);
 TPE_DEV int tpe1_joint_build_groups(tpe_ctx* ctx, int32_t n_groups, const int32_t* slots,
                                     const uint32_t* pick_streams, const int64_t* group_off, const int32_t* labels,

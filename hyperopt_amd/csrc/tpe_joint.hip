@@ -38,6 +38,10 @@
 //                                     (tpe_build.hip)
 //   k_joint_interleave                that build under label shards: the slot's
 //                                     [K][D] arrays from per-label columns
+//   k_joint_cond_logw / _weights / _cols   tpe_joint_condition_group: a slot given some of
+//                                     its dimensions -- L_k per component, each side's
+//                                     log-sum-exp over one fixed tree and W'_k, the free
+//                                     columns; then the fold above
 //
 // The extern "C" functions here are the per-device bodies tpe1_joint_*; the
 // public tpe_joint_* names are tpe_multi.hip's, which replicates the groups
@@ -50,7 +54,8 @@
 // joint_layout (a group's checks, JDim records and categorical tables, from
 // its per-dimension description), joint_reserve_slot, joint_upload_layout and
 // the fill, joint_fold_group, one synchronisation, joint_commit.  The fill is the upload
-// of joint_set (tpe_joint_set_group), or the gather of a device build: one
+// of joint_set (tpe_joint_set_group), the device-to-device copy of
+// joint_condition (tpe_joint_condition_group), or the gather of a device build: one
 // plan (JBuildPlan: joint_build_plan) and one driver (joint_build_gather, then
 // joint_build_fold) for one device, for every device of a replicated context,
 // and -- with a column buffer as the tasks' destination and the caller's
@@ -809,6 +814,131 @@ __global__ __launch_bounds__(kJBlock) void k_joint_best_cells(JP p, const double
     for (int d = threadIdx.x; d < p.D; d += kJBlock) row[3 + d] = jdraw<true>(p, p.dims[d], d, kc, k0, k1, g, round);
 }
 
+// ------------------------------------------------------------- condition ----
+// tpe_joint_condition_group: a slot's mixtures given the values of some of its
+// dimensions F.  Each side's conditional over the free dimensions R keeps its
+// components' means and sigmas; the weights become
+//   L_k = log W_k + sum_{d in F} log g_kd(x_d),   W'_k = max(exp(L_k - lse), 2^-1022),
+// g_kd the factor the round scores for the dimension: phi(y_d; mu_kd, s_kd) of a
+// dense one (the Jacobian of a log kind is the same for every k and cancels),
+// the mass of the value's rounding interval (quant_bounds, jmass on the fold's
+// record) of a quantized one, r_kd[x_d] of a categorical one.  The floor keeps
+// log W'_k finite for the fold.  A_S and the thresholds are the fold's, over R.
+struct JFix {
+    double x;     // the value as documents carry it
+    int32_t d;    // its dimension in the source slot
+    int32_t pad;
+};
+
+// one thread per component, both sides: L[k]
+__global__ __launch_bounds__(kJBlock) void k_joint_cond_logw(const JDim* __restrict__ dims, int32_t D, int32_t Kb,
+                                                             int32_t Ka, const double* __restrict__ W,
+                                                             const double* __restrict__ mu,
+                                                             const double* __restrict__ sig,
+                                                             const JFix* __restrict__ fix, int32_t nf, double pw,
+                                                             const double* __restrict__ ctab, int32_t ncat,
+                                                             double* __restrict__ L) {
+#pragma clang fp contract(off)
+    const int k = blockIdx.x * kJBlock + threadIdx.x;
+    if (k >= Kb + Ka) return;
+    double l = log(W[k]);
+    for (int f = 0; f < nf; ++f) {
+        const JFix t = fix[f];
+        const JDim j = dims[t.d];
+        const size_t o = (size_t)k * D + t.d;
+        const double x = t.x;
+        if (j.upper > 0) {   // r_kd[x]: log p[x] + log(a / (1 + a)) + [x == o_kd] log1p(1 / (a p[o_kd]))
+            if (!(x >= 0.0 && x < (double)j.upper && x == floor(x))) {
+                l = -kInf;
+                continue;
+            }
+            const double* __restrict__ p = ctab + j.cat_off;
+            const double* __restrict__ lp = ctab + 2 * (size_t)ncat + j.cat_off;
+            double lr = lp[(int)x];
+            if (k != 0 && k != Kb) {
+                const double a = (double)j.upper * pw / (double)(k < Kb ? Kb : Ka);
+                const double c = mu[o];
+                lr -= log1p(1.0 / a);
+                if (x == c) lr += log1p(1.0 / (a * p[(int)c]));
+            }
+            l += lr;
+            continue;
+        }
+        const double s = sig[o], m = mu[o];
+        if (j.q > 0.0) {
+            DLabel Lb{};
+            Lb.flags = j.flags;
+            Lb.q = j.q;
+            Lb.low = j.low;
+            Lb.high = j.high;
+            Lb.exp_low = j.elo;
+            Lb.exp_high = j.ehi;
+            double ub, lb;
+            bool neg;
+            if (j.log) quant_bounds<QUANT_LGMM>(Lb, x, ub, lb, neg);
+            else quant_bounds<QUANT_GMM>(Lb, x, ub, lb, neg);
+            const double a = 0.70710678118654752440 / s, mr = (m - j.centre) * a;   // the fold's record
+            l += log(jmass(fma(lb - j.centre, a, -mr), fma(ub - j.centre, a, -mr)));
+        } else {
+            const double y = j.log ? flog(x) : x;
+            const double z = (y - m) / s;
+            l += -0.5 * (z * z) - log(s * 2.50662827463100050242);
+        }
+    }
+    L[k] = l == l ? l : -kInf;   // (a value outside a log kind's support: no component reaches it)
+}
+
+// block b: side b's lse = L_max + log(sum_k exp(L_k - L_max)) over one fixed
+// tree (strided partials in component order, then halving), and W'_k; a side
+// whose every L_k is -inf stores 1 to refused[b] and writes no weight
+__global__ __launch_bounds__(kJBlock) void k_joint_cond_weights(const double* __restrict__ L, int32_t Kb, int32_t Ka,
+                                                                double* __restrict__ Wout,
+                                                                int32_t* __restrict__ refused) {
+#pragma clang fp contract(off)
+    const int side = blockIdx.x, K = side ? Ka : Kb, t = threadIdx.x;
+    const double* Ls = L + (side ? Kb : 0);
+    double* Ws = Wout + (side ? Kb : 0);
+    __shared__ double sh[kJBlock];
+    double a = -kInf;
+    for (int k = t; k < K; k += kJBlock) a = fmax(a, Ls[k]);
+    sh[t] = a;
+    __syncthreads();
+    for (int w = kJBlock / 2; w > 0; w >>= 1) {
+        if (t < w) sh[t] = fmax(sh[t], sh[t + w]);
+        __syncthreads();
+    }
+    const double M = sh[0];
+    __syncthreads();
+    if (!(M > -kInf && M < kInf)) {
+        if (t == 0) refused[side] = 1;
+        return;
+    }
+    a = 0.0;
+    for (int k = t; k < K; k += kJBlock) a += exp(Ls[k] - M);
+    sh[t] = a;
+    __syncthreads();
+    for (int w = kJBlock / 2; w > 0; w >>= 1) {
+        if (t < w) sh[t] += sh[t + w];
+        __syncthreads();
+    }
+    const double lse = M + log(sh[0]);
+    for (int k = t; k < K; k += kJBlock) Ws[k] = fmax(exp(Ls[k] - lse), 0x1.0p-1022);
+}
+
+// the free columns of mu and sigma, [K][D] -> [K][Dr], bit for bit
+__global__ __launch_bounds__(kJBlock) void k_joint_cond_cols(const double* __restrict__ mu,
+                                                             const double* __restrict__ sig, int32_t D, int32_t Dr,
+                                                             int64_t K, const int32_t* __restrict__ free_d,
+                                                             double* __restrict__ mu_out,
+                                                             double* __restrict__ sig_out) {
+    const int64_t e = (int64_t)blockIdx.x * kJBlock + threadIdx.x;
+    if (e >= K * Dr) return;
+    const int64_t k = e / Dr;
+    const size_t o = (size_t)k * D + free_d[e - k * Dr];
+    mu_out[e] = mu[o];
+    sig_out[e] = sig[o];
+}
+
 // ------------------------------------------------------------- host side ----
 template <typename T>
 using DevBuf = tpe_rt::DevBuf<T>;
@@ -821,6 +951,11 @@ struct JointState {   // one slot's folded posterior
     int32_t ncat = 0;     // entries of each categorical table
     uint32_t stream = TPE_JOINT_STREAM;
     bool ready = false, zero = false;
+    // the layout as the host laid it out and the prior weight of its fold: what
+    // tpe_joint_condition_group lays the free dimensions out from
+    std::vector<JDim> hd;
+    std::vector<double> hctab;
+    double pw = 0.0;
     DevBuf<JDim> dims;
     DevBuf<double> W, mu, sig, cst, P, logA;
     DevBuf<double> ctab;   // categorical tables: p, its running sums, log p (ncat each)
@@ -862,6 +997,9 @@ struct JointGroups {   // a context's slots and the scratch they share (one stre
     DevBuf<tpe_rt::JointWTask> wtask;     // under TPE_JOINT_BW_SCOTT: its weight columns
     DevBuf<double> bleaf;                 //   and their sums' scratch
     DevBuf<double> bcols;   // the build under label shards: the call's columns
+    DevBuf<JFix> cfix;                    // tpe_joint_condition_group: the fixed dimensions,
+    DevBuf<int32_t> cfree, cerr;          //   the free ones, a side's refusal,
+    DevBuf<double> cL, cW, cmu, csig;     //   L_k, W'_k and the free columns
     DevBuf<Partial> partials;
     DevBuf<uint32_t> rounds;
     std::vector<double> hres;
@@ -1112,7 +1250,11 @@ int joint_fold_group(tpe_ctx* ctx, JointState* J, const GInfo& I, double prior_w
 
 // the slot's record after the caller's synchronisation (a group the device
 // build flagged stays unset: it is the host build's)
-void joint_commit(JointState* J, const GInfo& I, uint32_t pick_stream, int32_t flag, int32_t fold_err) {
+void joint_commit(JointState* J, const GInfo& I, double prior_weight, uint32_t pick_stream, int32_t flag,
+                  int32_t fold_err) {
+    J->hd = I.hd;
+    J->hctab = I.ctab;
+    J->pw = prior_weight;
     J->D = I.D;
     J->S = I.S;
     J->quant = I.quant;
@@ -1193,7 +1335,99 @@ int joint_set(tpe_ctx* ctx, int32_t slot, uint32_t pick_stream, const tpe_joint_
     int32_t e = 0;
     HIPCHK(ctx, hipMemcpyAsync(&e, G->err.p, sizeof(int32_t), hipMemcpyDeviceToHost, st));
     HIPCHK(ctx, hipStreamSynchronize(st));   // the call's one synchronisation
-    joint_commit(J, I, pick_stream, 0, e);   // (set also when the box holds no below mass: the rounds refuse it)
+    joint_commit(J, I, prior_weight, pick_stream, 0, e);   // (set also when the box holds no below mass: the rounds refuse it)
+    if (J->zero) return zero_mass(ctx);
+    return TPE_OK;
+}
+
+// condition one slot on the values of some of its dimensions
+// (tpe_joint_condition_group).  Two phases: W' and the free columns into the
+// shared scratch, with the sides' refusals read back -- nothing of a slot is
+// touched before they are known -- then the destination is laid out, filled
+// from the scratch device to device and folded like any other slot.
+int joint_condition(tpe_ctx* ctx, int32_t src_slot, int32_t dst_slot, int32_t n_fixed, const int32_t* fdims,
+                    const double* values) {
+    if (!ctx) return TPE_ERR_ARG;
+    if (src_slot < 0 || src_slot >= kJMaxGroups || dst_slot < 0 || dst_slot >= kJMaxGroups)
+        return ctx->fail(TPE_ERR_ARG, "a joint slot is in [0, " + std::to_string(kJMaxGroups) + ")");
+    JointGroups* G = jgroups(ctx, false);
+    JointState* S = G ? G->slot[src_slot].get() : nullptr;
+    if (!S || !S->ready) return ctx->fail(TPE_ERR_ARG, "tpe_joint_condition_group: no joint posterior set");
+    if (!fdims || !values) return ctx->fail(TPE_ERR_ARG, "null pointer");
+    const int D = S->D, Kb = S->Kb, Ka = S->Ka, K = Kb + Ka;
+    if (n_fixed < 1 || n_fixed > D - 1)
+        return ctx->fail(TPE_ERR_ARG, "tpe_joint_condition_group: 1 to n_dims - 1 dimensions are fixed");
+    std::vector<uint8_t> fixed(D, 0);
+    std::vector<JFix> fix(n_fixed);
+    for (int f = 0; f < n_fixed; ++f) {
+        const int32_t d = fdims[f];
+        if (d < 0 || d >= D || fixed[d])
+            return ctx->fail(TPE_ERR_ARG, "tpe_joint_condition_group: fixed dimensions are distinct and in [0, n_dims)");
+        fixed[d] = 1;
+        fix[f] = JFix{values[f], d, 0};
+    }
+    for (int f = 0; f < n_fixed; ++f)
+        if (values[f] != values[f]) return ctx->fail(TPE_ERR_VALUE, "tpe_joint_condition_group: a fixed value is NaN");
+    // the free dimensions in their source order, laid out as a group of their own
+    const double pw = S->pw;
+    const uint32_t pick = S->stream;
+    std::vector<int32_t> free_d;
+    std::vector<JDimSpec> ds;
+    std::vector<double> cat_p;
+    for (int d = 0; d < D; ++d) {
+        if (fixed[d]) continue;
+        const JDim& j = S->hd[d];
+        free_d.push_back(d);
+        ds.push_back(JDimSpec{j.low, j.high, j.centre, j.q, j.flags, j.log, j.upper, j.stream});
+        for (int32_t c = 0; c < j.upper; ++c) cat_p.push_back(S->hctab[j.cat_off + c]);
+    }
+    const int Dr = D - n_fixed;
+    GInfo I{};
+    I.Kb = Kb;
+    I.Ka = Ka;
+    int rc = joint_layout(ctx, ds, cat_p.empty() ? nullptr : cat_p.data(), pw, I);
+    if (rc) return rc;
+    HIPCHK(ctx, hipSetDevice(ctx->device));
+    hipStream_t st = ctx->stream;
+    HIPCHK(ctx, G->err.reserve(1));
+    HIPCHK(ctx, G->cfix.reserve(n_fixed));
+    HIPCHK(ctx, G->cfree.reserve(Dr));
+    HIPCHK(ctx, G->cerr.reserve(2));
+    HIPCHK(ctx, G->cL.reserve(K));
+    HIPCHK(ctx, G->cW.reserve(K));
+    HIPCHK(ctx, G->cmu.reserve((size_t)K * Dr));
+    HIPCHK(ctx, G->csig.reserve((size_t)K * Dr));
+    HIPCHK(ctx, hipMemcpyAsync(G->cfix.p, fix.data(), n_fixed * sizeof(JFix), hipMemcpyHostToDevice, st));
+    HIPCHK(ctx, hipMemcpyAsync(G->cfree.p, free_d.data(), Dr * sizeof(int32_t), hipMemcpyHostToDevice, st));
+    HIPCHK(ctx, hipMemsetAsync(G->cerr.p, 0, 2 * sizeof(int32_t), st));
+    hipLaunchKernelGGL(k_joint_cond_logw, dim3((K + kJBlock - 1) / kJBlock), dim3(kJBlock), 0, st, S->dims.p, D, Kb, Ka,
+                       S->W.p, S->mu.p, S->sig.p, G->cfix.p, n_fixed, pw, S->cat ? S->ctab.p : nullptr, S->ncat,
+                       G->cL.p);
+    HIPCHK(ctx, hipGetLastError());
+    hipLaunchKernelGGL(k_joint_cond_weights, dim3(2), dim3(kJBlock), 0, st, G->cL.p, Kb, Ka, G->cW.p, G->cerr.p);
+    HIPCHK(ctx, hipGetLastError());
+    const int64_t cells = (int64_t)K * Dr;
+    hipLaunchKernelGGL(k_joint_cond_cols, dim3((unsigned)((cells + kJBlock - 1) / kJBlock)), dim3(kJBlock), 0, st,
+                       S->mu.p, S->sig.p, D, Dr, (int64_t)K, G->cfree.p, G->cmu.p, G->csig.p);
+    HIPCHK(ctx, hipGetLastError());
+    int32_t refused[2] = {0, 0};
+    HIPCHK(ctx, hipMemcpyAsync(refused, G->cerr.p, sizeof(refused), hipMemcpyDeviceToHost, st));
+    HIPCHK(ctx, hipStreamSynchronize(st));
+    if (refused[0] || refused[1])
+        return ctx->fail(TPE_ERR_VALUE, std::string("tpe_joint_condition_group: no component of the ") +
+                                            (refused[0] ? "below" : "above") + " mixture reaches the fixed values");
+    JointState* J = nullptr;   // (dst == src: the slot's own buffers, large enough as they are)
+    if ((rc = joint_reserve_slot(ctx, G, dst_slot, I, &J))) return rc;
+    if ((rc = joint_upload_layout(ctx, J, I))) return rc;
+    HIPCHK(ctx, hipMemcpyAsync(J->W.p, G->cW.p, K * sizeof(double), hipMemcpyDeviceToDevice, st));
+    HIPCHK(ctx, hipMemcpyAsync(J->mu.p, G->cmu.p, cells * sizeof(double), hipMemcpyDeviceToDevice, st));
+    HIPCHK(ctx, hipMemcpyAsync(J->sig.p, G->csig.p, cells * sizeof(double), hipMemcpyDeviceToDevice, st));
+    HIPCHK(ctx, hipMemsetAsync(G->err.p, 0, sizeof(int32_t), st));
+    if ((rc = joint_fold_group(ctx, J, I, pw, G->err.p))) return rc;
+    int32_t e = 0;
+    HIPCHK(ctx, hipMemcpyAsync(&e, G->err.p, sizeof(int32_t), hipMemcpyDeviceToHost, st));
+    HIPCHK(ctx, hipStreamSynchronize(st));
+    joint_commit(J, I, pw, pick, 0, e);
     if (J->zero) return zero_mass(ctx);
     return TPE_OK;
 }
@@ -1623,7 +1857,7 @@ int joint_build_fold(tpe_ctx* x, int d, JBuildPlan& P, int32_t* flags) {
     bool zero = false;
     for (int32_t g = 0; g < n_groups; ++g) {
         JointState* J = G->slot[P.slots[g]].get();
-        joint_commit(J, P.gi[g], P.picks[g], P.flags[g], eh[n_groups + g]);
+        joint_commit(J, P.gi[g], P.prior_weight, P.picks[g], P.flags[g], eh[n_groups + g]);
         zero |= J->ready && J->zero;
     }
     if (zero) return zero_mass(x);
@@ -1690,6 +1924,11 @@ int tpe1_joint_set_group(tpe_ctx* ctx, int32_t slot, uint32_t pick_stream, const
                          int32_t n_above, const double* wa, const double* mua, const double* siga) {
     return joint_set(ctx, slot, pick_stream, dims, q, upper, cat_p, prior_weight, n_dims, n_below, wb, mub, sigb,
                      n_above, wa, mua, siga);
+}
+
+int tpe1_joint_condition_group(tpe_ctx* ctx, int32_t src_slot, int32_t dst_slot, int32_t n_fixed,
+                               const int32_t* dims, const double* values) {
+    return joint_condition(ctx, src_slot, dst_slot, n_fixed, dims, values);
 }
 
 int tpe1_joint_clear_groups(tpe_ctx* ctx) {

@@ -855,6 +855,15 @@ int tpe_joint_set_group(tpe_ctx* ctx, int32_t slot, uint32_t pick_stream, const 
     });
 }
 
+// (every replica holds the source's bits and the weights' tree is fixed: the same destination everywhere)
+int tpe_joint_condition_group(tpe_ctx* ctx, int32_t src_slot, int32_t dst_slot, int32_t n_fixed, const int32_t* dims,
+                              const double* values) {
+    if (!ctx) return TPE_ERR_ARG;
+    return for_all(ctx, [&](tpe_ctx* x, int) {
+        return tpe1_joint_condition_group(x, src_slot, dst_slot, n_fixed, dims, values);
+    });
+}
+
 int tpe_joint_clear_groups(tpe_ctx* ctx) {
     if (!ctx) return TPE_ERR_ARG;
     return for_all(ctx, [&](tpe_ctx* x, int) { return tpe1_joint_clear_groups(x); });

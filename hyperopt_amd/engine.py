@@ -489,6 +489,31 @@ class Engine(object):
             slots.pop(int(slot), None)
         self._check(rc)
 
+    def joint_condition(self, slot, dims, values, dst=None):
+        """Condition a set slot on some of its dimensions held at `values`
+        (tpe_joint_condition_group): dims distinct dimension indices of the
+        slot, values the label values as documents carry them (x, not log x;
+        a category index).  Slot `dst` (None: `slot` itself, in place) becomes
+        the group over the free dimensions, in their order in `slot`: the
+        components' free means and sigmas, the weights W'_k proportional to
+        W_k prod_{d fixed} g_kd(x_d) on both sides, on the device -- nothing
+        is read back or uploaded but the arguments.  Its draws are the
+        conditional's and its scores differ from the source's at (values, .)
+        by a constant.  ValueError for a NaN value or values no component of a
+        side reaches (the destination is then left as it was)."""
+        slot = int(slot)
+        dst = slot if dst is None else int(dst)
+        dims = np.ascontiguousarray(dims, dtype=np.int32).ravel()
+        values = _f64(values).ravel()
+        if len(dims) != len(values):
+            raise ValueError('joint_condition: one value per fixed dimension')
+        D = getattr(self, 'joint_slots', {}).get(slot, 0)
+        rc = self.lib.tpe_joint_condition_group(self.h, slot, dst, len(dims), _ptr(dims), _ptr(values))
+        slots = self.__dict__.setdefault('joint_slots', {})
+        if rc in (L.TPE_OK, L.TPE_ERR_SAMPLE):
+            slots[dst] = D - len(dims)
+        self._check(rc)
+
     def clear_joint_groups(self):
         """Unset every joint slot (tpe_joint_clear_groups)."""
         self.joint_slots = {}

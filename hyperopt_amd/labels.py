@@ -228,10 +228,25 @@ def coerce(kind, v):
     return float(v)
 
 
-def sample_config(expr, specs, rng):
+def sample_config(expr, specs, rng, fixed=None):
     """One prior draw of the ACTIVE hyperparameters (the random-search
     proposal, rand.py:15-31 / pyll/stochastic.py:35-147): choices are drawn
-    first and only the selected branch is descended."""
+    first and only the selected branch is descended.
+
+    fixed (label -> value, optional): those labels take their value instead
+    of a draw, so a fixed choice index selects the branch that is sampled; a
+    fixed label under a branch that is not entered stays out, like any other.
+    A fixed label consumes no random numbers: the other active labels are
+    drawn in the order they always are, each from the state the draws before
+    it left -- without `fixed` (or with an empty one) the stream and the
+    values are unchanged."""
+    fixed = fixed or {}
+
+    def draw(lab):
+        s = specs[lab]
+        if lab in fixed:
+            return coerce(s.kind, fixed[lab])
+        return coerce(s.kind, IMPLS[s.kind](rng=rng, **s.args))
     values = {}
     seen, stack = set(), [as_apply(expr)]
     while stack:
@@ -242,9 +257,7 @@ def sample_config(expr, specs, rng):
         if n.name == 'hyperopt_param':
             lab = param_label(n)
             if lab not in values:
-                s = specs[lab]
-                fn = IMPLS[s.kind]
-                values[lab] = coerce(s.kind, fn(rng=rng, **s.args))
+                values[lab] = draw(lab)
             continue
         if n.name == 'switch':
             idx = n.pos_args[0]
@@ -253,8 +266,7 @@ def sample_config(expr, specs, rng):
                 if m.name == 'hyperopt_param':
                     lab = param_label(m)
                     if lab not in values:
-                        s = specs[lab]
-                        values[lab] = coerce(s.kind, IMPLS[s.kind](rng=rng, **s.args))
+                        values[lab] = draw(lab)
             pos = int(_eval_with(idx, values))
             stack.append(idx)
             stack.append(n.pos_args[1 + pos])

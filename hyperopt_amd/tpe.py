@@ -25,6 +25,8 @@ joint_categorical=True: the categorical ones too; joint_bandwidth='scott':
 the joint kernels' sigmas from the number of trials and the dimension);
 with `group=True` also those that share an hp.choice branch, one joint group
 per branch),
+`fixed` ({label: value}: the suggestion with those hyperparameters held; the
+free labels of a joint group then come from its conditional density),
 `precision` ('f64'; 'f32'
 is accepted and runs the same exact path -- see `suggest`), `device` (HIP ordinal), `devices` (a list of ordinals: one
 multi-device context splits every round over those GPUs, same documents as
@@ -330,8 +332,82 @@ def _joint_device_args(specs, labels, groups, quantized, categorical, prior_weig
     return args, kw
 
 
+def check_fixed(specs, fixed):
+    """tpe.suggest's `fixed` after validation: {label: value as documents
+    carry it} (labels.coerce), {} for None.  ValueError for anything that is
+    not a dict, an unknown label, a value that is not a finite number, a
+    bounded dense kind outside [low, high] (a log kind: [exp(low),
+    exp(high)]), a dense log kind that is not positive (a quantized one may be
+    0, its rounding interval reaching into the support), a quantized kind
+    whose value is not on its grid (v == round(v / q) * q) or whose rounding
+    interval [v - q/2, v + q/2] misses the support, and a category that is no
+    integer in [0, upper)."""
+    if fixed is None:
+        return {}
+    if not isinstance(fixed, dict):
+        raise ValueError('fixed must be a dict of label -> value')
+    out = {}
+    for label, value in fixed.items():
+        if label not in specs:
+            raise ValueError('fixed: unknown label %r' % (label,))
+        s = specs[label]
+        try:
+            v = float(value)
+        except (TypeError, ValueError):
+            raise ValueError('fixed[%r]: %r is not a number' % (label, value))
+        if not np.isfinite(v):
+            raise ValueError('fixed[%r]: %r is not finite' % (label, value))
+        a = s.args
+        if s.kind in ('randint', 'categorical'):
+            if v != np.floor(v) or not 0 <= v < a['upper']:
+                raise ValueError('fixed[%r]: %r is not an integer in [0, %d)' % (label, value, a['upper']))
+            out[label] = _labels.coerce(s.kind, v)
+            continue
+        log = s.kind in ('loguniform', 'qloguniform', 'lognormal', 'qlognormal')
+        q = a.get('q')
+        lo, hi = -np.inf, np.inf
+        if 'low' in a:
+            lo, hi = (np.exp(a['low']), np.exp(a['high'])) if log else (a['low'], a['high'])
+        if q is None:
+            if log and not v > 0.0:
+                raise ValueError('fixed[%r]: %r is not positive' % (label, value))
+            if not lo <= v <= hi:
+                raise ValueError('fixed[%r]: %r is outside [%r, %r]' % (label, value, lo, hi))
+        else:
+            if v != np.round(v / q) * q:
+                raise ValueError('fixed[%r]: %r is not on the grid of step %r' % (label, value, q))
+            if log:
+                lo = max(lo, 0.0)
+            if v + q / 2.0 < lo or v - q / 2.0 > hi or (log and not v + q / 2.0 > 0.0):
+                raise ValueError("fixed[%r]: the rounding interval of %r misses the label's support"
+                                 % (label, value))
+        out[label] = _labels.coerce(s.kind, v)
+    return out
+
+
+def _startup_docs(new_ids, domain, trials, seed, fixed):
+    """The startup phase's documents: rand.suggest's, unchanged, without
+    `fixed`; with it the same prior draws with the fixed labels held
+    (labels.sample_config: a fixed label consumes no random numbers, the
+    others are drawn in rand.suggest's order from one RandomState(seed))."""
+    if not fixed:
+        return rand.suggest(new_ids, domain, trials, seed)      # tpe.py:869-871
+    rng = np.random.RandomState(seed)
+    specs = specs_of(domain)
+    rval = []
+    for new_id in new_ids:
+        values = _labels.sample_config(domain.expr, specs, rng, fixed)
+        idxs = {k: ([new_id] if k in values else []) for k in specs}
+        vals = {k: ([values[k]] if k in values else []) for k in specs}
+        misc = dict(tid=new_id, cmd=domain.cmd, workdir=domain.workdir)
+        miscs_update_idxs_vals([misc], idxs, vals)
+        rval.extend(trials.new_trial_docs([new_id], [None], [domain.new_result()], [misc]))
+    return rval
+
+
 def _joint_rounds(eng, domain, trials, specs, gathered, gamma, prior_weight, seed, ids, n_candidates,
-                  group=False, quantized=False, categorical=False, view=None, bandwidth='neighbour'):
+                  group=False, quantized=False, categorical=False, view=None, bandwidth='neighbour',
+                  fixed=None):
     """One joint round per id and joint group: [label -> value] per id, or
     None when the call falls back to the independent path.  group=False: the
     unconditional group alone (joint_group), slot 0; group=True: every group
@@ -359,7 +435,17 @@ def _joint_rounds(eng, domain, trials, specs, gathered, gamma, prior_weight, see
     bandwidth: the rule of the groups' sigmas (posterior.JOINT_BANDWIDTHS),
     handed to both builders.  Under 'scott' no sorted position enters a
     mixture, so the device flags no tie: the groups with tied observations
-    (the rule for quantized labels) stay on the device."""
+    (the rule for quantized labels) stay on the device.
+
+    fixed (label -> value, validated: check_fixed): a group all of whose
+    labels are fixed is not built; a group with fixed and free labels is
+    built like any other, by either builder, and then conditioned in place
+    on the device (Engine.joint_condition): its slot holds the free labels in
+    their order in the group, and its winner's columns are theirs (one
+    logger.info line says how many groups were conditioned).  Groups without
+    a fixed label are untouched.  The fixed labels' values are the caller's
+    to put into the document."""
+    fixed = fixed or {}
     kinds = _post.JOINT_KINDS + (_post.JOINT_QUANT_KINDS if quantized else ()) + \
         (_post.JOINT_CAT_KINDS if categorical else ())
     labels = list(specs)
@@ -373,6 +459,7 @@ def _joint_rounds(eng, domain, trials, specs, gathered, gamma, prior_weight, see
         groups = [(0, g)] if g is not None else []
     if group and not groups:
         logger.info('multivariate TPE: no joint group, using the independent path')
+    groups = [(slot, g) for slot, g in groups if not all(k in fixed for k in g)]
     if not groups:
         return None
     eng.clear_joint_groups()
@@ -395,12 +482,21 @@ def _joint_rounds(eng, domain, trials, specs, gathered, gamma, prior_weight, see
                                       streams=[labels.index(k) for k in g], quantized=quantized,
                                       categorical=categorical, bandwidth=bandwidth)
             eng.set_joint_group(slot, _engine.L.TPE_JOINT_STREAM - slot, *mix, prior_weight=prior_weight)
+    free = {slot: [k for k in g if k not in fixed] for slot, g in groups}
+    if fixed:
+        n_cond = 0
+        for slot, g in groups:
+            held = [k for k in g if k in fixed]
+            if held:
+                eng.joint_condition(slot, [g.index(k) for k in held], [float(fixed[k]) for k in held])
+                n_cond += 1
+        logger.info('multivariate TPE: %d group(s) conditioned on fixed labels' % n_cond)
     won = eng.joint_suggest_batch(seed, ids, n_candidates)
     out = [{} for _ in ids]
     for slot, g in groups:
         values = won[slot][0]
         for j in range(len(ids)):
-            out[j].update({k: _labels.coerce(specs[k].kind, v) for k, v in zip(g, values[j])})
+            out[j].update({k: _labels.coerce(specs[k].kind, v) for k, v in zip(free[slot], values[j])})
     return out
 
 
@@ -412,7 +508,7 @@ def suggest(new_ids, domain, trials, seed,
             linear_forgetting=_default_linear_forgetting,
             precision='f64', device=0, batch=False, posterior_builder='auto', devices=None,
             multivariate=False, group=False, joint_quantized=False, joint_categorical=False,
-            joint_bandwidth='neighbour'):
+            joint_bandwidth='neighbour', fixed=None):
     """tpe.py:823-916.  Past the startup phase one document for new_ids[0],
     like the reference; `batch` (not in the reference) asks for one document
     per new_id:
@@ -510,6 +606,29 @@ def suggest(new_ids, domain, trials, seed,
     still goes to the host.  With the default every call returns the
     documents it always did.
 
+    fixed={label: value} (not in the reference; Optuna's PartialFixedSampler,
+    BoTorch's fixed_features) asks for the suggestion with those
+    hyperparameters already decided; it applies to every new id of the call
+    and composes with every other keyword.  The values are validated first
+    (check_fixed: ValueError before any engine is touched) and enter the
+    document through labels.coerce; the active labels are resolved from the
+    final values, so a fixed hp.choice index selects its branch and a fixed
+    label under a branch the document does not enter is dropped.  A fixed
+    label outside every joint group (all of them with multivariate=False)
+    still runs its independent round and its winner is replaced: every other
+    label's value is the unfixed call's, bit for bit.  In a joint group the
+    free labels come from the group's conditional density given the fixed
+    ones -- the point of modelling them together: each side's mixture keeps
+    its kernels and re-weights them by the fixed dimensions' factors, W'_k ~
+    W_k prod_{d fixed} g_kd(x_d), on the device (Engine.joint_condition,
+    DESIGN.md section 6b, "Fixed hyperparameters"), after either builder;
+    a group all of whose labels are fixed is not built, one without a fixed
+    label is untouched.  During the startup phase the documents are prior
+    draws with the fixed labels held (a fixed choice selects the branch that
+    is sampled; a fixed label consumes no random numbers, the others are
+    drawn in rand.suggest's order).  fixed=None and fixed={} return what the
+    call returns without the keyword.
+
     precision='f32' runs the exact fp64 path: a round draws every candidate
     and proves all but ~0.5 % of them out of the race from per-sub-bin score
     bounds before any lpdf is summed, so scoring the rest in fp32 would save
@@ -517,6 +636,8 @@ def suggest(new_ids, domain, trials, seed,
     winner; the fp32 lpdf contract (1e-4 relative) holds trivially.  The raw
     fp32 round stays available as Engine(precision='f32')."""
     t0 = time.time()
+    specs = specs_of(domain)
+    fixed = check_fixed(specs, fixed)   # (first: nothing else has run when it raises)
     if precision not in ('f64', 'f32'):
         raise ValueError("precision must be 'f64' or 'f32'")
     if posterior_builder not in ('auto', 'host', 'device'):
@@ -545,7 +666,8 @@ def suggest(new_ids, domain, trials, seed,
               precision=precision, device=device, posterior_builder=posterior_builder,
               devices=devices, multivariate=multivariate, group=group, joint_quantized=joint_quantized,
               joint_categorical=joint_categorical, joint_bandwidth=joint_bandwidth)
-    specs = specs_of(domain)
+    if fixed:   # (an empty one is not handed on)
+        kw['fixed'] = fixed
     labels = list(specs)
     # the device-resident history's view of the trials (None when the fast
     # layout does not apply); otherwise the general gather
@@ -564,7 +686,7 @@ def suggest(new_ids, domain, trials, seed,
         # then one TPE call per remaining id, each seeing the earlier ones
         # as pending trials
         k = max(0, min(len(new_ids), n_startup_jobs - n_docs))
-        rval = list(rand.suggest(list(new_ids[:k]), domain, trials, seed)) if k else []
+        rval = list(_startup_docs(list(new_ids[:k]), domain, trials, seed, fixed)) if k else []
         if k < len(new_ids):
             pview = _PendingView(trials)
             pview.trials.extend(rval)
@@ -574,7 +696,7 @@ def suggest(new_ids, domain, trials, seed,
                 rval.extend(docs)
         return rval
     if n_docs < n_startup_jobs:
-        return rand.suggest(new_ids, domain, trials, seed)      # tpe.py:869-871
+        return _startup_docs(new_ids, domain, trials, seed, fixed)
     if n_docs == 0:
         logger.info('TPE using 0 trials')                     # the prior-only posterior
     # a pending view (batch='pending') keeps its own context: its history
@@ -602,11 +724,12 @@ def suggest(new_ids, domain, trials, seed,
     joint = _joint_rounds(eng, domain, trials, specs, gathered, gamma, prior_weight, seed, ids,
                           n_EI_candidates, group=group, quantized=bool(joint_quantized),
                           categorical=bool(joint_categorical), view=jview,
-                          bandwidth=joint_bandwidth) if multivariate else None
+                          bandwidth=joint_bandwidth, fixed=fixed) if multivariate else None
     rval = []
     for j, new_id in enumerate(ids):
         values = {s.label: _labels.coerce(s.kind, res[j][i]['value'])
                   for i, s in enumerate(specs.values())}
+        values.update(fixed)
         if joint is not None:
             values.update(joint[j])
         rval.extend(_doc(new_id, domain, trials, specs, values))

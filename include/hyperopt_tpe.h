@@ -419,7 +419,8 @@ int tpe_import_posterior(tpe_ctx *ctx, const void *d_blobs, int64_t blob_bytes, 
  * separate from the resident per-label posterior.
  *
  * Multi-device contexts (tpe_ctx_create_multi), label-sharded or not, hold
- * every joint posterior on every device: tpe_joint_set_group and
+ * every joint posterior on every device: tpe_joint_set_group,
+ * tpe_joint_condition_group and
  * tpe_joint_clear_groups run on all of them (the fold is deterministic, so
  * the replicas are the same bits; an error on any device, TPE_ERR_SAMPLE
  * included, is the call's), and tpe_joint_build_groups builds every replica
@@ -516,6 +517,39 @@ int tpe_joint_set_group(tpe_ctx *ctx, int32_t slot, uint32_t pick_stream, const 
                         double prior_weight, int32_t n_dims, int32_t n_below, const double *wb,
                         const double *mub, const double *sigb, int32_t n_above, const double *wa,
                         const double *mua, const double *siga);
+/* Condition a set slot on the values of some of its dimensions ("suggest with
+ * these hyperparameters held fixed"): dst_slot receives the group over the
+ * free dimensions R of src_slot, in their source order, given the n_fixed
+ * dimensions F = dims[] (distinct indices of the source) at values[] -- label
+ * values as documents carry them: x, not log x; a category index as a double.
+ * A mixture of product kernels conditions in closed form: each side's
+ * conditional is again a mixture of product kernels over R whose components
+ * keep their means and sigmas (the free columns are copied bit for bit), and
+ * only the weights change,
+ *   L_k  = log W_k + sum_{d in F} log g_kd(x_d),
+ *   lse  = L_max + log(sum_k exp(L_k - L_max)),
+ *   W'_k = max(exp(L_k - lse), 2^-1022),
+ * g_kd the factor tpe_joint_set_group defines for the dimension: phi(y_d; mu_kd,
+ * s_kd) in the working space (dense), the rounding-interval mass (quantized),
+ * r_kd[x_d] (categorical, a_Sd with the source's K_S, which does not change).
+ * The floor keeps log W'_k finite for the fold (it adds at most K 2^-1022 of
+ * relative mass); a component with L_k = -inf (an empty quantized interval)
+ * takes it.  The truncation needs nothing more: A_S is the fold's, over R, and
+ * lpdf_S(x_R | x_F) differs from the source's lpdf_S(x_F, x_R) by a constant, so
+ * the conditioned slot's scores order candidates as the source orders them at
+ * x_F.  dst_slot keeps the source's pick stream, each free dimension's stream,
+ * q, upper, cat_p, the prior weight and both component counts: it is the slot
+ * tpe_joint_set_group(W', free columns) makes.  dst_slot == src_slot conditions
+ * in place, with the same result.  The sums run over one fixed tree per side
+ * (no atomics), so equal sources give equal bits on every device.
+ * TPE_ERR_ARG: a slot out of range or src_slot not set; n_fixed outside
+ * [1, n_dims - 1]; a repeated or out-of-range dimension; a NULL pointer.
+ * TPE_ERR_VALUE: a NaN value; every component of a side has L_k = -inf (a value
+ * no component reaches) -- the destination is left as it was.  TPE_ERR_SAMPLE
+ * as tpe_joint_set_group.  A multi-device context conditions every device's
+ * replica; an error on any device is the call's. */
+int tpe_joint_condition_group(tpe_ctx *ctx, int32_t src_slot, int32_t dst_slot, int32_t n_fixed,
+                              const int32_t *dims, const double *values);
 /* Unset every slot (their buffers are kept for the next posterior). */
 int tpe_joint_clear_groups(tpe_ctx *ctx);
 /* Joint groups built on the device from the current build of the resident

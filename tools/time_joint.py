@@ -7,6 +7,7 @@
     python tools/time_joint.py --build [--legs device_build,...] [--dims 32] [--trials 10000] [--reps 20] [--out FILE]
     python tools/time_joint.py --no-timings --quality-bandwidth [--out FILE]
     python tools/time_joint.py --devices 0,0 --quantized --legs dense | --build [--out FILE]
+    python tools/time_joint.py --fixed [--dims 32] [--trials 10000] [--fix 8] [--reps 20] [--out FILE]
 
 On a synthetic history of `--trials` trials over `--dims` dense continuous
 labels (kinds cycled over uniform / loguniform / normal / lognormal):
@@ -70,6 +71,13 @@ Engine.joint_last_shards), the joint build behind a label-sharded univariate
 build; the tpe.suggest legs of --build get devices=[...] too.  Two contexts on
 one GPU show what the fork, the merge and the duplicated launches cost, not a
 speed-up.
+
+--fixed: on the --dims x --trials history (default d32), after the device
+build of the group: Engine.joint_condition with the first --fix labels held
+(fixed_timings) against what it replaces -- Engine.joint_get_group of both
+sides, the rule in numpy, Engine.set_joint_group of the result -- and a whole
+tpe.suggest(multivariate=True) call with and without fixed=.  Medians, the
+smallest and the largest of --reps calls.  --devices applies.
 
 Prints one JSON document (and writes it to --out).
 """
@@ -474,6 +482,101 @@ def build_timings(reps, n_dims=32, n_trials=10000, legs=BUILD_LEGS):
     return res
 
 
+FIXED_VALUE = {'uniform': 1.75, 'loguniform': 0.4, 'normal': 0.25, 'lognormal': 1.5}
+
+
+def numpy_condition(group, fixed, values, side):
+    """The conditioning rule on one side's read-back arrays (dense labels):
+    (W', the free columns of mu and sigma)."""
+    W, mu, sig = side
+    with np.errstate(divide='ignore'):
+        L = np.log(W)
+    for d, x in zip(fixed, values):
+        y = np.log(x) if group[d][1] in ('loguniform', 'lognormal') else x
+        z = (y - mu[:, d]) / sig[:, d]
+        L = L - 0.5 * z * z - np.log(sig[:, d] * 2.50662827463100050242)
+    top = np.max(L)
+    rel = L - (top + np.log(np.sum(np.exp(L - top))))
+    free = [d for d in range(len(group)) if d not in fixed]
+    return (np.maximum(np.exp(rel), 2.0 ** -1022), np.ascontiguousarray(mu[:, free]),
+            np.ascontiguousarray(sig[:, free]))
+
+
+def fixed_timings(reps, n_dims=32, n_trials=10000, n_fixed=8):
+    """Engine.joint_condition on the device-built d32 group with the first
+    n_fixed labels held, against the path it replaces, wall time of `reps`
+    calls after one warm-up call each:
+
+    * condition: joint_condition(0, ..., dst=1) -- the three kernels, the
+      fold and the call's two synchronisations;
+    * get_group / numpy_rule / set_group: the read-back of both sides, the
+      rule in numpy on them, set_joint_group of the result (host_path: the
+      three in one call);
+    * suggest / suggest_fixed: a whole tpe.suggest(multivariate=True,
+      posterior_builder='device') call for one new id without and with
+      fixed= on that history as Trials.
+
+    Checks first that the conditioned slot and the host path's slot give the
+    same winner index and values to 1e-9."""
+    from hyperopt_amd import _lib as L
+    from hyperopt_amd import posterior as P, tpe, workloads
+    from hyperopt_amd.base import Domain
+    group, tids, losses, obs = history(n_dims, n_trials)
+    dev_kw = dict(devices=list(DEVICES)) if DEVICES else {}
+
+    class Owner(object):
+        pass
+    view = (tids, losses, n_trials, obs, Owner())
+    eng = make_engine()
+    P.DeviceHistoryUploader().build(eng, group, view, 0.25, 1.0)
+    ids = list(range(n_dims))
+    args = [(0, L.TPE_JOINT_STREAM, ids, ids)]
+    assert not eng.build_joint_groups(args)[0], 'the device flagged the timing history'
+    fixed = list(range(n_fixed))
+    values = [FIXED_VALUE[group[d][1]] for d in fixed]
+    free = [d for d in ids if d not in fixed]
+    dims = P.joint_mixture(group, obs, P.Splitter(tids, losses, 0.25), 1.0).dims[free]
+
+    def host_path():
+        b, a = (numpy_condition(group, fixed, values, eng.joint_get_group(0, side)) for side in (0, 1))
+        eng.set_joint_group(2, L.TPE_JOINT_STREAM, dims, *(b + a))
+    eng.joint_condition(0, fixed, values, dst=1)
+    host_path()
+    won_dev, won_host = eng.joint_suggest(1, 24, round=5, slot=1), eng.joint_suggest(1, 24, round=5, slot=2)
+    assert won_dev[1] == won_host[1] and np.allclose(won_dev[0], won_host[0], rtol=1e-9, atol=0.0)
+
+    def spread(fn, n):
+        fn()
+        out = []
+        for _ in range(n):
+            t = time.perf_counter()
+            fn()
+            out.append((time.perf_counter() - t) * 1e3)
+        return dict(median_ms=float(np.median(out)), min_ms=float(np.min(out)), max_ms=float(np.max(out)), reps=n)
+    sides = [eng.joint_get_group(0, side) for side in (0, 1)]
+    cond = [numpy_condition(group, fixed, values, s) for s in sides]
+    res = dict(dims=n_dims, trials=n_trials, fixed=n_fixed, k_below=len(sides[0][0]), k_above=len(sides[1][0]))
+    if DEVICES:
+        res['devices'] = list(DEVICES)
+    res['device_build'] = spread(lambda: eng.build_joint_groups(args), reps)
+    res['condition'] = spread(lambda: eng.joint_condition(0, fixed, values, dst=1), reps)
+    res['get_group'] = spread(lambda: [eng.joint_get_group(0, side) for side in (0, 1)], reps)
+    res['numpy_rule'] = spread(lambda: [numpy_condition(group, fixed, values, s) for s in sides], reps)
+    res['set_group'] = spread(lambda: eng.set_joint_group(2, L.TPE_JOINT_STREAM, dims, *(cond[0] + cond[1])), reps)
+    res['host_path'] = spread(host_path, reps)
+    res['host_path_over_condition'] = res['host_path']['median_ms'] / res['condition']['median_ms']
+    eng.close()
+    hist = workloads.History(group, tids, losses, obs)
+    domain = Domain(lambda d: 0.0, workloads.hp_space(group))
+    held = {group[d][0]: v for d, v in zip(fixed, values)}
+    for leg, kw in (('suggest', {}), ('suggest_fixed', dict(fixed=held))):
+        trials = workloads.history_trials(hist)
+        kw = dict(kw, **dev_kw)
+        res[leg] = spread(lambda: tpe.suggest([n_trials], domain, trials, 3, multivariate=True,
+                                              posterior_builder='device', **kw), reps)
+    return res
+
+
 def quality_bandwidth(evals=100, seeds=10):
     """The three quality objectives above with joint_bandwidth 'neighbour' and
     'scott' (each with the joint keyword its space needs), and the independent
@@ -589,6 +692,8 @@ def main(argv):
     ap.add_argument('--categorical', action='store_true', help='the dense and categorical d32 legs')
     ap.add_argument('--quality-categorical', action='store_true')
     ap.add_argument('--build', action='store_true', help='the device joint build against the host build')
+    ap.add_argument('--fixed', action='store_true', help='Engine.joint_condition against the host path it replaces')
+    ap.add_argument('--fix', type=int, default=8, help='--fixed: how many labels are held')
     ap.add_argument('--quality-bandwidth', action='store_true',
                     help="the three quality objectives with joint_bandwidth 'neighbour' and 'scott'")
     ap.add_argument('--legs', default=None,
@@ -610,6 +715,8 @@ def main(argv):
         res['categorical'] = categorical_timings(a.reps, legs=tuple((a.legs or 'dense,categorical').split(',')))
     elif a.build:
         res['build'] = build_timings(a.reps, a.dims, a.trials, legs=tuple(a.legs.split(',')) if a.legs else BUILD_LEGS)
+    elif a.fixed:
+        res['fixed'] = fixed_timings(a.reps, a.dims, a.trials, a.fix)
     elif not a.no_timings:
         res['timings'] = timings(a.dims, a.trials, a.reps)
     if a.quality:
