@@ -187,6 +187,11 @@ SIGNATURES = {
     'tpe_joint_suggest_group': (ctypes.c_int, [_P, _I32, _U64, _U32, _I64, _P, _P, _PD, _PD]),
     'tpe_joint_suggest_batch': (ctypes.c_int, [_P, _U64, _P, _I32, _I64, _P, _P, _P, _P]),
     'tpe_joint_last_shards': (ctypes.c_int, [_P, ctypes.POINTER(_I32), ctypes.POINTER(_I32)]),
+    'tpe_pool_set': (ctypes.c_int, [_P, _P, _I64, _I32]),
+    'tpe_pool_clear': (ctypes.c_int, [_P]),
+    'tpe_pool_size': (ctypes.c_int, [_P, ctypes.POINTER(_I64), ctypes.POINTER(_I32)]),
+    'tpe_pool_rank': (ctypes.c_int, [_P, _I32, _P, _P, _P, _P, _I64, _I32, _P, _P, ctypes.POINTER(_I32), _P, _P,
+                                     _P]),
 }
 
 _lib = None

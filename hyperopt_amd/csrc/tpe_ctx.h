@@ -617,6 +617,9 @@ struct tpe_ctx {
     // alone, 1 candidate shards, 2 round shards; the devices that ran one
     int32_t joint_shard_mode = 0, joint_shard_devs = 1;
 
+    // the resident candidate pool and its ranking scratch (tpe_pool.hip)
+    std::shared_ptr<void> pool;
+
     int fail(int code, const std::string& m) {
         err = m;
         return code;
@@ -781,12 +784,24 @@ TPE_DEV int tpe1_joint_draw_group(tpe_ctx* ctx, int32_t slot, uint64_t seed, uin
                                   int64_t cand_offset, double* values, int32_t* comp);
 TPE_DEV int tpe1_joint_score_group(tpe_ctx* ctx, int32_t slot, const double* values, int64_t n, double* ll,
                                    double* lg);
+TPE_DEV int tpe1_joint_score_device(tpe_ctx* ctx, int32_t slot, const double* d_values, int64_t n, double** d_ll,
+                                    double** d_lg);
 TPE_DEV int tpe1_joint_suggest_group(tpe_ctx* ctx, int32_t slot, uint64_t seed, uint32_t round,
                                      int64_t n_candidates, int64_t cand_offset, double* values, int64_t* index,
                                      double* ll, double* lg);
 TPE_DEV int tpe1_joint_suggest_batch(tpe_ctx* ctx, uint64_t seed, const uint32_t* rounds, int32_t n_rounds,
                                      int64_t n_candidates, int64_t cand_offset, double* values, int64_t* index,
                                      double* ll, double* lg);
+}
+// the resident candidate pool of one device (tpe_pool.hip)
+extern "C" {
+TPE_DEV int tpe1_pool_set(tpe_ctx* ctx, const double* values, int64_t n, int32_t n_cols);
+TPE_DEV int tpe1_pool_clear(tpe_ctx* ctx);
+TPE_DEV int tpe1_pool_size(const tpe_ctx* ctx, int64_t* n, int32_t* n_cols);
+TPE_DEV int tpe1_pool_rank(tpe_ctx* ctx, int32_t n_groups, const int32_t* slots, const int64_t* group_off,
+                           const int32_t* group_cols, const int64_t* taken, int64_t n_taken, int32_t top_k,
+                           int64_t* top_index, double* top_score, int32_t* n_top, double* score,
+                           double* lpdf_below, double* lpdf_above);
 }
 // the set slots of a context, ascending (only >= 0: that slot alone): their
 // dimensions into D[TPE_JOINT_MAX_GROUPS], their number back

@@ -1024,8 +1024,9 @@ constexpr int64_t kJFlatCap = (int64_t)1 << 20;
 // their flat count): every candidate's lpdfs, no bests
 int launch_round(tpe_ctx* ctx, JointGroups* G, JointState* J, bool sample, int64_t n, int64_t cand_offset,
                  uint64_t seed, uint32_t round, bool lpdfs, int32_t* nparts, int32_t* err,
-                 const uint32_t* rounds = nullptr, uint32_t ncell = 0) {
+                 const uint32_t* rounds = nullptr, uint32_t ncell = 0, const double* vals_dev = nullptr) {
     const int D = J->D;
+    const double* vals_in = vals_dev ? vals_dev : G->vals.p;   // supplied candidates: the caller's device array
     const bool qv = J->quant || J->cat;   // the quantized variant
     const int S = qv ? J->S : D;   // values a lane keeps in LDS (dr == 0)
     const int dr = qv ? 0 : (D <= kJRegSmall ? kJRegSmall : (D <= kJReg ? kJReg : 0));
@@ -1065,7 +1066,7 @@ int launch_round(tpe_ctx* ctx, JointGroups* G, JointState* J, bool sample, int64
                                split ? nullptr : olg, parts, err);                                              \
         else                                                                                                    \
             hipLaunchKernelGGL((k_joint_round<DR, TABC, false __VA_ARGS__>), grid, dim3(threads), lds, ctx->stream, p, \
-                               J->rec.p, J->cst.p, G->vals.p, n, cand_offset, seed, round, rounds, ncell,       \
+                               J->rec.p, J->cst.p, vals_in, n, cand_offset, seed, round, rounds, ncell,         \
                                (int32_t)split, G->part.p, G->aux.p, split ? nullptr : oll,                      \
                                split ? nullptr : olg, parts, err);                                              \
     } while (0)
@@ -2021,6 +2022,28 @@ int tpe1_joint_score_group(tpe_ctx* ctx, int32_t slot, const double* values, int
     HIPCHK(ctx, hipMemcpyAsync(ll, G->ll.p, n * sizeof(double), hipMemcpyDeviceToHost, ctx->stream));
     HIPCHK(ctx, hipMemcpyAsync(lg, G->lg.p, n * sizeof(double), hipMemcpyDeviceToHost, ctx->stream));
     HIPCHK(ctx, hipStreamSynchronize(ctx->stream));
+    return TPE_OK;
+}
+
+// tpe1_joint_score_group on configurations already on the device (d_values[n D],
+// complete on the context's stream): the round is queued, nothing is waited
+// for, and *d_ll / *d_lg are the slot scratch that will hold the lpdfs -- valid
+// until the next joint call on the context (tpe_pool.hip copies them out on the
+// same stream before it scores its next group)
+int tpe1_joint_score_device(tpe_ctx* ctx, int32_t slot, const double* d_values, int64_t n, double** d_ll,
+                            double** d_lg) {
+    if (!ctx) return TPE_ERR_ARG;
+    JointGroups* G = nullptr;
+    JointState* J = nullptr;
+    int rc = joint_ready(ctx, slot, &G, &J, "tpe_pool_rank");
+    if (rc) return rc;
+    if (!d_values || !d_ll || !d_lg) return ctx->fail(TPE_ERR_ARG, "null pointer");
+    if ((rc = check_range(ctx, n, 0))) return rc;
+    HIPCHK(ctx, hipSetDevice(ctx->device));
+    int32_t nparts = 0;
+    if ((rc = launch_round(ctx, G, J, false, n, 0, 0, 0, true, &nparts, G->err.p, nullptr, 0, d_values))) return rc;
+    *d_ll = G->ll.p;
+    *d_lg = G->lg.p;
     return TPE_OK;
 }
 

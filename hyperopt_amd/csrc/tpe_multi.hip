@@ -964,6 +964,26 @@ int tpe_joint_suggest_batch(tpe_ctx* ctx, uint64_t seed, const uint32_t* rounds,
         values, index, ll, lg);
 }
 
+// the candidate pool lives on one device: a multi-device context refuses it
+int tpe_pool_set(tpe_ctx* ctx, const double* values, int64_t n, int32_t n_cols) {
+    if (!ctx) return TPE_ERR_ARG;
+    if (!ctx->peers.empty()) return ctx->fail(TPE_ERR_ARG, "tpe_pool_set: not available on a multi-device context");
+    return tpe1_pool_set(ctx, values, n, n_cols);
+}
+
+int tpe_pool_clear(tpe_ctx* ctx) { return tpe1_pool_clear(ctx); }
+
+int tpe_pool_size(const tpe_ctx* ctx, int64_t* n, int32_t* n_cols) { return tpe1_pool_size(ctx, n, n_cols); }
+
+int tpe_pool_rank(tpe_ctx* ctx, int32_t n_groups, const int32_t* slots, const int64_t* group_off,
+                  const int32_t* group_cols, const int64_t* taken, int64_t n_taken, int32_t top_k, int64_t* top_index,
+                  double* top_score, int32_t* n_top, double* score, double* lpdf_below, double* lpdf_above) {
+    if (!ctx) return TPE_ERR_ARG;
+    if (!ctx->peers.empty()) return ctx->fail(TPE_ERR_ARG, "tpe_pool_rank: not available on a multi-device context");
+    return tpe1_pool_rank(ctx, n_groups, slots, group_off, group_cols, taken, n_taken, top_k, top_index, top_score,
+                          n_top, score, lpdf_below, lpdf_above);
+}
+
 int tpe_joint_last_shards(const tpe_ctx* ctx, int32_t* mode, int32_t* n_devices) {
     if (!ctx) return TPE_ERR_ARG;
     if (mode) *mode = ctx->joint_shard_mode;

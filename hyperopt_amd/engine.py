@@ -681,6 +681,62 @@ class Engine(object):
                                        _ptr(la), _ptr(out)))
         return lb, la, out[0]
 
+    # -- candidate pools ------------------------------------------------------
+    def pool_set(self, values):
+        """Upload a pool of whole configurations (tpe_pool_set): values [n, L]
+        float64, one column per label of the posterior, NaN where the label
+        is not active.  It stays on the device across posterior rebuilds."""
+        values = _f64(values)
+        if values.ndim != 2:
+            raise ValueError('values must be [n, n_labels]')
+        self._check(self.lib.tpe_pool_set(self.h, _ptr(values), values.shape[0], values.shape[1]))
+        self.pool_token = None   # (tpe.suggest's: whose pool this is)
+
+    def pool_clear(self):
+        self._check(self.lib.tpe_pool_clear(self.h))
+        self.pool_token = None
+
+    def pool_size(self):
+        """(n, n_cols) of the resident pool, (0, 0) without one."""
+        n, c = ctypes.c_int64(), ctypes.c_int32()
+        self._check(self.lib.tpe_pool_size(self.h, ctypes.byref(n), ctypes.byref(c)))
+        return int(n.value), int(c.value)
+
+    def pool_rank(self, k, groups=None, taken=None, want_scores=False, want_terms=False):
+        """The k best entries of the resident pool under the current posterior
+        (tpe_pool_rank): (index [n_top], score [n_top]), best first in
+        broadcast_best's order, the entries listed in `taken` left out.
+        groups: [(slot, [columns])] -- joint groups whose ll - lg stands in
+        place of their columns' terms.  want_scores adds the score of every
+        entry [n]; want_terms the two lpdf planes [n, L + len(groups)]."""
+        groups = list(groups or [])
+        slots = np.ascontiguousarray([int(s) for s, _ in groups], dtype=np.int32)
+        off = np.zeros(len(groups) + 1, dtype=np.int64)
+        for g, (_, cols) in enumerate(groups):
+            off[g + 1] = off[g] + len(cols)
+        cols = np.ascontiguousarray([int(c) for _, cs in groups for c in cs], dtype=np.int32)
+        tk = np.ascontiguousarray([] if taken is None else taken, dtype=np.int64).ravel()
+        n, L_ = self.pool_size()
+        cap = max(0, min(int(k), n))
+        index = np.empty(max(cap, 1), dtype=np.int64)
+        top = np.empty(max(cap, 1))
+        n_top = ctypes.c_int32(0)
+        score = np.empty(n) if want_scores else None
+        lb = np.empty((n, L_ + len(groups))) if want_terms else None
+        la = np.empty((n, L_ + len(groups))) if want_terms else None
+        self._check(self.lib.tpe_pool_rank(self.h, len(groups), _ptr(slots) if len(groups) else None,
+                                           _ptr(off) if len(groups) else None,
+                                           _ptr(cols) if len(groups) else None,
+                                           _ptr(tk) if len(tk) else None, len(tk),
+                                           max(min(int(k), 2 ** 31 - 1), 0), _ptr(index),
+                                           _ptr(top), ctypes.byref(n_top), _ptr(score), _ptr(lb), _ptr(la)))
+        out = (index[:n_top.value].copy(), top[:n_top.value].copy())
+        if want_scores:
+            out += (score,)
+        if want_terms:
+            out += (lb, la)
+        return out
+
     def last_timing(self):
         a, b = ctypes.c_float(), ctypes.c_float()
         self._check(self.lib.tpe_last_timing(self.h, ctypes.byref(a), ctypes.byref(b)))

@@ -27,6 +27,9 @@ with `group=True` also those that share an hp.choice branch, one joint group
 per branch),
 `fixed` ({label: value}: the suggestion with those hyperparameters held; the
 free labels of a joint group then come from its conditional density),
+`pool` (a `Pool` of configurations: the suggestion is the untaken entry with
+the largest log l(x) - log g(x), ranked on the device; `pool_replace=True`
+takes no entry out),
 `precision` ('f64'; 'f32'
 is accepted and runs the same exact path -- see `suggest`), `device` (HIP ordinal), `devices` (a list of ordinals: one
 multi-device context splits every round over those GPUs, same documents as
@@ -42,6 +45,7 @@ for bit) or 'auto' (device once the history holds DEVICE_BUILD_MIN_OBS
 observations over all labels, where the host build starts to dominate the
 suggestion).
 """
+import itertools
 import logging
 import time
 
@@ -53,6 +57,7 @@ from . import labels as _labels
 from . import posterior as _post
 from . import rand
 from .base import miscs_update_idxs_vals
+from .space import as_apply
 
 logger = logging.getLogger(__name__)
 
@@ -118,7 +123,7 @@ def device_inputs(specs, tids, losses, obs):
     return _post.device_inputs(labels, tids, losses, obs)
 
 
-def _doc(new_id, domain, trials, specs, values):
+def _doc(new_id, domain, trials, specs, values, pool_index=None):
     flat = getattr(domain, '_hyperopt_amd_flat', None)
     if flat is None:
         flat = _labels.always_active(domain.expr)
@@ -130,6 +135,8 @@ def _doc(new_id, domain, trials, specs, values):
     idxs = {k: ([new_id] if k in active else []) for k in specs}
     vals = {k: ([values[k]] if k in active else []) for k in specs}
     misc = dict(tid=new_id, cmd=domain.cmd, workdir=domain.workdir)
+    if pool_index is not None:
+        misc['pool_index'] = pool_index
     miscs_update_idxs_vals([misc], idxs, vals)
     return trials.new_trial_docs([new_id], [None], [domain.new_result()], [misc])
 
@@ -350,39 +357,141 @@ def check_fixed(specs, fixed):
     for label, value in fixed.items():
         if label not in specs:
             raise ValueError('fixed: unknown label %r' % (label,))
-        s = specs[label]
-        try:
-            v = float(value)
-        except (TypeError, ValueError):
-            raise ValueError('fixed[%r]: %r is not a number' % (label, value))
-        if not np.isfinite(v):
-            raise ValueError('fixed[%r]: %r is not finite' % (label, value))
-        a = s.args
-        if s.kind in ('randint', 'categorical'):
-            if v != np.floor(v) or not 0 <= v < a['upper']:
-                raise ValueError('fixed[%r]: %r is not an integer in [0, %d)' % (label, value, a['upper']))
-            out[label] = _labels.coerce(s.kind, v)
-            continue
-        log = s.kind in ('loguniform', 'qloguniform', 'lognormal', 'qlognormal')
-        q = a.get('q')
-        lo, hi = -np.inf, np.inf
-        if 'low' in a:
-            lo, hi = (np.exp(a['low']), np.exp(a['high'])) if log else (a['low'], a['high'])
-        if q is None:
-            if log and not v > 0.0:
-                raise ValueError('fixed[%r]: %r is not positive' % (label, value))
-            if not lo <= v <= hi:
-                raise ValueError('fixed[%r]: %r is outside [%r, %r]' % (label, value, lo, hi))
-        else:
-            if v != np.round(v / q) * q:
-                raise ValueError('fixed[%r]: %r is not on the grid of step %r' % (label, value, q))
-            if log:
-                lo = max(lo, 0.0)
-            if v + q / 2.0 < lo or v - q / 2.0 > hi or (log and not v + q / 2.0 > 0.0):
-                raise ValueError("fixed[%r]: the rounding interval of %r misses the label's support"
-                                 % (label, value))
-        out[label] = _labels.coerce(s.kind, v)
+        out[label] = check_label_value(specs[label], value, 'fixed[%r]' % (label,))
     return out
+
+
+def check_label_value(s, value, who):
+    """One label's value as documents carry it (labels.coerce), after the
+    checks check_fixed lists for the label's kind -- s its LabelSpec; `who`
+    opens the ValueError's message (check_fixed: 'fixed[<label>]', Pool: the
+    entry and the label)."""
+    try:
+        v = float(value)
+    except (TypeError, ValueError):
+        raise ValueError('%s: %r is not a number' % (who, value))
+    if not np.isfinite(v):
+        raise ValueError('%s: %r is not finite' % (who, value))
+    a = s.args
+    if s.kind in ('randint', 'categorical'):
+        if v != np.floor(v) or not 0 <= v < a['upper']:
+            raise ValueError('%s: %r is not an integer in [0, %d)' % (who, value, a['upper']))
+        return _labels.coerce(s.kind, v)
+    log = s.kind in ('loguniform', 'qloguniform', 'lognormal', 'qlognormal')
+    q = a.get('q')
+    lo, hi = -np.inf, np.inf
+    if 'low' in a:
+        lo, hi = (np.exp(a['low']), np.exp(a['high'])) if log else (a['low'], a['high'])
+    if q is None:
+        if log and not v > 0.0:
+            raise ValueError('%s: %r is not positive' % (who, value))
+        if not lo <= v <= hi:
+            raise ValueError('%s: %r is outside [%r, %r]' % (who, value, lo, hi))
+    else:
+        if v != np.round(v / q) * q:
+            raise ValueError('%s: %r is not on the grid of step %r' % (who, value, q))
+        if log:
+            lo = max(lo, 0.0)
+        if v + q / 2.0 < lo or v - q / 2.0 > hi or (log and not v + q / 2.0 > 0.0):
+            raise ValueError("%s: the rounding interval of %r misses the label's support"
+                             % (who, value))
+    return _labels.coerce(s.kind, v)
+
+
+_pool_tokens = itertools.count(1)
+
+
+class Pool(object):
+    """A finite set of configurations for tpe.suggest(pool=...) to choose
+    from (a tabular benchmark, the architectures that fit, checkpoints that
+    exist): the suggestion is then the untaken entry with the largest
+    acquisition log l(x) - log g(x), not a draw from l.
+
+    space: the space given to fmin, or a Domain.  points: a non-empty list of
+    dicts label -> value, each holding exactly the labels active in that
+    configuration, in the form trials.argmin and space_eval use (an hp.choice
+    as its index).  ValueError, naming the entry and the label, for an unknown
+    label, a value check_fixed would refuse for the label, and an entry whose
+    labels are not labels.active_labels(expr, point).
+
+    values: [n, L] float64, NaN where a label is not active, columns in the
+    order of specs_of(domain); labels: that order; points: the validated
+    entries (values through labels.coerce); token: unique per object -- an
+    engine uploads the pool once and keeps it while the token is the same."""
+
+    def __init__(self, space, points):
+        if not _labels.is_node(space) and hasattr(space, 'expr'):   # a Domain
+            self.expr = space.expr
+            specs = specs_of(space)
+        else:
+            self.expr = as_apply(space)
+            specs = _labels.compile_space(self.expr)
+        points = list(points)
+        if not points:
+            raise ValueError('Pool: points must not be empty')
+        self.labels = list(specs)
+        col = {k: i for i, k in enumerate(self.labels)}
+        self.values = np.full((len(points), len(self.labels)), np.nan)
+        self.points = []
+        for i, point in enumerate(points):
+            if not isinstance(point, dict):
+                raise ValueError('Pool: entry %d is not a dict of label -> value' % i)
+            out = {}
+            for label, value in point.items():
+                if label not in specs:
+                    raise ValueError('Pool: entry %d: unknown label %r' % (i, label))
+                out[label] = check_label_value(specs[label], value, 'Pool: entry %d, label %r' % (i, label))
+            try:
+                active = _labels.active_labels(self.expr, out)
+            except KeyError as e:
+                raise ValueError('Pool: entry %d: label %r is active in this configuration and has no value'
+                                 % (i, e.args[0]))
+            if set(out) != active:
+                odd = sorted(set(out) ^ active)[0]
+                raise ValueError('Pool: entry %d: label %r is %s' % (
+                    i, odd, 'not active in this configuration' if odd in out
+                    else 'active in this configuration and has no value'))
+            for label, v in out.items():
+                self.values[i, col[label]] = float(v)
+            self.points.append(out)
+        self.token = ('pool', next(_pool_tokens))
+
+    def __len__(self):
+        return len(self.points)
+
+
+def pool_taken(pool, trials):
+    """The entries of `pool` the trials hold already, ascending: every index
+    some document of trials.trials, whatever its state, carries in
+    misc['pool_index'] (other values of that key are ignored)."""
+    taken = set()
+    for doc in trials.trials:
+        i = doc['misc'].get('pool_index')
+        if isinstance(i, (int, np.integer)) and not isinstance(i, bool) and 0 <= i < len(pool):
+            taken.add(int(i))
+    return sorted(taken)
+
+
+def _pool_doc(new_id, domain, trials, specs, pool, index):
+    return _doc(new_id, domain, trials, specs, dict(pool.points[index]), pool_index=int(index))
+
+
+def _pool_startup_docs(new_ids, domain, trials, seed, pool, taken):
+    """The startup phase over a pool: with rng = RandomState(seed), each new
+    id in order takes free[rng.randint(len(free))] of the untaken indices in
+    ascending order, and that index is removed; fewer documents when the pool
+    runs out."""
+    rng = np.random.RandomState(seed)
+    specs = specs_of(domain)
+    out_of = set(taken)
+    free = [i for i in range(len(pool)) if i not in out_of]
+    rval = []
+    for new_id in new_ids:
+        if not free:
+            break
+        index = free.pop(int(rng.randint(len(free))))
+        rval.extend(_pool_doc(new_id, domain, trials, specs, pool, index))
+    return rval
 
 
 def _startup_docs(new_ids, domain, trials, seed, fixed):
@@ -446,6 +555,37 @@ def _joint_rounds(eng, domain, trials, specs, gathered, gamma, prior_weight, see
     a fixed label are untouched.  The fixed labels' values are the caller's
     to put into the document."""
     fixed = fixed or {}
+    groups = _joint_build(eng, domain, trials, specs, gathered, gamma, prior_weight, group=group,
+                          quantized=quantized, categorical=categorical, view=view, bandwidth=bandwidth,
+                          fixed=fixed)
+    if not groups:
+        return None
+    free = {slot: [k for k in g if k not in fixed] for slot, g in groups}
+    if fixed:
+        n_cond = 0
+        for slot, g in groups:
+            held = [k for k in g if k in fixed]
+            if held:
+                eng.joint_condition(slot, [g.index(k) for k in held], [float(fixed[k]) for k in held])
+                n_cond += 1
+        logger.info('multivariate TPE: %d group(s) conditioned on fixed labels' % n_cond)
+    won = eng.joint_suggest_batch(seed, ids, n_candidates)
+    out = [{} for _ in ids]
+    for slot, g in groups:
+        values = won[slot][0]
+        for j in range(len(ids)):
+            out[j].update({k: _labels.coerce(specs[k].kind, v) for k, v in zip(free[slot], values[j])})
+    return out
+
+
+def _joint_build(eng, domain, trials, specs, gathered, gamma, prior_weight, group=False, quantized=False,
+                 categorical=False, view=None, bandwidth='neighbour', fixed=None):
+    """The building half of _joint_rounds, shared with the pool ranking: the
+    call's joint groups [(slot, [labels])], each built into its slot of the
+    engine by the device or the host as _joint_rounds describes -- or None
+    when there is none (the independent path).  Groups all of whose labels
+    are in `fixed` are left out; nothing is conditioned and no round runs."""
+    fixed = fixed or {}
     kinds = _post.JOINT_KINDS + (_post.JOINT_QUANT_KINDS if quantized else ()) + \
         (_post.JOINT_CAT_KINDS if categorical else ())
     labels = list(specs)
@@ -482,22 +622,7 @@ def _joint_rounds(eng, domain, trials, specs, gathered, gamma, prior_weight, see
                                       streams=[labels.index(k) for k in g], quantized=quantized,
                                       categorical=categorical, bandwidth=bandwidth)
             eng.set_joint_group(slot, _engine.L.TPE_JOINT_STREAM - slot, *mix, prior_weight=prior_weight)
-    free = {slot: [k for k in g if k not in fixed] for slot, g in groups}
-    if fixed:
-        n_cond = 0
-        for slot, g in groups:
-            held = [k for k in g if k in fixed]
-            if held:
-                eng.joint_condition(slot, [g.index(k) for k in held], [float(fixed[k]) for k in held])
-                n_cond += 1
-        logger.info('multivariate TPE: %d group(s) conditioned on fixed labels' % n_cond)
-    won = eng.joint_suggest_batch(seed, ids, n_candidates)
-    out = [{} for _ in ids]
-    for slot, g in groups:
-        values = won[slot][0]
-        for j in range(len(ids)):
-            out[j].update({k: _labels.coerce(specs[k].kind, v) for k, v in zip(free[slot], values[j])})
-    return out
+    return groups
 
 
 def suggest(new_ids, domain, trials, seed,
@@ -508,7 +633,7 @@ def suggest(new_ids, domain, trials, seed,
             linear_forgetting=_default_linear_forgetting,
             precision='f64', device=0, batch=False, posterior_builder='auto', devices=None,
             multivariate=False, group=False, joint_quantized=False, joint_categorical=False,
-            joint_bandwidth='neighbour', fixed=None):
+            joint_bandwidth='neighbour', fixed=None, pool=None, pool_replace=False):
     """tpe.py:823-916.  Past the startup phase one document for new_ids[0],
     like the reference; `batch` (not in the reference) asks for one document
     per new_id:
@@ -629,6 +754,33 @@ def suggest(new_ids, domain, trials, seed,
     drawn in rand.suggest's order).  fixed=None and fixed={} return what the
     call returns without the keyword.
 
+    pool=tpe.Pool(space, points) (not in the reference) restricts the call to
+    a finite set of configurations: the document is the pool entry with the
+    largest acquisition log l(x) - log g(x) -- the sum over the entry's active
+    labels of lpdf_below - lpdf_above under this call's posterior, a joint
+    group's ll - lg in place of its labels' terms under multivariate=True --
+    instead of a draw from l ("Candidate pools").  The
+    posterior is built exactly as without the keyword, by whichever builder
+    the call selects, and the joint groups with it; no round is drawn: one
+    Engine.pool_rank call ranks the whole pool, which the engine holds on the
+    device from the first call on (it is uploaded again only for another Pool
+    object).  An entry is taken when any document of trials.trials, whatever
+    its state, carries its index in misc['pool_index'], as the documents of
+    such a call do: the call is a function of the trials like every other,
+    fmin visits no entry twice, and batch='pending' keeps its sequential
+    meaning with nothing extra.  batch=True returns the K best distinct
+    entries of one ranking, best first.  During the startup phase each new id
+    in order takes free[rng.randint(len(free))] of the untaken indices in
+    ascending order, rng = RandomState(seed), without replacement.  The call
+    returns fewer documents than ids when the pool runs out and [] when
+    nothing is free, which ends fmin's run.  pool_replace=True takes nothing:
+    every call then ranks the whole pool.  n_EI_candidates is ignored with a
+    pool, and seed is read in the startup phase only.  ValueError, before any
+    engine is touched: pool with a non-empty fixed (filter the pool instead),
+    pool with more than one device, a pool whose labels are not the domain's,
+    pool_replace without a pool.  With pool=None every call returns what it
+    returned before.
+
     precision='f32' runs the exact fp64 path: a round draws every candidate
     and proves all but ~0.5 % of them out of the race from per-sub-bin score
     bounds before any lpdf is summed, so scoring the rest in fp32 would save
@@ -654,6 +806,17 @@ def suggest(new_ids, domain, trials, seed,
         raise ValueError('joint_bandwidth must be one of %r' % (_post.JOINT_BANDWIDTHS,))
     if joint_bandwidth != 'neighbour' and not multivariate:
         raise ValueError('joint_bandwidth=%r needs multivariate=True' % (joint_bandwidth,))
+    if pool_replace and pool is None:
+        raise ValueError('pool_replace=True needs a pool')
+    if pool is not None:
+        if not isinstance(pool, Pool):
+            raise ValueError('pool must be a tpe.Pool')
+        if fixed:
+            raise ValueError('pool with fixed: filter the pool instead')
+        if devices and len(list(devices)) > 1:
+            raise ValueError('pool with devices=%r: a pool is ranked on one device' % (list(devices),))
+        if pool.labels != list(specs):
+            raise ValueError("pool: its labels %r are not the domain's %r" % (pool.labels, list(specs)))
     if multivariate and devices and len(list(devices)) > 1:
         # every device holds a replica of every joint group and runs a shard
         # of every joint round: the call needs all of them, startup phase or not
@@ -668,6 +831,17 @@ def suggest(new_ids, domain, trials, seed,
               joint_categorical=joint_categorical, joint_bandwidth=joint_bandwidth)
     if fixed:   # (an empty one is not handed on)
         kw['fixed'] = fixed
+    taken = []
+    if pool is not None:
+        kw.update(pool=pool, pool_replace=pool_replace)
+        taken = [] if pool_replace else pool_taken(pool, trials)
+        if len(taken) == len(pool):
+            return []   # (nothing is free: fmin's _ask stops on an empty answer)
+
+    def startup_docs(ids):
+        if pool is not None:
+            return _pool_startup_docs(ids, domain, trials, seed, pool, taken)
+        return _startup_docs(ids, domain, trials, seed, fixed)
     labels = list(specs)
     # the device-resident history's view of the trials (None when the fast
     # layout does not apply); otherwise the general gather
@@ -686,7 +860,7 @@ def suggest(new_ids, domain, trials, seed,
         # then one TPE call per remaining id, each seeing the earlier ones
         # as pending trials
         k = max(0, min(len(new_ids), n_startup_jobs - n_docs))
-        rval = list(_startup_docs(list(new_ids[:k]), domain, trials, seed, fixed)) if k else []
+        rval = list(startup_docs(list(new_ids[:k]))) if k else []
         if k < len(new_ids):
             pview = _PendingView(trials)
             pview.trials.extend(rval)
@@ -696,7 +870,7 @@ def suggest(new_ids, domain, trials, seed,
                 rval.extend(docs)
         return rval
     if n_docs < n_startup_jobs:
-        return _startup_docs(new_ids, domain, trials, seed, fixed)
+        return startup_docs(new_ids)
     if n_docs == 0:
         logger.info('TPE using 0 trials')                     # the prior-only posterior
     # a pending view (batch='pending') keeps its own context: its history
@@ -712,6 +886,27 @@ def suggest(new_ids, domain, trials, seed,
             return eng.suggest(seed, n_EI_candidates, round=ids[0])[None]
         return eng.suggest_batch(seed, ids, n_EI_candidates)
     info = {}
+    if pool is not None:
+        # the posterior and the joint groups as below, by the same builders;
+        # no round: one ranking of the resident pool, its best entries to the
+        # ids in order
+        _resident_posterior(eng, domain, trials, specs, view, gathered, gamma, prior_weight,
+                            posterior_builder, info=info)
+        jview = view if (JOINT_DEVICE_BUILD and info.get('resident')) else None
+        groups = _joint_build(eng, domain, trials, specs, gathered, gamma, prior_weight, group=group,
+                              quantized=bool(joint_quantized), categorical=bool(joint_categorical),
+                              view=jview, bandwidth=joint_bandwidth) if multivariate else None
+        if getattr(eng, 'pool_token', None) != pool.token:
+            eng.pool_set(pool.values)
+            eng.pool_token = pool.token
+        index, _ = eng.pool_rank(len(ids), groups=[(slot, [labels.index(k) for k in g])
+                                                   for slot, g in groups or []], taken=taken)
+        rval = []
+        for new_id, i in zip(ids, index):
+            rval.extend(_pool_doc(new_id, domain, trials, specs, pool, int(i)))
+        logger.info('tpe.suggest: %d trials, %d labels, pool of %d (%d taken), %.1f ms' % (
+            n_docs, len(specs), len(pool), len(taken), (time.time() - t0) * 1e3))
+        return rval
     _, res = _resident_posterior(eng, domain, trials, specs, view, gathered, gamma, prior_weight,
                                  posterior_builder, n_candidates=n_EI_candidates, n_rounds=len(ids),
                                  round_call=round_call, info=info)

@@ -668,6 +668,65 @@ int tpe_joint_suggest_batch(tpe_ctx *ctx, uint64_t seed, const uint32_t *rounds,
  * Either pointer may be NULL. */
 int tpe_joint_last_shards(const tpe_ctx *ctx, int32_t *mode, int32_t *n_devices);
 
+/* ---- candidate pools ------------------------------------------------------
+ * Rank a finite, caller-supplied set of whole configurations under the
+ * current posterior (no reference counterpart: the reference only draws its
+ * candidates, tpe.py:686-724; the acquisition is the one broadcast_best ranks
+ * by, tpe.py:769-778, summed over a configuration's labels).
+ *
+ * tpe_pool_set uploads the pool once: values[n][n_cols] row-major, one column
+ * per label of the posterior it will be ranked under, NaN where the label is
+ * not active in the entry (a conditional branch not taken); values as documents
+ * carry them (x, not log x; a category index as a double).  It stays on the
+ * device, column-major, across tpe_set_posterior and every build, until the
+ * next tpe_pool_set, tpe_pool_clear or tpe_ctx_destroy.  tpe_pool_size reports
+ * it (0, 0: none).
+ *
+ * tpe_pool_rank, for every entry i:
+ *   term of an active column c (value v): lb - la, lb and la the lpdfs
+ *       tpe_score(ctx, c, v) defines under the resident posterior, one fp64
+ *       subtraction;
+ *   a listed joint group g (slot slots[g], set by tpe_joint_set_group or a
+ *       device build) covers the columns group_cols[group_off[g] ..
+ *       group_off[g + 1]): they get no term of their own, the group's lb, la
+ *       are tpe_joint_score_group's ll, lg on those columns in that order, and
+ *       the group is inactive for an entry with a NaN in any of them;
+ *   score[i] = the fp64 sum, from 0.0 and left to right, of the uncovered
+ *       active columns' terms in ascending column order, then the listed
+ *       groups' in the order listed (no term: 0.0; a NaN term, e.g. -inf - -inf:
+ *       NaN).  One thread adds an entry's terms and every term is computed from
+ *       the entry's own value alone, so a score depends neither on n, on the
+ *       entry's position nor on the other entries; equal inputs give equal bits.
+ * The order is broadcast_best's: NaN greatest, then the larger score, then the
+ * lowest index.  Entries listed in taken[n_taken] are left out (duplicates and
+ * indices outside [0, n) are ignored); *n_top = min(top_k, entries not taken)
+ * pairs (top_index, top_score) are written, best first.  score (NULL, or [n])
+ * receives every entry's score, taken ones included; lpdf_below / lpdf_above
+ * (both NULL, or both [n][n_cols + n_groups] row-major) the terms' lpdfs,
+ * column n_cols + g the group g's, NaN in both for an inactive or covered
+ * cell.
+ * One stream synchronisation per call (the optional vectors are copied after
+ * it); nothing is uploaded but the arguments.
+ * TPE_ERR_ARG: no pool set; no posterior, or n_cols is not its label count; a
+ * slot that is unset or listed twice; a column out of range or in two groups;
+ * a group whose column count is not its slot's D; top_k < 1; n < 1 or
+ * n_cols < 1 (tpe_pool_set); a NULL pointer where one is needed; a TPE_F32
+ * context; a multi-device context (tpe_pool_set too).  TPE_ERR_VALUE: at
+ * tpe_pool_set a value of +-inf; at tpe_pool_rank what the plain round flags
+ * for a supplied candidate -- an active categorical value that is no integer
+ * in [0, upper), a quantized LGMM1 value whose interval's upper end is
+ * negative.  TPE_ERR_SAMPLE as tpe_joint_score_group.  On an error the
+ * outputs are untouched. */
+int tpe_pool_set(tpe_ctx *ctx, const double *values /* [n][n_cols] row-major, NaN = label not active */,
+                 int64_t n, int32_t n_cols);
+int tpe_pool_clear(tpe_ctx *ctx);
+int tpe_pool_size(const tpe_ctx *ctx, int64_t *n, int32_t *n_cols);
+int tpe_pool_rank(tpe_ctx *ctx, int32_t n_groups, const int32_t *slots, const int64_t *group_off /* [n_groups+1] */,
+                  const int32_t *group_cols, const int64_t *taken, int64_t n_taken, int32_t top_k,
+                  int64_t *top_index, double *top_score, int32_t *n_top,
+                  double *score /* [n] or NULL */,
+                  double *lpdf_below, double *lpdf_above /* [n][n_cols + n_groups] or NULL: diagnostics */);
+
 /* Score a caller-supplied candidate set for one resident label (the parity
  * entry point: identical candidates in, both lpdf vectors and the winner
  * out).  lpdf_below / lpdf_above may be NULL. */
