@@ -620,6 +620,9 @@ struct tpe_ctx {
     // the resident candidate pool and its ranking scratch (tpe_pool.hip)
     std::shared_ptr<void> pool;
 
+    // the reusable buffers of tpe_mo_keys (tpe_mo.hip)
+    std::shared_ptr<void> mo;
+
     int fail(int code, const std::string& m) {
         err = m;
         return code;

@@ -737,6 +737,23 @@ class Engine(object):
             out += (lb, la)
         return out
 
+    def mo_keys(self, F, want_counts=False):
+        """The Pareto-compliant order of the objective vectors F [n, M], all
+        minimised (tpe_mo_keys; posterior.mo_keys is its numpy restatement):
+        keys [n] float64 -- row i's position under ascending dominated_by,
+        descending dominates, ascending i; NaN for a row with a NaN.
+        want_counts adds (dominated_by, dominates) [n] int32, -1 for such a
+        row."""
+        F = np.ascontiguousarray(F, dtype=np.float64)
+        if F.ndim != 2:
+            raise ValueError('F must be [n, n_objectives]')
+        n = F.shape[0]
+        keys = np.empty(n)
+        by = np.empty(n, dtype=np.int32) if want_counts else None
+        do = np.empty(n, dtype=np.int32) if want_counts else None
+        self._check(self.lib.tpe_mo_keys(self.h, _ptr(F), n, F.shape[1], _ptr(keys), _ptr(by), _ptr(do)))
+        return (keys, by, do) if want_counts else keys
+
     def last_timing(self):
         a, b = ctypes.c_float(), ctypes.c_float()
         self._check(self.lib.tpe_last_timing(self.h, ctypes.byref(a), ctypes.byref(b)))

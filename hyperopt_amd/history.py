@@ -209,7 +209,13 @@ def raw_losses(domain, docs):
     """domain.loss(result, spec) of every doc (tpe.py:843), None kept.  The
     plain Domain.loss is result.get('loss') (base.py): read through C-level
     map()s when every result is a dict -- this loop is most of a
-    device-path suggestion's host time at 10k trials."""
+    device-path suggestion's host time at 10k trials.  A domain that holds
+    the whole column already (tpe.suggest(objectives=...): each complete
+    trial's key in the order of the objective vectors) hands it over through
+    its loss_column(docs)."""
+    column = getattr(domain, 'loss_column', None)
+    if column is not None:
+        return column(docs)
     if type(domain).loss is _plain_loss:
         try:
             return list(map(dict.get, map(_result_of, docs), repeat('loss')))
@@ -242,7 +248,9 @@ _result_of = itemgetter('result')
 _caches = weakref.WeakKeyDictionary()
 
 
-def gather(domain, trials, labels):
+def _cache_of(trials, labels):
+    """The per-Trials HistoryCache for these labels (a new one, uncached, for
+    trials that cannot be weakly referenced)."""
     key = tuple(labels)
     try:
         cache = _caches.get(trials)
@@ -254,23 +262,24 @@ def gather(domain, trials, labels):
             _caches[trials] = cache
         except TypeError:
             pass
-    return cache.gather(domain, trials)
+    return cache
+
+
+def gather(domain, trials, labels):
+    return _cache_of(trials, labels).gather(domain, trials)
 
 
 def device_view(domain, trials, labels):
     """HistoryCache.device_view through the per-Trials cache."""
-    key = tuple(labels)
-    try:
-        cache = _caches.get(trials)
-    except TypeError:
-        cache = None
-    if cache is None or cache.labels != list(key):
-        cache = HistoryCache(key)
-        try:
-            _caches[trials] = cache
-        except TypeError:
-            pass
-    return cache.device_view(domain, trials)
+    return _cache_of(trials, labels).device_view(domain, trials)
+
+
+def has_from_tid(trials, labels):
+    """Whether any document of the trials carries a misc.from_tid other than
+    its tid, from the per-Trials cache (ingest looks at each document once)."""
+    cache = _cache_of(trials, labels)
+    cache.ingest(trials.trials)
+    return cache.has_from
 
 
 def isnan(x):

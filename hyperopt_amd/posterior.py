@@ -94,6 +94,61 @@ class Splitter(object):
         return o_vals[side == 1], o_vals[side == 2]
 
 
+MO_MAX_OBJECTIVES = 8
+MO_MAX_ROWS = 1 << 20
+# bytes of comparison results mo_counts forms at a time: a block of rows
+# against all rows holds about eight one-byte matrices (both "every"
+# accumulators, one comparison each, the two dominance matrices and their
+# negations), so a block is MO_CHUNK_BYTES / (8 n) rows
+MO_CHUNK_BYTES = 64 << 20
+
+
+def mo_counts(F):
+    """The dominance counts of the objective vectors F [n, M], all minimised
+    (the numpy restatement of tpe_mo_keys, include/hyperopt_tpe.h): (by, do)
+    int32 [n] -- by[i] the rows that dominate i (F[j] <= F[i] everywhere, <
+    somewhere; IEEE comparisons), do[i] the rows i dominates.  A row with a
+    NaN is compared with nobody: -1 in both, and it counts for no other row.
+    Blocks of rows against all rows, MO_CHUNK_BYTES of comparisons at a time."""
+    F = np.asarray(F, dtype=np.float64)
+    if F.ndim != 2 or not 1 <= F.shape[1] <= MO_MAX_OBJECTIVES:
+        raise ValueError('F must be [n, 1 .. %d objectives]' % MO_MAX_OBJECTIVES)
+    n, M = F.shape
+    by = np.full(n, -1, dtype=np.int32)
+    do = np.full(n, -1, dtype=np.int32)
+    valid = np.flatnonzero(~np.isnan(F).any(axis=1))
+    G = np.ascontiguousarray(F[valid].T)                 # [M, rows without a NaN]
+    nv = len(valid)
+    rows = max(1, MO_CHUNK_BYTES // (8 * max(nv, 1)))
+    for a in range(0, nv, rows):
+        b = min(nv, a + rows)
+        le = np.ones((b - a, nv), dtype=bool)            # every F[i] <= F[j]
+        ge = np.ones((b - a, nv), dtype=bool)            # every F[i] >= F[j]
+        for m in range(M):
+            le &= G[m, a:b, None] <= G[m, None, :]
+            ge &= G[m, a:b, None] >= G[m, None, :]
+        # every <= and not every >=: some <.  Equal rows: neither dominates.
+        do[valid[a:b]] = np.count_nonzero(le & ~ge, axis=1)
+        by[valid[a:b]] = np.count_nonzero(ge & ~le, axis=1)
+    return by, do
+
+
+def mo_keys(F, counts=None):
+    """The Pareto-compliant total order of the objective vectors F [n, M] as
+    one loss column: keys[i] is row i's position, 0 .. as a float64, under
+    ascending by, then descending do, then ascending i (mo_counts; by is 0
+    exactly on the Pareto front and smaller for a than for b whenever a
+    dominates b, so the order never puts a dominated row before one that
+    dominates it).  NaN for a row with a NaN.  The keys are distinct, so a
+    split by them never meets a tie.  M = 1: the stable argsort rank."""
+    by, do = mo_counts(F) if counts is None else counts
+    keys = np.full(len(by), np.nan)
+    valid = np.flatnonzero(by >= 0)
+    order = np.lexsort((valid, -do[valid].astype(np.int64), by[valid]))
+    keys[valid[order]] = np.arange(len(valid), dtype=np.float64)
+    return keys
+
+
 def linear_forgetting_weights(n, lf):
     if n == 0:
         return np.asarray([])

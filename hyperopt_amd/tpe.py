@@ -30,6 +30,9 @@ free labels of a joint group then come from its conditional density),
 `pool` (a `Pool` of configurations: the suggestion is the untaken entry with
 the largest log l(x) - log g(x), ranked on the device; `pool_replace=True`
 takes no entry out),
+`objectives` (result-dict keys minimised together: each complete trial's loss
+becomes its position in a Pareto-compliant order of the objective vectors,
+computed on the device; `pareto_front` lists the non-dominated trials),
 `precision` ('f64'; 'f32'
 is accepted and runs the same exact path -- see `suggest`), `device` (HIP ordinal), `devices` (a list of ordinals: one
 multi-device context splits every round over those GPUs, same documents as
@@ -47,6 +50,7 @@ suggestion).
 """
 import itertools
 import logging
+import operator
 import time
 
 import numpy as np
@@ -73,6 +77,12 @@ DEVICE_BUILD_MIN_OBS = 16384
 # groups are built on the device from it too (False: always on the host -- the
 # same documents; for timing one against the other, tools/time_joint.py)
 JOINT_DEVICE_BUILD = True
+# objectives=... under posterior_builder='auto': complete trials from which
+# the keys come from the kernel (Engine.mo_keys) instead of posterior.mo_keys
+# -- the crossover tools/time_mo.py measured on an MI355X at two objectives
+# (profiles/mo_keys_timing.json): 64 rows 0.037 ms on the device against 0.030
+# ms in numpy, 128 rows 0.041 against 0.051, 1024 rows 0.066 against 1.69
+MO_DEVICE_MIN_TRIALS = 128
 
 # host-side restatements, exported under the reference's names
 ap_filter_trials_split = _post.split_history
@@ -625,6 +635,139 @@ def _joint_build(eng, domain, trials, specs, gathered, gamma, prior_weight, grou
     return groups
 
 
+def check_objectives(objectives):
+    """tpe.suggest's `objectives` after validation: a tuple of 1 to
+    posterior.MO_MAX_OBJECTIVES distinct result-dict keys, None for None.
+    ValueError for anything that is not a sequence of strings (one string is
+    not one), an empty one, a repeated key and too many."""
+    if objectives is None:
+        return None
+    if isinstance(objectives, (str, bytes)) or not isinstance(objectives, (list, tuple)):
+        raise ValueError('objectives must be a list or tuple of result keys')
+    objectives = tuple(objectives)
+    if not objectives:
+        raise ValueError('objectives must not be empty')
+    for key in objectives:
+        if not isinstance(key, str):
+            raise ValueError('objectives: %r is not a string' % (key,))
+    if len(set(objectives)) != len(objectives):
+        raise ValueError('objectives: %r names a key twice' % (objectives,))
+    if len(objectives) > _post.MO_MAX_OBJECTIVES:
+        raise ValueError('objectives: at most %d, got %d' % (_post.MO_MAX_OBJECTIVES, len(objectives)))
+    return objectives
+
+
+def objective_rows(docs, objectives, domain=None, check_from=True):
+    """The objective vectors of the complete documents among `docs`:
+    (complete documents in the order of docs, F [their number, len(objectives)]
+    float64).  A document is complete when its loss -- domain.loss(result,
+    spec), result.get('loss') without a domain -- is not None (a pending or
+    failed one has none); 'loss' among the objectives is that value, every
+    other key is read from the result.  ValueError for a complete document
+    that lacks a key (the message names its tid and the key) and, with
+    check_from, for any document with a from_tid other than its tid: the best
+    of a group is not defined for vectors (tpe.suggest asks the history
+    cache, which has looked at every document once already)."""
+    # (C-level passes over the documents, as history.raw_losses reads the
+    # losses: at 10k trials a Python loop per document costs more than the
+    # ranking itself)
+    docs = list(docs)
+    results = list(map(_history._result_of, docs))
+    if domain is None or type(domain).loss is _history._plain_loss:
+        raw = list(map(dict.get, results, itertools.repeat('loss')))
+    else:
+        raw = _history.raw_losses(domain, docs)
+    if check_from:
+        froms = list(map(dict.get, map(_misc_of, docs), itertools.repeat('from_tid')))
+        if froms.count(None) != len(froms):
+            for d, f in zip(docs, froms):
+                if f is not None and f != d['tid']:
+                    raise ValueError('objectives: trial %r has from_tid %r; groups of trials are not '
+                                     'supported with several objectives' % (d['tid'], f))
+    if None in raw:
+        done = [i for i, v in enumerate(raw) if v is not None]
+        docs = [docs[i] for i in done]
+        raw = [raw[i] for i in done]
+        results = [results[i] for i in done]
+    F = np.empty((len(docs), len(objectives)))
+    for m, key in enumerate(objectives):
+        col = raw if key == 'loss' else list(map(dict.get, results, itertools.repeat(key)))
+        if None in col:
+            raise ValueError('objectives: trial %r has no %r in its result'
+                             % (docs[col.index(None)]['tid'], key))
+        F[:, m] = col
+    return docs, F
+
+
+_misc_of = operator.itemgetter('misc')
+
+
+def objective_keys(F, builder='auto', engine=None):
+    """posterior.mo_keys(F) by the builder the call selects: 'host' numpy,
+    'device' the kernel (Engine.mo_keys on `engine`, a callable returning the
+    Engine), 'auto' the kernel from MO_DEVICE_MIN_TRIALS rows on.  The same
+    integers either way."""
+    if len(F) and (builder == 'device' or (builder == 'auto' and len(F) >= MO_DEVICE_MIN_TRIALS)):
+        if len(F) > _post.MO_MAX_ROWS:
+            raise ValueError('objectives: at most %d complete trials' % _post.MO_MAX_ROWS)
+        return engine().mo_keys(F)
+    return _post.mo_keys(F)
+
+
+class _KeyedDomain(object):
+    """A domain whose loss is a column computed beforehand: the complete
+    documents' keys by the identity of their result dicts, None (pending:
+    +inf) for every other document -- also the ones a batch='pending' view
+    adds.  Everything else is the wrapped domain's, attribute writes (the
+    caches specs_of and _doc keep on a domain) included.  src: the list the
+    complete documents `docs` were taken from; when every one of its
+    documents is complete the keys are its column as they stand, and the
+    lookup by identity is built only for another list."""
+
+    def __init__(self, domain, docs, keys, src=None):
+        keys = keys.tolist()
+        whole = src is not None and len(src) == len(docs)
+        object.__setattr__(self, '_domain', domain)
+        object.__setattr__(self, '_src', src if whole else None)
+        object.__setattr__(self, '_column', keys)
+        object.__setattr__(self, '_docs', docs)
+        object.__setattr__(self, '_lookup', None)
+
+    def __getattr__(self, name):
+        return getattr(self._domain, name)
+
+    def __setattr__(self, name, value):
+        setattr(self._domain, name, value)
+
+    @property
+    def _key_of(self):
+        if self._lookup is None:
+            object.__setattr__(self, '_lookup', dict(zip(map(id, map(_history._result_of, self._docs)),
+                                                         self._column)))
+        return self._lookup
+
+    def loss(self, result, config=None):
+        return self._key_of.get(id(result))
+
+    def loss_column(self, docs):
+        if docs is self._src:
+            return self._column
+        return list(map(self._key_of.get, map(id, map(_history._result_of, docs))))
+
+
+def pareto_front(trials, objectives):
+    """The complete trials of `trials` that no other one dominates under the
+    objectives (all minimised; posterior.mo_counts: by == 0), in tid order.
+    Complete as in objective_rows, 'loss' read as result.get('loss'); a trial
+    with a NaN objective is on no front."""
+    objectives = check_objectives(objectives)
+    if objectives is None:
+        raise ValueError('pareto_front needs objectives')
+    docs, F = objective_rows(trials.trials, objectives)
+    by, _ = _post.mo_counts(F) if len(docs) else (np.zeros(0, dtype=np.int32), None)
+    return sorted((d for d, b in zip(docs, by) if b == 0), key=lambda d: d['tid'])
+
+
 def suggest(new_ids, domain, trials, seed,
             prior_weight=_default_prior_weight,
             n_startup_jobs=_default_n_startup_jobs,
@@ -633,7 +776,7 @@ def suggest(new_ids, domain, trials, seed,
             linear_forgetting=_default_linear_forgetting,
             precision='f64', device=0, batch=False, posterior_builder='auto', devices=None,
             multivariate=False, group=False, joint_quantized=False, joint_categorical=False,
-            joint_bandwidth='neighbour', fixed=None, pool=None, pool_replace=False):
+            joint_bandwidth='neighbour', fixed=None, pool=None, pool_replace=False, objectives=None):
     """tpe.py:823-916.  Past the startup phase one document for new_ids[0],
     like the reference; `batch` (not in the reference) asks for one document
     per new_id:
@@ -781,6 +924,37 @@ def suggest(new_ids, domain, trials, seed,
     pool_replace without a pool.  With pool=None every call returns what it
     returned before.
 
+    objectives=('loss', 'latency', ...) (not in the reference; Optuna's MOTPE
+    serves the same studies) minimises several entries of the result dict at
+    once: 1 to 8 distinct keys, 'loss' read through domain.loss, the others
+    from the result -- the objective function returns {'loss': err, 'latency':
+    ms, 'status': STATUS_OK}.  Past the startup phase the call is the call
+    without the keyword on another loss column: every complete trial's loss is
+    replaced by its key, its position in a Pareto-compliant total order of the
+    trials' objective vectors ("Several objectives") --
+    ascending number of trials that dominate it (0 exactly on the Pareto
+    front), then descending number of trials it dominates, then trial order.
+    The front usually holds more trials than the below set, so the second
+    criterion decides most below sets: it favours front points that dominate
+    many trials (the knee) over the front's extremes.  The keys are distinct
+    integers, so the split meets no tie.  They are computed once per call from
+    all the trials (results arrive in any order) and reach every reader of the
+    losses -- the resident view, the general gather, the joint builds,
+    batch='pending''s view -- so the keyword composes with every other one
+    unchanged.  posterior_builder 'host' computes them in numpy
+    (posterior.mo_keys), 'device' with one all-pairs kernel and a radix sort
+    (Engine.mo_keys), 'auto' on the device from MO_DEVICE_MIN_TRIALS complete
+    trials on; the same integers, so the same documents.  A trial without a
+    loss (pending, failed) keeps +inf and takes no part in the ranking; one
+    with a NaN in any objective keeps NaN and stays out of the history, as a
+    NaN loss does.  ValueError, before any engine is touched: objectives that
+    are not such a sequence, a complete trial that lacks one of the keys (the
+    message names the tid and the key), a document with a from_tid (the best
+    of a group is not defined for vectors).  The startup phase is unchanged,
+    and objectives=('loss',) with distinct losses returns the plain call's
+    documents.  tpe.pareto_front(trials, objectives) lists the front.  With
+    objectives=None every call returns what it returned before.
+
     precision='f32' runs the exact fp64 path: a round draws every candidate
     and proves all but ~0.5 % of them out of the race from per-sub-bin score
     bounds before any lpdf is summed, so scoring the rest in fp32 would save
@@ -788,8 +962,26 @@ def suggest(new_ids, domain, trials, seed,
     winner; the fp32 lpdf contract (1e-4 relative) holds trivially.  The raw
     fp32 round stays available as Engine(precision='f32')."""
     t0 = time.time()
+    objectives = check_objectives(objectives)   # (first: nothing else has run when it raises)
+    if objectives is not None:
+        # the call below on another loss column: the keys once, from all the
+        # trials; every place that reads losses reads them through the domain
+        src = trials.trials
+        # (a from_tid: flagged by the history cache, named by the full check)
+        docs, F = objective_rows(src, objectives, domain,
+                                 check_from=_history.has_from_tid(trials, list(specs_of(domain))))
+        keys = objective_keys(F, posterior_builder if posterior_builder in ('host', 'device') else 'auto',
+                              lambda: _engine.get_engine(list(devices) if devices else device, 'f64', 'main'))
+        logger.info('tpe.suggest: %d objectives, %d complete trials ranked, %.1f ms' % (
+            len(objectives), len(docs), (time.time() - t0) * 1e3))
+        return suggest(new_ids, _KeyedDomain(domain, docs, keys, src), trials, seed, prior_weight=prior_weight,
+                       n_startup_jobs=n_startup_jobs, n_EI_candidates=n_EI_candidates, gamma=gamma,
+                       linear_forgetting=linear_forgetting, precision=precision, device=device, batch=batch,
+                       posterior_builder=posterior_builder, devices=devices, multivariate=multivariate,
+                       group=group, joint_quantized=joint_quantized, joint_categorical=joint_categorical,
+                       joint_bandwidth=joint_bandwidth, fixed=fixed, pool=pool, pool_replace=pool_replace)
     specs = specs_of(domain)
-    fixed = check_fixed(specs, fixed)   # (first: nothing else has run when it raises)
+    fixed = check_fixed(specs, fixed)
     if precision not in ('f64', 'f32'):
         raise ValueError("precision must be 'f64' or 'f32'")
     if posterior_builder not in ('auto', 'host', 'device'):

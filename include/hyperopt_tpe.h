@@ -727,6 +727,37 @@ int tpe_pool_rank(tpe_ctx *ctx, int32_t n_groups, const int32_t *slots, const in
                   double *score /* [n] or NULL */,
                   double *lpdf_below, double *lpdf_above /* [n][n_cols + n_groups] or NULL: diagnostics */);
 
+/* ---- several objectives ---------------------------------------------------
+ * The Pareto-compliant total order of n objective vectors, all objectives
+ * minimised (no reference counterpart: the reference splits the trials by one
+ * loss, tpe.py:624-648; tpe.suggest(objectives=...) splits them by these keys
+ * instead).  objectives[n][n_obj] row-major, row i the vector F[i] of trial i,
+ * compared by IEEE comparisons: -0.0 equals 0.0, +-inf are ordinary values.
+ *   i dominates j: F[i][m] <= F[j][m] for every m and F[i][m] < F[j][m] for
+ *       one; equal rows do not dominate each other;
+ *   dominated_by[i]: the number of rows that dominate i (0 exactly on the
+ *       Pareto front; smaller for a than for b whenever a dominates b);
+ *   dominates[i]: the number of rows i dominates;
+ *   the order: ascending dominated_by, then descending dominates, then
+ *       ascending i; keys[i] is row i's position in it, 0 .. n - 1 (distinct
+ *       integers as doubles; n_obj = 1: the stable argsort rank of the column);
+ *   a row with a NaN in any objective is compared with nobody and counted by
+ *       nobody: keys[i] = NaN, dominated_by[i] = dominates[i] = -1, and the
+ *       other rows' keys are their positions among the rows without a NaN.
+ * All n^2 pairs are tested on the device, each row's two counters summed as
+ * integers (the same bits on every run and device); one radix sort of (by,
+ * n - do, i) packed into 3 x 21 bits gives the positions, hence n <= 2^20.
+ * dominated_by and dominates may each be NULL.
+ * One stream synchronisation per call.  Nothing is kept on the context but
+ * reusable buffers (counted by tpe_device_bytes); no posterior, history or
+ * pool is read or changed.  A multi-device context runs it on its primary
+ * device.
+ * TPE_ERR_ARG: a NULL objectives or keys; n < 1 or n > 2^20; n_obj outside
+ * [1, 8].  On an error the outputs are untouched. */
+int tpe_mo_keys(tpe_ctx *ctx, const double *objectives /* [n][n_obj] row-major */,
+                int64_t n, int32_t n_obj, double *keys /* [n] */,
+                int32_t *dominated_by /* [n] or NULL */, int32_t *dominates /* [n] or NULL */);
+
 /* Score a caller-supplied candidate set for one resident label (the parity
  * entry point: identical candidates in, both lpdf vectors and the winner
  * out).  lpdf_below / lpdf_above may be NULL. */
