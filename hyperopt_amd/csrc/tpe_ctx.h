@@ -418,6 +418,100 @@ struct QExchange {
     virtual ~QExchange() {}
 };
 
+// A context's round state by lifetime: the option values, the last round's
+// statistics, and what is valid only between a round's launches and its sync.
+
+// The option values (TPE_OPT_*): written by tpe1_set_option alone -- a round
+// reads them.  (sharded_round turns value_only off around its candidate
+// shards' calls.)
+struct Options {
+    bool dedup = true;                   // quantized grid-value tables
+    bool timing = true;                  // HIP-event timing of rounds (TPE_OPT_TIMING)
+    bool splitk = true;                  // split-K for small sampled rounds
+    int32_t chunks_forced = 0;           // TPE_OPT_CHUNKS: 1 = off, > 1 = fixed, 0 = auto
+    // fp32 screen of the fp64 round (sampled tile-map rounds, TPE_F64): per
+    // candidate an upper bound of its score, per (round, label) the largest
+    // lower bound and the compacted candidates that can still win
+    bool screen = true;                  // TPE_OPT_SCREEN
+    bool expand = true;                  // TPE_OPT_EXPAND: expansion screen when eligible
+    // hot-bin prefilter of the expansion screen (TPE_OPT_HOT, tpe_device.h)
+    int32_t hot = 1;                     // 0 off, 1 on, 2 test: force the fallback
+    bool early = true;                   // early exit of quantized / categorical tile rounds
+    bool zero_win = true;                // packed re-score skips the exactly-zero above terms
+    int32_t bx_split = 0;                // TPE_OPT_BX_SPLIT (0: auto)
+    int64_t pk_sliced = 8192;            // TPE_OPT_PK_SLICED (0: never sliced)
+    int32_t bx_t_force = 0;              // TPE_OPT_BX_T (0: auto)
+    bool value_only = false;             // TPE_OPT_VALUE_ONLY: packed rounds skip the lpdfs of certified winners
+    int32_t mode_mask = 31;              // TPE_OPT_MODE_MASK: the label families sampled rounds launch
+    // windowed screen (large tile-map rounds): candidates keyed by (round,
+    // label, bin) and stably sorted with their (x' fp32, index) values
+    bool window = true;                  // TPE_OPT_WINDOW
+    int32_t win_t = tpe::kWinTDefault;   // TPE_OPT_WIN_T
+    int32_t win_groups = 0;              // TPE_OPT_WIN_GROUPS (0: auto)
+    bool aux_families = false;           // TPE_OPT_AUX_FAMILIES
+    // the whole problem, set by the caller for the life of the context (one
+    // process per GPU, each holding one shard: TPE_OPT_WHOLE_N / _ROUNDS)
+    int64_t whole_n = 0;
+    int32_t whole_rounds = 0;
+    int64_t joint_flat_cap = 0;          // TPE_OPT_JOINT_CAP (0: tpe_joint.hip's kJFlatCap)
+    // the two capacities the engine itself adapts, after a round overflowed
+    // them and before it runs again (run_round)
+    double hot_cap_div = 16.0;           // TPE_OPT_HOT_DIV: hot lists hold n / hot_cap_div per cell (shrinks)
+    int64_t pk_cap = 1 << 16;            // TPE_OPT_RESCORE_CAP: candidates the packed re-score's buffers hold (grows)
+};
+
+// The last round's statistics: what the tpe_last_* getters report.  The
+// families a round does not launch (TPE_OPT_MODE_MASK) keep theirs.
+struct RoundStats {
+    int64_t evals = 0;
+    float mode_ms[kNumModes] = {};       // per family (tpe_last_mode_stats)
+    int64_t mode_evals[kNumModes] = {};
+    float score_ms = 0.f, round_ms = 0.f;
+    int64_t screen_total = 0, screen_rescored = 0;
+    int64_t screen_exec = 0;             // terms summed by the screen
+    int64_t screen_rescore_terms = 0;    // fp64 terms of the re-scored candidates
+    int32_t screen_mode = 0;             // tpe_last_screen_mode
+    float screen_ms = 0.f;
+    unsigned long long drawn[2] = {0, 0};   // candidates the early-exit kernels drew: quantized, categorical
+    bool cat_early = false;              // the categorical labels ran k_cat_tiles
+    bool hot_ran = false;                // the hot-bin prefilter ran,
+    int64_t hot_listed = 0;              //   the candidates it listed
+    int32_t hot_fallback = 0;            //   and its flag word when the round re-ran the plain screen
+    // another device's share of the same round: work summed, times the
+    // slowest device's; the screen mode and the prefilter's report stay this
+    // (the primary) device's
+    void merge(const RoundStats& o) {
+        evals += o.evals;
+        screen_total += o.screen_total;
+        screen_rescored += o.screen_rescored;
+        screen_exec += o.screen_exec;
+        screen_rescore_terms += o.screen_rescore_terms;
+        drawn[0] += o.drawn[0];
+        drawn[1] += o.drawn[1];
+        score_ms = std::max(score_ms, o.score_ms);
+        round_ms = std::max(round_ms, o.round_ms);
+        screen_ms = std::max(screen_ms, o.screen_ms);
+        for (int m = 0; m < kNumModes; ++m) {
+            mode_ms[m] = std::max(mode_ms[m], o.mode_ms[m]);
+            mode_evals[m] += o.mode_evals[m];
+        }
+    }
+};
+
+// What the launches of the round being queued leave for the code after its
+// one sync; run_round starts every attempt from a default-constructed one.
+struct InFlight {
+    bool mode_ran[kNumModes] = {};       // the family's bracket was recorded (evm)
+    int64_t evals_q[2] = {0, 0};         // the quantized families' evaluations (launch_quantized)
+    bool dense_one = false;              // the dense rows hold their winner in slot 0 only (k_reduce)
+    bool zw_pending = false;             // the zero windows were launched (built iff the plan was not empty)
+    bool pk_plan_pending = false;        // the packed plan awaits the sync
+    bool screen_pending = false;         // scr_cnt_h awaits the sync
+    bool screen_exec_pending = false;    // pin.screen_exec awaits the sync
+    int32_t evw_used = 0;                // windowed units whose k_screen_win brackets were recorded (evw)
+    int64_t hot_cells = 0;               // cells of the prefilter's lists (hot_cnt_h)
+};
+
 }  // namespace tpe_rt
 
 struct tpe_ctx {
@@ -433,14 +527,10 @@ struct tpe_ctx {
     hipStream_t stream = nullptr;
     hipEvent_t ev0 = nullptr, ev1 = nullptr, ev2 = nullptr;
     hipEvent_t evm[kNumModes][2] = {};   // per-family kernel brackets
-    bool mode_ran[kNumModes] = {};
-    float mode_ms[kNumModes] = {};
-    int64_t mode_evals[kNumModes] = {};
     std::string err;
-    float score_ms = 0.f, round_ms = 0.f;
-    int64_t evals = 0;
-    bool dedup = true;                   // quantized grid-value tables
-    bool timing = true;                  // HIP-event timing of rounds (TPE_OPT_TIMING)
+    tpe_rt::Options opt;                 // the option values
+    tpe_rt::RoundStats stats;            // the last round's statistics
+    tpe_rt::InFlight fl;                 // the round being queued
 
     // The resident posterior (tpe_set_posterior) and a separate one-label
     // slot for the single-op entry points, so that GMM1_lpdf / GMM1 sampling
@@ -468,35 +558,18 @@ struct tpe_ctx {
     DevBuf<int64_t> xfound;              // per (round, label) cell: the first candidate index found
                                          // holding its label's best drawable score (early exit)
     DevBuf<unsigned long long> xdrawn;   // candidates the early-exit kernels drew: quantized, categorical
-    unsigned long long xdrawn_h[2] = {0, 0};
-    bool cat_early = false;              // the last round's categorical labels ran k_cat_tiles
     DevBuf<double> xs, slice_part;       // split-K map: candidates, slice sums
-    bool splitk = true;                  // split-K for small sampled rounds
     DevBuf<double> chunk_part;           // chunked packed map: x | below sum | above chunk sums
-    int32_t chunks_forced = 0;           // TPE_OPT_CHUNKS: 1 = off, > 1 = fixed, 0 = auto
-    // fp32 screen of the fp64 round (sampled tile-map rounds, TPE_F64): per
-    // candidate an upper bound of its score, per (round, label) the largest
-    // lower bound and the compacted candidates that can still win
-    bool screen = true;                  // TPE_OPT_SCREEN
+    // the fp32 screen of the fp64 round (Options::screen)
     DevBuf<float> scr_hi;
     DevBuf<double> scr_hid;              // expansion screen: fp64 upper bounds
     DevBuf<double2> bx_lohi;             //   packed map: fp64 (lower, upper) per candidate
-    bool expand = true;                  // TPE_OPT_EXPAND: expansion screen when eligible
-    // hot-bin prefilter of the expansion screen (TPE_OPT_HOT, tpe_device.h)
-    int32_t hot = 1;                     // 0 off, 1 on, 2 test: force the fallback
-    bool early = true;                   // early exit of quantized / categorical tile rounds
-    bool zero_win = true;                // packed re-score skips the exactly-zero above terms
-    bool zw_pending = false;             //   its windows launched this round (built iff its plan was not empty)
-    double hot_cap_div = 16.0;           // hot lists hold n / hot_cap_div per cell (shrinks on overflow)
+    // hot-bin prefilter of the expansion screen (Options::hot, tpe_device.h)
     DevBuf<double> hot_x;                // per cell: listed candidates' x (the fp64 draw kernel)
     DevBuf<uint32_t> rs_done;            // the round tail's last-workgroup counters (zeroed by its fills)
-    bool dense_one = false;              // this round's dense rows hold their winner in slot 0 only (k_reduce)
     DevBuf<int32_t> hot_pc;              // per sub-bin word: the label's set bits before it (k_hot_prefix)
     DevBuf<uint32_t> hot_ucell;          // per (dense label, sampling component): its u-cells (k_hot_ucells)
     DevBuf<uint4> samp_img;              // per dense label: stage_samp's LDS image (k_samp_image)
-    int32_t bx_split = 0;                // TPE_OPT_BX_SPLIT (0: auto)
-    int64_t pk_sliced = 8192;            // TPE_OPT_PK_SLICED (0: never sliced)
-    int32_t bx_t_force = 0;              // TPE_OPT_BX_T (0: auto)
     double bx_t_next = 64.0;             // the cut T of the next index built (set by its caller)
     DevBuf<int32_t> hot_i, hot_cnt;      //   their indices; per cell the count
     DevBuf<int32_t> hot_mi, hot_mcnt;    //   the marked candidates (k_hot_bx -> k_hot_draw); per segment the count
@@ -505,17 +578,7 @@ struct tpe_ctx {
     DevBuf<int32_t> hot_flag;            // fallback flag
     DevBuf<int32_t> hot_items;           // k_screen_hot's work items: per cell the first, then the counter
     tpe_rt::PinVec<int32_t> hot_cnt_h;
-    int64_t hot_listed = 0;              // last round: candidates the prefilter listed
-    int32_t hot_fallback = 0;            // last round: 1 if it re-ran the plain screen
-    bool hot_ran = false;
-    int64_t hot_cells = 0;               //   cells of its lists (hot_cnt_h, read after the round's sync)
-    bool hot_redo = false;               // the round runs again without the prefilter (its check failed)
     DevBuf<int64_t> rs_plan;             // the re-score's plan (k_rescore_plan: total, entries, sliced)
-    bool value_only = false;             // TPE_OPT_VALUE_ONLY: packed rounds skip the lpdfs of certified winners
-    int32_t mode_mask = 31;              // TPE_OPT_MODE_MASK: the label families sampled rounds launch
-    int64_t pk_cap = 1 << 16;            // packed re-score: candidates its buffers hold (grows)
-    bool pk_plan_pending = false;        // the packed plan awaits the round's sync
-    bool pk_redo = false;                // the round runs again after a plan overflow
     tpe_label_result* dev_out = nullptr; // tpe_suggest_batch_device: the caller's device buffer
     float prep_ms = 0.f;                 // device ms of the last expansion-index build (bx_prepare)
     hipEvent_t ev_prep[2] = {};          //   its bracket, read when asked (tpe_last_prepare)
@@ -556,14 +619,7 @@ struct tpe_ctx {
     DevBuf<int32_t> rs_win;              //   packed map: each entry's zero window
     DevBuf<int64_t> rs_g;                //   and their global indices
     std::vector<tpe_rt::RescoreChunkH> scr_chunks_h;
-    int64_t screen_total = 0, screen_rescored = 0;   // last round
-    int32_t screen_mode = 0;             // last round: tpe_last_screen_mode
-    bool screen_pending = false;         // scr_cnt_h awaits the round's final sync
-    // windowed screen (large tile-map rounds): candidates keyed by (round,
-    // label, bin) and stably sorted with their (x' fp32, index) values
-    bool window = true;                  // TPE_OPT_WINDOW
-    int32_t win_t = tpe::kWinTDefault;   // TPE_OPT_WIN_T
-    int32_t win_groups = 0;              // TPE_OPT_WIN_GROUPS (0: auto)
+    // the windowed screen's sort buffers (Options::window)
     DevBuf<uint32_t> win_keys[2], win_keys2[2];   // two slots: sort of group g + 1
     DevBuf<uint8_t> win_keys8[2], win_keys8b[2];  //   (coarse per-cell keys of large cells)
     DevBuf<uint64_t> win_vals[2], win_vals2[2];   //   while group g is screened
@@ -571,17 +627,10 @@ struct tpe_ctx {
     hipStream_t aux = nullptr;           // key + sort of the next label group
     hipEvent_t ev_fork = nullptr, ev_sorted[2] = {}, ev_done[2] = {};
     hipEvent_t ev_cat[2] = {};           // the quantized + categorical labels' round on aux: fork, join
-    bool aux_families = false;                 // TPE_OPT_AUX_FAMILIES
     std::vector<hipEvent_t> evw;         // per unit: k_screen_win brackets (timing)
-    int32_t evw_used = 0;
     DevBuf<unsigned long long> win_evals;   // (candidate, component) terms the screen summed
     DevBuf<float2> win_lohi;             // packed map: per candidate (lower, upper) score bound
-    int64_t screen_exec = 0;             // last round: terms summed by the screen
-    int64_t screen_rescore_terms = 0;    // last round: fp64 terms of the re-scored candidates
-    bool screen_exec_pending = false;
-    unsigned long long screen_exec_h = 0;
     hipEvent_t evs[2] = {};              // brackets k_screen alone
-    float screen_ms = 0.f;
     tpe_rt::BuildBufs build;             // device posterior builder scratch
     int64_t built_n_trials = 0;          // last tpe_build_posterior: history size
     int32_t built_n_below = 0;           //   and its below-set size
@@ -595,10 +644,6 @@ struct tpe_ctx {
     std::shared_ptr<void> share;         // posterior export / import scratch (tpe_share.hip)
     int64_t hint_n = 0;                  // candidates per round over all shards (0: this call's)
     int32_t hint_rounds = 0;             // rounds over all shards (0: this call's)
-    // the same, set by the caller for the life of the context (one process
-    // per GPU, each holding one shard: TPE_OPT_WHOLE_N / _ROUNDS)
-    int64_t opt_whole_n = 0;
-    int32_t opt_whole_rounds = 0;
     tpe_rt::QExchange* qx = nullptr;
     int32_t shard_id = 0;                // this context's position in a sharded round
     // label shards of a multi-device context (tpe_multi.hip; set by
@@ -612,7 +657,6 @@ struct tpe_ctx {
 
     // the joint (multivariate) posterior and its scratch (tpe_joint.hip)
     std::shared_ptr<void> joint;
-    int64_t joint_flat_cap = 0;          // TPE_OPT_JOINT_CAP (0: tpe_joint.hip's kJFlatCap)
     // the last joint round's split (tpe_joint_last_shards): 0 the primary
     // alone, 1 candidate shards, 2 round shards; the devices that ran one
     int32_t joint_shard_mode = 0, joint_shard_devs = 1;

@@ -3636,6 +3636,15 @@ struct RoundArgs {
     // problem, so every sharding gives bit-identical winners
     int64_t total_slots;       // candidates x rounds over all shards
     uint32_t gx_whole;         // grid.x the whole problem would use
+    const uint32_t* rounds_h;
+    tpe_label_result* out;
+    int32_t only_label;        // >= 0: tpe_score's one label
+    // what an attempt of the round launches (run_round): the families
+    // (TPE_OPT_MODE_MASK, or the dense ones alone after a prefilter
+    // fallback), without the hot-bin prefilter after that fallback, and
+    // whether the packed re-score's buffers were already grown for it
+    int32_t fam;
+    bool no_hot, regrown;
 };
 
 // The launches of an early-exit tile round (k_qfused_tiles, k_cat_tiles):
@@ -3689,8 +3698,8 @@ int run_fills(tpe_ctx* ctx, FillSet& f) {
 }
 
 // the per-(round, label) first-find indices (reset at the round's start,
-// run_round; nullptr: early exit off)
-int64_t* early_found(tpe_ctx* ctx) { return ctx->early ? ctx->xfound.p : nullptr; }
+// round_attempt; nullptr: early exit off)
+int64_t* early_found(tpe_ctx* ctx) { return ctx->opt.early ? ctx->xfound.p : nullptr; }
 
 // The candidates an early-exit tile round of one family drew, counted the
 // same way whatever order the workgroups ran in: per
@@ -3727,8 +3736,8 @@ void launch_early_drawn(tpe_ctx* ctx, const int32_t* group, int nl, const RoundA
 }
 
 void bracket(tpe_ctx* ctx, int mode, int which) {
-    ctx->mode_ran[mode] = true;
-    if (ctx->timing) (void)hipEventRecord(ctx->evm[mode][which], ctx->stream);
+    ctx->fl.mode_ran[mode] = true;
+    if (ctx->opt.timing) (void)hipEventRecord(ctx->evm[mode][which], ctx->stream);
 }
 
 template <typename T, int MODE, bool SAMPLE>
@@ -3742,7 +3751,7 @@ void launch_round(tpe_ctx* ctx, const Groups& g, const RoundArgs& a) {
                 1, std::min<int64_t>({(int64_t)a.gx, (a.n + kCatR * kBlock - 1) / (kCatR * kBlock),
                                       kHotWgs / std::max<int64_t>(1, (int64_t)nl * a.gz)}));
             int64_t* found = early_found(ctx);
-            ctx->cat_early = true;
+            ctx->stats.cat_early = true;
             for (const EarlyPhase& ph :
                  early_phases(a, (int64_t)kCatR * kBlock, cgx, found != nullptr, (int64_t)nl * a.gz))
                 hipLaunchKernelGGL((k_cat_tiles<kCatR>), dim3(ph.grid, nl, a.gz), dim3(kBlock), 0, ctx->stream,
@@ -3780,19 +3789,19 @@ void launch_round(tpe_ctx* ctx, const Groups& g, const RoundArgs& a) {
 // TPE_OPT_CHUNKS forces a count (tests): chunk = ceil(na_max / count).
 constexpr int32_t kChunkLen = 8192;
 
-int dense_chunks(const tpe_ctx* ctx) {
+int32_t dense_na_max(const tpe_ctx* ctx) {
     int32_t na_max = 1;
     for (int m : {DENSE_GMM, DENSE_LGMM})
         for (int li : ctx->P->h_group[m]) na_max = std::max(na_max, ctx->P->h_labels[li].na);
-    if (ctx->chunks_forced) return ctx->chunks_forced;
-    return (int)((na_max + kChunkLen - 1) / kChunkLen);
+    return na_max;
+}
+
+int dense_chunks(const tpe_ctx* ctx) {
+    return ctx->opt.chunks_forced ? ctx->opt.chunks_forced : (dense_na_max(ctx) + kChunkLen - 1) / kChunkLen;
 }
 
 int32_t dense_chunk_len(const tpe_ctx* ctx, int nch) {
-    int32_t na_max = 1;
-    for (int m : {DENSE_GMM, DENSE_LGMM})
-        for (int li : ctx->P->h_group[m]) na_max = std::max(na_max, ctx->P->h_labels[li].na);
-    return ctx->chunks_forced ? (na_max + nch - 1) / nch : kChunkLen;
+    return ctx->opt.chunks_forced ? (dense_na_max(ctx) + nch - 1) / nch : kChunkLen;
 }
 
 // nb + na summed over the dense labels: the terms an unwindowed screen sums
@@ -3829,7 +3838,7 @@ int launch_screen_packed(tpe_ctx* ctx, const int32_t* grp, int nl, int nch, cons
     HIPCHK(ctx, hipMemsetAsync(ctx->scr_cnt.p, 0, nl * sizeof(int32_t), ctx->stream));
     RoundSel* rsel = reinterpret_cast<RoundSel*>(ctx->scr_rsel.p);
     bool use_bx = false;
-    if (ctx->expand && cap >= kWinMinN && a.n <= kBxR * kBlock) {
+    if (ctx->opt.expand && cap >= kWinMinN && a.n <= kBxR * kBlock) {
         ctx->bx_t_next = kBxT;   // (the packed map: value-only certification)
         int rc = tpe_rt::bx_prepare(ctx);
         if (rc) return rc;
@@ -3840,26 +3849,26 @@ int launch_screen_packed(tpe_ctx* ctx, const int32_t* grp, int nl, int nch, cons
         // packed slot map of kBxR candidates per thread, then the per-round
         // selection -- ~1 candidate per (round, label) left to re-score
         tpe_rt::Posterior& P = *ctx->P;
-        ctx->screen_mode = 3;
+        ctx->stats.screen_mode = 3;
         HIPCHK(ctx, ctx->win_evals.reserve(1));
         HIPCHK(ctx, hipMemsetAsync(ctx->win_evals.p, 0, sizeof(unsigned long long), ctx->stream));
         HIPCHK(ctx, ctx->bx_lohi.reserve((size_t)nl * cap));
         const Slots Sb{(int32_t)a.n, (int32_t)((kBxR * kBlock) / a.n), a.n_rounds};
         const uint32_t gxb = (uint32_t)((a.n_rounds + Sb.rpb - 1) / Sb.rpb);
-        if (ctx->timing) HIPCHK(ctx, hipEventRecord(ctx->evs[0], ctx->stream));
+        if (ctx->opt.timing) HIPCHK(ctx, hipEventRecord(ctx->evs[0], ctx->stream));
         hipLaunchKernelGGL((k_screen_bx<kBxR, true>), dim3(gxb, nl, 1), dim3(kBlock), 0, ctx->stream,
                            P.labels.p, grp, P.comps64.p, P.samp.p, P.bx.p, P.bx_tab.p, P.bx_loff.p,
                            P.bx_list.p, a.n, a.cand_offset, a.seed, ctx->rounds.p, nl, nullptr, nullptr,
                            nullptr, nullptr, ctx->win_evals.p, ctx->errflag.p, Sb, nullptr, nullptr, nullptr,
                            ctx->bx_lohi.p, (int64_t)0);
-        if (ctx->timing) HIPCHK(ctx, hipEventRecord(ctx->evs[1], ctx->stream));
+        if (ctx->opt.timing) HIPCHK(ctx, hipEventRecord(ctx->evs[1], ctx->stream));
         hipLaunchKernelGGL(k_pick_win<double2>, dim3((unsigned)((a.n_rounds + kBlock - 1) / kBlock), nl),
                            dim3(kBlock), 0, ctx->stream, ctx->bx_lohi.p, a.n_rounds, (int32_t)a.n,
-                           ctx->scr_cnt.p, ctx->scr_list.p, cap, rsel, nl, ctx->value_only ? 1 : 0);
+                           ctx->scr_cnt.p, ctx->scr_list.p, cap, rsel, nl, ctx->opt.value_only ? 1 : 0);
         HIPCHK(ctx, hipMemcpyAsync(&ctx->pin[0].screen_exec, ctx->win_evals.p, sizeof(unsigned long long),
                                    hipMemcpyDeviceToHost, ctx->stream));
-        ctx->screen_exec_pending = true;
-    } else if (ctx->window && cap >= kWinMinN && (int64_t)nl * cap <= ((int64_t)1 << 30)) {
+        ctx->fl.screen_exec_pending = true;
+    } else if (ctx->opt.window && cap >= kWinMinN && (int64_t)nl * cap <= ((int64_t)1 << 30)) {
         // windowed: every round's candidates of a label sorted together into
         // tiles of neighbours (tpe_window.hip), bounds per candidate, then
         // the per-round selection
@@ -3874,22 +3883,22 @@ int launch_screen_packed(tpe_ctx* ctx, const int32_t* grp, int nl, int nch, cons
         if ((rc = tpe_rt::win_screen(ctx, wa, &sorted))) return rc;
         hipLaunchKernelGGL(k_pick_win<float2>, dim3((unsigned)((a.n_rounds + kBlock - 1) / kBlock), nl),
                            dim3(kBlock), 0, ctx->stream, ctx->win_lohi.p, a.n_rounds, (int32_t)a.n,
-                           ctx->scr_cnt.p, ctx->scr_list.p, cap, rsel, nl, ctx->value_only ? 1 : 0);
+                           ctx->scr_cnt.p, ctx->scr_list.p, cap, rsel, nl, ctx->opt.value_only ? 1 : 0);
         HIPCHK(ctx, hipMemcpyAsync(&ctx->pin[0].screen_exec, ctx->win_evals.p, sizeof(unsigned long long),
                                    hipMemcpyDeviceToHost, ctx->stream));
-        ctx->screen_exec_pending = true;
+        ctx->fl.screen_exec_pending = true;
     } else {
         HIPCHK(ctx, ctx->chunk_part.reserve(planes));
-        if (ctx->timing) HIPCHK(ctx, hipEventRecord(ctx->evs[0], ctx->stream));
+        if (ctx->opt.timing) HIPCHK(ctx, hipEventRecord(ctx->evs[0], ctx->stream));
         hipLaunchKernelGGL((k_round_chunk<float, kScreenR>), dim3(gx8, nl, nch), dim3(kBlock), 0,
                            ctx->stream, ctx->P->labels.p, grp, ctx->P->comps32.p, ctx->P->samp.p, a.n,
                            a.cand_offset, a.seed, ctx->rounds.p, chunk, ctx->chunk_part.p, ctx->errflag.p,
                            S8);
-        if (ctx->timing) HIPCHK(ctx, hipEventRecord(ctx->evs[1], ctx->stream));
+        if (ctx->opt.timing) HIPCHK(ctx, hipEventRecord(ctx->evs[1], ctx->stream));
         hipLaunchKernelGGL((k_pick_packed<kScreenR>), dim3(gx8, nl), dim3(kBlock), 0, ctx->stream,
                            ctx->P->labels.p, grp, a.n, nl, nch, chunk, ctx->chunk_part.p, ctx->scr_cnt.p,
                            ctx->scr_list.p, cap, rsel, S8);
-        ctx->screen_exec += (int64_t)a.n_rounds * a.n * dense_terms(ctx);
+        ctx->stats.screen_exec += (int64_t)a.n_rounds * a.n * dense_terms(ctx);
     }
     // the re-score planned on the device (no mid-round read-back): per
     // label chunks of kRP * 256 listed candidates, buffers for pk_cap of
@@ -3898,11 +3907,11 @@ int launch_screen_packed(tpe_ctx* ctx, const int32_t* grp, int nl, int nch, cons
     HIPCHK(ctx, hipMemcpyAsync(ctx->scr_cnt_h.data(), ctx->scr_cnt.p, nl * sizeof(int32_t),
                                hipMemcpyDeviceToHost, ctx->stream));
     constexpr int64_t per = (int64_t)kRP * kBlock;
-    const int64_t pcap = std::max<int64_t>(1, std::min<int64_t>(ctx->pk_cap, (int64_t)nl * cap));
+    const int64_t pcap = std::max<int64_t>(1, std::min<int64_t>(ctx->opt.pk_cap, (int64_t)nl * cap));
     const int64_t ne_max = nl + (pcap + per - 1) / per;
     // a few listed candidates: sliced (k_rescore_slices_packed), entries of
     // kRsW candidates, s_max slices each
-    const int64_t sl_max = std::min<int64_t>(ctx->pk_sliced, pcap);
+    const int64_t sl_max = std::min<int64_t>(ctx->opt.pk_sliced, pcap);
     const int64_t ne_sl = sl_max > 0 ? nl + (sl_max + kRsW - 1) / kRsW : 0;
     const int32_t spc = (chunk + kSumSlice - 1) / kSumSlice;
     int32_t s_max = 0;
@@ -3925,10 +3934,10 @@ int launch_screen_packed(tpe_ctx* ctx, const int32_t* grp, int nl, int nch, cons
     hipLaunchKernelGGL(k_rescore_plan, dim3(1), dim3(kPlanBlock), 0, ctx->stream, ctx->scr_cnt.p, (int64_t)nl,
                        (int32_t)per, sl_max, pcap, tabd, ctx->scr_range.p, ctx->scr_off.p, plan);
     HIPCHK(ctx, hipMemcpyAsync(&ctx->pin[0].plan, plan, sizeof(RescorePlan), hipMemcpyDeviceToHost, ctx->stream));
-    ctx->pk_plan_pending = true;
+    ctx->fl.pk_plan_pending = true;
     {
         tpe_rt::Posterior& P = *ctx->P;
-        if (ctx->zero_win && !P.zw_ready) {   // once per posterior
+        if (ctx->opt.zero_win && !P.zw_ready) {   // once per posterior
             HIPCHK(ctx, P.zw_hi.reserve(P.comps64.cap));
             HIPCHK(ctx, P.zw_lo.reserve(P.comps64.cap));
             HIPCHK(ctx, P.zw_wide.reserve(P.comps64.cap));
@@ -3938,13 +3947,13 @@ int launch_screen_packed(tpe_ctx* ctx, const int32_t* grp, int nl, int nch, cons
             hipLaunchKernelGGL(k_zero_windows, dim3((unsigned)nd), dim3(kZwBlock), 0, ctx->stream, plan, P.labels.p,
                                P.groups.p + P.group_off[DENSE_GMM], P.comps64.p, P.zw_hi.p, P.zw_lo.p,
                                P.zw_wide.p, P.zw_n.p);
-            ctx->zw_pending = true;   // built iff the plan was chunked (read after the round's sync)
+            ctx->fl.zw_pending = true;   // built iff the plan was chunked (read after the round's sync)
         }
         if (ne_sl > 0) {
             // (zero windows only when an earlier round of this posterior
             // built them: k_zero_windows skips a sliced plan -- 0.67 ms at
             // config 5, more than the slices it would let a re-score skip)
-            const bool zw = ctx->zero_win && P.zw_ready;
+            const bool zw = ctx->opt.zero_win && P.zw_ready;
             HIPCHK(ctx, ctx->rs_win.reserve((size_t)2 * ne_sl));
             const unsigned g_sl = (unsigned)std::min<int64_t>(ne_sl, 1024);
             hipLaunchKernelGGL(k_rescore_draw_packed, dim3((unsigned)((ne_sl + kBlock / kRsW - 1) / (kBlock / kRsW))),
@@ -3963,7 +3972,7 @@ int launch_screen_packed(tpe_ctx* ctx, const int32_t* grp, int nl, int nch, cons
                            ctx->stream, ctx->P->labels.p, grp, ctx->P->comps64.p, ctx->P->samp.p,
                            a.cand_offset, a.seed, ctx->rounds.p, chunk, ctx->scr_cnt.p,
                            ctx->scr_list.p, cap, tabd, ctx->scr_off.p, plan, pcap, ctx->scr_planes.p,
-                           ctx->zero_win ? P.zw_hi.p : nullptr, ctx->zero_win ? P.zw_lo.p : nullptr,
+                           ctx->opt.zero_win ? P.zw_hi.p : nullptr, ctx->opt.zero_win ? P.zw_lo.p : nullptr,
                            P.zw_wide.p, P.zw_n.p);
         hipLaunchKernelGGL(k_finish_rescore, dim3(g), dim3(kBlock), 0, ctx->stream,
                            ctx->P->labels.p, grp, ctx->P->comps64.p, a.cand_offset, nch, ctx->scr_cnt.p,
@@ -3975,8 +3984,8 @@ int launch_screen_packed(tpe_ctx* ctx, const int32_t* grp, int nl, int nch, cons
                        ctx->stream, ctx->P->labels.p, grp, nl, a.n_rounds, ctx->P->n_labels, rsel, ctx->scr_res.p,
                        ctx->scr_off.p, plan, ctx->P->samp.p, a.cand_offset, a.seed, ctx->rounds.p,
                        ctx->partials.p);
-    ctx->screen_total += cells * a.n;
-    ctx->screen_pending = true;
+    ctx->stats.screen_total += cells * a.n;
+    ctx->fl.screen_pending = true;
     return ctx->hip(hipGetLastError(), "packed screen launch");
 }
 
@@ -4004,7 +4013,7 @@ int hot_tau_prepare(tpe_ctx* ctx, int64_t n) {
     const int32_t* grp = P.groups.p + P.group_off[DENSE_GMM];
     if (ctx->hot_tau0.cap < (size_t)nl) ctx->hot_tau0_gen = 0;   // (re)allocated: recompute
     HIPCHK(ctx, ctx->hot_tau0.reserve(nl));
-    if (ctx->hot_tau0_gen == P.bx_gen && ctx->hot_tau0_n == n && ctx->hot != 2) return TPE_OK;
+    if (ctx->hot_tau0_gen == P.bx_gen && ctx->hot_tau0_n == n && ctx->opt.hot != 2) return TPE_OK;
     HIPCHK(ctx, ctx->hot_bits.reserve((size_t)(P.bx_sb.cap + 31) / 32));
     HIPCHK(ctx, hipMemsetAsync(ctx->hot_tau0.p, 0, nl * sizeof(unsigned long long), ctx->stream));
     const unsigned sbw = (unsigned)std::min<int64_t>((P.bx_sb_max + kBlock - 1) / kBlock,
@@ -4012,7 +4021,7 @@ int hot_tau_prepare(tpe_ctx* ctx, int64_t n) {
     hipLaunchKernelGGL(k_hot_tau0, dim3(sbw, nl), dim3(kBlock), 0,
                        ctx->stream, grp, P.bx.p, P.bx_sb.p, P.bx_sbp.p, (float)(kHotFill / (double)n),
                        ctx->hot_tau0.p);
-    if (ctx->hot == 2)   // test mode: a threshold no candidate reaches -> the fallback
+    if (ctx->opt.hot == 2)   // test mode: a threshold no candidate reaches -> the fallback
         HIPCHK(ctx, hipMemsetAsync(ctx->hot_tau0.p, 0xff, nl * sizeof(unsigned long long), ctx->stream));
     hipLaunchKernelGGL(k_hot_bits, dim3(sbw, nl), dim3(kBlock), 0,
                        ctx->stream, grp, P.bx.p, P.bx_sb.p, ctx->hot_tau0.p, ctx->hot_bits.p);
@@ -4034,7 +4043,7 @@ int hot_tau_prepare(tpe_ctx* ctx, int64_t n) {
         hipLaunchKernelGGL(k_samp_image, dim3((unsigned)nl), dim3(kBlock), 0, ctx->stream, P.labels.p, grp, P.samp.p,
                            ctx->samp_img.p);
     }
-    ctx->hot_tau0_gen = ctx->hot == 2 ? 0 : P.bx_gen;
+    ctx->hot_tau0_gen = ctx->opt.hot == 2 ? 0 : P.bx_gen;
     ctx->hot_tau0_n = n;
     return ctx->hip(hipGetLastError(), "hot-bin threshold launch");
 }
@@ -4044,7 +4053,7 @@ int hot_tau_prepare(tpe_ctx* ctx, int64_t n) {
 // overflow (which makes that round screen every candidate instead)
 constexpr int64_t kHotMinCap = 1 << 12;
 int64_t hot_stride(const tpe_ctx* ctx, int64_t n) {
-    return std::min<int64_t>(n, std::max<int64_t>(kHotMinCap, (int64_t)((double)n / ctx->hot_cap_div)));
+    return std::min<int64_t>(n, std::max<int64_t>(kHotMinCap, (int64_t)((double)n / ctx->opt.hot_cap_div)));
 }
 
 // the re-score's table, plan and sliced buffers for `cells` lists of up
@@ -4073,19 +4082,16 @@ int launch_dense(tpe_ctx* ctx, const Groups& g, const RoundArgs& a) {
     if constexpr (sizeof(T) == 8) comps = ctx->P->comps64.p; else comps = ctx->P->comps32.p;
     const int32_t* grp = ctx->P->groups.p + ctx->P->group_off[DENSE_GMM];
     const int nch = a.S.cpack ? dense_chunks(ctx) : 1;
-    if (sizeof(T) == 8 && ctx->screen && a.S.cpack == 0) {   // fp32 screen + fp64 re-score
+    if (sizeof(T) == 8 && ctx->opt.screen && a.S.cpack == 0) {   // fp32 screen + fp64 re-score
         const size_t cells = (size_t)a.n_rounds * nl;
         bool use_bx = false, hot = false, plan_done = false;
-        ctx->hot_ran = false;
-        ctx->hot_listed = 0;
-        ctx->hot_fallback = 0;
-        if (ctx->expand && a.n >= kWinMinN && a.cand_in == nullptr) {
+        if (ctx->opt.expand && a.n >= kWinMinN && a.cand_in == nullptr) {
             ctx->bx_t_next = kBxTTile;   // (tile rounds: the hot-bin prefilter)
             int rc = tpe_rt::bx_prepare(ctx);
             if (rc) return rc;
             use_bx = ctx->P->bx_ok;
         }
-        hot = use_bx && ctx->hot != 0 && ctx->P->bx_sb.p != nullptr && !ctx->hot_redo;
+        hot = use_bx && ctx->opt.hot != 0 && ctx->P->bx_sb.p != nullptr && !a.no_hot;
         for (int m : {DENSE_GMM, DENSE_LGMM})   // k_hot_bx stages every label's sampling records
             for (int li : ctx->P->h_group[m]) hot = hot && ctx->P->h_labels[li].ns >= 1 && ctx->P->h_labels[li].ns <= kSampLds;
         // the expansion screen's appends: a cell's hot list at most (the
@@ -4113,7 +4119,7 @@ int launch_dense(tpe_ctx* ctx, const Groups& g, const RoundArgs& a) {
                 s_max = std::max(s_max, (d.nb + kSumSlice - 1) / kSumSlice + (d.na + kSumSlice - 1) / kSumSlice);
             }
         const unsigned sx = (unsigned)std::min<int64_t>((a.n + 8 * kBlock - 1) / (8 * kBlock), 1024);
-        ctx->screen_mode = use_bx ? 3 : (ctx->window && a.n >= kWinMinN && a.cand_in == nullptr) ? 2 : 1;
+        ctx->stats.screen_mode = use_bx ? 3 : (ctx->opt.window && a.n >= kWinMinN && a.cand_in == nullptr) ? 2 : 1;
         if (!use_bx) {   // the expansion screen adds its own resets to the same launch
             const int rc = run_fills(ctx, fs);
             if (rc) return rc;
@@ -4137,7 +4143,7 @@ int launch_dense(tpe_ctx* ctx, const Groups& g, const RoundArgs& a) {
                 const int rc = run_fills(ctx, fs);
                 if (rc) return rc;
             }
-            if (ctx->timing) HIPCHK(ctx, hipEventRecord(ctx->evs[0], ctx->stream));
+            if (ctx->opt.timing) HIPCHK(ctx, hipEventRecord(ctx->evs[0], ctx->stream));
             if (hot) {
                 // hot-bin prefilter: draw + sub-bin bounds, then the
                 // expansion screen over the listed candidates only
@@ -4167,14 +4173,14 @@ int launch_dense(tpe_ctx* ctx, const Groups& g, const RoundArgs& a) {
                 // listed)
                 const int64_t segs = (int64_t)hg.x;
                 const int64_t mcap = std::max<int64_t>(
-                    1024, (int64_t)((double)((tiles_c + segs - 1) / segs * hr * kBlock) / ctx->hot_cap_div));
+                    1024, (int64_t)((double)((tiles_c + segs - 1) / segs * hr * kBlock) / ctx->opt.hot_cap_div));
                 HIPCHK(ctx, ctx->hot_mi.reserve(cells * segs * mcap));
                 HIPCHK(ctx, ctx->hot_mcnt.reserve(cells * segs));
                 hipLaunchKernelGGL((k_hot_bx<kHotR>), hg, dim3(kBlock), ucw_bytes, ctx->stream, P.labels.p, grp,
                                    ctx->samp_img.p, ctx->hot_ucell.p, a.n, a.cand_offset, a.seed, ctx->rounds.p, nl,
                                    ctx->hot_mcnt.p, ctx->hot_mi.p, mcap, ctx->hot_flag.p);
                 // (the screen's bracket: the mark kernel alone -- the roofline's kernel)
-                if (ctx->timing) HIPCHK(ctx, hipEventRecord(ctx->evs[1], ctx->stream));
+                if (ctx->opt.timing) HIPCHK(ctx, hipEventRecord(ctx->evs[1], ctx->stream));
                 // the exact draw of the marked: a workgroup per mark segment, at
                 // most kHotDrawWgs over the round
                 const int64_t dw = std::max<int64_t>(
@@ -4195,7 +4201,7 @@ int launch_dense(tpe_ctx* ctx, const Groups& g, const RoundArgs& a) {
                                    ctx->scr_cnt.p, ctx->scr_idx.p, ctx->win_evals.p, P.bx_sb.p, ctx->hot_t.p, lst);
             } else {
                 screen_bx_all(ctx, grp, nl, a);
-                if (ctx->timing) HIPCHK(ctx, hipEventRecord(ctx->evs[1], ctx->stream));
+                if (ctx->opt.timing) HIPCHK(ctx, hipEventRecord(ctx->evs[1], ctx->stream));
             }
             {
                 const int rc = rescore_reserve(ctx, cells, lst, s_max);
@@ -4218,8 +4224,8 @@ int launch_dense(tpe_ctx* ctx, const Groups& g, const RoundArgs& a) {
                 const int rc = defer_read(ctx, &ctx->pin[0].screen_exec, ctx->win_evals.p, sizeof(unsigned long long));
                 if (rc) return rc;
             }
-            ctx->screen_exec_pending = true;
-        } else if (ctx->window && a.n >= kWinMinN && a.cand_in == nullptr) {
+            ctx->fl.screen_exec_pending = true;
+        } else if (ctx->opt.window && a.n >= kWinMinN && a.cand_in == nullptr) {
             // windowed: units of (batch of rounds, group of labels); with
             // several units each is keyed and sorted on the aux stream into
             // one of two buffer slots while the main stream screens and
@@ -4234,7 +4240,7 @@ int launch_dense(tpe_ctx* ctx, const Groups& g, const RoundArgs& a) {
             std::vector<Unit> units;
             const int32_t zb = (int32_t)tpe_rt::win_rounds_per_batch(a.n, nl);
             // label groups only when a batch is big enough to hide its sort
-            const int32_t ng = ctx->win_groups > 0 ? std::min<int32_t>(ctx->win_groups, nl) : 1;
+            const int32_t ng = ctx->opt.win_groups > 0 ? std::min<int32_t>(ctx->opt.win_groups, nl) : 1;
             size_t max_total = 0;
             int64_t max_cells = 1;
             for (int32_t z0 = 0; z0 < a.n_rounds; z0 += zb)
@@ -4253,7 +4259,7 @@ int launch_dense(tpe_ctx* ctx, const Groups& g, const RoundArgs& a) {
                 HIPCHK(ctx, hipEventCreate(&e));
                 ctx->evw.push_back(e);
             }
-            ctx->evw_used = ctx->timing ? (int32_t)units.size() : 0;
+            ctx->fl.evw_used = ctx->opt.timing ? (int32_t)units.size() : 0;
             const bool pipe = units.size() > 1;
             if (pipe) {   // the aux stream starts after this round's setup on the main one
                 HIPCHK(ctx, hipEventRecord(ctx->ev_fork, ctx->stream));
@@ -4277,9 +4283,9 @@ int launch_dense(tpe_ctx* ctx, const Groups& g, const RoundArgs& a) {
                 } else if ((rc = tpe_rt::win_sort(ctx, wa, ctx->stream, &sorted))) {
                     return rc;
                 }
-                if (ctx->timing) HIPCHK(ctx, hipEventRecord(ctx->evw[2 * ui], ctx->stream));
+                if (ctx->opt.timing) HIPCHK(ctx, hipEventRecord(ctx->evw[2 * ui], ctx->stream));
                 if ((rc = tpe_rt::win_tiles(ctx, wa, sorted, ctx->stream))) return rc;
-                if (ctx->timing) HIPCHK(ctx, hipEventRecord(ctx->evw[2 * ui + 1], ctx->stream));
+                if (ctx->opt.timing) HIPCHK(ctx, hipEventRecord(ctx->evw[2 * ui + 1], ctx->stream));
                 hipLaunchKernelGGL(k_select<float>, dim3(sx, u.ny, u.nz), dim3(kBlock), 0, ctx->stream, ctx->scr_hi.p,
                                    a.n, nl, ctx->scr_lb.p, ctx->scr_cnt.p, ctx->scr_idx.p, u.z0, u.y0, u.ny,
                                    sorted);
@@ -4289,18 +4295,18 @@ int launch_dense(tpe_ctx* ctx, const Groups& g, const RoundArgs& a) {
                 const int rc = defer_read(ctx, &ctx->pin[0].screen_exec, ctx->win_evals.p, sizeof(unsigned long long));
                 if (rc) return rc;
             }
-            ctx->screen_exec_pending = true;
+            ctx->fl.screen_exec_pending = true;
         } else {
-            if (ctx->timing) HIPCHK(ctx, hipEventRecord(ctx->evs[0], ctx->stream));
+            if (ctx->opt.timing) HIPCHK(ctx, hipEventRecord(ctx->evs[0], ctx->stream));
             const unsigned sgx = (unsigned)((a.n + kScreenR * kBlock - 1) / (kScreenR * kBlock));
             hipLaunchKernelGGL((k_screen<kScreenR, true>), dim3(sgx, nl, a.gz), dim3(kBlock), 0, ctx->stream,
                                ctx->P->labels.p, grp, ctx->P->comps32.p, ctx->P->samp.p, a.n,
                                a.cand_offset, a.seed, ctx->rounds.p, nl, ctx->scr_hi.p, ctx->scr_lb.p,
                                ctx->errflag.p, a.S, nullptr, nullptr, nullptr);
-            if (ctx->timing) HIPCHK(ctx, hipEventRecord(ctx->evs[1], ctx->stream));
+            if (ctx->opt.timing) HIPCHK(ctx, hipEventRecord(ctx->evs[1], ctx->stream));
             hipLaunchKernelGGL(k_select<float>, dim3(sx, nl, a.gz), dim3(kBlock), 0, ctx->stream, ctx->scr_hi.p,
                                a.n, nl, ctx->scr_lb.p, ctx->scr_cnt.p, ctx->scr_idx.p, 0, 0, nl, nullptr);
-            ctx->screen_exec += (int64_t)a.n_rounds * a.n * dense_terms(ctx);
+            ctx->stats.screen_exec += (int64_t)a.n_rounds * a.n * dense_terms(ctx);
         }
         HIPCHK(ctx, ctx->scr_cnt_h.resize(cells));
         {
@@ -4308,8 +4314,8 @@ int launch_dense(tpe_ctx* ctx, const Groups& g, const RoundArgs& a) {
             if (rc) return rc;
         }
         if (hot) {
-            ctx->hot_ran = true;   // (its lists and flag are read after the round's one sync)
-            ctx->hot_cells = (int64_t)cells;
+            ctx->stats.hot_ran = true;   // (its lists and flag are read after the round's one sync)
+            ctx->fl.hot_cells = (int64_t)cells;
         }
         const int64_t per_full = (int64_t)kRescoreR * kBlock;
         const int64_t ne_sliced = (int64_t)cells + kSlicedRescoreMax / kRsW;
@@ -4341,13 +4347,13 @@ int launch_dense(tpe_ctx* ctx, const Groups& g, const RoundArgs& a) {
                            ctx->P->labels.p, grp, ctx->P->comps64.p, nl, chp, plan, ctx->rs_x.p, ctx->rs_g.p, s_max,
                            ctx->rs_part.p, ctx->scr_res.p, ctx->rs_done.p + 1, (int64_t)cells, ctx->P->n_labels,
                            a.tiles, ctx->scr_off.p, ctx->partials.p);
-        ctx->dense_one = true;   // (k_reduce reads a dense row's first slot only)
-        ctx->screen_total += (int64_t)cells * a.n;
-        ctx->screen_pending = true;
+        ctx->fl.dense_one = true;   // (k_reduce reads a dense row's first slot only)
+        ctx->stats.screen_total += (int64_t)cells * a.n;
+        ctx->fl.screen_pending = true;
         bracket(ctx, DENSE_GMM, 1);
         return ctx->hip(hipGetLastError(), "screen launch");
     }
-    if (sizeof(T) == 8 && ctx->screen && a.S.cpack != 0) {   // packed map, screened
+    if (sizeof(T) == 8 && ctx->opt.screen && a.S.cpack != 0) {   // packed map, screened
         const int rc = launch_screen_packed(ctx, grp, nl, nch, a);
         bracket(ctx, DENSE_GMM, 1);
         return rc;
@@ -4401,7 +4407,7 @@ int launch_quantized(tpe_ctx* ctx, const Groups& g, const RoundArgs& a, int64_t*
     {
         std::vector<QInfo> qi(nq);
         int64_t tab = 0, maxG = 0;
-        bool fused = ctx->dedup;
+        bool fused = ctx->opt.dedup;
         const int64_t total = a.total_slots;
         for (int qpos = 0; qpos < nq && fused; ++qpos) {
             const int li = qpos < nqg ? ctx->P->h_group[QUANT_GMM][qpos] : ctx->P->h_group[QUANT_LGMM][qpos - nqg];
@@ -4539,7 +4545,7 @@ int launch_quantized(tpe_ctx* ctx, const Groups& g, const RoundArgs& a, int64_t*
         const int64_t jmin = (int64_t)(mm[qpos] ^ 0x8000000000000000ull);
         const int64_t jmax = (int64_t)(mm[nq + qpos] ^ 0x8000000000000000ull);
         const int64_t G = (mm[qpos] <= mm[nq + qpos]) ? jmax - jmin + 1 : 0;
-        qi[qpos] = QInfo{jmin, (ctx->dedup && G > 0 && 2 * G <= total) ? G : 0, tab, 1, 0, 0};
+        qi[qpos] = QInfo{jmin, (ctx->opt.dedup && G > 0 && 2 * G <= total) ? G : 0, tab, 1, 0, 0};
         tab += qi[qpos].G;
         maxG = std::max(maxG, qi[qpos].G);
         const int li = qpos < nqg ? ctx->P->h_group[QUANT_GMM][qpos] : ctx->P->h_group[QUANT_LGMM][qpos - nqg];
@@ -4625,9 +4631,14 @@ int launch_splitk(tpe_ctx* ctx, const Groups& g, const RoundArgs& a, int32_t s_m
     return ctx->hip(hipGetLastError(), "split-K launch");
 }
 
-int run_round(tpe_ctx* ctx, uint64_t seed, const uint32_t* rounds_h, int32_t n_rounds, int64_t n,
-              int64_t cand_offset, const double* cand_in_dev, double* olb, double* ola,
-              tpe_label_result* out, int32_t only_label) {
+// A round in three parts: its arguments (round_args: the checks and the slot
+// map), one attempt (round_attempt: queue the families, reduce, read back,
+// synchronise) and the bookkeeping after the sync (round_stats: the
+// read-backs into ctx->stats).  run_round loops over the attempts.
+
+int round_args(tpe_ctx* ctx, uint64_t seed, const uint32_t* rounds_h, int32_t n_rounds, int64_t n,
+               int64_t cand_offset, const double* cand_in_dev, double* olb, double* ola,
+               tpe_label_result* out, int32_t only_label, RoundArgs* args) {
     if (ctx->P->n_labels == 0) return ctx->fail(TPE_ERR_ARG, "no posterior set (tpe_set_posterior)");
     if (n < 0 || n_rounds <= 0) return ctx->fail(TPE_ERR_ARG, "bad candidate/round count");
     if (cand_offset < 0 || cand_offset + n > (int64_t)UINT32_MAX)
@@ -4636,7 +4647,7 @@ int run_round(tpe_ctx* ctx, uint64_t seed, const uint32_t* rounds_h, int32_t n_r
     // categorical labels on the second stream) is settled after the dense
     // labels' kernels are queued when this round takes the side families to
     // the second stream; first thing otherwise
-    if (!(ctx->build.pending && only_label < 0 && cand_in_dev == nullptr && n > 0 && ctx->aux_families &&
+    if (!(ctx->build.pending && only_label < 0 && cand_in_dev == nullptr && n > 0 && ctx->opt.aux_families &&
           ctx->aux && !ctx->qx))
         TPE_SETTLE(ctx);
     // slot map: packed (whole rounds per workgroup) for candidate sets smaller
@@ -4656,80 +4667,88 @@ int run_round(tpe_ctx* ctx, uint64_t seed, const uint32_t* rounds_h, int32_t n_r
         gx = (uint32_t)tiles;
         gz = (uint32_t)n_rounds;
     }
+    // the whole problem (ctx->hint_*: set by a multi-device context for its shards)
+    const int64_t n_whole =
+        ctx->hint_n > 0 ? ctx->hint_n : (ctx->opt.whole_n > 0 ? ctx->opt.whole_n : n);
+    const int32_t rounds_whole = ctx->hint_rounds > 0
+                                     ? ctx->hint_rounds
+                                     : (ctx->opt.whole_rounds > 0 ? ctx->opt.whole_rounds : n_rounds);
+    const uint32_t gx_whole =
+        S.cpack ? (uint32_t)((rounds_whole + S.rpb - 1) / S.rpb) : gx;
+    // the families this round launches (TPE_OPT_MODE_MASK); the others keep
+    // their statistics from the round that last ran them, and their result
+    // entries are unspecified
+    const int32_t fam = only_label >= 0 ? 31 : ctx->opt.mode_mask;
+    *args = RoundArgs{n, cand_offset, seed, n_rounds, tiles, cand_in_dev, olb, ola, S, gx, gz,
+                      n_whole * rounds_whole, gx_whole, rounds_h, out, only_label, fam, false, false};
+    return TPE_OK;
+}
+
+// what a round's attempt asks of run_round
+enum class Next {
+    kDone,
+    kGrowRescore,   // the packed re-score listed more than its buffers hold: the round again
+    kNoPrefilter,   // the prefilter's check failed: the dense families again without it
+};
+
+int round_attempt(tpe_ctx* ctx, const RoundArgs& a, Next* next) {
+    const int64_t n = a.n;
+    const int32_t n_rounds = a.n_rounds, tiles = a.tiles, fam = a.fam;
+    const Slots& S = a.S;
     const int32_t L = ctx->P->n_labels;
+    *next = Next::kDone;
+    ctx->fl = tpe_rt::InFlight{};
     ctx->rep.clear();   // (an earlier round that failed between its reads and its flush)
     HIPCHK(ctx, ctx->partials.reserve((size_t)n_rounds * L * std::max(tiles, 1)));
     HIPCHK(ctx, ctx->results.reserve((size_t)n_rounds * L));
     HIPCHK(ctx, ctx->rounds.reserve(n_rounds));
     HIPCHK(ctx, ctx->errflag.reserve(1));
-    HIPCHK(ctx, hipMemcpyAsync(ctx->rounds.p, rounds_h, n_rounds * sizeof(uint32_t),
+    HIPCHK(ctx, hipMemcpyAsync(ctx->rounds.p, a.rounds_h, n_rounds * sizeof(uint32_t),
                                hipMemcpyHostToDevice, ctx->stream));
     HIPCHK(ctx, ctx->xdrawn.reserve(2));
     {
         FillSet f{};
         add_fill(f, ctx->errflag.p, sizeof(int32_t), 0);
         add_fill(f, ctx->xdrawn.p, 2 * sizeof(unsigned long long), 0);
-        if (ctx->early && S.cpack == 0 && cand_in_dev == nullptr) {   // early_found: no find yet
+        if (ctx->opt.early && S.cpack == 0 && a.cand_in == nullptr) {   // early_found: no find yet
             HIPCHK(ctx, ctx->xfound.reserve((size_t)n_rounds * L));
             add_fill(f, ctx->xfound.p, (size_t)n_rounds * L * sizeof(int64_t), 0x7f7f7f7fu);
         }
         const int rc = run_fills(ctx, f);
         if (rc) return rc;
     }
-    // the families this round launches (TPE_OPT_MODE_MASK); the others keep
-    // their statistics from the round that last ran them, and their result
-    // entries are unspecified
-    const int32_t fam = only_label >= 0 ? 31 : ctx->mode_mask;
-    const bool dense_on = (fam & 3) != 0;
+    // the launched families' statistics start over
+    RoundStats& st = ctx->stats;
     Groups g;
     for (int m = 0; m < kNumModes; ++m) {
         g.dev[m] = ctx->P->groups.p + ctx->P->group_off[m];
         g.count[m] = (fam >> m) & 1 ? (int32_t)ctx->P->h_group[m].size() : 0;
         if (!((fam >> m) & 1)) continue;
-        ctx->mode_ran[m] = false;
-        ctx->mode_ms[m] = 0.f;
-        ctx->mode_evals[m] = 0;
+        st.mode_ms[m] = 0.f;
+        st.mode_evals[m] = 0;
     }
-    if (only_label >= 0) {  // tpe_score: launch the one label's mode only
+    if (fam & 3) {   // the dense families: the screen's and the prefilter's
+        st.screen_total = st.screen_rescored = st.screen_exec = st.screen_rescore_terms = 0;
+        st.screen_mode = 0;
+        st.hot_ran = false;
+        st.hot_listed = 0;
+        st.hot_fallback = 0;
+    }
+    if (fam & (1 << CAT)) st.cat_early = false;
+    if (a.only_label >= 0) {  // tpe_score: launch the one label's mode only
         HIPCHK(ctx, ctx->one_group.reserve(1));
-        HIPCHK(ctx, hipMemcpyAsync(ctx->one_group.p, &only_label, sizeof(int32_t),
+        HIPCHK(ctx, hipMemcpyAsync(ctx->one_group.p, &a.only_label, sizeof(int32_t),
                                    hipMemcpyHostToDevice, ctx->stream));
         for (int m = 0; m < kNumModes; ++m) g.count[m] = 0;
-        const int m = ctx->P->h_labels[only_label].mode;
+        const int m = ctx->P->h_labels[a.only_label].mode;
         g.dev[m] = ctx->one_group.p;
         g.count[m] = 1;
     }
-    // the whole problem (ctx->hint_*: set by a multi-device context for its shards)
-    const int64_t n_whole =
-        ctx->hint_n > 0 ? ctx->hint_n : (ctx->opt_whole_n > 0 ? ctx->opt_whole_n : n);
-    const int32_t rounds_whole = ctx->hint_rounds > 0
-                                     ? ctx->hint_rounds
-                                     : (ctx->opt_whole_rounds > 0 ? ctx->opt_whole_rounds : n_rounds);
-    const uint32_t gx_whole =
-        S.cpack ? (uint32_t)((rounds_whole + S.rpb - 1) / S.rpb) : gx;
-    RoundArgs a{n, cand_offset, seed, n_rounds, tiles, cand_in_dev, olb, ola, S, gx, gz,
-                n_whole * rounds_whole, gx_whole};
-    if (dense_on) {
-        ctx->screen_total = ctx->screen_rescored = 0;
-        ctx->hot_ran = false;
-        ctx->hot_listed = 0;
-        ctx->hot_fallback = 0;
-        ctx->screen_mode = 0;
-        ctx->screen_exec = 0;
-        ctx->screen_rescore_terms = 0;
-    }
-    if (fam & (1 << CAT)) ctx->cat_early = false;
-    ctx->dense_one = false;
-    ctx->pk_plan_pending = false;
-    ctx->zw_pending = false;
-    ctx->evw_used = 0;
-    ctx->screen_pending = false;
-    ctx->screen_exec_pending = false;
-    const bool sample = cand_in_dev == nullptr;
-    int64_t evals_q[2] = {0, 0};
-    if (ctx->timing) HIPCHK(ctx, hipEventRecord(ctx->ev0, ctx->stream));
+    const bool sample = a.cand_in == nullptr;
+    int64_t* evals_q = ctx->fl.evals_q;
+    if (ctx->opt.timing) HIPCHK(ctx, hipEventRecord(ctx->ev0, ctx->stream));
     // split-K for small sampled rounds (packed map, one tile per label)
-    const bool splitk = sample && ctx->splitk && n > 0 && S.cpack != 0 &&
+    const bool splitk = sample && ctx->opt.splitk && n > 0 && S.cpack != 0 &&
                         a.total_slots <= kSplitKMaxSlots;
     if (splitk) {
         TPE_SETTLE(ctx);
@@ -4758,7 +4777,7 @@ int run_round(tpe_ctx* ctx, uint64_t seed, const uint32_t* rounds_h, int32_t n_r
         // slots, tables and draw counters; forked after the round's resets,
         // joined before the reduction.  (A multi-device shard's quantized
         // window exchange stays on the main stream.)
-        const bool side = ctx->aux_families && ctx->aux && !ctx->qx && a.tiles > 0 &&
+        const bool side = ctx->opt.aux_families && ctx->aux && !ctx->qx && a.tiles > 0 &&
                           g.count[CAT] + g.count[QUANT_GMM] + g.count[QUANT_LGMM] > 0;
         int rc = TPE_OK;
         bool dense_done = false;
@@ -4804,7 +4823,7 @@ int run_round(tpe_ctx* ctx, uint64_t seed, const uint32_t* rounds_h, int32_t n_r
     }
     HIPCHK(ctx, hipGetLastError());
     TPE_SETTLE(ctx);   // (every path above settled it; a guard)
-    if (ctx->timing) HIPCHK(ctx, hipEventRecord(ctx->ev1, ctx->stream));
+    if (ctx->opt.timing) HIPCHK(ctx, hipEventRecord(ctx->ev1, ctx->stream));
     if (tiles == 1) {
         const int64_t nr = (int64_t)n_rounds * L;
         hipLaunchKernelGGL(k_emit, dim3((unsigned)((nr + kBlock - 1) / kBlock)), dim3(kBlock), 0,
@@ -4812,11 +4831,12 @@ int run_round(tpe_ctx* ctx, uint64_t seed, const uint32_t* rounds_h, int32_t n_r
         HIPCHK(ctx, hipGetLastError());
     } else if (tiles > 1) {
         hipLaunchKernelGGL(k_reduce, dim3(L, n_rounds), dim3(kReduceBlock), 0, ctx->stream,
-                           ctx->partials.p, tiles, L, ctx->results.p, ctx->P->labels.p, ctx->dense_one ? 1 : 0);
+                           ctx->partials.p, tiles, L, ctx->results.p, ctx->P->labels.p, ctx->fl.dense_one ? 1 : 0);
         HIPCHK(ctx, hipGetLastError());
     }
-    if (ctx->timing) HIPCHK(ctx, hipEventRecord(ctx->ev2, ctx->stream));
+    if (ctx->opt.timing) HIPCHK(ctx, hipEventRecord(ctx->ev2, ctx->stream));
     PinScalars& pin = ctx->pin[0];
+    tpe_label_result* out = a.out;
     const size_t n_res = (size_t)n_rounds * L;
     if (tiles > 0 && ctx->dev_out)
         HIPCHK(ctx, hipMemcpyAsync(ctx->dev_out, ctx->results.p, n_res * sizeof(tpe_label_result),
@@ -4855,29 +4875,31 @@ int run_round(tpe_ctx* ctx, uint64_t seed, const uint32_t* rounds_h, int32_t n_r
     unpack_reads(ctx);
     if (tiles > 0 && out && !pieces) copy_out(out, ctx->res_h.data(), res_bytes);
     if (tiles == 0 && out) std::memset(out, 0, res_bytes);   // (no candidates: empty records; the caller's array is uninitialised)
-    if (ctx->zw_pending) {
-        ctx->P->zw_ready = pin.plan.total > 0 && !pin.plan.sliced;
-        ctx->zw_pending = false;
+    if (ctx->fl.zw_pending) ctx->P->zw_ready = pin.plan.total > 0 && !pin.plan.sliced;
+    if (ctx->fl.pk_plan_pending && pin.plan.overflow && !a.regrown) {
+        *next = Next::kGrowRescore;   // (nothing was re-scored)
+    } else if ((fam & 3) && st.hot_ran && pin.hot_flag && !a.no_hot && pin.err == 0) {
+        // a cell's best lower bound stayed below tau0 (bit 1: its list may
+        // miss a winner) or a list overflowed (bit 2)
+        *next = Next::kNoPrefilter;
     }
-    if (ctx->pk_plan_pending && pin.plan.overflow && !ctx->pk_redo) {
-        // the packed re-score listed more candidates than its buffers hold:
-        // nothing was re-scored; the round again with buffers for them all
-        ctx->pk_cap = pin.plan.total + pin.plan.total / 4 + 1024;
-        ctx->pk_redo = true;
-        const int rc = run_round(ctx, seed, rounds_h, n_rounds, n, cand_offset, cand_in_dev, olb, ola, out,
-                                 only_label);
-        ctx->pk_redo = false;
-        return rc;
-    }
-    const int32_t errh = pin.err;
-    ctx->xdrawn_h[0] = pin.xdrawn[0];
-    ctx->xdrawn_h[1] = pin.xdrawn[1];
-    if (dense_on) ctx->screen_ms = 0.f;
-    if (ctx->screen_exec_pending) {
-        ctx->screen_exec += (int64_t)ctx->pin[0].screen_exec;
-        ctx->screen_exec_pending = false;
-    }
-    if (ctx->screen_pending) {
+    return TPE_OK;
+}
+
+// After an attempt's sync: its read-backs and event brackets into ctx->stats,
+// the kernels' error word into the round's return code.
+int round_stats(tpe_ctx* ctx, const RoundArgs& a) {
+    const int64_t n = a.n;
+    const int32_t n_rounds = a.n_rounds, fam = a.fam, L = ctx->P->n_labels;
+    const bool sample = a.cand_in == nullptr;
+    const PinScalars& pin = ctx->pin[0];
+    const int64_t* evals_q = ctx->fl.evals_q;
+    RoundStats& st = ctx->stats;
+    st.drawn[0] = pin.xdrawn[0];
+    st.drawn[1] = pin.xdrawn[1];
+    if (fam & 3) st.screen_ms = 0.f;
+    if (ctx->fl.screen_exec_pending) st.screen_exec += (int64_t)pin.screen_exec;
+    if (ctx->fl.screen_pending) {
         // cell = round x (dense GMM1 labels, then dense LGMM1 labels)
         const std::vector<int32_t>& gg = ctx->P->h_group[DENSE_GMM];
         const std::vector<int32_t>& gl = ctx->P->h_group[DENSE_LGMM];
@@ -4886,97 +4908,115 @@ int run_round(tpe_ctx* ctx, uint64_t seed, const uint32_t* rounds_h, int32_t n_r
             const int32_t cnt = ctx->scr_cnt_h[c];
             const size_t y = c % nld;
             const DLabel& d = ctx->P->h_labels[y < gg.size() ? gg[y] : gl[y - gg.size()]];
-            ctx->screen_rescored += cnt;
-            ctx->screen_rescore_terms += (int64_t)cnt * (d.nb + d.na);
+            st.screen_rescored += cnt;
+            st.screen_rescore_terms += (int64_t)cnt * (d.nb + d.na);
         }
-        ctx->screen_pending = false;
-        if (ctx->timing && ctx->evw_used > 0) {   // windowed tile rounds: the units' k_screen_win
-            for (int32_t u = 0; u < ctx->evw_used; ++u) {
+        if (ctx->opt.timing && ctx->fl.evw_used > 0) {   // windowed tile rounds: the units' k_screen_win
+            for (int32_t u = 0; u < ctx->fl.evw_used; ++u) {
                 float ms = 0.f;
                 HIPCHK(ctx, hipEventElapsedTime(&ms, ctx->evw[2 * u], ctx->evw[2 * u + 1]));
-                ctx->screen_ms += ms;
+                st.screen_ms += ms;
             }
-        } else if (ctx->timing) {
-            HIPCHK(ctx, hipEventElapsedTime(&ctx->screen_ms, ctx->evs[0], ctx->evs[1]));
+        } else if (ctx->opt.timing) {
+            HIPCHK(ctx, hipEventElapsedTime(&st.screen_ms, ctx->evs[0], ctx->evs[1]));
         }
     }
-    if (ctx->timing) {
-        HIPCHK(ctx, hipEventElapsedTime(&ctx->score_ms, ctx->ev0, ctx->ev1));
-        HIPCHK(ctx, hipEventElapsedTime(&ctx->round_ms, ctx->ev0, ctx->ev2));
+    if (ctx->opt.timing) {
+        HIPCHK(ctx, hipEventElapsedTime(&st.score_ms, ctx->ev0, ctx->ev1));
+        HIPCHK(ctx, hipEventElapsedTime(&st.round_ms, ctx->ev0, ctx->ev2));
     } else {
-        ctx->score_ms = ctx->round_ms = 0.f;
+        st.score_ms = st.round_ms = 0.f;
     }
     for (int m = 0; m < kNumModes; ++m)
-        if (ctx->mode_ran[m])
-            if (ctx->timing)
-                HIPCHK(ctx, hipEventElapsedTime(&ctx->mode_ms[m], ctx->evm[m][0], ctx->evm[m][1]));
+        if (ctx->fl.mode_ran[m])
+            if (ctx->opt.timing)
+                HIPCHK(ctx, hipEventElapsedTime(&st.mode_ms[m], ctx->evm[m][0], ctx->evm[m][1]));
     int64_t evals = 0;
     for (int32_t l = 0; l < L; ++l) {
-        if (only_label >= 0 && l != only_label) continue;
+        if (a.only_label >= 0 && l != a.only_label) continue;
         const DLabel& d = ctx->P->h_labels[l];
         if (!((fam >> d.mode) & 1)) continue;   // not launched (TPE_OPT_MODE_MASK)
         if (sample && (d.mode == QUANT_GMM || d.mode == QUANT_LGMM)) continue;  // counted below
-        if (d.mode == CAT && ctx->cat_early) continue;   // counted below: the candidates drawn
+        if (d.mode == CAT && st.cat_early) continue;   // counted below: the candidates drawn
         const int64_t e = ((d.mode == CAT) ? 2 * n : n * (int64_t)(d.nb + d.na)) * n_rounds;
         evals += e;
         // sampled rounds time both dense families in one launch (chain)
         const bool merged = sample && d.mode == DENSE_LGMM;
-        ctx->mode_evals[merged ? DENSE_GMM : d.mode] += e;
+        st.mode_evals[merged ? DENSE_GMM : d.mode] += e;
     }
-    ctx->mode_evals[QUANT_GMM] += evals_q[0];
-    ctx->mode_evals[QUANT_LGMM] += evals_q[1];
-    if (ctx->cat_early) {   // 2 lookups per categorical candidate actually drawn
-        ctx->mode_evals[CAT] += 2 * (int64_t)ctx->xdrawn_h[1];
-        evals += 2 * (int64_t)ctx->xdrawn_h[1];
+    st.mode_evals[QUANT_GMM] += evals_q[0];
+    st.mode_evals[QUANT_LGMM] += evals_q[1];
+    if (st.cat_early) {   // 2 lookups per categorical candidate actually drawn
+        st.mode_evals[CAT] += 2 * (int64_t)st.drawn[1];
+        evals += 2 * (int64_t)st.drawn[1];
     }
-    ctx->evals = evals + evals_q[0] + evals_q[1];
-    if (tiles == 0 && out) {
+    st.evals = evals + evals_q[0] + evals_q[1];
+    if (a.tiles == 0 && a.out) {
         for (int32_t j = 0; j < n_rounds * L; ++j)
-            out[j] = tpe_label_result{NAN, NAN, NAN, NAN, -1, j % L, 0};
+            a.out[j] = tpe_label_result{NAN, NAN, NAN, NAN, -1, j % L, 0};
     }
-    if (dense_on && ctx->hot_ran) {
-        for (int64_t c = 0; c < ctx->hot_cells; ++c) ctx->hot_listed += ctx->hot_cnt_h[c];
-        const int32_t hf = pin.hot_flag;
-        if (hf && !ctx->hot_redo && errh == 0) {
-            // a cell's best lower bound stayed below tau0 (bit 1: its list may
-            // miss a winner) or a list overflowed (bit 2): the dense labels run
-            // again with every candidate through the expansion screen (the
-            // same draws; their results replace these), and later rounds list
-            // more after an overflow.  Only the dense families re-run
-            // (TPE_OPT_MODE_MASK): the quantized and categorical labels'
-            // partial rows, draw counts and evaluations stay this run's, and
-            // the reduction reads them again.  tpe_last_hot reports the
-            // fallback (bench: hot_fallbacks), which no test or bench has seen
-            // outside the forced TPE_OPT_HOT = 2
-            if ((hf & 2) && ctx->hot_cap_div > 1.0) ctx->hot_cap_div = std::max(1.0, ctx->hot_cap_div / 4.0);
-            const int64_t listed = ctx->hot_listed;
-            int64_t side_evals = 0;
-            for (int m = QUANT_GMM; m <= CAT; ++m)
-                if ((fam >> m) & 1) side_evals += ctx->mode_evals[m];
-            const unsigned long long drawn0 = ctx->xdrawn_h[0], drawn1 = ctx->xdrawn_h[1];
-            const bool cat_early = ctx->cat_early;
-            const int32_t mask = ctx->mode_mask;
-            ctx->mode_mask = fam & ((1 << DENSE_GMM) | (1 << DENSE_LGMM));
-            ctx->hot_redo = true;
-            const int rc = run_round(ctx, seed, rounds_h, n_rounds, n, cand_offset, cand_in_dev, olb, ola, out,
-                                     only_label);
-            ctx->hot_redo = false;
-            ctx->mode_mask = mask;
-            ctx->hot_ran = true;
-            ctx->hot_fallback = hf;
-            ctx->hot_listed = listed;
-            ctx->evals += side_evals;
-            ctx->xdrawn_h[0] = drawn0;
-            ctx->xdrawn_h[1] = drawn1;
-            ctx->cat_early = cat_early;
-            return rc;
-        }
-    }
+    if ((fam & 3) && st.hot_ran)
+        for (int64_t c = 0; c < ctx->fl.hot_cells; ++c) st.hot_listed += ctx->hot_cnt_h[c];
+    const int32_t errh = pin.err;
     if (errh & 1) return ctx->fail(TPE_ERR_SAMPLE, "truncated sampler: interval [low, high) not reached");
     if (errh & 2) return ctx->fail(TPE_ERR_VALUE, "negative arg to lognormal_cdf");
     if (errh & 4) return ctx->fail(TPE_ERR_VALUE, "categorical sample out of range");
     if (errh & 8) return ctx->fail(TPE_ERR_VALUE, "quantized sample beyond 2^52 grid steps");
     return TPE_OK;
+}
+
+// The statistics of a round whose dense families ran again without the
+// prefilter (flag word hf): the first attempt's for the quantized and
+// categorical labels, which ran once -- their evaluations, draw counts and
+// times -- and for what the prefilter listed; the second attempt's for the
+// dense families, the screen and the round's times.
+RoundStats after_fallback(const RoundStats& first, RoundStats redo, int32_t fam, int32_t hf) {
+    redo.hot_ran = true;
+    redo.hot_fallback = hf;
+    redo.hot_listed = first.hot_listed;
+    for (int m = QUANT_GMM; m <= CAT; ++m)   // (their per-family entries the second attempt left alone)
+        if ((fam >> m) & 1) redo.evals += first.mode_evals[m];
+    redo.drawn[0] = first.drawn[0];
+    redo.drawn[1] = first.drawn[1];
+    redo.cat_early = first.cat_early;
+    return redo;
+}
+
+int run_round(tpe_ctx* ctx, uint64_t seed, const uint32_t* rounds_h, int32_t n_rounds, int64_t n,
+              int64_t cand_offset, const double* cand_in_dev, double* olb, double* ola,
+              tpe_label_result* out, int32_t only_label) {
+    RoundArgs a;
+    int rc = round_args(ctx, seed, rounds_h, n_rounds, n, cand_offset, cand_in_dev, olb, ola, out, only_label, &a);
+    if (rc) return rc;
+    const int32_t fam = a.fam;
+    RoundStats first;    // of the attempt whose prefilter fell back
+    int32_t hf = 0;      //   and its flag word
+    for (;;) {           // at most one more attempt for each of the two reasons
+        Next next;
+        if ((rc = round_attempt(ctx, a, &next))) return rc;
+        if (next == Next::kGrowRescore) {   // the round again with buffers for them all
+            const int64_t total = ctx->pin[0].plan.total;
+            ctx->opt.pk_cap = total + total / 4 + 1024;
+            a.regrown = true;
+            continue;
+        }
+        rc = round_stats(ctx, a);
+        if (rc || next != Next::kNoPrefilter) break;
+        // the dense labels again with every candidate through the expansion
+        // screen (the same draws; their results replace these), and later
+        // rounds list more after an overflow.  The quantized and categorical
+        // labels' partial rows stay the first attempt's, and the reduction
+        // reads them again.  tpe_last_hot reports the fallback (bench:
+        // hot_fallbacks), which no test or bench has seen outside the forced
+        // TPE_OPT_HOT = 2
+        hf = ctx->pin[0].hot_flag;
+        if ((hf & 2) && ctx->opt.hot_cap_div > 1.0) ctx->opt.hot_cap_div = std::max(1.0, ctx->opt.hot_cap_div / 4.0);
+        first = ctx->stats;
+        a.fam = fam & ((1 << DENSE_GMM) | (1 << DENSE_LGMM));
+        a.no_hot = true;
+    }
+    if (hf) ctx->stats = after_fallback(first, ctx->stats, fam, hf);
+    return rc;
 }
 
 // the sampling records of a host-uploaded posterior: one block per label,
@@ -5472,7 +5512,7 @@ int tpe_screen_probe(tpe_ctx* ctx, int32_t label, const double* cand, int64_t n,
     HIPCHK(ctx, hipMemcpyAsync(ctx->one_group.p, &label, sizeof(int32_t), hipMemcpyHostToDevice, ctx->stream));
     HIPCHK(ctx, hipMemcpyAsync(ctx->cand.p, cand, n * sizeof(double), hipMemcpyHostToDevice, ctx->stream));
     bool use_bx = false;
-    if (ctx->expand && n >= 2048) {
+    if (ctx->opt.expand && n >= 2048) {
         ctx->bx_t_next = kBxTTile;
         int rc = tpe_rt::bx_prepare(ctx);
         if (rc) return rc;
@@ -5486,7 +5526,7 @@ int tpe_screen_probe(tpe_ctx* ctx, int32_t label, const double* cand, int64_t n,
                            P.bx_loff.p, P.bx_list.p, n, 0, 0, ctx->rounds.p, 1, nullptr, nullptr, nullptr,
                            nullptr, nullptr, ctx->errflag.p, Slots{0, 0, 1}, ctx->cand.p, ctx->out_lb.p,
                            ctx->out_la.p, nullptr, (int64_t)0);
-    } else if (ctx->window && n >= 2048) {   // the windowed screen's tiles of sorted neighbours
+    } else if (ctx->opt.window && n >= 2048) {   // the windowed screen's tiles of sorted neighbours
         int rc = tpe_rt::win_prepare(ctx);
         if (rc) return rc;
         if (n > ((int64_t)1 << 30)) return ctx->fail(TPE_ERR_ARG, "screen probe: too many candidates");
@@ -5566,28 +5606,28 @@ int tpe_merge_results(const tpe_label_result* parts, int32_t n_parts, int32_t n,
 
 int tpe_last_timing(const tpe_ctx* ctx, float* score_ms, float* round_ms) {
     if (!ctx) return TPE_ERR_ARG;
-    if (score_ms) *score_ms = ctx->score_ms;
-    if (round_ms) *round_ms = ctx->round_ms;
+    if (score_ms) *score_ms = ctx->stats.score_ms;
+    if (round_ms) *round_ms = ctx->stats.round_ms;
     return TPE_OK;
 }
 
-int64_t tpe_last_evals(const tpe_ctx* ctx) { return ctx ? ctx->evals : -1; }
+int64_t tpe_last_evals(const tpe_ctx* ctx) { return ctx ? ctx->stats.evals : -1; }
 
 int tpe_last_screen(const tpe_ctx* ctx, int64_t* screened, int64_t* rescored, float* screen_ms) {
     if (!ctx) return TPE_ERR_ARG;
-    if (screened) *screened = ctx->screen_total;
-    if (rescored) *rescored = ctx->screen_rescored;
-    if (screen_ms) *screen_ms = ctx->screen_ms;
+    if (screened) *screened = ctx->stats.screen_total;
+    if (rescored) *rescored = ctx->stats.screen_rescored;
+    if (screen_ms) *screen_ms = ctx->stats.screen_ms;
     return TPE_OK;
 }
 
 int tpe_last_screen_terms(const tpe_ctx* ctx, int64_t* terms) {
     if (!ctx) return TPE_ERR_ARG;
-    if (terms) *terms = ctx->screen_exec;
+    if (terms) *terms = ctx->stats.screen_exec;
     return TPE_OK;
 }
 
-int32_t tpe_last_screen_mode(const tpe_ctx* ctx) { return ctx ? ctx->screen_mode : -1; }
+int32_t tpe_last_screen_mode(const tpe_ctx* ctx) { return ctx ? ctx->stats.screen_mode : -1; }
 
 int tpe_last_prepare(tpe_ctx* ctx, float* ms) {
     if (!ctx) return TPE_ERR_ARG;
@@ -5602,15 +5642,15 @@ int tpe_last_prepare(tpe_ctx* ctx, float* ms) {
 
 int tpe_last_hot(const tpe_ctx* ctx, int64_t* listed, int32_t* fallback) {
     if (!ctx) return TPE_ERR_ARG;
-    if (listed) *listed = ctx->hot_ran ? ctx->hot_listed : -1;
-    if (fallback) *fallback = ctx->hot_fallback;
+    if (listed) *listed = ctx->stats.hot_ran ? ctx->stats.hot_listed : -1;
+    if (fallback) *fallback = ctx->stats.hot_fallback;
     return TPE_OK;
 }
 
 int tpe_last_drawn(const tpe_ctx* ctx, int64_t* quantized, int64_t* categorical) {
     if (!ctx) return TPE_ERR_ARG;
-    if (quantized) *quantized = (int64_t)ctx->xdrawn_h[0];
-    if (categorical) *categorical = (int64_t)ctx->xdrawn_h[1];
+    if (quantized) *quantized = (int64_t)ctx->stats.drawn[0];
+    if (categorical) *categorical = (int64_t)ctx->stats.drawn[1];
     return TPE_OK;
 }
 
@@ -5618,7 +5658,7 @@ int64_t tpe_device_bytes(void) { return tpe_rt::device_bytes_held().load(std::me
 
 int tpe_last_rescore_terms(const tpe_ctx* ctx, int64_t* terms) {
     if (!ctx) return TPE_ERR_ARG;
-    if (terms) *terms = ctx->screen_rescore_terms;
+    if (terms) *terms = ctx->stats.screen_rescore_terms;
     return TPE_OK;
 }
 
@@ -5629,12 +5669,12 @@ TPE_DEV int tpe1_prepare(tpe_ctx* ctx, int64_t n_candidates, int32_t n_rounds) {
     if (n_candidates < 0 || n_rounds < 1) return ctx->fail(TPE_ERR_ARG, "bad candidate/round count");
     // the rounds that use the index: tile rounds of >= kWinMinN candidates,
     // packed rounds of >= kWinMinN slots in total (launch_dense)
-    if (ctx->precision != TPE_F64 || !ctx->screen || !ctx->expand || n_candidates * n_rounds < kWinMinN)
+    if (ctx->precision != TPE_F64 || !ctx->opt.screen || !ctx->opt.expand || n_candidates * n_rounds < kWinMinN)
         return TPE_OK;
     HIPCHK(ctx, hipSetDevice(ctx->device));
     ctx->bx_t_next = n_candidates >= kTile ? kBxTTile : kBxT;   // (the map the rounds take)
     int rc = tpe_rt::bx_prepare(ctx);
-    if (rc == TPE_OK && ctx->hot && n_candidates >= kWinMinN) rc = hot_tau_prepare(ctx, n_candidates);
+    if (rc == TPE_OK && ctx->opt.hot && n_candidates >= kWinMinN) rc = hot_tau_prepare(ctx, n_candidates);
     return rc;
 }
 
@@ -5652,27 +5692,27 @@ TPE_DEV int tpe1_set_option(tpe_ctx* ctx, int32_t option, int64_t value) {
     if (!ctx) return TPE_ERR_ARG;
     TPE_SETTLE(ctx);   // (the header's rule: a pending deferred rebuild's report first)
     switch (option) {
-        case TPE_OPT_SCREEN: ctx->screen = value != 0; break;
-        case TPE_OPT_SPLITK: ctx->splitk = value != 0; break;
-        case TPE_OPT_DEDUP: ctx->dedup = value != 0; break;
+        case TPE_OPT_SCREEN: ctx->opt.screen = value != 0; break;
+        case TPE_OPT_SPLITK: ctx->opt.splitk = value != 0; break;
+        case TPE_OPT_DEDUP: ctx->opt.dedup = value != 0; break;
         case TPE_OPT_CHUNKS:
             if (value < 0 || value > 4096) return ctx->fail(TPE_ERR_ARG, "chunks must be in [0, 4096]");
-            ctx->chunks_forced = (int32_t)value;
+            ctx->opt.chunks_forced = (int32_t)value;
             break;
-        case TPE_OPT_TIMING: ctx->timing = value != 0; break;
-        case TPE_OPT_WINDOW: ctx->window = value != 0; break;
-        case TPE_OPT_EXPAND: ctx->expand = value != 0; break;
-        case TPE_OPT_EARLY: ctx->early = value != 0; break;
-        case TPE_OPT_ZERO_WIN: ctx->zero_win = value != 0; break;
-        case TPE_OPT_VALUE_ONLY: ctx->value_only = value != 0; break;
+        case TPE_OPT_TIMING: ctx->opt.timing = value != 0; break;
+        case TPE_OPT_WINDOW: ctx->opt.window = value != 0; break;
+        case TPE_OPT_EXPAND: ctx->opt.expand = value != 0; break;
+        case TPE_OPT_EARLY: ctx->opt.early = value != 0; break;
+        case TPE_OPT_ZERO_WIN: ctx->opt.zero_win = value != 0; break;
+        case TPE_OPT_VALUE_ONLY: ctx->opt.value_only = value != 0; break;
         case TPE_OPT_BX_T:
             if (value != 0 && (value < 32 || value > 128)) return ctx->fail(TPE_ERR_ARG, "index cut T must be 0 or in [32, 128]");
-            ctx->bx_t_force = (int32_t)value;
+            ctx->opt.bx_t_force = (int32_t)value;
             break;
         case TPE_OPT_PK_SLICED:
             if (value < 0 || value > kSlicedRescoreMax)
                 return ctx->fail(TPE_ERR_ARG, "packed sliced re-score limit must be in [0, 65536]");
-            ctx->pk_sliced = value;
+            ctx->opt.pk_sliced = value;
             break;
         case TPE_OPT_DEFER_REPORT:
             if (!ctx->peers.empty() && value) return ctx->fail(TPE_ERR_ARG, "deferred reports: single-device contexts only");
@@ -5681,44 +5721,44 @@ TPE_DEV int tpe1_set_option(tpe_ctx* ctx, int32_t option, int64_t value) {
         case TPE_OPT_JOINT_CAP:
             if (value < 0 || value > ((int64_t)1 << 30))
                 return ctx->fail(TPE_ERR_ARG, "joint flat candidate cap must be in [0, 2^30]");
-            ctx->joint_flat_cap = value;
+            ctx->opt.joint_flat_cap = value;
             break;
         case TPE_OPT_BX_SPLIT:
             if (value < 0 || value > 8) return ctx->fail(TPE_ERR_ARG, "index window split must be in [0, 8]");
-            ctx->bx_split = (int32_t)value;
+            ctx->opt.bx_split = (int32_t)value;
             break;
         case TPE_OPT_MODE_MASK:
             if (value < 1 || value > 31) return ctx->fail(TPE_ERR_ARG, "family mask must be in [1, 31]");
-            ctx->mode_mask = (int32_t)value;
+            ctx->opt.mode_mask = (int32_t)value;
             break;
-        case TPE_OPT_AUX_FAMILIES: ctx->aux_families = value != 0; break;
+        case TPE_OPT_AUX_FAMILIES: ctx->opt.aux_families = value != 0; break;
         case TPE_OPT_RESCORE_CAP:
             if (value < 1) return ctx->fail(TPE_ERR_ARG, "re-score capacity must be positive");
-            ctx->pk_cap = value;
+            ctx->opt.pk_cap = value;
             break;
         case TPE_OPT_HOT_DIV:
             if (value < 1 || value > (1 << 20)) return ctx->fail(TPE_ERR_ARG, "hot list divisor must be in [1, 2^20]");
-            ctx->hot_cap_div = (double)value;
+            ctx->opt.hot_cap_div = (double)value;
             break;
         case TPE_OPT_HOT:
             if (value < 0 || value > 2) return ctx->fail(TPE_ERR_ARG, "hot must be 0, 1 or 2");
-            ctx->hot = (int32_t)value;
+            ctx->opt.hot = (int32_t)value;
             break;
         case TPE_OPT_WIN_GROUPS:
             if (value < 0 || value > 64) return ctx->fail(TPE_ERR_ARG, "window groups must be in [0, 64]");
-            ctx->win_groups = (int32_t)value;
+            ctx->opt.win_groups = (int32_t)value;
             break;
         case TPE_OPT_WIN_T:
             if (value < 8 || value > 62) return ctx->fail(TPE_ERR_ARG, "window cut must be in [8, 62]");
-            ctx->win_t = (int32_t)value;
+            ctx->opt.win_t = (int32_t)value;
             break;
         case TPE_OPT_WHOLE_N:
             if (value < 0) return ctx->fail(TPE_ERR_ARG, "whole candidate count must be >= 0");
-            ctx->opt_whole_n = value;
+            ctx->opt.whole_n = value;
             break;
         case TPE_OPT_WHOLE_ROUNDS:
             if (value < 0 || value > INT32_MAX) return ctx->fail(TPE_ERR_ARG, "whole round count");
-            ctx->opt_whole_rounds = (int32_t)value;
+            ctx->opt.whole_rounds = (int32_t)value;
             break;
         default: return ctx->fail(TPE_ERR_ARG, "unknown option " + std::to_string(option));
     }
@@ -5728,8 +5768,8 @@ TPE_DEV int tpe1_set_option(tpe_ctx* ctx, int32_t option, int64_t value) {
 int tpe_last_mode_stats(const tpe_ctx* ctx, float* ms, int64_t* evals) {
     if (!ctx) return TPE_ERR_ARG;
     for (int m = 0; m < kNumModes; ++m) {
-        if (ms) ms[m] = ctx->mode_ms[m];
-        if (evals) evals[m] = ctx->mode_evals[m];
+        if (ms) ms[m] = ctx->stats.mode_ms[m];
+        if (evals) evals[m] = ctx->stats.mode_evals[m];
     }
     return TPE_OK;
 }

@@ -885,7 +885,7 @@ uint64_t tpe_rt::next_bx_gen() {
 int tpe_rt::bx_prepare(tpe_ctx* ctx) {
     tpe_rt::Posterior& P = *ctx->P;
     if (P.bx_ready) return TPE_OK;
-    const bool timed = ctx->timing && ctx->ev_prep[0];
+    const bool timed = ctx->opt.timing && ctx->ev_prep[0];
     if (timed) HIPCHK(ctx, hipEventRecord(ctx->ev_prep[0], ctx->stream));
     const int rc = bx_build(ctx);
     if (rc == TPE_OK && timed) {
@@ -928,7 +928,7 @@ int tpe_rt::bx_build(tpe_ctx* ctx) {
     P.bx_h.assign(P.n_labels, BxLabel{});
     // the window's cut: forced (TPE_OPT_BX_T), else what the coming rounds
     // need (tile rounds through the hot-bin prefilter: kBxTTile)
-    const double T = ctx->bx_t_force > 0 ? (double)ctx->bx_t_force : ctx->bx_t_next;
+    const double T = ctx->opt.bx_t_force > 0 ? (double)ctx->opt.bx_t_force : ctx->bx_t_next;
     bool ok = true;
     int64_t rows = 0, lsum = 0;
     int32_t bins_max = 0;
@@ -1011,7 +1011,7 @@ int tpe_rt::bx_build(tpe_ctx* ctx) {
     // (round 6, 16 bins per wave: config 3 split 1 / 2 / 4 / 8 -> 0.364 /
     // 0.361 / 0.354 / 0.382 ms index, config 5 1 / 2 / 3 / 4 / 6 -> 2.97 /
     // 2.73 / 2.68 / 2.67 / 2.75 ms, r6ag: at most 4 parts)
-    const int nsplit = ctx->bx_split > 0 ? std::min(ctx->bx_split, kBxMaxSplit)
+    const int nsplit = ctx->opt.bx_split > 0 ? std::min(ctx->opt.bx_split, kBxMaxSplit)
                        : wgs >= 4096     ? 3
                                          : (int)std::max<int64_t>(1, std::min<int64_t>(4, 8192 / std::max<int64_t>(wgs, 1)));
     if (nsplit > 1) HIPCHK(ctx, P.bx_part.reserve((size_t)nsplit * kPartSums * rows));

@@ -2062,19 +2062,19 @@ int tpe1_joint_suggest_group(tpe_ctx* ctx, int32_t slot, uint64_t seed, uint32_t
     HIPCHK(ctx, G->res.reserve(3 + J->D));
     HIPCHK(ctx, hipMemsetAsync(G->err.p, 0, sizeof(int32_t), ctx->stream));
     int32_t nparts = 0;
-    if (ctx->timing) HIPCHK(ctx, hipEventRecord(ctx->ev0, ctx->stream));
+    if (ctx->opt.timing) HIPCHK(ctx, hipEventRecord(ctx->ev0, ctx->stream));
     if ((rc = launch_round(ctx, G, J, true, n_candidates, cand_offset, seed, round, false, &nparts, G->err.p)))
         return rc;
     hipLaunchKernelGGL(k_joint_best, dim3(1), dim3(kJBlock), 0, ctx->stream, J->jp(), G->partials.p, nparts,
                        cand_offset, seed, round, 1, G->res.p);
     HIPCHK(ctx, hipGetLastError());
-    if (ctx->timing) HIPCHK(ctx, hipEventRecord(ctx->ev1, ctx->stream));
+    if (ctx->opt.timing) HIPCHK(ctx, hipEventRecord(ctx->ev1, ctx->stream));
     std::vector<double> h(3 + J->D);
     HIPCHK(ctx, hipMemcpyAsync(h.data(), G->res.p, h.size() * sizeof(double), hipMemcpyDeviceToHost, ctx->stream));
     if ((rc = read_err(ctx, G))) return rc;
-    if (ctx->timing) {   // the round's device time (tpe_last_timing: both figures)
-        HIPCHK(ctx, hipEventElapsedTime(&ctx->round_ms, ctx->ev0, ctx->ev1));
-        ctx->score_ms = ctx->round_ms;
+    if (ctx->opt.timing) {   // the round's device time (tpe_last_timing: both figures)
+        HIPCHK(ctx, hipEventElapsedTime(&ctx->stats.round_ms, ctx->ev0, ctx->ev1));
+        ctx->stats.score_ms = ctx->stats.round_ms;
     }
     *ll = h[0];
     *lg = h[1];
@@ -2112,7 +2112,7 @@ int tpe1_joint_suggest_batch(tpe_ctx* ctx, uint64_t seed, const uint32_t* rounds
         sumD += J->D;
     }
     const int64_t R = n_rounds, n = n_candidates;
-    const int64_t cap = ctx->joint_flat_cap > 0 ? ctx->joint_flat_cap : kJFlatCap;
+    const int64_t cap = ctx->opt.joint_flat_cap > 0 ? ctx->opt.joint_flat_cap : kJFlatCap;
     const int64_t per = n <= cap ? std::min<int64_t>(R, cap / n) : 0;   // rounds of a packed chunk
     HIPCHK(ctx, hipSetDevice(ctx->device));
     hipStream_t st = ctx->stream;
@@ -2126,7 +2126,7 @@ int tpe1_joint_suggest_batch(tpe_ctx* ctx, uint64_t seed, const uint32_t* rounds
     int32_t* err = reinterpret_cast<int32_t*>(G->bres.p);
     HIPCHK(ctx, hipMemsetAsync(G->bres.p, 0, sizeof(double), st));
     HIPCHK(ctx, hipMemcpyAsync(G->rounds.p, rounds, R * sizeof(uint32_t), hipMemcpyHostToDevice, st));
-    if (ctx->timing) HIPCHK(ctx, hipEventRecord(ctx->ev0, st));
+    if (ctx->opt.timing) HIPCHK(ctx, hipEventRecord(ctx->ev0, st));
     double* row0 = G->bres.p + 1;
     for (JointState* J : set) {
         const size_t w = 3 + J->D;
@@ -2152,16 +2152,16 @@ int tpe1_joint_suggest_batch(tpe_ctx* ctx, uint64_t seed, const uint32_t* rounds
         }
         row0 += (size_t)R * w;
     }
-    if (ctx->timing) HIPCHK(ctx, hipEventRecord(ctx->ev1, st));
+    if (ctx->opt.timing) HIPCHK(ctx, hipEventRecord(ctx->ev1, st));
     G->hres.resize(total);
     HIPCHK(ctx, hipMemcpyAsync(G->hres.data(), G->bres.p, total * sizeof(double), hipMemcpyDeviceToHost, st));
     HIPCHK(ctx, hipStreamSynchronize(st));
     int32_t e = 0;
     std::memcpy(&e, G->hres.data(), sizeof(e));
     if (e & 1) return not_reached(ctx);
-    if (ctx->timing) {
-        HIPCHK(ctx, hipEventElapsedTime(&ctx->round_ms, ctx->ev0, ctx->ev1));
-        ctx->score_ms = ctx->round_ms;
+    if (ctx->opt.timing) {
+        HIPCHK(ctx, hipEventElapsedTime(&ctx->stats.round_ms, ctx->ev0, ctx->ev1));
+        ctx->stats.score_ms = ctx->stats.round_ms;
     }
     const size_t ns = set.size();
     const double* h = G->hres.data() + 1;

@@ -215,47 +215,11 @@ struct Shard {
     int32_t round_lo = 0, n_rounds = 0;
 };
 
-// Aggregate the last round's statistics of all devices into the primary:
-// work summed, times the slowest device's.
+// Aggregate the last round's statistics of all devices into the primary
+// (RoundStats::merge: work summed, times the slowest device's; the screen
+// mode is the primary's own).
 void aggregate_stats(tpe_ctx* c) {
-    const int n = ndev(c);
-    int64_t evals = 0, scr_t = 0, scr_r = 0, scr_x = 0, scr_rt = 0;
-    unsigned long long drawn[2] = {0, 0};
-    float score_ms = 0.f, round_ms = 0.f, scr_ms = 0.f;
-    float mode_ms[tpe_rt::kNumModes] = {};
-    int64_t mode_ev[tpe_rt::kNumModes] = {};
-    for (int d = 0; d < n; ++d) {
-        const tpe_ctx* x = dev(c, d);
-        evals += x->evals;
-        scr_t += x->screen_total;
-        scr_r += x->screen_rescored;
-        scr_x += x->screen_exec;
-        scr_rt += x->screen_rescore_terms;
-        drawn[0] += x->xdrawn_h[0];
-        drawn[1] += x->xdrawn_h[1];
-        score_ms = std::max(score_ms, x->score_ms);
-        round_ms = std::max(round_ms, x->round_ms);
-        scr_ms = std::max(scr_ms, x->screen_ms);
-        for (int m = 0; m < tpe_rt::kNumModes; ++m) {
-            mode_ms[m] = std::max(mode_ms[m], x->mode_ms[m]);
-            mode_ev[m] += x->mode_evals[m];
-        }
-    }
-    c->evals = evals;
-    c->screen_total = scr_t;
-    c->screen_rescored = scr_r;
-    c->screen_exec = scr_x;
-    c->screen_rescore_terms = scr_rt;
-    c->xdrawn_h[0] = drawn[0];
-    c->xdrawn_h[1] = drawn[1];
-    c->screen_mode = dev(c, 0)->screen_mode;
-    c->score_ms = score_ms;
-    c->round_ms = round_ms;
-    c->screen_ms = scr_ms;
-    for (int m = 0; m < tpe_rt::kNumModes; ++m) {
-        c->mode_ms[m] = mode_ms[m];
-        c->mode_evals[m] = mode_ev[m];
-    }
+    for (int d = 1; d < ndev(c); ++d) c->stats.merge(dev(c, d)->stats);
 }
 
 // One sharded round (tpe_suggest / tpe_suggest_batch): shards by candidate
@@ -297,11 +261,11 @@ int sharded_round(tpe_ctx* c, uint64_t seed, const uint32_t* rounds, int32_t n_r
         tpe_label_result* o = by_cand ? parts.data() + (size_t)d * n_rounds * L
                                       : out + (size_t)sh[d].round_lo * L;
         // candidate shards merge by score: a value-only cell has none
-        const bool vo = x->value_only;
-        if (by_cand) x->value_only = false;
+        const bool vo = x->opt.value_only;
+        if (by_cand) x->opt.value_only = false;
         int r = tpe1_suggest_batch(x, seed, rounds + sh[d].round_lo, sh[d].n_rounds, sh[d].n_cand,
                                    cand_offset + sh[d].cand_lo, o);
-        x->value_only = vo;
+        x->opt.value_only = vo;
         x->hint_n = 0;
         x->hint_rounds = 0;
         x->qx = nullptr;
@@ -421,11 +385,11 @@ using JointRun = std::function<int(tpe_ctx*, const Shard&, double*, int64_t*, do
 void joint_timing(tpe_ctx* c) {   // (the slowest device's, as aggregate_stats)
     float score_ms = 0.f, round_ms = 0.f;
     for (int d = 0; d < ndev(c); ++d) {
-        score_ms = std::max(score_ms, dev(c, d)->score_ms);
-        round_ms = std::max(round_ms, dev(c, d)->round_ms);
+        score_ms = std::max(score_ms, dev(c, d)->stats.score_ms);
+        round_ms = std::max(round_ms, dev(c, d)->stats.round_ms);
     }
-    c->score_ms = score_ms;
-    c->round_ms = round_ms;
+    c->stats.score_ms = score_ms;
+    c->stats.round_ms = round_ms;
 }
 
 int joint_sharded(tpe_ctx* c, int32_t n_rounds, int64_t n, int32_t ns, const int32_t* D, const JointRun& run,

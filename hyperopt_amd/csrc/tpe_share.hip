@@ -148,7 +148,7 @@ int tpe_export_posterior(tpe_ctx* ctx, void* d_out, int64_t cap, int64_t* bytes_
     HIPCHK(ctx, hipSetDevice(ctx->device));
     ctx->P = &ctx->resident;
     // the index of the coming large rounds: the exporter's own (queued now if not yet built)
-    if (!P.bx_ready && ctx->screen && ctx->expand && ctx->precision == TPE_F64) {
+    if (!P.bx_ready && ctx->opt.screen && ctx->opt.expand && ctx->precision == TPE_F64) {
         const int rc = tpe_rt::bx_prepare(ctx);
         if (rc) return rc;
     }

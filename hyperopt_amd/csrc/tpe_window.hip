@@ -681,9 +681,9 @@ int64_t tpe_rt::win_rounds_per_batch(int64_t n, int32_t nl) {
 
 int tpe_rt::win_prepare(tpe_ctx* ctx) {
     tpe_rt::Posterior& P = *ctx->P;
-    if (P.win_ready && P.win_t == ctx->win_t) return TPE_OK;
-    P.win_t = ctx->win_t;
-    const double T = (double)ctx->win_t;
+    if (P.win_ready && P.win_t == ctx->opt.win_t) return TPE_OK;
+    P.win_t = ctx->opt.win_t;
+    const double T = (double)ctx->opt.win_t;
     const int nl = (int)(P.h_group[DENSE_GMM].size() + P.h_group[DENSE_LGMM].size());
     if (nl == 0) {
         P.win_ready = true;
@@ -844,7 +844,7 @@ int tpe_rt::win_screen(tpe_ctx* ctx, const WinScreenArgs& a, const uint64_t** so
     WinScreenArgs b = a;
     b.slot = 0;
     if ((rc = win_sort(ctx, b, ctx->stream, sorted_vals))) return rc;
-    const bool timed = ctx->timing && !a.cand_in;
+    const bool timed = ctx->opt.timing && !a.cand_in;
     if (timed) HIPCHK(ctx, hipEventRecord(ctx->evs[0], ctx->stream));
     if ((rc = win_tiles(ctx, b, *sorted_vals, ctx->stream))) return rc;
     if (timed) HIPCHK(ctx, hipEventRecord(ctx->evs[1], ctx->stream));
