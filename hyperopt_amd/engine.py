@@ -737,13 +737,16 @@ class Engine(object):
             out += (lb, la)
         return out
 
-    def mo_keys(self, F, want_counts=False):
+    def mo_keys(self, F, want_counts=False, G=None):
         """The Pareto-compliant order of the objective vectors F [n, M], all
         minimised (tpe_mo_keys; posterior.mo_keys is its numpy restatement):
         keys [n] float64 -- row i's position under ascending dominated_by,
         descending dominates, ascending i; NaN for a row with a NaN.
         want_counts adds (dominated_by, dominates) [n] int32, -1 for such a
-        row."""
+        row.  G [n, K] (constraints, <= 0 satisfied): the order with the
+        feasible rows first and the infeasible ones by ascending violation
+        (tpe_mo_keys_constrained); want_counts then returns (keys,
+        dominated_by, dominates, violation [n] float64)."""
         F = np.ascontiguousarray(F, dtype=np.float64)
         if F.ndim != 2:
             raise ValueError('F must be [n, n_objectives]')
@@ -751,8 +754,16 @@ class Engine(object):
         keys = np.empty(n)
         by = np.empty(n, dtype=np.int32) if want_counts else None
         do = np.empty(n, dtype=np.int32) if want_counts else None
-        self._check(self.lib.tpe_mo_keys(self.h, _ptr(F), n, F.shape[1], _ptr(keys), _ptr(by), _ptr(do)))
-        return (keys, by, do) if want_counts else keys
+        if G is None:
+            self._check(self.lib.tpe_mo_keys(self.h, _ptr(F), n, F.shape[1], _ptr(keys), _ptr(by), _ptr(do)))
+            return (keys, by, do) if want_counts else keys
+        G = np.ascontiguousarray(G, dtype=np.float64)
+        if G.ndim != 2 or G.shape[0] != n:
+            raise ValueError('G must be [n, n_constraints], a row for every row of F')
+        v = np.empty(n) if want_counts else None
+        self._check(self.lib.tpe_mo_keys_constrained(self.h, _ptr(F), n, F.shape[1], _ptr(G), G.shape[1],
+                                                     _ptr(keys), _ptr(by), _ptr(do), _ptr(v)))
+        return (keys, by, do, v) if want_counts else keys
 
     def last_timing(self):
         a, b = ctypes.c_float(), ctypes.c_float()

@@ -95,6 +95,7 @@ class Splitter(object):
 
 
 MO_MAX_OBJECTIVES = 8
+MO_MAX_CONSTRAINTS = 8
 MO_MAX_ROWS = 1 << 20
 # bytes of comparison results mo_counts forms at a time: a block of rows
 # against all rows holds about eight one-byte matrices (both "every"
@@ -103,21 +104,60 @@ MO_MAX_ROWS = 1 << 20
 MO_CHUNK_BYTES = 64 << 20
 
 
-def mo_counts(F):
+def mo_violation(G, F=None):
+    """The total violation of the constraint rows G [n, K] (c <= 0 satisfied,
+    c > 0 violated by that amount): v[i] = ((0.0 + max(G[i, 0], 0)) +
+    max(G[i, 1], 0)) + ... in float64, column by column in this order -- the
+    bits tpe_mo_keys_constrained gives (additions only).  -inf and -0.0
+    contribute zero, +inf is an ordinary value.  NaN for a row with a NaN in
+    G, and in F [n, M] when it is given (a dead row).  v == 0: feasible."""
+    G = np.asarray(G, dtype=np.float64)
+    if G.ndim != 2 or not 1 <= G.shape[1] <= MO_MAX_CONSTRAINTS:
+        raise ValueError('G must be [n, 1 .. %d constraints]' % MO_MAX_CONSTRAINTS)
+    v = np.zeros(len(G))
+    with np.errstate(over='ignore'):                     # (a sum past the largest double is +inf, as on the device)
+        for k in range(G.shape[1]):
+            v = v + np.where(G[:, k] > 0.0, G[:, k], 0.0)
+    dead = np.isnan(G).any(axis=1)
+    if F is not None:
+        F = np.asarray(F, dtype=np.float64)
+        if F.ndim != 2 or len(F) != len(G):
+            raise ValueError('F and G must have a row for every trial')
+        dead |= np.isnan(F).any(axis=1)
+    v[dead] = np.nan
+    return v
+
+
+def mo_counts(F, G=None):
     """The dominance counts of the objective vectors F [n, M], all minimised
     (the numpy restatement of tpe_mo_keys, include/hyperopt_tpe.h): (by, do)
     int32 [n] -- by[i] the rows that dominate i (F[j] <= F[i] everywhere, <
     somewhere; IEEE comparisons), do[i] the rows i dominates.  A row with a
     NaN is compared with nobody: -1 in both, and it counts for no other row.
-    Blocks of rows against all rows, MO_CHUNK_BYTES of comparisons at a time."""
+    Blocks of rows against all rows, MO_CHUNK_BYTES of comparisons at a time.
+
+    With the constraint rows G [n, K] (tpe_mo_keys_constrained): a row with a
+    NaN in F or G is such a row; the feasible rows (mo_violation == 0) are
+    counted among themselves -- an infeasible row dominates nobody and nobody
+    dominates it; an infeasible row's by is the number of live rows of
+    strictly smaller violation (every feasible row is one) and its do is 0."""
     F = np.asarray(F, dtype=np.float64)
     if F.ndim != 2 or not 1 <= F.shape[1] <= MO_MAX_OBJECTIVES:
         raise ValueError('F must be [n, 1 .. %d objectives]' % MO_MAX_OBJECTIVES)
+    if G is not None:
+        v = mo_violation(G, F)
+        out = ~(v == 0.0)                                 # dead or infeasible
+        by, do = mo_counts(np.where(out[:, None], np.nan, F))
+        bad = np.flatnonzero(v > 0.0)
+        live = np.sort(v[~np.isnan(v)])
+        by[bad] = np.searchsorted(live, v[bad], side='left')
+        do[bad] = 0
+        return by, do
     n, M = F.shape
     by = np.full(n, -1, dtype=np.int32)
     do = np.full(n, -1, dtype=np.int32)
     valid = np.flatnonzero(~np.isnan(F).any(axis=1))
-    G = np.ascontiguousarray(F[valid].T)                 # [M, rows without a NaN]
+    cols = np.ascontiguousarray(F[valid].T)              # [M, rows without a NaN]
     nv = len(valid)
     rows = max(1, MO_CHUNK_BYTES // (8 * max(nv, 1)))
     for a in range(0, nv, rows):
@@ -125,23 +165,26 @@ def mo_counts(F):
         le = np.ones((b - a, nv), dtype=bool)            # every F[i] <= F[j]
         ge = np.ones((b - a, nv), dtype=bool)            # every F[i] >= F[j]
         for m in range(M):
-            le &= G[m, a:b, None] <= G[m, None, :]
-            ge &= G[m, a:b, None] >= G[m, None, :]
+            le &= cols[m, a:b, None] <= cols[m, None, :]
+            ge &= cols[m, a:b, None] >= cols[m, None, :]
         # every <= and not every >=: some <.  Equal rows: neither dominates.
         do[valid[a:b]] = np.count_nonzero(le & ~ge, axis=1)
         by[valid[a:b]] = np.count_nonzero(ge & ~le, axis=1)
     return by, do
 
 
-def mo_keys(F, counts=None):
+def mo_keys(F, counts=None, G=None):
     """The Pareto-compliant total order of the objective vectors F [n, M] as
     one loss column: keys[i] is row i's position, 0 .. as a float64, under
     ascending by, then descending do, then ascending i (mo_counts; by is 0
     exactly on the Pareto front and smaller for a than for b whenever a
     dominates b, so the order never puts a dominated row before one that
     dominates it).  NaN for a row with a NaN.  The keys are distinct, so a
-    split by them never meets a tie.  M = 1: the stable argsort rank."""
-    by, do = mo_counts(F) if counts is None else counts
+    split by them never meets a tie.  M = 1: the stable argsort rank.
+    With the constraint rows G the counts are mo_counts(F, G)'s: the feasible
+    rows first, in their order among themselves, then the infeasible ones by
+    ascending violation and position -- the same three-field order."""
+    by, do = mo_counts(F, G) if counts is None else counts
     keys = np.full(len(by), np.nan)
     valid = np.flatnonzero(by >= 0)
     order = np.lexsort((valid, -do[valid].astype(np.int64), by[valid]))

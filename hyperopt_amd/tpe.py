@@ -33,6 +33,8 @@ takes no entry out),
 `objectives` (result-dict keys minimised together: each complete trial's loss
 becomes its position in a Pareto-compliant order of the objective vectors,
 computed on the device; `pareto_front` lists the non-dominated trials),
+`constraints` (result-dict keys that must be <= 0: feasible trials rank before
+every infeasible one, those by ascending total violation),
 `precision` ('f64'; 'f32'
 is accepted and runs the same exact path -- see `suggest`), `device` (HIP ordinal), `devices` (a list of ordinals: one
 multi-device context splits every round over those GPUs, same documents as
@@ -81,7 +83,10 @@ JOINT_DEVICE_BUILD = True
 # the keys come from the kernel (Engine.mo_keys) instead of posterior.mo_keys
 # -- the crossover tools/time_mo.py measured on an MI355X at two objectives
 # (profiles/mo_keys_timing.json): 64 rows 0.037 ms on the device against 0.030
-# ms in numpy, 128 rows 0.041 against 0.051, 1024 rows 0.066 against 1.69
+# ms in numpy, 128 rows 0.041 against 0.051, 1024 rows 0.066 against 1.69.
+# (With two constraints, profiles/mo_constraints_timing.json: 128 rows 0.063
+# against 0.044, 512 rows 0.095 against 0.127 -- the one threshold serves both
+# calls; DESIGN.md, "Constraints".)
 MO_DEVICE_MIN_TRIALS = 128
 
 # host-side restatements, exported under the reference's names
@@ -657,7 +662,32 @@ def check_objectives(objectives):
     return objectives
 
 
-def objective_rows(docs, objectives, domain=None, check_from=True):
+def check_constraints(constraints, objectives=None):
+    """tpe.suggest's `constraints` after validation, by check_objectives'
+    rules: a tuple of 1 to posterior.MO_MAX_CONSTRAINTS distinct result-dict
+    keys, None for None.  ValueError also for 'loss' as a constraint and for a
+    name that is one of the (validated) `objectives` as well."""
+    if constraints is None:
+        return None
+    if isinstance(constraints, (str, bytes)) or not isinstance(constraints, (list, tuple)):
+        raise ValueError('constraints must be a list or tuple of result keys')
+    constraints = tuple(constraints)
+    if not constraints:
+        raise ValueError('constraints must not be empty')
+    for key in constraints:
+        if not isinstance(key, str):
+            raise ValueError('constraints: %r is not a string' % (key,))
+    if len(set(constraints)) != len(constraints):
+        raise ValueError('constraints: %r names a key twice' % (constraints,))
+    if len(constraints) > _post.MO_MAX_CONSTRAINTS:
+        raise ValueError('constraints: at most %d, got %d' % (_post.MO_MAX_CONSTRAINTS, len(constraints)))
+    for key in constraints:
+        if key == 'loss' or key in (objectives or ()):
+            raise ValueError('constraints: %r is an objective' % (key,))
+    return constraints
+
+
+def objective_rows(docs, objectives, domain=None, check_from=True, constraints=None):
     """The objective vectors of the complete documents among `docs`:
     (complete documents in the order of docs, F [their number, len(objectives)]
     float64).  A document is complete when its loss -- domain.loss(result,
@@ -667,7 +697,9 @@ def objective_rows(docs, objectives, domain=None, check_from=True):
     that lacks a key (the message names its tid and the key) and, with
     check_from, for any document with a from_tid other than its tid: the best
     of a group is not defined for vectors (tpe.suggest asks the history
-    cache, which has looked at every document once already)."""
+    cache, which has looked at every document once already).  With
+    `constraints` the answer is (documents, F, G [their number,
+    len(constraints)]), G read from the results like the other keys."""
     # (C-level passes over the documents, as history.raw_losses reads the
     # losses: at 10k trials a Python loop per document costs more than the
     # ranking itself)
@@ -696,22 +728,32 @@ def objective_rows(docs, objectives, domain=None, check_from=True):
             raise ValueError('objectives: trial %r has no %r in its result'
                              % (docs[col.index(None)]['tid'], key))
         F[:, m] = col
-    return docs, F
+    if constraints is None:
+        return docs, F
+    G = np.empty((len(docs), len(constraints)))
+    for k, key in enumerate(constraints):
+        col = list(map(dict.get, results, itertools.repeat(key)))
+        if None in col:
+            raise ValueError('constraints: trial %r has no %r in its result'
+                             % (docs[col.index(None)]['tid'], key))
+        G[:, k] = col
+    return docs, F, G
 
 
 _misc_of = operator.itemgetter('misc')
 
 
-def objective_keys(F, builder='auto', engine=None):
+def objective_keys(F, builder='auto', engine=None, G=None):
     """posterior.mo_keys(F) by the builder the call selects: 'host' numpy,
     'device' the kernel (Engine.mo_keys on `engine`, a callable returning the
     Engine), 'auto' the kernel from MO_DEVICE_MIN_TRIALS rows on.  The same
-    integers either way."""
+    integers either way.  G: the constraint rows (posterior.mo_keys(F, G=G),
+    Engine.mo_keys(F, G=G))."""
     if len(F) and (builder == 'device' or (builder == 'auto' and len(F) >= MO_DEVICE_MIN_TRIALS)):
         if len(F) > _post.MO_MAX_ROWS:
             raise ValueError('objectives: at most %d complete trials' % _post.MO_MAX_ROWS)
-        return engine().mo_keys(F)
-    return _post.mo_keys(F)
+        return engine().mo_keys(F) if G is None else engine().mo_keys(F, G=G)
+    return _post.mo_keys(F) if G is None else _post.mo_keys(F, G=G)
 
 
 class _KeyedDomain(object):
@@ -755,17 +797,29 @@ class _KeyedDomain(object):
         return list(map(self._key_of.get, map(id, map(_history._result_of, docs))))
 
 
-def pareto_front(trials, objectives):
+def pareto_front(trials, objectives, constraints=None):
     """The complete trials of `trials` that no other one dominates under the
     objectives (all minimised; posterior.mo_counts: by == 0), in tid order.
     Complete as in objective_rows, 'loss' read as result.get('loss'); a trial
-    with a NaN objective is on no front."""
+    with a NaN objective is on no front.  With `constraints` (result keys,
+    <= 0 satisfied): the feasible trials that no feasible trial dominates --
+    with objectives=('loss',) the best feasible trial(s) -- and [] when no
+    trial is feasible (by == 0 alone would then name the least-violating
+    one: the violation has to be 0 as well)."""
     objectives = check_objectives(objectives)
     if objectives is None:
         raise ValueError('pareto_front needs objectives')
-    docs, F = objective_rows(trials.trials, objectives)
-    by, _ = _post.mo_counts(F) if len(docs) else (np.zeros(0, dtype=np.int32), None)
-    return sorted((d for d, b in zip(docs, by) if b == 0), key=lambda d: d['tid'])
+    constraints = check_constraints(constraints, objectives)
+    if constraints is None:
+        docs, F = objective_rows(trials.trials, objectives)
+        by, _ = _post.mo_counts(F) if len(docs) else (np.zeros(0, dtype=np.int32), None)
+        return sorted((d for d, b in zip(docs, by) if b == 0), key=lambda d: d['tid'])
+    docs, F, G = objective_rows(trials.trials, objectives, constraints=constraints)
+    if not len(docs):
+        return []
+    by, _ = _post.mo_counts(F, G)
+    v = _post.mo_violation(G, F)
+    return sorted((d for d, b, vi in zip(docs, by, v) if b == 0 and vi == 0), key=lambda d: d['tid'])
 
 
 def suggest(new_ids, domain, trials, seed,
@@ -776,7 +830,8 @@ def suggest(new_ids, domain, trials, seed,
             linear_forgetting=_default_linear_forgetting,
             precision='f64', device=0, batch=False, posterior_builder='auto', devices=None,
             multivariate=False, group=False, joint_quantized=False, joint_categorical=False,
-            joint_bandwidth='neighbour', fixed=None, pool=None, pool_replace=False, objectives=None):
+            joint_bandwidth='neighbour', fixed=None, pool=None, pool_replace=False, constraints=None,
+            objectives=None):
     """tpe.py:823-916.  Past the startup phase one document for new_ids[0],
     like the reference; `batch` (not in the reference) asks for one document
     per new_id:
@@ -955,6 +1010,30 @@ def suggest(new_ids, domain, trials, seed,
     documents.  tpe.pareto_front(trials, objectives) lists the front.  With
     objectives=None every call returns what it returned before.
 
+    constraints=('mem_over', 'lat_over') (not in the reference; Optuna's
+    constraints_func) names 1 to 8 further result-dict keys, each a hard limit
+    in Optuna's convention: c <= 0 satisfied, c > 0 violated by that amount --
+    the objective function returns {'loss': err, 'mem_over': gb - 16.0,
+    'status': STATUS_OK}.  With or without `objectives` (None: the one
+    objective 'loss', read through domain.loss).  The call is again the plain
+    call on a column of keys, now from the order feasibility first (DESIGN.md
+    section 6b, "Constraints"): the feasible trials -- total violation v =
+    sum_k max(c_k, 0) equal to 0 -- in the order above, dominance counted
+    among feasible trials only; then the infeasible ones by ascending v, then
+    trial order.  An infeasible trial never enters the below set before a
+    feasible one however good its objectives are, and when fewer feasible
+    trials exist than the below set holds, the least-violating infeasible
+    ones fill it.  A trial with a NaN in an objective or a constraint keeps
+    NaN.  The builders are those of `objectives` (posterior.mo_keys(F, G=G),
+    Engine.mo_keys(F, G=G); the same integers), and so is the validation
+    (check_constraints; also ValueError: 'loss' or an objective named as a
+    constraint, a complete trial without one of the keys, a from_tid).  The
+    startup phase is unchanged.  Domain, Trials, fmin's argmin and
+    trials.best_trial know nothing of feasibility: they still report the
+    smallest loss; tpe.pareto_front(trials, ('loss',), constraints=...) gives
+    the best feasible trial.  With constraints=None every call returns what
+    it returned before.
+
     precision='f32' runs the exact fp64 path: a round draws every candidate
     and proves all but ~0.5 % of them out of the race from per-sub-bin score
     bounds before any lpdf is summed, so scoring the rest in fp32 would save
@@ -963,17 +1042,31 @@ def suggest(new_ids, domain, trials, seed,
     fp32 round stays available as Engine(precision='f32')."""
     t0 = time.time()
     objectives = check_objectives(objectives)   # (first: nothing else has run when it raises)
-    if objectives is not None:
+    constraints = check_constraints(constraints, objectives)
+    if objectives is not None or constraints is not None:
         # the call below on another loss column: the keys once, from all the
         # trials; every place that reads losses reads them through the domain
         src = trials.trials
+        builder = posterior_builder if posterior_builder in ('host', 'device') else 'auto'
+
+        def engine():
+            return _engine.get_engine(list(devices) if devices else device, 'f64', 'main')
         # (a from_tid: flagged by the history cache, named by the full check)
-        docs, F = objective_rows(src, objectives, domain,
-                                 check_from=_history.has_from_tid(trials, list(specs_of(domain))))
-        keys = objective_keys(F, posterior_builder if posterior_builder in ('host', 'device') else 'auto',
-                              lambda: _engine.get_engine(list(devices) if devices else device, 'f64', 'main'))
-        logger.info('tpe.suggest: %d objectives, %d complete trials ranked, %.1f ms' % (
-            len(objectives), len(docs), (time.time() - t0) * 1e3))
+        check_from = _history.has_from_tid(trials, list(specs_of(domain)))
+        if constraints is None:
+            docs, F = objective_rows(src, objectives, domain, check_from=check_from)
+            keys = objective_keys(F, builder, engine)
+            logger.info('tpe.suggest: %d objectives, %d complete trials ranked, %.1f ms' % (
+                len(objectives), len(docs), (time.time() - t0) * 1e3))
+        else:
+            names = objectives or ('loss',)
+            docs, F, G = objective_rows(src, names, domain, check_from=check_from, constraints=constraints)
+            keys = objective_keys(F, builder, engine, G=G)
+            if logger.isEnabledFor(logging.INFO):      # (the count is a pass over the rows)
+                logger.info('tpe.suggest: %d objectives, %d constraints, %d complete trials ranked, %d of them '
+                            'feasible, %.1f ms' % (len(names), len(constraints), len(docs),
+                                                   int(np.count_nonzero(_post.mo_violation(G, F) == 0.0)),
+                                                   (time.time() - t0) * 1e3))
         return suggest(new_ids, _KeyedDomain(domain, docs, keys, src), trials, seed, prior_weight=prior_weight,
                        n_startup_jobs=n_startup_jobs, n_EI_candidates=n_EI_candidates, gamma=gamma,
                        linear_forgetting=linear_forgetting, precision=precision, device=device, batch=batch,

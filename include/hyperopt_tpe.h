@@ -758,6 +758,39 @@ int tpe_mo_keys(tpe_ctx *ctx, const double *objectives /* [n][n_obj] row-major *
                 int64_t n, int32_t n_obj, double *keys /* [n] */,
                 int32_t *dominated_by /* [n] or NULL */, int32_t *dominates /* [n] or NULL */);
 
+/* The same order under constraints (tpe.suggest(constraints=...)): feasible
+ * rows first, in the order above among themselves, then the infeasible rows by
+ * ascending violation.  constraints[n][n_con] row-major, c <= 0 satisfied,
+ * c > 0 violated by that amount; IEEE comparisons throughout.
+ *   a row with a NaN in any objective or constraint is dead: keys[i] = NaN,
+ *       dominated_by[i] = dominates[i] = -1, violation[i] = NaN, and it counts
+ *       for no other row;
+ *   violation[i] = ((0.0 + max(G[i][0], 0)) + max(G[i][1], 0)) + ... in fp64,
+ *       in this order (additions only: the bits a host loop gives; -inf and
+ *       -0.0 contribute zero, +inf is an ordinary value);
+ *   a row is feasible when violation[i] == 0;
+ *   feasible rows: dominated_by and dominates as above, counted among the
+ *       feasible rows only -- an infeasible row dominates nobody and is
+ *       dominated by nobody;
+ *   infeasible rows: dominated_by[i] = the live rows of strictly smaller
+ *       violation (every feasible row is one: at least the number of feasible
+ *       rows, more than any feasible row's), dominates[i] = 0;
+ *   the order: ascending dominated_by, descending dominates, ascending i;
+ *       keys[i] is the position, 0 .. (live rows) - 1.  Every row feasible:
+ *       tpe_mo_keys' keys.  No row feasible: ascending violation, then i.
+ * dominated_by, dominates and violation may each be NULL.  One upload, one
+ * stream synchronisation, pinned read-back; its own reusable buffers (counted
+ * by tpe_device_bytes) are allocated by the first such call, never by
+ * tpe_mo_keys, whose results it does not change.  A multi-device context runs
+ * it on its primary device.
+ * TPE_ERR_ARG: a NULL objectives, constraints or keys; n < 1 or n > 2^20;
+ * n_obj or n_con outside [1, 8].  On an error the outputs are untouched. */
+int tpe_mo_keys_constrained(tpe_ctx *ctx, const double *objectives /* [n][n_obj] row-major */,
+                            int64_t n, int32_t n_obj,
+                            const double *constraints /* [n][n_con] row-major */, int32_t n_con,
+                            double *keys /* [n] */, int32_t *dominated_by /* [n] or NULL */,
+                            int32_t *dominates /* [n] or NULL */, double *violation /* [n] or NULL */);
+
 /* Score a caller-supplied candidate set for one resident label (the parity
  * entry point: identical candidates in, both lpdf vectors and the winner
  * out).  lpdf_below / lpdf_above may be NULL. */

@@ -2,6 +2,8 @@
 
     python tools/time_mo.py --gpus 1 [--reps 20] [--host-max-n 10000] [--out FILE]
     python tools/time_mo.py --gpus 1 --quality [--out FILE]
+    python tools/time_mo.py --gpus 1 --constraints K [--out FILE]
+    python tools/time_mo.py --gpus 1 --quality-constrained [--evals 100] [--out FILE]
 
 * Engine.mo_keys (tpe_mo_keys: upload, all-pairs kernel, pack, radix sort,
   scatter, read-back; one synchronisation) at n in {1000, 10000, 50000} x M in
@@ -25,6 +27,23 @@
 evaluations of a two-objective toy problem (ZDT1 in four dimensions, reference
 point (1.1, 6)), for tpe.suggest(objectives=('loss', 'cost')), for tpe.suggest
 on loss + cost and for rand.suggest, over 10 seeds.
+
+--constraints K (tpe.suggest(constraints=...), K constraint columns):
+* Engine.mo_keys(F, G=G) against Engine.mo_keys(F) on the same F, the two
+  alternating in one process, at n in {1000, 10000, 50000} x 2 objectives, G =
+  uniform - 0.6 (about a third of the rows feasible at K = 2); the host builder
+  posterior.mo_keys(F, G=G) up to --host-max-n rows;
+* the crossover with constraints at 64, 128 and 512 rows, both builders;
+* a whole tpe.suggest step on the config-3 history with objectives=('loss',
+  'cost') and with K constraints as well, alternating; and tpe.objective_rows
+  alone with and without the constraint columns -- the share of the difference
+  that is the host reading K more columns.
+
+--quality-constrained (reported, not asserted): minimise (x - 1)^2 + (y - 1)^2
+on [0, 1]^2 under c = x + y - 1 <= 0 (the optimum 0.5 lies on the boundary);
+the best feasible loss after --evals evaluations over --seeds seeds for
+tpe.suggest(constraints=('c',)), for tpe.suggest on loss + 10 max(c, 0) and for
+rand.suggest.
 
 Results are appended to --out as one JSON object per line."""
 import argparse
@@ -131,6 +150,124 @@ def step_times(args):
     return [rec]
 
 
+def constrained_key_times(eng, args):
+    from hyperopt_amd import posterior as P
+    K, out = args.constraints, []
+    for n in SIZES:
+        rng = np.random.RandomState(n + 2)
+        F = rng.uniform(size=(n, 2))
+        G = rng.uniform(size=(n, K)) - 0.6
+        legs = dict(unconstrained=lambda: eng.mo_keys(F), constrained=lambda: eng.mo_keys(F, G=G))
+        ts = {k: [] for k in legs}
+        for k in legs:
+            legs[k]()                  # warm-up
+        for _ in range(args.reps):     # alternating
+            for k in legs:
+                t0 = time.perf_counter()
+                legs[k]()
+                ts[k].append((time.perf_counter() - t0) * 1e3)
+        rec = dict(what='mo_keys_constrained', n=n, M=2, K=K,
+                   feasible=int(np.count_nonzero(P.mo_violation(G, F) == 0.0)))
+        for k, v in ts.items():
+            rec[k] = dict(median_ms=float(np.median(v)), min_ms=float(min(v)), max_ms=float(max(v)), reps=len(v))
+        rec['constrained_over_unconstrained'] = rec['constrained']['median_ms'] / rec['unconstrained']['median_ms']
+        if n <= args.host_max_n:
+            rec['host'] = timed(lambda: P.mo_keys(F, G=G), 3)
+            rec['same_keys'] = bool(np.array_equal(P.mo_keys(F, G=G), eng.mo_keys(F, G=G)))
+        else:
+            rec['host'] = 'not measured'
+        print(json.dumps(rec), flush=True)
+        out.append(rec)
+    rec = dict(what='mo_crossover_constrained', M=2, K=K, sizes={})
+    for n in (64, 128, 512):
+        rng = np.random.RandomState(n)
+        F = rng.uniform(size=(n, 2))
+        G = rng.uniform(size=(n, K)) - 0.6
+        rec['sizes'][n] = dict(device_ms=timed(lambda: eng.mo_keys(F, G=G), args.reps)['median_ms'],
+                               host_ms=timed(lambda: P.mo_keys(F, G=G), args.reps)['median_ms'])
+    print(json.dumps(rec), flush=True)
+    return out + [rec]
+
+
+def constrained_step_times(args):
+    from hyperopt_amd import tpe, workloads
+    from hyperopt_amd.base import Domain
+    K = args.constraints
+    names = tuple('c%d' % k for k in range(K))
+    hist = workloads.mixed_history(32, 10000, seed=0)
+    trials = workloads.history_trials(hist)
+    rng = np.random.RandomState(1)
+    cost = rng.uniform(size=len(trials.trials))
+    G = rng.uniform(size=(len(trials.trials), K)) - 0.6
+    for d, c, g in zip(trials.trials, cost, G):
+        d['result']['cost'] = float(c)
+        d['result'].update(zip(names, map(float, g)))
+    domain = Domain(lambda d: 0.0, workloads.hp_space(hist.labels))
+    n = len(trials.trials)
+    legs = dict(objectives=lambda: tpe.suggest([n], domain, trials, 3, objectives=('loss', 'cost')),
+                objectives_and_constraints=lambda: tpe.suggest([n], domain, trials, 3, objectives=('loss', 'cost'),
+                                                               constraints=names))
+    ts = {k: [] for k in legs}
+    for k in legs:
+        legs[k]()                      # warm-up
+    for _ in range(args.reps):         # alternating
+        for k in legs:
+            t0 = time.perf_counter()
+            legs[k]()
+            ts[k].append((time.perf_counter() - t0) * 1e3)
+    rec = dict(what='mo_step_constrained', labels=32, trials=n, K=K)
+    for k, v in ts.items():
+        rec[k] = dict(median_ms=float(np.median(v)), min_ms=float(min(v)), max_ms=float(max(v)), reps=len(v))
+    rows = dict(rows_ms=lambda: tpe.objective_rows(trials.trials, ('loss', 'cost'), domain),
+                rows_with_constraints_ms=lambda: tpe.objective_rows(trials.trials, ('loss', 'cost'), domain,
+                                                                    constraints=names))
+    tr = {k: [] for k in rows}
+    for _ in range(args.reps + 1):     # alternating; the first pair is the warm-up
+        for k in rows:
+            t0 = time.perf_counter()
+            rows[k]()
+            tr[k].append((time.perf_counter() - t0) * 1e3)
+    for k, v in tr.items():
+        rec[k] = float(np.median(v[1:]))
+    rec['step_difference_ms'] = rec['objectives_and_constraints']['median_ms'] - rec['objectives']['median_ms']
+    rec['rows_difference_ms'] = rec['rows_with_constraints_ms'] - rec['rows_ms']
+    print(json.dumps(rec), flush=True)
+    return [rec]
+
+
+def quality_constrained(args):
+    from hyperopt_amd import STATUS_OK, Trials, fmin, hp, rand, tpe
+    space = {'x': hp.uniform('x', 0, 1), 'y': hp.uniform('y', 0, 1)}
+
+    def parts(cfg):
+        return (cfg['x'] - 1) ** 2 + (cfg['y'] - 1) ** 2, cfg['x'] + cfg['y'] - 1
+
+    def constrained(cfg):
+        f, c = parts(cfg)
+        return {'loss': f, 'f': f, 'c': c, 'status': STATUS_OK}
+
+    def penalised(cfg):
+        f, c = parts(cfg)
+        return {'loss': f + 10.0 * max(c, 0.0), 'f': f, 'c': c, 'status': STATUS_OK}
+    algos = dict(constraints=(constrained, partial(tpe.suggest, constraints=('c',))),
+                 tpe_on_the_penalty=(penalised, tpe.suggest), random=(constrained, rand.suggest))
+    rec = dict(what='mo_quality_constrained', problem='(x-1)^2 + (y-1)^2 under x + y <= 1, optimum 0.5',
+               evaluations=args.evals, seeds=args.seeds)
+    for name, (fn, algo) in algos.items():
+        best, feasible = [], []
+        for seed in range(args.seeds):
+            trials = Trials()
+            fmin(fn, space, algo=algo, max_evals=args.evals, trials=trials, rstate=np.random.RandomState(seed))
+            ok = [d['result']['f'] for d in trials.trials if d['result']['c'] <= 0]
+            feasible.append(len(ok))
+            best.append(min(ok) if ok else float('nan'))
+        rec[name] = dict(mean=float(np.nanmean(best)), std=float(np.nanstd(best)), min=float(np.nanmin(best)),
+                         max=float(np.nanmax(best)), feasible_trials_mean=float(np.mean(feasible)),
+                         runs_without_a_feasible_trial=int(np.isnan(best).sum()))
+    print(json.dumps(rec), flush=True)
+    return [rec]
+
+
 def hypervolume(F, ref):
     """The area dominated by the rows of F [n, 2] inside the box below `ref`."""
     F = F[(F < ref).all(axis=1)]
@@ -185,13 +322,27 @@ def main():
     ap.add_argument('--reps', type=int, default=20)
     ap.add_argument('--host-max-n', type=int, default=10000)
     ap.add_argument('--quality', action='store_true')
-    ap.add_argument('--evals', type=int, default=200)
+    ap.add_argument('--constraints', type=int, default=0, metavar='K')
+    ap.add_argument('--quality-constrained', action='store_true')
+    ap.add_argument('--evals', type=int)
     ap.add_argument('--seeds', type=int, default=10)
     ap.add_argument('--out')
     args = ap.parse_args()
     if args.gpus != 1:
         ap.error('the keys are computed on one device: --gpus 1')
-    if args.quality:
+    if args.evals is None:
+        args.evals = 100 if args.quality_constrained else 200
+    if args.constraints and not 1 <= args.constraints <= 8:
+        ap.error('--constraints: 1 to 8 columns')
+    if args.quality_constrained:
+        recs = quality_constrained(args)
+    elif args.constraints:
+        from hyperopt_amd.engine import Engine
+        eng = Engine(0, 'f64')
+        recs = constrained_key_times(eng, args)
+        eng.close()
+        recs += constrained_step_times(args)
+    elif args.quality:
         recs = quality(args)
     else:
         from hyperopt_amd.engine import Engine
