@@ -65,6 +65,7 @@ TPE_OPT_JOINT_CAP = 26
 
 TPE_JOINT_STREAM = 0x7FFFFFFF
 TPE_JOINT_MAX_GROUPS = 64
+TPE_POOL_STREAM = 0x7FFFFFBF
 TPE_JOINT_FLAG_TIE = 1
 TPE_JOINT_FLAG_CATEGORY = 2
 TPE_JOINT_FLAG_COUNT = 4
@@ -192,6 +193,8 @@ SIGNATURES = {
     'tpe_pool_size': (ctypes.c_int, [_P, ctypes.POINTER(_I64), ctypes.POINTER(_I32)]),
     'tpe_pool_rank': (ctypes.c_int, [_P, _I32, _P, _P, _P, _P, _I64, _I32, _P, _P, ctypes.POINTER(_I32), _P, _P,
                                      _P]),
+    'tpe_pool_draw': (ctypes.c_int, [_P, _I32, _P, _P, _P, _P, _I64, _U64, _P, _I32, _I64, _I32, _P, _P,
+                                     ctypes.POINTER(_I32), _P, _P, _P, _P, _P]),
     'tpe_mo_keys': (ctypes.c_int, [_P, _P, _I64, _I32, _P, _P, _P]),
     'tpe_mo_keys_constrained': (ctypes.c_int, [_P, _P, _I64, _I32, _P, _I32, _P, _P, _P, _P]),
 }

@@ -849,6 +849,11 @@ TPE_DEV int tpe1_pool_rank(tpe_ctx* ctx, int32_t n_groups, const int32_t* slots,
                            const int32_t* group_cols, const int64_t* taken, int64_t n_taken, int32_t top_k,
                            int64_t* top_index, double* top_score, int32_t* n_top, double* score,
                            double* lpdf_below, double* lpdf_above);
+TPE_DEV int tpe1_pool_draw(tpe_ctx* ctx, int32_t n_groups, const int32_t* slots, const int64_t* group_off,
+                           const int32_t* group_cols, const int64_t* taken, int64_t n_taken, uint64_t seed,
+                           const uint32_t* rounds, int32_t n_rounds, int64_t m, int32_t distinct,
+                           int64_t* best_index, double* best_score, int32_t* n_best, int64_t* drawn,
+                           int32_t* n_drawn, double* lsum, double* keys, double* score);
 }
 // the set slots of a context, ascending (only >= 0: that slot alone): their
 // dimensions into D[TPE_JOINT_MAX_GROUPS], their number back

@@ -948,6 +948,17 @@ int tpe_pool_rank(tpe_ctx* ctx, int32_t n_groups, const int32_t* slots, const in
                           n_top, score, lpdf_below, lpdf_above);
 }
 
+int tpe_pool_draw(tpe_ctx* ctx, int32_t n_groups, const int32_t* slots, const int64_t* group_off,
+                  const int32_t* group_cols, const int64_t* taken, int64_t n_taken, uint64_t seed,
+                  const uint32_t* rounds, int32_t n_rounds, int64_t m, int32_t distinct, int64_t* best_index,
+                  double* best_score, int32_t* n_best, int64_t* drawn, int32_t* n_drawn, double* lsum, double* keys,
+                  double* score) {
+    if (!ctx) return TPE_ERR_ARG;
+    if (!ctx->peers.empty()) return ctx->fail(TPE_ERR_ARG, "tpe_pool_draw: not available on a multi-device context");
+    return tpe1_pool_draw(ctx, n_groups, slots, group_off, group_cols, taken, n_taken, seed, rounds, n_rounds, m,
+                          distinct, best_index, best_score, n_best, drawn, n_drawn, lsum, keys, score);
+}
+
 int tpe_joint_last_shards(const tpe_ctx* ctx, int32_t* mode, int32_t* n_devices) {
     if (!ctx) return TPE_ERR_ARG;
     if (mode) *mode = ctx->joint_shard_mode;

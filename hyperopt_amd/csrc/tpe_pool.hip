@@ -22,6 +22,16 @@
 //   k_pool_group   the joint lpdfs -> the group's plane
 //   k_pool_sum     per entry: terms added left to right -> score, key, index
 //   hipcub stable descending radix sort of (key, index), k_pool_top reads the head
+// Per tpe_pool_draw (TPE's draw on a finite pool: Gumbel top-m on log l, then
+// the best l/g inside the drawn set), after the planes and k_pool_sum above:
+//   lsum   : double[n]                     the working-space log l per entry
+//   key, idx as above, per round: order_key(lsum + Gumbel) (0: not free)
+//   k_pool_lsum    per entry: the below terms added in k_pool_sum's order
+//   k_pool_key     (round, entry): the Philox word pair -> Gumbel noise -> key
+//   the same sort; k_pool_pick / k_pool_pick_final: (order_key(score), lowest
+//                  index) over the first d sorted entries
+//   k_pool_drawn   the drawn set to the caller's vector (diagnostics)
+//   k_pool_take    one thread: the round's pick is not free for the next round
 #include <hip/hip_runtime.h>
 #include <hipcub/hipcub.hpp>
 
@@ -297,6 +307,143 @@ __global__ __launch_bounds__(kBlock) void k_pool_top(const uint32_t* __restrict_
     top_s[j] = score[i];
 }
 
+// lsum[i]: from 0.0, the below lpdfs in k_pool_sum's order, each in the
+// label's working space -- a dense log label's lb is the document-space
+// density (k_pool_dense subtracts log v), so its term is lb + flog(v); a
+// group's is ll plus the flog(v) of its dense log columns, in the order the
+// group lists them.
+__global__ __launch_bounds__(kBlock) void k_pool_lsum(const DLabel* __restrict__ labels,
+                                                      const double* __restrict__ vals, int64_t n, int32_t n_cols,
+                                                      const int32_t* __restrict__ cover, int32_t n_groups,
+                                                      const int32_t* __restrict__ goff,
+                                                      const int32_t* __restrict__ gcols,
+                                                      const double* __restrict__ lb, double* __restrict__ lsum) {
+    const int64_t i = (int64_t)blockIdx.x * kBlock + threadIdx.x;
+    if (i >= n) return;
+    double s = 0.0;
+    for (int c = 0; c < n_cols; ++c) {
+        if (cover[c] >= 0) continue;
+        const double v = vals[(size_t)c * n + i];
+        if (v != v) continue;
+        double term = lb[(size_t)c * n + i];
+        if (labels[c].mode == DENSE_LGMM) term += flog(v);
+        s += term;
+    }
+    for (int g = 0; g < n_groups; ++g) {
+        bool active = true;
+        double jac = 0.0;
+        for (int d = goff[g]; d < goff[g + 1]; ++d) {
+            const double v = vals[(size_t)gcols[d] * n + i];
+            active &= v == v;
+            if (labels[gcols[d]].mode == DENSE_LGMM) jac += flog(v);
+        }
+        if (!active) continue;
+        const double term = lb[(size_t)(n_cols + g) * n + i] + jac;
+        s += term;
+    }
+    lsum[i] = s;
+}
+
+// One round's keys: entry i's standard Gumbel noise from its own Philox
+// counter (i, 0, TPE_POOL_STREAM, round) -- 52 bits of the first two words,
+// u = (t + 0.5) 2^-52 strictly inside (0, 1), G = -log(-log u) -- added to
+// lsum[i].  The sort key is 0 for an entry that is not free; keys_out
+// (diagnostics) gets every entry's key.
+__global__ __launch_bounds__(kBlock) void k_pool_key(const double* __restrict__ lsum,
+                                                     const uint8_t* __restrict__ taken, int64_t n, uint32_t k0,
+                                                     uint32_t k1, uint32_t round, uint64_t* __restrict__ key,
+                                                     uint32_t* __restrict__ idx, double* __restrict__ keys_out) {
+    const int64_t i = (int64_t)blockIdx.x * kBlock + threadIdx.x;
+    if (i >= n) return;
+    const U4 w = philox4x32_10(U4{(uint32_t)i, 0u, (uint32_t)TPE_POOL_STREAM, round}, k0, k1);
+    const uint64_t t = ((uint64_t)w.x << 20) | (uint64_t)(w.y >> 12);
+    const double u = ((double)t + 0.5) * 0x1.0p-52;
+    const double gumbel = -flog(-flog(u));
+    const double k = lsum[i] + gumbel;
+    key[i] = taken[i] ? 0ull : order_key(k);
+    idx[i] = (uint32_t)i;
+    if (keys_out) keys_out[i] = k;
+}
+
+// the better of the workgroup's (key, index) pairs, in thread 0
+__device__ __forceinline__ void pool_block_best(uint64_t& k, int64_t& i) {
+    __shared__ uint64_t sk[kBlock / 64];
+    __shared__ int64_t si[kBlock / 64];
+    for (int off = 32; off > 0; off >>= 1) {
+        const uint64_t ok = __shfl_down(k, off, 64);
+        const int64_t oi = __shfl_down(i, off, 64);
+        if (better(ok, oi, k, i)) {
+            k = ok;
+            i = oi;
+        }
+    }
+    if ((threadIdx.x & 63) == 0) {
+        sk[threadIdx.x >> 6] = k;
+        si[threadIdx.x >> 6] = i;
+    }
+    __syncthreads();
+    if (threadIdx.x == 0)
+        for (int w = 1; w < kBlock / 64; ++w)
+            if (better(sk[w], si[w], k, i)) {
+                k = sk[w];
+                i = si[w];
+            }
+}
+
+constexpr int64_t kNoEntry = INT64_MAX;   // with key 0 (no score's key): loses to every entry
+
+// the best score among the first d sorted entries (the drawn set): a partial
+// per workgroup, then one workgroup over the partials
+__global__ __launch_bounds__(kBlock) void k_pool_pick(const uint32_t* __restrict__ idx,
+                                                      const double* __restrict__ score, int64_t d,
+                                                      uint64_t* __restrict__ part_k, int64_t* __restrict__ part_i) {
+    uint64_t k = 0ull;
+    int64_t i = kNoEntry;
+    for (int64_t p = (int64_t)blockIdx.x * kBlock + threadIdx.x; p < d; p += (int64_t)gridDim.x * kBlock) {
+        const int64_t e = idx[p];
+        const uint64_t ke = order_key(score[e]);
+        if (better(ke, e, k, i)) {
+            k = ke;
+            i = e;
+        }
+    }
+    pool_block_best(k, i);
+    if (threadIdx.x == 0) {
+        part_k[blockIdx.x] = k;
+        part_i[blockIdx.x] = i;
+    }
+}
+
+__global__ __launch_bounds__(kBlock) void k_pool_pick_final(const uint64_t* __restrict__ part_k,
+                                                            const int64_t* __restrict__ part_i, int32_t n_part,
+                                                            const double* __restrict__ score, int64_t n,
+                                                            int64_t* __restrict__ best_i,
+                                                            double* __restrict__ best_s) {
+    uint64_t k = 0ull;
+    int64_t i = kNoEntry;
+    for (int p = threadIdx.x; p < n_part; p += kBlock)
+        if (better(part_k[p], part_i[p], k, i)) {
+            k = part_k[p];
+            i = part_i[p];
+        }
+    pool_block_best(k, i);
+    if (threadIdx.x == 0) {
+        *best_i = i;
+        *best_s = (i >= 0 && i < n) ? score[i] : __builtin_nan("");
+    }
+}
+
+__global__ __launch_bounds__(kBlock) void k_pool_drawn(const uint32_t* __restrict__ idx, int64_t d,
+                                                       int64_t* __restrict__ out) {
+    const int64_t p = (int64_t)blockIdx.x * kBlock + threadIdx.x;
+    if (p < d) out[p] = (int64_t)idx[p];
+}
+
+__global__ void k_pool_take(const int64_t* __restrict__ best_i, int64_t n, uint8_t* __restrict__ flag) {
+    const int64_t i = *best_i;
+    if (i >= 0 && i < n) flag[i] = 1;
+}
+
 struct PoolState {
     int64_t n = 0;
     int32_t n_cols = 0;
@@ -316,6 +463,10 @@ struct PoolState {
     DevBuf<double> uvals, ut_lb, ut_la;
     DevBuf<int32_t> ucol;
     DevBuf<uint16_t> umap;
+    // tpe_pool_draw: lsum [n]; the pick's partials; the diagnostics' vectors
+    DevBuf<double> lsum, keys_all;
+    DevBuf<uint64_t> part_k;
+    DevBuf<int64_t> part_i, drawn;
     DevBuf<int32_t> err;
     PinVec<int32_t> err_h;
     PinVec<int64_t> top_i_h;
@@ -436,60 +587,81 @@ int tpe1_pool_size(const tpe_ctx* ctx, int64_t* n, int32_t* n_cols) {
     return TPE_OK;
 }
 
-int tpe1_pool_rank(tpe_ctx* ctx, int32_t n_groups, const int32_t* slots, const int64_t* group_off,
-                   const int32_t* group_cols, const int64_t* taken, int64_t n_taken, int32_t top_k,
-                   int64_t* top_index, double* top_score, int32_t* n_top_out, double* score, double* lpdf_below,
-                   double* lpdf_above) {
-    if (!ctx) return TPE_ERR_ARG;
+}  // extern "C"
+
+namespace {
+
+// What tpe_pool_rank and tpe_pool_draw share, `fn` naming the entry point in
+// the messages: the checks of the context (pool_context) and of the groups and
+// `taken` (pool_groups), then everything queued up to the scores (pool_scores).
+struct PoolCall {
+    PoolState* S = nullptr;
+    int64_t n = 0;
+    int32_t L = 0, n_groups = 0;
+    std::vector<int32_t> meta;       // cover [L] | goff [n_groups + 1] | gcols
+    int64_t n_free = 0;              // the entries not in `taken`
+    size_t sort_bytes = 0;
+    const int32_t* goff() const { return meta.data() + L; }
+    const int32_t* d_cover() const { return S->meta.p; }
+    const int32_t* d_goff() const { return S->meta.p + L; }
+    const int32_t* d_gcols() const { return S->meta.p + L + n_groups + 1; }
+};
+
+int pool_context(tpe_ctx* ctx, const std::string& fn, PoolCall& pc) {
     TPE_SETTLE(ctx);
-    if (!ctx->peers.empty())
-        return ctx->fail(TPE_ERR_ARG, "tpe_pool_rank: not available on a multi-device context");
-    if (ctx->precision != TPE_F64) return ctx->fail(TPE_ERR_ARG, "tpe_pool_rank: needs a TPE_F64 context");
+    if (!ctx->peers.empty()) return ctx->fail(TPE_ERR_ARG, fn + ": not available on a multi-device context");
+    if (ctx->precision != TPE_F64) return ctx->fail(TPE_ERR_ARG, fn + ": needs a TPE_F64 context");
     PoolState* S = pool_of(ctx, false);
-    if (!S || S->n < 1) return ctx->fail(TPE_ERR_ARG, "tpe_pool_rank: no pool set (tpe_pool_set)");
+    if (!S || S->n < 1) return ctx->fail(TPE_ERR_ARG, fn + ": no pool set (tpe_pool_set)");
     Posterior& P = ctx->resident;
-    if (P.n_labels == 0) return ctx->fail(TPE_ERR_ARG, "tpe_pool_rank: no posterior set");
+    if (P.n_labels == 0) return ctx->fail(TPE_ERR_ARG, fn + ": no posterior set");
     if (S->n_cols != P.n_labels)
-        return ctx->fail(TPE_ERR_ARG, "tpe_pool_rank: the pool has " + std::to_string(S->n_cols) +
+        return ctx->fail(TPE_ERR_ARG, fn + ": the pool has " + std::to_string(S->n_cols) +
                                           " columns, the posterior " + std::to_string(P.n_labels) + " labels");
-    if (top_k < 1) return ctx->fail(TPE_ERR_ARG, "tpe_pool_rank: top_k must be at least 1");
-    if (!top_index || !top_score || !n_top_out || (lpdf_below == nullptr) != (lpdf_above == nullptr) ||
-        n_groups < 0 || n_taken < 0 || (n_taken > 0 && !taken) ||
+    pc.S = S;
+    pc.n = S->n;
+    pc.L = S->n_cols;
+    return TPE_OK;
+}
+
+int pool_groups(tpe_ctx* ctx, const std::string& fn, PoolCall& pc, int32_t n_groups, const int32_t* slots,
+                const int64_t* group_off, const int32_t* group_cols, const int64_t* taken, int64_t n_taken) {
+    if (n_groups < 0 || n_taken < 0 || (n_taken > 0 && !taken) ||
         (n_groups > 0 && (!slots || !group_off || !group_cols)))
-        return ctx->fail(TPE_ERR_ARG, "tpe_pool_rank: null pointer or negative count");
-    if (n_groups > TPE_JOINT_MAX_GROUPS) return ctx->fail(TPE_ERR_ARG, "tpe_pool_rank: too many groups");
-    const int64_t n = S->n;
-    const int32_t L = S->n_cols;
+        return ctx->fail(TPE_ERR_ARG, fn + ": null pointer or negative count");
+    if (n_groups > TPE_JOINT_MAX_GROUPS) return ctx->fail(TPE_ERR_ARG, fn + ": too many groups");
+    const int64_t n = pc.n;
+    const int32_t L = pc.L;
+    pc.n_groups = n_groups;
     // the groups: set, distinct slots; columns in range, in one group at most; D columns each
     const int64_t n_gc = n_groups ? group_off[n_groups] : 0;
-    if (n_gc < 0 || n_gc > L) return ctx->fail(TPE_ERR_ARG, "tpe_pool_rank: the groups list more columns than the pool has");
-    std::vector<int32_t> meta((size_t)L + n_groups + 1 + n_gc, -1);
-    int32_t* cover = meta.data();
-    int32_t* goff = meta.data() + L;
+    if (n_gc < 0 || n_gc > L) return ctx->fail(TPE_ERR_ARG, fn + ": the groups list more columns than the pool has");
+    pc.meta.assign((size_t)L + n_groups + 1 + n_gc, -1);
+    int32_t* cover = pc.meta.data();
+    int32_t* goff = pc.meta.data() + L;
     int32_t* gcols = goff + n_groups + 1;
     goff[0] = 0;
     {
         bool seen[TPE_JOINT_MAX_GROUPS] = {};
-        if (n_groups && group_off[0] != 0) return ctx->fail(TPE_ERR_ARG, "tpe_pool_rank: group_off[0] must be 0");
+        if (n_groups && group_off[0] != 0) return ctx->fail(TPE_ERR_ARG, fn + ": group_off[0] must be 0");
         for (int32_t g = 0; g < n_groups; ++g) {
             const int32_t slot = slots[g];
             int32_t D = 0;
             if (slot < 0 || slot >= TPE_JOINT_MAX_GROUPS || tpe1_joint_set_slots(ctx, slot, &D) != 1)
-                return ctx->fail(TPE_ERR_ARG, "tpe_pool_rank: group " + std::to_string(g) + ": slot not set");
-            if (seen[slot])
-                return ctx->fail(TPE_ERR_ARG, "tpe_pool_rank: slot " + std::to_string(slot) + " listed twice");
+                return ctx->fail(TPE_ERR_ARG, fn + ": group " + std::to_string(g) + ": slot not set");
+            if (seen[slot]) return ctx->fail(TPE_ERR_ARG, fn + ": slot " + std::to_string(slot) + " listed twice");
             seen[slot] = true;
             const int64_t a = group_off[g], b = group_off[g + 1];
             if (b < a || b - a != D)
-                return ctx->fail(TPE_ERR_ARG, "tpe_pool_rank: group " + std::to_string(g) + " lists " +
+                return ctx->fail(TPE_ERR_ARG, fn + ": group " + std::to_string(g) + " lists " +
                                                   std::to_string(b - a) + " columns, its slot has " +
                                                   std::to_string(D) + " dimensions");
             for (int64_t k = a; k < b; ++k) {
                 const int32_t c = group_cols[k];
                 if (c < 0 || c >= L)
-                    return ctx->fail(TPE_ERR_ARG, "tpe_pool_rank: column " + std::to_string(c) + " out of range");
+                    return ctx->fail(TPE_ERR_ARG, fn + ": column " + std::to_string(c) + " out of range");
                 if (cover[c] >= 0)
-                    return ctx->fail(TPE_ERR_ARG, "tpe_pool_rank: column " + std::to_string(c) + " in two groups");
+                    return ctx->fail(TPE_ERR_ARG, fn + ": column " + std::to_string(c) + " in two groups");
                 cover[c] = g;
                 gcols[k] = c;
             }
@@ -497,17 +669,31 @@ int tpe1_pool_rank(tpe_ctx* ctx, int32_t n_groups, const int32_t* slots, const i
         }
     }
     // the entries left after `taken` (duplicates and indices outside the pool ignored)
-    int64_t n_free = n;
+    pc.n_free = n;
     {
         std::vector<int64_t> tk;
         tk.reserve((size_t)n_taken);
         for (int64_t t = 0; t < n_taken; ++t)
             if (taken[t] >= 0 && taken[t] < n) tk.push_back(taken[t]);
         std::sort(tk.begin(), tk.end());
-        n_free -= (int64_t)(std::unique(tk.begin(), tk.end()) - tk.begin());
+        pc.n_free -= (int64_t)(std::unique(tk.begin(), tk.end()) - tk.begin());
     }
-    const int32_t n_top = (int32_t)std::min<int64_t>(top_k, n_free);
+    return TPE_OK;
+}
 
+// the call's planes, scores and rank keys, queued on the context's stream
+// (n_out: the pairs the caller reads back); a joint group's error has
+// synchronised the stream
+int pool_scores(tpe_ctx* ctx, PoolCall& pc, const int32_t* slots, const int64_t* taken, int64_t n_taken,
+                int64_t n_out) {
+    PoolState* S = pc.S;
+    Posterior& P = ctx->resident;
+    const int64_t n = pc.n;
+    const int32_t L = pc.L, n_groups = pc.n_groups;
+    const std::vector<int32_t>& meta = pc.meta;
+    const int32_t* goff = pc.goff();
+    const int64_t n_top = n_out;
+    size_t& sort_bytes = pc.sort_bytes;
     HIPCHK(ctx, hipSetDevice(ctx->device));
     hipStream_t st = ctx->stream;
     const size_t planes = (size_t)(L + n_groups) * n;
@@ -522,12 +708,11 @@ int tpe1_pool_rank(tpe_ctx* ctx, int32_t n_groups, const int32_t* slots, const i
     HIPCHK(ctx, S->taken_i.reserve(std::max<int64_t>(n_taken, 1)));
     HIPCHK(ctx, S->meta.reserve(meta.size()));
     HIPCHK(ctx, S->err.reserve(1));
-    HIPCHK(ctx, S->top_i.reserve(std::max(n_top, 1)));
-    HIPCHK(ctx, S->top_s.reserve(std::max(n_top, 1)));
+    HIPCHK(ctx, S->top_i.reserve(std::max<int64_t>(n_top, 1)));
+    HIPCHK(ctx, S->top_s.reserve(std::max<int64_t>(n_top, 1)));
     HIPCHK(ctx, S->err_h.resize(1));
-    HIPCHK(ctx, S->top_i_h.resize(std::max(n_top, 1)));
-    HIPCHK(ctx, S->top_s_h.resize(std::max(n_top, 1)));
-    size_t sort_bytes = 0;
+    HIPCHK(ctx, S->top_i_h.resize(std::max<int64_t>(n_top, 1)));
+    HIPCHK(ctx, S->top_s_h.resize(std::max<int64_t>(n_top, 1)));
     hipcub::DoubleBuffer<uint64_t> kb(S->key.p, S->key2.p);
     hipcub::DoubleBuffer<uint32_t> vb(S->idx.p, S->idx2.p);
     HIPCHK(ctx, hipcub::DeviceRadixSort::SortPairsDescending(nullptr, sort_bytes, kb, vb, (int)n, 0, 64, st));
@@ -598,7 +783,44 @@ int tpe1_pool_rank(tpe_ctx* ctx, int32_t n_groups, const int32_t* slots, const i
     hipLaunchKernelGGL(k_pool_sum, dim3(blocks_of(n, kBlock)), dim3(kBlock), 0, st, S->vals.p, n, L, d_cover,
                        n_groups, d_goff, d_gcols, S->lb.p, S->la.p, S->taken.p, S->score.p, S->key.p, S->idx.p);
     HIPCHK(ctx, hipGetLastError());
+    return TPE_OK;
+}
+
+// after the call's synchronisation: what the kernels flagged in the values
+int pool_flags(tpe_ctx* ctx, const std::string& fn, const PoolCall& pc) {
+    const int32_t e = pc.S->err_h[0];
+    if (e & 4) return ctx->fail(TPE_ERR_VALUE, fn + ": categorical value out of range");
+    if (e & 2) return ctx->fail(TPE_ERR_VALUE, fn + ": negative arg to lognormal_cdf");
+    return TPE_OK;
+}
+
+}  // namespace
+
+extern "C" {
+
+int tpe1_pool_rank(tpe_ctx* ctx, int32_t n_groups, const int32_t* slots, const int64_t* group_off,
+                   const int32_t* group_cols, const int64_t* taken, int64_t n_taken, int32_t top_k,
+                   int64_t* top_index, double* top_score, int32_t* n_top_out, double* score, double* lpdf_below,
+                   double* lpdf_above) {
+    if (!ctx) return TPE_ERR_ARG;
+    const std::string fn = "tpe_pool_rank";
+    PoolCall pc;
+    if (const int rc = pool_context(ctx, fn, pc)) return rc;
+    if (top_k < 1) return ctx->fail(TPE_ERR_ARG, "tpe_pool_rank: top_k must be at least 1");
+    if (!top_index || !top_score || !n_top_out || (lpdf_below == nullptr) != (lpdf_above == nullptr))
+        return ctx->fail(TPE_ERR_ARG, "tpe_pool_rank: null pointer or negative count");
+    if (const int rc = pool_groups(ctx, fn, pc, n_groups, slots, group_off, group_cols, taken, n_taken)) return rc;
+    PoolState* S = pc.S;
+    const int64_t n = pc.n;
+    const int32_t L = pc.L;
+    const int32_t n_top = (int32_t)std::min<int64_t>(top_k, pc.n_free);
+    if (const int rc = pool_scores(ctx, pc, slots, taken, n_taken, n_top)) return rc;
+    hipStream_t st = ctx->stream;
+    const size_t planes = (size_t)(L + n_groups) * n;
     if (n_top > 0) {
+        hipcub::DoubleBuffer<uint64_t> kb(S->key.p, S->key2.p);
+        hipcub::DoubleBuffer<uint32_t> vb(S->idx.p, S->idx2.p);
+        size_t sort_bytes = pc.sort_bytes;
         // stable and descending: equal keys keep their ascending index
         HIPCHK(ctx, hipcub::DeviceRadixSort::SortPairsDescending(S->tmp.p, sort_bytes, kb, vb, (int)n, 0, 64, st));
         hipLaunchKernelGGL(k_pool_top, dim3(blocks_of(n_top, kBlock)), dim3(kBlock), 0, st, vb.Current(), S->score.p,
@@ -610,9 +832,7 @@ int tpe1_pool_rank(tpe_ctx* ctx, int32_t n_groups, const int32_t* slots, const i
     }
     HIPCHK(ctx, hipMemcpyAsync(S->err_h.data(), S->err.p, sizeof(int32_t), hipMemcpyDeviceToHost, st));
     HIPCHK(ctx, hipStreamSynchronize(st));   // the call's one synchronisation
-    const int32_t e = S->err_h[0];
-    if (e & 4) return ctx->fail(TPE_ERR_VALUE, "tpe_pool_rank: categorical value out of range");
-    if (e & 2) return ctx->fail(TPE_ERR_VALUE, "tpe_pool_rank: negative arg to lognormal_cdf");
+    if (const int rc = pool_flags(ctx, fn, pc)) return rc;
     // the optional vectors (diagnostics) are plain copies after it: the
     // outputs stay untouched when the values were refused
     if (score) HIPCHK(ctx, hipMemcpy(score, S->score.p, n * sizeof(double), hipMemcpyDeviceToHost));
@@ -631,6 +851,87 @@ int tpe1_pool_rank(tpe_ctx* ctx, int32_t n_groups, const int32_t* slots, const i
     std::memcpy(top_index, S->top_i_h.data(), (size_t)n_top * sizeof(int64_t));
     std::memcpy(top_score, S->top_s_h.data(), (size_t)n_top * sizeof(double));
     *n_top_out = n_top;
+    return TPE_OK;
+}
+
+int tpe1_pool_draw(tpe_ctx* ctx, int32_t n_groups, const int32_t* slots, const int64_t* group_off,
+                   const int32_t* group_cols, const int64_t* taken, int64_t n_taken, uint64_t seed,
+                   const uint32_t* rounds, int32_t n_rounds, int64_t m, int32_t distinct, int64_t* best_index,
+                   double* best_score, int32_t* n_best_out, int64_t* drawn, int32_t* n_drawn, double* lsum,
+                   double* keys, double* score) {
+    if (!ctx) return TPE_ERR_ARG;
+    const std::string fn = "tpe_pool_draw";
+    PoolCall pc;
+    if (const int rc = pool_context(ctx, fn, pc)) return rc;
+    if (m < 1) return ctx->fail(TPE_ERR_ARG, "tpe_pool_draw: m must be at least 1");
+    if (n_rounds < 1 || n_rounds > 4096) return ctx->fail(TPE_ERR_ARG, "tpe_pool_draw: n_rounds must be in [1, 4096]");
+    if (!rounds || !best_index || !best_score || !n_best_out || (drawn == nullptr) != (n_drawn == nullptr))
+        return ctx->fail(TPE_ERR_ARG, "tpe_pool_draw: null pointer or negative count");
+    if (const int rc = pool_groups(ctx, fn, pc, n_groups, slots, group_off, group_cols, taken, n_taken)) return rc;
+    PoolState* S = pc.S;
+    const int64_t n = pc.n;
+    // what is free is known here round by round: the rounds that find an
+    // entry, and how many each draws
+    const int64_t cap = std::min(m, n);
+    const int32_t n_best = distinct ? (int32_t)std::min<int64_t>(n_rounds, pc.n_free) : (pc.n_free > 0 ? n_rounds : 0);
+    const auto drawn_in = [&](int32_t j) { return std::min(m, pc.n_free - (distinct ? j : 0)); };
+    if (const int rc = pool_scores(ctx, pc, slots, taken, n_taken, n_rounds)) return rc;
+    hipStream_t st = ctx->stream;
+    constexpr int kPickBlocks = 256;
+    HIPCHK(ctx, S->lsum.reserve(n));
+    HIPCHK(ctx, S->part_k.reserve(kPickBlocks));
+    HIPCHK(ctx, S->part_i.reserve(kPickBlocks));
+    if (keys) HIPCHK(ctx, S->keys_all.reserve((size_t)n_rounds * n));
+    if (drawn) HIPCHK(ctx, S->drawn.reserve((size_t)n_rounds * cap));
+    hipLaunchKernelGGL(k_pool_lsum, dim3(blocks_of(n, kBlock)), dim3(kBlock), 0, st, ctx->resident.labels.p, S->vals.p,
+                       n, pc.L, pc.d_cover(), n_groups, pc.d_goff(), pc.d_gcols(), S->lb.p, S->lsum.p);
+    HIPCHK(ctx, hipGetLastError());
+    const uint32_t k0 = (uint32_t)(seed & 0xffffffffull), k1 = (uint32_t)(seed >> 32);
+    // `keys` asks for every round's keys, the rounds past the last pick included
+    for (int32_t j = 0; j < (keys ? n_rounds : n_best); ++j) {
+        hipLaunchKernelGGL(k_pool_key, dim3(blocks_of(n, kBlock)), dim3(kBlock), 0, st, S->lsum.p, S->taken.p, n, k0,
+                           k1, rounds[j], S->key.p, S->idx.p, keys ? S->keys_all.p + (size_t)j * n : nullptr);
+        HIPCHK(ctx, hipGetLastError());
+        if (j >= n_best) continue;
+        const int64_t d = drawn_in(j);
+        // stable and descending: equal keys keep their ascending index, and
+        // the entries that are not free (key 0) come last
+        hipcub::DoubleBuffer<uint64_t> kb(S->key.p, S->key2.p);
+        hipcub::DoubleBuffer<uint32_t> vb(S->idx.p, S->idx2.p);
+        HIPCHK(ctx, hipcub::DeviceRadixSort::SortPairsDescending(S->tmp.p, pc.sort_bytes, kb, vb, (int)n, 0, 64, st));
+        const int32_t n_part = (int32_t)std::min<int64_t>(blocks_of(d, kBlock), kPickBlocks);
+        hipLaunchKernelGGL(k_pool_pick, dim3(n_part), dim3(kBlock), 0, st, vb.Current(), S->score.p, d, S->part_k.p,
+                           S->part_i.p);
+        hipLaunchKernelGGL(k_pool_pick_final, dim3(1), dim3(kBlock), 0, st, S->part_k.p, S->part_i.p, n_part,
+                           S->score.p, n, S->top_i.p + j, S->top_s.p + j);
+        if (drawn)
+            hipLaunchKernelGGL(k_pool_drawn, dim3(blocks_of(d, kBlock)), dim3(kBlock), 0, st, vb.Current(), d,
+                               S->drawn.p + (size_t)j * cap);
+        if (distinct) hipLaunchKernelGGL(k_pool_take, dim3(1), dim3(1), 0, st, S->top_i.p + j, n, S->taken.p);
+        HIPCHK(ctx, hipGetLastError());
+    }
+    if (n_best > 0) {
+        HIPCHK(ctx, hipMemcpyAsync(S->top_i_h.data(), S->top_i.p, n_best * sizeof(int64_t), hipMemcpyDeviceToHost,
+                                   st));
+        HIPCHK(ctx, hipMemcpyAsync(S->top_s_h.data(), S->top_s.p, n_best * sizeof(double), hipMemcpyDeviceToHost,
+                                   st));
+    }
+    HIPCHK(ctx, hipMemcpyAsync(S->err_h.data(), S->err.p, sizeof(int32_t), hipMemcpyDeviceToHost, st));
+    HIPCHK(ctx, hipStreamSynchronize(st));   // the call's one synchronisation
+    if (const int rc = pool_flags(ctx, fn, pc)) return rc;
+    // the optional vectors (diagnostics), copied after it as in tpe_pool_rank
+    if (score) HIPCHK(ctx, hipMemcpy(score, S->score.p, n * sizeof(double), hipMemcpyDeviceToHost));
+    if (lsum) HIPCHK(ctx, hipMemcpy(lsum, S->lsum.p, n * sizeof(double), hipMemcpyDeviceToHost));
+    if (keys) HIPCHK(ctx, hipMemcpy(keys, S->keys_all.p, (size_t)n_rounds * n * sizeof(double), hipMemcpyDeviceToHost));
+    if (drawn) {
+        for (int32_t j = 0; j < n_best; ++j)
+            HIPCHK(ctx, hipMemcpy(drawn + (size_t)j * cap, S->drawn.p + (size_t)j * cap,
+                                  (size_t)drawn_in(j) * sizeof(int64_t), hipMemcpyDeviceToHost));
+        for (int32_t j = 0; j < n_rounds; ++j) n_drawn[j] = j < n_best ? (int32_t)drawn_in(j) : 0;
+    }
+    std::memcpy(best_index, S->top_i_h.data(), (size_t)n_best * sizeof(int64_t));
+    std::memcpy(best_score, S->top_s_h.data(), (size_t)n_best * sizeof(double));
+    *n_best_out = n_best;
     return TPE_OK;
 }
 

@@ -737,6 +737,57 @@ class Engine(object):
             out += (lb, la)
         return out
 
+    def pool_draw(self, seed, rounds, m, groups=None, taken=None, distinct=True, want_drawn=False,
+                  want_lsum=False, want_keys=False, want_scores=False):
+        """TPE's draw on the resident pool (tpe_pool_draw), once per round of
+        `rounds`: m entries drawn from the good-trial density l without
+        replacement (Gumbel top-m on the working-space log l, seeded by
+        (seed, round, entry)), of which the one with the best score is kept.
+        Returns (index [n_best], score [n_best]), one pair per round; fewer
+        than len(rounds) when the pool runs out.  groups and taken as in
+        pool_rank; distinct: a round's pick is not free in the later rounds of
+        the call.  want_drawn adds the list of the rounds' drawn sets (int64
+        arrays, in drawn order); want_lsum the draw weights log l [n];
+        want_keys every entry's key per round [len(rounds), n]; want_scores
+        the score of every entry [n]."""
+        groups = list(groups or [])
+        slots = np.ascontiguousarray([int(s) for s, _ in groups], dtype=np.int32)
+        off = np.zeros(len(groups) + 1, dtype=np.int64)
+        for g, (_, cols) in enumerate(groups):
+            off[g + 1] = off[g] + len(cols)
+        cols = np.ascontiguousarray([int(c) for _, cs in groups for c in cs], dtype=np.int32)
+        tk = np.ascontiguousarray([] if taken is None else taken, dtype=np.int64).ravel()
+        rounds = np.ascontiguousarray(np.asarray(rounds, dtype=np.int64).ravel() & 0xFFFFFFFF, dtype=np.uint32)
+        R = len(rounds)
+        n, _ = self.pool_size()
+        m = max(min(int(m), 2 ** 62), 0)
+        cap = max(1, min(m, n))
+        index = np.empty(max(R, 1), dtype=np.int64)
+        best = np.empty(max(R, 1))
+        n_best = ctypes.c_int32(0)
+        drawn = np.empty((max(R, 1), cap), dtype=np.int64) if want_drawn else None
+        n_drawn = np.zeros(max(R, 1), dtype=np.int32) if want_drawn else None
+        lsum = np.empty(n) if want_lsum else None
+        keys = np.empty((R, n)) if want_keys else None
+        score = np.empty(n) if want_scores else None
+        self._check(self.lib.tpe_pool_draw(self.h, len(groups), _ptr(slots) if len(groups) else None,
+                                           _ptr(off) if len(groups) else None,
+                                           _ptr(cols) if len(groups) else None,
+                                           _ptr(tk) if len(tk) else None, len(tk),
+                                           int(seed) & 0xFFFFFFFFFFFFFFFF, _ptr(rounds) if R else None, R, m,
+                                           1 if distinct else 0, _ptr(index), _ptr(best), ctypes.byref(n_best),
+                                           _ptr(drawn), _ptr(n_drawn), _ptr(lsum), _ptr(keys), _ptr(score)))
+        out = (index[:n_best.value].copy(), best[:n_best.value].copy())
+        if want_drawn:
+            out += ([drawn[j, :n_drawn[j]].copy() for j in range(n_best.value)],)
+        if want_lsum:
+            out += (lsum,)
+        if want_keys:
+            out += (keys,)
+        if want_scores:
+            out += (score,)
+        return out
+
     def mo_keys(self, F, want_counts=False, G=None):
         """The Pareto-compliant order of the objective vectors F [n, M], all
         minimised (tpe_mo_keys; posterior.mo_keys is its numpy restatement):

@@ -29,7 +29,8 @@ per branch),
 free labels of a joint group then come from its conditional density),
 `pool` (a `Pool` of configurations: the suggestion is the untaken entry with
 the largest log l(x) - log g(x), ranked on the device; `pool_replace=True`
-takes no entry out),
+takes no entry out; `pool_candidates=m`: that many entries are first drawn from
+l, seeded, and the best of them is suggested),
 `objectives` (result-dict keys minimised together: each complete trial's loss
 becomes its position in a Pareto-compliant order of the objective vectors,
 computed on the device; `pareto_front` lists the non-dominated trials),
@@ -487,6 +488,20 @@ def pool_taken(pool, trials):
     return sorted(taken)
 
 
+def check_pool_candidates(pool_candidates, pool):
+    """suggest's pool_candidates as an int >= 1, or None; ValueError for a
+    bool, a non-integer, a value below 1, or a value without a pool."""
+    if pool_candidates is None:
+        return None
+    if isinstance(pool_candidates, bool) or not isinstance(pool_candidates, (int, np.integer)):
+        raise ValueError('pool_candidates=%r: an integer >= 1, or None' % (pool_candidates,))
+    if pool_candidates < 1:
+        raise ValueError('pool_candidates=%r: must be at least 1' % (pool_candidates,))
+    if pool is None:
+        raise ValueError('pool_candidates=%r needs a pool' % (pool_candidates,))
+    return int(pool_candidates)
+
+
 def _pool_doc(new_id, domain, trials, specs, pool, index):
     return _doc(new_id, domain, trials, specs, dict(pool.points[index]), pool_index=int(index))
 
@@ -830,8 +845,8 @@ def suggest(new_ids, domain, trials, seed,
             linear_forgetting=_default_linear_forgetting,
             precision='f64', device=0, batch=False, posterior_builder='auto', devices=None,
             multivariate=False, group=False, joint_quantized=False, joint_categorical=False,
-            joint_bandwidth='neighbour', fixed=None, pool=None, pool_replace=False, constraints=None,
-            objectives=None):
+            joint_bandwidth='neighbour', fixed=None, pool=None, pool_candidates=None, pool_replace=False,
+            constraints=None, objectives=None):
     """tpe.py:823-916.  Past the startup phase one document for new_ids[0],
     like the reference; `batch` (not in the reference) asks for one document
     per new_id:
@@ -973,11 +988,28 @@ def suggest(new_ids, domain, trials, seed,
     returns fewer documents than ids when the pool runs out and [] when
     nothing is free, which ends fmin's run.  pool_replace=True takes nothing:
     every call then ranks the whole pool.  n_EI_candidates is ignored with a
-    pool, and seed is read in the startup phase only.  ValueError, before any
-    engine is touched: pool with a non-empty fixed (filter the pool instead),
-    pool with more than one device, a pool whose labels are not the domain's,
-    pool_replace without a pool.  With pool=None every call returns what it
-    returned before.
+    pool, and without pool_candidates seed is read in the startup phase only.
+    ValueError, before any engine is touched: pool with a non-empty fixed
+    (filter the pool instead), pool with more than one device, a pool whose
+    labels are not the domain's, pool_replace without a pool.  With pool=None
+    every call returns what it returned before.
+
+    pool_candidates=m (an integer >= 1; None: the ranking above, unchanged)
+    makes the pool call TPE's own step ("Drawing from
+    the pool"): m of the free entries are drawn from the good-trial density l
+    -- with probability proportional to l(x) in the labels' working space
+    (log x for the log kinds), without replacement, seeded by (seed, new_id,
+    entry) -- and the document is the drawn entry with the largest
+    log l(x) - log g(x).  One Engine.pool_draw call answers every id, each
+    with its own draw: two workers with different seeds, and the ids of a
+    batch, explore different parts of the pool.  batch=True picks distinct
+    entries (every id's draw leaves out the earlier ids' picks);
+    pool_replace=True lets them repeat.  m at least the number of free
+    entries draws them all and returns the ranking's documents; the call
+    returns fewer documents than ids when the pool runs out.  The posterior,
+    the joint groups, the taken set and the startup phase are those of the
+    pool call without the keyword.  ValueError, before any engine is touched:
+    pool_candidates without a pool, a bool, a non-integer, a value below 1.
 
     objectives=('loss', 'latency', ...) (not in the reference; Optuna's MOTPE
     serves the same studies) minimises several entries of the result dict at
@@ -1043,6 +1075,8 @@ def suggest(new_ids, domain, trials, seed,
     t0 = time.time()
     objectives = check_objectives(objectives)   # (first: nothing else has run when it raises)
     constraints = check_constraints(constraints, objectives)
+    pool_candidates = check_pool_candidates(pool_candidates, pool)
+    pool_kw = {} if pool_candidates is None else dict(pool_candidates=pool_candidates)   # (None is not handed on)
     if objectives is not None or constraints is not None:
         # the call below on another loss column: the keys once, from all the
         # trials; every place that reads losses reads them through the domain
@@ -1072,7 +1106,8 @@ def suggest(new_ids, domain, trials, seed,
                        linear_forgetting=linear_forgetting, precision=precision, device=device, batch=batch,
                        posterior_builder=posterior_builder, devices=devices, multivariate=multivariate,
                        group=group, joint_quantized=joint_quantized, joint_categorical=joint_categorical,
-                       joint_bandwidth=joint_bandwidth, fixed=fixed, pool=pool, pool_replace=pool_replace)
+                       joint_bandwidth=joint_bandwidth, fixed=fixed, pool=pool, pool_replace=pool_replace,
+                       **pool_kw)
     specs = specs_of(domain)
     fixed = check_fixed(specs, fixed)
     if precision not in ('f64', 'f32'):
@@ -1118,7 +1153,7 @@ def suggest(new_ids, domain, trials, seed,
         kw['fixed'] = fixed
     taken = []
     if pool is not None:
-        kw.update(pool=pool, pool_replace=pool_replace)
+        kw.update(pool=pool, pool_replace=pool_replace, **pool_kw)
         taken = [] if pool_replace else pool_taken(pool, trials)
         if len(taken) == len(pool):
             return []   # (nothing is free: fmin's _ask stops on an empty answer)
@@ -1184,13 +1219,21 @@ def suggest(new_ids, domain, trials, seed,
         if getattr(eng, 'pool_token', None) != pool.token:
             eng.pool_set(pool.values)
             eng.pool_token = pool.token
-        index, _ = eng.pool_rank(len(ids), groups=[(slot, [labels.index(k) for k in g])
-                                                   for slot, g in groups or []], taken=taken)
+        cols = [(slot, [labels.index(k) for k in g]) for slot, g in groups or []]
+        if pool_candidates is None:
+            index, _ = eng.pool_rank(len(ids), groups=cols, taken=taken)
+            how = ''
+        else:
+            # TPE's own step on the pool: per id (its round) pool_candidates
+            # entries drawn from l, the best l/g among them
+            index, _ = eng.pool_draw(seed, ids, pool_candidates, groups=cols, taken=taken,
+                                     distinct=not pool_replace)
+            how = ', %d drawn per id' % min(pool_candidates, len(pool) - len(taken))
         rval = []
         for new_id, i in zip(ids, index):
             rval.extend(_pool_doc(new_id, domain, trials, specs, pool, int(i)))
-        logger.info('tpe.suggest: %d trials, %d labels, pool of %d (%d taken), %.1f ms' % (
-            n_docs, len(specs), len(pool), len(taken), (time.time() - t0) * 1e3))
+        logger.info('tpe.suggest: %d trials, %d labels, pool of %d (%d taken)%s, %.1f ms' % (
+            n_docs, len(specs), len(pool), len(taken), how, (time.time() - t0) * 1e3))
         return rval
     _, res = _resident_posterior(eng, domain, trials, specs, view, gathered, gamma, prior_weight,
                                  posterior_builder, n_candidates=n_EI_candidates, n_rounds=len(ids),

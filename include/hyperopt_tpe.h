@@ -727,6 +727,58 @@ int tpe_pool_rank(tpe_ctx *ctx, int32_t n_groups, const int32_t *slots, const in
                   double *score /* [n] or NULL */,
                   double *lpdf_below, double *lpdf_above /* [n][n_cols + n_groups] or NULL: diagnostics */);
 
+/* tpe_pool_draw: TPE's own step on the resident pool -- draw m entries from
+ * the good-trial density l, seeded and without replacement, and return the
+ * drawn entry with the best l/g -- once per round, all on the device.  The
+ * pool, the posterior, the groups, `taken`, the planes lb / la and score[i] are
+ * tpe_pool_rank's.
+ *   lsum[i] (the draw weight, log l of entry i): the fp64 sum, from 0.0 and
+ *       left to right, over the same terms in the same order as score[i], each
+ *       term the below lpdf in the label's working space: lb for every kind
+ *       but a dense log label (loguniform, lognormal), whose term is
+ *       lb + log v (one fp64 add; v the entry's value); a group's is
+ *       ll + (the sum, from 0.0, of log v_d over its dense log columns in the
+ *       order the group lists them).  No term: 0.0.  In the working space the
+ *       prior of uniform and loguniform labels is flat (the document-space
+ *       density's Jacobian 1/x would weight a log-spaced grid by 1/x); for the
+ *       normal kinds the prior's own factor remains.
+ *   noise of entry i (its pool index) in round r under seed s:
+ *       (w0, w1, ., .) = philox4x32_10(counter (i, 0, TPE_POOL_STREAM, r),
+ *       key (s & 0xffffffff, s >> 32)); t = (w0 << 20) | (w1 >> 12), 52 bits;
+ *       u = (t + 0.5) 2^-52, exact and strictly inside (0, 1);
+ *       G = -log(-log u), standard Gumbel; key_r[i] = lsum[i] + G.  A key
+ *       depends on (s, r, i, lsum[i]) alone.
+ *   round j = 0 .. n_rounds - 1, in order, r = rounds[j]: free_j is the entries
+ *       not in `taken` and, with distinct != 0, not among best_index[0 .. j);
+ *       an empty free_j ends the call with *n_best = j.  drawn_j is the
+ *       d_j = min(m, |free_j|) entries of free_j first by key descending (NaN
+ *       greatest), then index ascending -- the Gumbel top-m form of a draw
+ *       without replacement with probabilities proportional to l (m = 1:
+ *       P(i) = l_i / sum l); an entry with l = 0 is drawn only when fewer than
+ *       d_j entries have a finite key.  best_index[j] is the entry of drawn_j
+ *       first in tpe_pool_rank's order of score, best_score[j] its score.
+ *   With m >= |free_0| and distinct != 0, best_index / best_score are
+ *   tpe_pool_rank's top n_rounds bit for bit, whatever the seed.
+ * Diagnostics, each NULL or given: drawn [n_rounds][min(m, n)] with n_drawn
+ * [n_rounds] (both or neither): row j's first n_drawn[j] = d_j values are
+ * drawn_j in that order, 0 for a round past *n_best; lsum [n]; keys
+ * [n_rounds][n]: every entry's key of the round, entries that are not free
+ * included; score [n] as tpe_pool_rank's.
+ * One stream synchronisation per call, the planes computed once per call; the
+ * optional vectors are copied after it.  Errors as tpe_pool_rank (TPE_ERR_ARG,
+ * a multi-device or TPE_F32 context included; TPE_ERR_VALUE; TPE_ERR_SAMPLE),
+ * and TPE_ERR_ARG for m < 1, n_rounds outside [1, 4096], a NULL rounds,
+ * best_index, best_score or n_best, drawn without n_drawn or the reverse.  On
+ * an error the outputs are untouched. */
+#define TPE_POOL_STREAM 0x7FFFFFBF   /* the first stream below the pick streams TPE_JOINT_STREAM - j */
+int tpe_pool_draw(tpe_ctx *ctx, int32_t n_groups, const int32_t *slots, const int64_t *group_off,
+                  const int32_t *group_cols, const int64_t *taken, int64_t n_taken,
+                  uint64_t seed, const uint32_t *rounds, int32_t n_rounds, int64_t m, int32_t distinct,
+                  int64_t *best_index /* [n_rounds] */, double *best_score /* [n_rounds] */, int32_t *n_best,
+                  int64_t *drawn /* [n_rounds][min(m, n)] or NULL */, int32_t *n_drawn /* [n_rounds] or NULL */,
+                  double *lsum /* [n] or NULL */, double *keys /* [n_rounds][n] or NULL */,
+                  double *score /* [n] or NULL */);
+
 /* ---- several objectives ---------------------------------------------------
  * The Pareto-compliant total order of n objective vectors, all objectives
  * minimised (no reference counterpart: the reference splits the trials by one

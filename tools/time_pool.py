@@ -1,6 +1,8 @@
 """Timings of the candidate-pool ranking (Engine.pool_rank; needs the GPU).
 
     python tools/time_pool.py --gpus 1 [--sizes 17,20] [--reps 20] [--out FILE]
+    python tools/time_pool.py --gpus 1 --draw 24 [--sizes 17,20] [--reps 20] [--out FILE]
+    python tools/time_pool.py --gpus 1 --explore 24 [--seeds 20] [--out FILE]
     rocprofv3 --kernel-trace --stats -d DIR -o run --output-format csv -- \\
         python tools/time_pool.py --gpus 1 --trace-leg [--sizes 17]
     python tools/time_pool.py --kernel-stats DIR/.../run_kernel_stats.csv --sizes 17 --out FILE
@@ -23,6 +25,15 @@ labels, the (entry, component) terms per second of k_pool_dense beside those
 of the plain fp64 round on supplied candidates (k_round<double, DENSE_*,
 false>, what tpe_score launches): terms = entries x the components of both
 mixtures of every dense label, over the kernels' average time per call.
+
+--draw M: Engine.pool_draw (M entries drawn from l per round, the best l/g of
+them) at 1 and 8 rounds beside Engine.pool_rank at k = 1 and k = 8 on the same
+pools, the same medians, and their differences -- nothing else is run.
+--explore M: fmin over a pool of 4096 prior draws of the config-3 space (32
+labels, loss = the sum of the labels' bowls, no noise), per seed once with the
+ranking (pool_candidates=None) and once with pool_candidates=M: the best loss
+after 50, 100 and 200 evaluations, and how many distinct entries two workers
+with different seeds propose from the same 100 trials.
 
 Results are appended to --out as one JSON object per line."""
 import argparse
@@ -105,6 +116,67 @@ def timings(args):
     return out
 
 
+def draw_timings(args):
+    eng, hist = setup()
+    out = []
+    for lg in args.sizes:
+        n = 1 << lg
+        eng.pool_set(draw_pool(hist, n))
+        rec = dict(what='pool_draw', labels=len(hist.labels), trials=len(hist.tids), n=n, m=args.draw)
+        for k in (1, 8):
+            rounds = list(range(100, 100 + k))
+            rec['pool_rank_k%d' % k] = timed(lambda: eng.pool_rank(k), args.reps)
+            rec['pool_draw_r%d' % k] = timed(lambda: eng.pool_draw(7, rounds, args.draw), args.reps)
+            rec['draw_minus_rank_r%d_ms' % k] = (rec['pool_draw_r%d' % k]['median_ms']
+                                                 - rec['pool_rank_k%d' % k]['median_ms'])
+        # everything drawn: the ranking's entries
+        rec['pool_sized_draw_is_rank'] = bool(np.array_equal(eng.pool_draw(7, list(range(8)), n)[0],
+                                                             eng.pool_rank(8)[0]))
+        print(json.dumps(rec), flush=True)
+        out.append(rec)
+    eng.close()
+    return out
+
+
+def explore(args):
+    from functools import partial
+    from hyperopt_amd import Trials, fmin, tpe
+    from hyperopt_amd.base import Domain
+    from hyperopt_amd.workloads import bowl, hp_space, mixed_space, prior_draw
+    labels = mixed_space(32)
+    kinds = {name: kind for name, kind, _ in labels}
+    space = hp_space(labels)
+
+    def loss(cfg):
+        return float(sum(bowl(kinds[k], np.asarray(float(v))) for k, v in cfg.items()))
+    rng = np.random.RandomState(5)
+    cols = {name: prior_draw(kind, a, rng, 4096) for name, kind, a in labels}
+    pts = [{k: (int(v[i]) if kinds[k] == 'randint' else float(v[i])) for k, v in cols.items()} for i in range(4096)]
+    domain = Domain(loss, space)
+    pool = tpe.Pool(domain, pts)
+    marks = (50, 100, 200)
+    rec = dict(what='pool_explore', n=len(pool), labels=len(labels), m=args.explore, seeds=args.seeds,
+               pool_best=min(loss(p) for p in pts))
+    for name, m in (('rank', None), ('draw', args.explore)):
+        best = {k: [] for k in marks}
+        distinct = []
+        for seed in range(args.seeds):
+            algo = partial(tpe.suggest, pool=pool, pool_candidates=m)
+            trials, rstate = Trials(), np.random.RandomState(seed)
+            for k in marks:
+                fmin(loss, space, algo=algo, max_evals=k, trials=trials, rstate=rstate)
+                best[k].append(min(trials.losses()))
+                if k == 100:   # two workers, the same trials, different seeds
+                    a = algo([1000], domain, trials, 2 * seed + 1)
+                    b = algo([1000], domain, trials, 2 * seed + 2)
+                    distinct.append(len({a[0]['misc']['pool_index'], b[0]['misc']['pool_index']}))
+        rec[name] = dict(best_loss={str(k): dict(mean=float(np.mean(v)), median=float(np.median(v)),
+                                                 min=float(min(v)), max=float(max(v))) for k, v in best.items()},
+                         distinct_of_two_workers=float(np.mean(distinct)))
+    print(json.dumps(rec), flush=True)
+    return [rec]
+
+
 def trace_leg(args):
     eng, hist = setup()
     _, dense = dense_components(eng, hist)
@@ -152,12 +224,16 @@ def main():
     ap.add_argument('--reps', type=int, default=20)
     ap.add_argument('--trace-leg', action='store_true')
     ap.add_argument('--kernel-stats')
+    ap.add_argument('--draw', type=int, default=0, metavar='M', help='time pool_draw with M drawn per round')
+    ap.add_argument('--explore', type=int, default=0, metavar='M', help='fmin over a pool: ranking against pool_candidates=M')
+    ap.add_argument('--seeds', type=int, default=20)
     ap.add_argument('--out')
     args = ap.parse_args()
     if args.gpus != 1:
         ap.error('the pool is ranked on one device: --gpus 1')
     args.sizes = [int(s) for s in args.sizes.split(',')]
-    recs = kernel_stats(args) if args.kernel_stats else trace_leg(args) if args.trace_leg else timings(args)
+    recs = (kernel_stats(args) if args.kernel_stats else trace_leg(args) if args.trace_leg
+            else draw_timings(args) if args.draw else explore(args) if args.explore else timings(args))
     if args.out:
         with open(args.out, 'a') as f:
             for r in recs:
