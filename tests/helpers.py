@@ -90,6 +90,25 @@ def _assert_same(a, b):
         assert np.array_equal(a[f], b[f], equal_nan=f != 'index' and f != 'label'), f
 
 
+def value_only_cells(exact, vo):
+    """A value-only round against the exact round of the same call
+    (test_value_only, test_value_only_edges_gpu): the same index and value
+    everywhere; a decided cell (lpdfs NaN where the exact round has them) says
+    so (TPE_STATUS_VALUE_ONLY) and carries no score; every other cell is the
+    exact round's record, bit for bit.  Returns the mask of decided cells."""
+    assert np.array_equal(exact['index'], vo['index'])
+    assert exact['value'].tobytes() == vo['value'].tobytes()
+    decided = np.isnan(vo['lpdf_below']) & ~np.isnan(exact['lpdf_below'])
+    # a decided cell says so (TPE_STATUS_VALUE_ONLY); every other one is ok
+    assert np.all(vo['status'][decided] == 1) and np.all(vo['status'][~decided] == 0)
+    assert np.all(exact['status'] == 0)
+    assert np.all(np.isnan(vo['score'][decided])) and np.all(np.isnan(vo['lpdf_above'][decided]))
+    # the cells the screen did not decide alone are the exact round's, bit for bit
+    same = ~decided
+    assert np.ascontiguousarray(exact[same]).tobytes() == np.ascontiguousarray(vo[same]).tobytes()
+    return decided
+
+
 # -- device posterior builds against the CPU oracle (test_gpu_build, test_history_gpu) --
 ALL_KINDS = [
     ('u', 'uniform', dict(low=-5.0, high=5.0)),

@@ -10,6 +10,8 @@ buffers hold runs again with larger ones): same bytes."""
 import numpy as np
 import pytest
 
+from tests.helpers import value_only_cells
+
 pytestmark = pytest.mark.gpu
 
 
@@ -33,16 +35,7 @@ def _both(eng, fn):
 
 
 def _check(exact, vo):
-    assert np.array_equal(exact['index'], vo['index'])
-    assert exact['value'].tobytes() == vo['value'].tobytes()
-    decided = np.isnan(vo['lpdf_below']) & ~np.isnan(exact['lpdf_below'])
-    # a decided cell says so (TPE_STATUS_VALUE_ONLY); every other one is ok
-    assert np.all(vo['status'][decided] == 1) and np.all(vo['status'][~decided] == 0)
-    assert np.all(exact['status'] == 0)
-    # the cells the screen did not decide alone are the exact round's, bit for bit
-    same = ~decided
-    assert np.ascontiguousarray(exact[same]).tobytes() == np.ascontiguousarray(vo[same]).tobytes()
-    return int(decided.sum())
+    return int(value_only_cells(exact, vo).sum())
 
 
 def test_value_only_config5(eng):
