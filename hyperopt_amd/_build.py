@@ -26,7 +26,8 @@ SOURCES = [os.path.join(HERE, 'csrc', 'tpe_engine.hip'),
            os.path.join(HERE, 'csrc', 'tpe_share.hip'),
            os.path.join(HERE, 'csrc', 'tpe_joint.hip'),
            os.path.join(HERE, 'csrc', 'tpe_pool.hip'),
-           os.path.join(HERE, 'csrc', 'tpe_mo.hip')]
+           os.path.join(HERE, 'csrc', 'tpe_mo.hip'),
+           os.path.join(HERE, 'csrc', 'tpe_importance.hip')]
 DEPS = SOURCES + [os.path.join(HERE, 'csrc', 'tpe_device.h'),
                   os.path.join(HERE, 'csrc', 'tpe_ctx.h'),
                   os.path.join(HERE, 'csrc', 'tpe_exp_table.h'),

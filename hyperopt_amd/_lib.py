@@ -197,6 +197,7 @@ SIGNATURES = {
                                      ctypes.POINTER(_I32), _P, _P, _P, _P, _P]),
     'tpe_mo_keys': (ctypes.c_int, [_P, _P, _I64, _I32, _P, _P, _P]),
     'tpe_mo_keys_constrained': (ctypes.c_int, [_P, _P, _I64, _I32, _P, _I32, _P, _P, _P, _P]),
+    'tpe_importance': (ctypes.c_int, [_P, _I32, _P, _P, _P, _P, _P, _P, _P, _P, _P]),
 }
 
 _lib = None

@@ -667,6 +667,9 @@ struct tpe_ctx {
     // the reusable buffers of tpe_mo_keys (tpe_mo.hip)
     std::shared_ptr<void> mo;
 
+    // the reusable buffers of tpe_importance (tpe_importance.hip)
+    std::shared_ptr<void> imp;
+
     int fail(int code, const std::string& m) {
         err = m;
         return code;

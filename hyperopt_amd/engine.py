@@ -816,6 +816,38 @@ class Engine(object):
                                                      _ptr(keys), _ptr(by), _ptr(do), _ptr(v)))
         return (keys, by, do, v) if want_counts else keys
 
+    def importance(self, labels, cells, alpha, want_planes=False):
+        """The importance sums of resident labels (tpe_importance): labels the
+        label indices, each once; cells one (x, w, merge) per label
+        (posterior.importance_cells); alpha per label, in (0, 1).  Returns v
+        [len(labels)] float64, v[s] = sum_j w_j p(x_j) (m(x_j) - alpha)^2 over
+        the label's cells; want_planes adds the lists of the labels' lpdf_below
+        and lpdf_above arrays at their x (Engine.score's bits; a quantized
+        label with merge > 1: the lpdf with the step merge q)."""
+        labels = np.ascontiguousarray(labels, dtype=np.int32).ravel()
+        cells = list(cells)
+        alpha = _f64(alpha).ravel()
+        if len(cells) != len(labels) or len(alpha) != len(labels):
+            raise ValueError('importance: one (x, w, merge) and one alpha per label')
+        xs = [_f64(c[0]).ravel() for c in cells]
+        ws = [_f64(c[1]).ravel() for c in cells]
+        if any(len(a) != len(b) for a, b in zip(xs, ws)):
+            raise ValueError('importance: one weight per cell')
+        merge = np.ascontiguousarray([int(c[2]) for c in cells], dtype=np.int32)
+        off = np.zeros(len(labels) + 1, dtype=np.int64)
+        off[1:] = np.cumsum([len(a) for a in xs])
+        x = _f64(np.concatenate(xs)) if xs else np.zeros(0)
+        w = _f64(np.concatenate(ws)) if ws else np.zeros(0)
+        v = np.zeros(len(labels))
+        lb = np.empty(len(x)) if want_planes else None
+        la = np.empty(len(x)) if want_planes else None
+        self._check(self.lib.tpe_importance(self.h, len(labels), _ptr(labels), _ptr(off), _ptr(x), _ptr(w),
+                                            _ptr(merge), _ptr(alpha), _ptr(v), _ptr(lb), _ptr(la)))
+        if not want_planes:
+            return v
+        return (v, [lb[off[s]:off[s + 1]] for s in range(len(labels))],
+                [la[off[s]:off[s + 1]] for s in range(len(labels))])
+
     def last_timing(self):
         a, b = ctypes.c_float(), ctypes.c_float()
         self._check(self.lib.tpe_last_timing(self.h, ctypes.byref(a), ctypes.byref(b)))

@@ -48,13 +48,20 @@ CONTINUOUS = ('uniform', 'quniform', 'loguniform', 'qloguniform',
 CATEGORICAL = ('randint', 'categorical')
 
 
-def split_history(l_idxs, l_vals, gamma, gamma_cap=DEFAULT_LF):
+def split_history(l_idxs, l_vals, gamma, gamma_cap=DEFAULT_LF, n_below=None):
     """Global loss-rank split (tpe.py:636-645): tids of the n_below best
-    trials and of the rest."""
+    trials and of the rest.  n_below (default None: the reference's
+    min(ceil(gamma sqrt(n)), gamma_cap) and its np.argsort) sets the size of
+    the below set itself; the sort is then stable, ties going by trial order
+    (tpe.importance: the below set is a quantile of the trials)."""
     l_idxs = np.asarray(l_idxs)
     l_vals = np.asarray(l_vals)
-    n_below = min(int(np.ceil(gamma * np.sqrt(len(l_vals)))), gamma_cap)
-    order = np.argsort(l_vals)
+    if n_below is None:
+        n_below = min(int(np.ceil(gamma * np.sqrt(len(l_vals)))), gamma_cap)
+        order = np.argsort(l_vals)
+    else:
+        n_below = int(n_below)
+        order = np.argsort(l_vals, kind='stable')
     return l_idxs[order[:n_below]], l_idxs[order[n_below:]]
 
 
@@ -73,8 +80,8 @@ class Splitter(object):
     membership of a tid is looked up by binary search in the sorted tids
     (one O(M log N) pass per label instead of np.isin's sorts)."""
 
-    def __init__(self, l_idxs, l_vals, gamma, gamma_cap=DEFAULT_LF):
-        below, above = split_history(l_idxs, l_vals, gamma, gamma_cap)
+    def __init__(self, l_idxs, l_vals, gamma, gamma_cap=DEFAULT_LF, n_below=None):
+        below, above = split_history(l_idxs, l_vals, gamma, gamma_cap, n_below=n_below)
         tids = np.concatenate([below, above])
         side = np.concatenate([np.ones(len(below), dtype=np.int8),
                                np.full(len(above), 2, dtype=np.int8)])
@@ -295,6 +302,69 @@ def label_posterior(label, kind, args, below, above, prior_weight):
     mix = [adaptive_parzen_normal(tr(np.asarray(o, dtype=float)), pw, mu, sigma)
            for o in (below, above)]
     return LabelPosterior(label, fam, mix[0], mix[1], q=q)
+
+
+IMPORTANCE_TAIL = 4.0   # prior sigmas an unbounded label's cells reach past its prior mean and observations
+
+
+def importance_cells(kind, args, obs, n_grid):
+    """The cells tpe.importance sums one label's terms over (DESIGN.md
+    section 6b, "Hyperparameter importance"): (x, w, merge) -- the point each
+    cell's densities are taken at, its weight, and the support values a cell
+    of a quantized kind merges (1 for every other kind).
+
+    Dense kinds: n_grid equal cells of width h in the working space (log x
+    for the log kinds) -- over [low, high] for uniform / loguniform, over
+    [min(mu, t_min) - 4 sigma, max(mu, t_max) + 4 sigma] for normal /
+    lognormal (t the observations `obs` in the working space, mu and sigma the
+    prior's); x the midpoint mapped back, w = h, or h x for the log kinds
+    (the midpoint rule in log x of an x-space density).  Quantized kinds: the
+    support k q, k = round(a / q) .. round(b / q) over the same range [a, b]
+    mapped back to x (k >= 0 for the log kinds); merge = ceil(S / n_grid)
+    consecutive values of the S make a cell, x their mean, w = 1; the cell's
+    mass is the quantized lpdf's with the step merge q.  Categorical kinds:
+    one cell per category, w = 1."""
+    n_grid = int(n_grid)
+    if n_grid < 1:
+        raise ValueError('n_grid must be at least 1')
+    if kind in CATEGORICAL:
+        upper = int(args['upper'])
+        return np.arange(upper, dtype=np.float64), np.ones(upper), 1
+    if kind not in CONTINUOUS:
+        raise ValueError('unknown distribution %r' % kind)
+    log = kind in ('loguniform', 'qloguniform', 'lognormal', 'qlognormal')
+    quant = kind in ('quniform', 'qloguniform', 'qnormal', 'qlognormal')
+    if kind in ('uniform', 'quniform', 'loguniform', 'qloguniform'):
+        a, b = float(args['low']), float(args['high'])
+    else:
+        mu, sigma = float(args['mu']), float(args['sigma'])
+        a = b = mu
+        t = np.asarray(obs, dtype=float)
+        if len(t):
+            if kind == 'lognormal':
+                t = np.log(t)
+            elif kind == 'qlognormal':
+                t = np.log(np.maximum(t, EPS))
+            a, b = min(mu, float(np.min(t))), max(mu, float(np.max(t)))
+        a, b = a - IMPORTANCE_TAIL * sigma, b + IMPORTANCE_TAIL * sigma
+    if not quant:
+        h = (b - a) / n_grid
+        mid = a + (np.arange(n_grid) + 0.5) * h
+        if log:
+            x = np.exp(mid)
+            return x, h * x, 1
+        return mid, np.full(n_grid, h), 1
+    q = float(args['q'])
+    if log:
+        a, b = float(np.exp(a)), float(np.exp(b))
+    k0, k1 = int(np.round(a / q)), int(np.round(b / q))
+    if log:
+        k0, k1 = max(k0, 0), max(k1, 0)
+    S = k1 - k0 + 1
+    merge = -(-S // n_grid)
+    cells = -(-S // merge)
+    x = (k0 + np.arange(cells) * merge + 0.5 * (merge - 1)) * q
+    return x, np.ones(cells), merge
 
 
 JOINT_KINDS = ('uniform', 'loguniform', 'normal', 'lognormal')

@@ -50,6 +50,11 @@ posterior.build_reference_order -- so the mixtures are the host build's bit
 for bit) or 'auto' (device once the history holds DEVICE_BUILD_MIN_OBS
 observations over all labels, where the host build starts to dominate the
 suggestion).
+
+`importance(space, trials)` (not in the reference) tells which hyperparameters
+mattered: per label the variance of the model's good-trial probability under
+the label's observed values, from the same Parzen mixtures, summed on the
+device (`Engine.importance`).
 """
 import itertools
 import logging
@@ -835,6 +840,126 @@ def pareto_front(trials, objectives, constraints=None):
     by, _ = _post.mo_counts(F, G)
     v = _post.mo_violation(G, F)
     return sorted((d for d, b, vi in zip(docs, by, v) if b == 0 and vi == 0), key=lambda d: d['tid'])
+
+
+def importance(space, trials, quantile=0.1, n_grid=4096, prior_weight=_default_prior_weight,
+               normalize=True, curves=False, device=0, objectives=None, constraints=None):
+    """Which hyperparameters mattered (not in the reference; Optuna's
+    get_param_importances with the PED-ANOVA evaluator asks the same
+    question): {label: importance}, sorted descending, ties in label order.
+
+    space: the space given to fmin, or a Domain.  The n complete trials (a
+    loss that is not None; a NaN loss stays out as always) are split at the
+    quantile: the n_below = ceil(quantile n) best by loss are "good" (stable
+    sort, ties by trial order).  For a label observed nb times among them and
+    na times among the rest, alpha = nb / (nb + na), l and g are
+    posterior.label_posterior's mixtures of the two observation lists (the
+    estimator tpe.suggest samples from, with prior_weight and linear
+    forgetting), p = alpha l + (1 - alpha) g models the label's observed
+    values and m(x) = alpha l(x) / p(x) is the model's probability that a
+    trial with that value is good.  The label's raw importance is the variance
+    of m under p, weighted by how often the label is active,
+        V = sum_cells w_j p(x_j) (m(x_j) - alpha)^2,    I = (nb + na) / n  V
+    -- alpha^2 times the Pearson divergence of l from p, PED-ANOVA's quantity
+    with the global baseline -- summed over posterior.importance_cells' cells
+    (n_grid of them for a dense label; DESIGN.md section 6b, "Hyperparameter
+    importance").  A label with nb = 0 or na = 0 has V = 0.  normalize=True
+    returns I / np.sum(I) (the labels in the space's order), all zeros when
+    the sum is 0.  A label whose sum is NaN (a NaN lpdf at one of its cells: a
+    NaN or non-positive observation of a log kind, say) keeps NaN, comes
+    last in the dict and is left out of the normalising sum: the other
+    labels' shares are those among themselves.
+
+    The mixtures of every label are uploaded to a context of their own
+    (engine.get_engine(device, 'f64', 'importance'): the history tpe.suggest
+    keeps resident on the 'main' one stays there) and one Engine.importance
+    call sums every label's cells on the device.
+
+    curves=True returns (importances, {label: (x, w, p, m)}) for the labels
+    with observations on both sides: the cells and, at each, the density p
+    and the good-trial probability m -- the partial-dependence view.
+
+    objectives / constraints replace the loss by the keys tpe.suggest ranks
+    the trials with under the same keywords.
+
+    ValueError, before any engine is touched: quantile outside (0, 1), n_grid
+    not an integer >= 1, fewer than 2 complete trials, and what
+    check_objectives, check_constraints and objective_rows refuse."""
+    objectives = check_objectives(objectives)
+    constraints = check_constraints(constraints, objectives)
+    if isinstance(quantile, bool) or not isinstance(quantile, (int, float, np.integer, np.floating)) \
+            or not 0.0 < quantile < 1.0:
+        raise ValueError('importance: quantile must lie in (0, 1), got %r' % (quantile,))
+    if isinstance(n_grid, bool) or not isinstance(n_grid, (int, np.integer)) or n_grid < 1:
+        raise ValueError('importance: n_grid must be an integer >= 1, got %r' % (n_grid,))
+    if not _labels.is_node(space) and hasattr(space, 'expr'):   # a Domain
+        domain = space
+    else:
+        from .base import Domain
+        domain = Domain(None, space)
+    specs = specs_of(domain)
+    names = list(specs)
+
+    def engine():
+        return _engine.get_engine(device, 'f64', 'importance')
+    if objectives is not None or constraints is not None:
+        src = trials.trials
+        check_from = _history.has_from_tid(trials, names)
+        if constraints is None:
+            docs, F = objective_rows(src, objectives, domain, check_from=check_from)
+            G = None
+        else:
+            docs, F, G = objective_rows(src, objectives or ('loss',), domain, check_from=check_from,
+                                        constraints=constraints)
+        if len(docs) < 2:
+            raise ValueError('importance: needs at least 2 complete trials, got %d' % len(docs))
+        domain = _KeyedDomain(domain, docs, objective_keys(F, 'auto', engine, G=G), src)
+    tids, losses, obs = _history.gather(domain, trials, names)
+    done = losses < np.inf                       # (pending and failed trials carry +inf)
+    tids, losses = tids[done], losses[done]
+    n = len(tids)
+    if n < 2:
+        raise ValueError('importance: needs at least 2 complete trials, got %d' % n)
+    splitter = _post.Splitter(tids, losses, 0.0, n_below=int(np.ceil(quantile * n)))
+    posts, sel, cells, alphas, active = [], [], [], [], np.zeros(len(names))
+    for li, (label, s) in enumerate(specs.items()):
+        oi, ov = obs[label]
+        if not done.all():
+            keep = np.isin(oi, tids)
+            oi, ov = oi[keep], ov[keep]
+        b, a = splitter.split(oi, ov)
+        posts.append(_post.label_posterior(label, s.kind, s.args, b, a, prior_weight))
+        active[li] = (len(b) + len(a)) / n
+        if len(b) and len(a):
+            sel.append(li)
+            cells.append(_post.importance_cells(s.kind, s.args, ov, n_grid))
+            alphas.append(len(b) / (len(b) + len(a)))
+    raw = np.zeros(len(names))
+    planes = None
+    if sel:
+        eng = engine()
+        eng.set_posterior(*_post.pack(posts))
+        out = eng.importance(sel, cells, alphas, want_planes=curves)
+        v, planes = (out[0], out[1:]) if curves else (out, None)
+        raw[sel] = active[sel] * v
+    bad = np.isnan(raw)
+    if normalize:
+        # (a NaN label stays NaN and takes no part in the others' shares)
+        total = np.sum(raw[~bad])
+        raw = np.where(bad, np.nan, raw / total if total != 0 else 0.0)
+    order = sorted(range(len(names)), key=lambda i: (bool(bad[i]), 0.0 if bad[i] else -raw[i], i))
+    result = {names[i]: float(raw[i]) for i in order}
+    if not curves:
+        return result
+    views = {}
+    for k, li in enumerate(sel):
+        x, w, _ = cells[k]
+        with np.errstate(invalid='ignore', divide='ignore'):
+            lik = alphas[k] * np.exp(planes[0][k])
+            p = lik + (1.0 - alphas[k]) * np.exp(planes[1][k])
+            m = np.where(p > 0, lik / p, alphas[k])
+        views[names[li]] = (x, w, p, m)
+    return result, views
 
 
 def suggest(new_ids, domain, trials, seed,

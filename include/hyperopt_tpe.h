@@ -843,6 +843,44 @@ int tpe_mo_keys_constrained(tpe_ctx *ctx, const double *objectives /* [n][n_obj]
                             double *keys /* [n] */, int32_t *dominated_by /* [n] or NULL */,
                             int32_t *dominates /* [n] or NULL */, double *violation /* [n] or NULL */);
 
+/* Hyperparameter importance from the resident posterior (tpe.importance;
+ * no reference counterpart -- Optuna's PED-ANOVA evaluator is the nearest).
+ * For each of the n_sel selected labels, with l / g its below / above mixture,
+ * alpha the share of its observations among the good trials and the cells
+ * (x_j, w_j), j in [cell_off[s], cell_off[s + 1]):
+ *     p(x) = alpha l(x) + (1 - alpha) g(x),   m(x) = alpha l(x) / p(x),
+ *     v[s] = sum_j w_j p(x_j) (m(x_j) - alpha)^2
+ * -- the variance, under the density of the label's observed values, of the
+ * model's probability that a trial with that value is good.  The lpdfs at x_j
+ * are tpe_score's, bit for bit; a cell of a quantized label with merge[s] > 1
+ * takes the quantized lpdf with the step merge[s] q (the mass of merge[s]
+ * consecutive support values around their mean x_j).  Per cell, from lb =
+ * log l(x_j) and la = log g(x_j), in this order and without cancellation:
+ *     d = lb - la
+ *     d <= 0:  t = expm1(d),   dev =  alpha (1 - alpha) t / (1 + alpha t)
+ *     d >  0:  t = expm1(-d),  dev = -alpha (1 - alpha) t / (1 + (1 - alpha) t)
+ *     term = w_j (alpha exp(lb) + (1 - alpha) exp(la)) dev^2
+ * a cell with lb = la = -inf contributes 0, a NaN lpdf makes v[s] NaN.  The
+ * terms of 256 consecutive cells are added in a fixed order and a label's
+ * partial sums in ascending order: v[s] is the same bits on every run, and
+ * whichever other labels the call lists, in whatever order.  v[s] = 0 for a
+ * label without cells.  lb / la (both or neither): the two lpdf planes, in the
+ * layout of x.  The call runs on the resident posterior however it was set or
+ * built and changes neither it nor the pool; one stream synchronisation; a
+ * multi-device context runs it on its primary device (not a label-sharded
+ * one).  TPE_F64 contexts.
+ * TPE_ERR_ARG (tpe_last_error names the function): no posterior; a NULL
+ * argument other than lb / la; a label out of range or listed twice; alpha
+ * outside (0, 1); merge < 1, or merge != 1 on a label that is not quantized;
+ * cell_off[0] != 0 or decreasing offsets.  TPE_ERR_VALUE: a categorical
+ * label's point that is not an integer in [0, upper); a quantized LGMM1
+ * label's cell whose upper end is negative.  On an error the outputs are
+ * untouched. */
+int tpe_importance(tpe_ctx *ctx, int32_t n_sel, const int32_t *labels,
+                   const int64_t *cell_off /* [n_sel + 1] */, const double *x, const double *w,
+                   const int32_t *merge /* [n_sel] */, const double *alpha /* [n_sel] */,
+                   double *v /* [n_sel] */, double *lb, double *la /* [cell_off[n_sel]] or NULL */);
+
 /* Score a caller-supplied candidate set for one resident label (the parity
  * entry point: identical candidates in, both lpdf vectors and the winner
  * out).  lpdf_below / lpdf_above may be NULL. */
