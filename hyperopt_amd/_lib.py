@@ -65,6 +65,7 @@ TPE_OPT_JOINT_CAP = 26
 
 TPE_JOINT_STREAM = 0x7FFFFFFF
 TPE_JOINT_MAX_GROUPS = 64
+TPE_INTERACTIONS_MAX_GRID = 1024
 TPE_POOL_STREAM = 0x7FFFFFBF
 TPE_JOINT_FLAG_TIE = 1
 TPE_JOINT_FLAG_CATEGORY = 2
@@ -198,6 +199,9 @@ SIGNATURES = {
     'tpe_mo_keys': (ctypes.c_int, [_P, _P, _I64, _I32, _P, _P, _P]),
     'tpe_mo_keys_constrained': (ctypes.c_int, [_P, _P, _I64, _I32, _P, _I32, _P, _P, _P, _P]),
     'tpe_importance': (ctypes.c_int, [_P, _I32, _P, _P, _P, _P, _P, _P, _P, _P, _P]),
+    'tpe_interactions': (ctypes.c_int, [_P, _I32, _I32, _P, _P, _P, _P, _I64, _P, _P, _P, _I64, _P, _P, _P,
+                                        ctypes.c_double, _I32, _P, _P, _P, _P, _P]),
+    'tpe_interactions_last_pair_ms': (ctypes.c_int, [_P, ctypes.POINTER(ctypes.c_float)]),
 }
 
 _lib = None

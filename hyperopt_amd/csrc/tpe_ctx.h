@@ -670,6 +670,9 @@ struct tpe_ctx {
     // the reusable buffers of tpe_importance (tpe_importance.hip)
     std::shared_ptr<void> imp;
 
+    // the reusable buffers of tpe_interactions (tpe_interaction.hip)
+    std::shared_ptr<void> inter;
+
     int fail(int code, const std::string& m) {
         err = m;
         return code;

@@ -848,6 +848,46 @@ class Engine(object):
         return (v, [lb[off[s]:off[s + 1]] for s in range(len(labels))],
                 [la[off[s]:off[s + 1]] for s in range(len(labels))])
 
+    def interactions(self, y, h, low, high, below, above, alpha, pairs, want_planes=False):
+        """The pairwise interaction sums of one joint group (tpe_interactions):
+        y [D, n_grid] the labels' cell midpoints and h [D] the cell widths
+        (posterior.interaction_axis), low / high [D] the working-space bounds
+        (NaN: not bounded); below / above the sides' (W [K], mu [K, D], sigma
+        [K, D]) (posterior.joint_mixture); alpha in (0, 1); pairs [P, 2]
+        label positions.  Returns (H, V) [P] float64 -- the interaction and
+        the joint importance of each pair; want_planes adds the pairs' joint
+        densities (L, G) [P, n_grid, n_grid].  Needs no resident posterior."""
+        y = _f64(y)
+        if y.ndim != 2:
+            raise ValueError('interactions: y must be [labels, n_grid]')
+        D, n_grid = y.shape
+        h, low, high = _f64(h).ravel(), _f64(low).ravel(), _f64(high).ravel()
+        if len(h) != D or len(low) != D or len(high) != D:
+            raise ValueError('interactions: one h, low and high per label')
+        sides = []
+        for side in (below, above):
+            w, mu, sig = _f64(side[0]).ravel(), _f64(side[1]), _f64(side[2])
+            if mu.shape != (len(w), D) or sig.shape != mu.shape:
+                raise ValueError('interactions: a side is (W [K], mu [K, D], sigma [K, D])')
+            sides.append((w, mu, sig))
+        pairs = np.ascontiguousarray(pairs, dtype=np.int32).reshape(-1, 2)
+        P = len(pairs)
+        H, V = np.zeros(P), np.zeros(P)
+        L = np.empty((P, n_grid, n_grid)) if want_planes else None
+        G = np.empty((P, n_grid, n_grid)) if want_planes else None
+        (wb, mub, sigb), (wa, mua, siga) = sides
+        self._check(self.lib.tpe_interactions(self.h, D, n_grid, _ptr(y), _ptr(h), _ptr(low), _ptr(high),
+                                              len(wb), _ptr(wb), _ptr(mub), _ptr(sigb),
+                                              len(wa), _ptr(wa), _ptr(mua), _ptr(siga),
+                                              float(alpha), P, _ptr(pairs), _ptr(H), _ptr(V), _ptr(L), _ptr(G)))
+        return (H, V, L, G) if want_planes else (H, V)
+
+    def interactions_last_pair_ms(self):
+        """Device ms of the pair kernel in the last interactions call."""
+        ms = ctypes.c_float()
+        self._check(self.lib.tpe_interactions_last_pair_ms(self.h, ctypes.byref(ms)))
+        return ms.value
+
     def last_timing(self):
         a, b = ctypes.c_float(), ctypes.c_float()
         self._check(self.lib.tpe_last_timing(self.h, ctypes.byref(a), ctypes.byref(b)))

@@ -307,6 +307,24 @@ def label_posterior(label, kind, args, below, above, prior_weight):
 IMPORTANCE_TAIL = 4.0   # prior sigmas an unbounded label's cells reach past its prior mean and observations
 
 
+def _cell_range(kind, args, obs):
+    """[a, b] of a continuous label's cells in the working space (log x for
+    the log kinds): the bounds, or IMPORTANCE_TAIL prior sigmas past the prior
+    mean and the observations."""
+    if kind in ('uniform', 'quniform', 'loguniform', 'qloguniform'):
+        return float(args['low']), float(args['high'])
+    mu, sigma = float(args['mu']), float(args['sigma'])
+    a = b = mu
+    t = np.asarray(obs, dtype=float)
+    if len(t):
+        if kind == 'lognormal':
+            t = np.log(t)
+        elif kind == 'qlognormal':
+            t = np.log(np.maximum(t, EPS))
+        a, b = min(mu, float(np.min(t))), max(mu, float(np.max(t)))
+    return a - IMPORTANCE_TAIL * sigma, b + IMPORTANCE_TAIL * sigma
+
+
 def importance_cells(kind, args, obs, n_grid):
     """The cells tpe.importance sums one label's terms over (DESIGN.md
     section 6b, "Hyperparameter importance"): (x, w, merge) -- the point each
@@ -334,19 +352,7 @@ def importance_cells(kind, args, obs, n_grid):
         raise ValueError('unknown distribution %r' % kind)
     log = kind in ('loguniform', 'qloguniform', 'lognormal', 'qlognormal')
     quant = kind in ('quniform', 'qloguniform', 'qnormal', 'qlognormal')
-    if kind in ('uniform', 'quniform', 'loguniform', 'qloguniform'):
-        a, b = float(args['low']), float(args['high'])
-    else:
-        mu, sigma = float(args['mu']), float(args['sigma'])
-        a = b = mu
-        t = np.asarray(obs, dtype=float)
-        if len(t):
-            if kind == 'lognormal':
-                t = np.log(t)
-            elif kind == 'qlognormal':
-                t = np.log(np.maximum(t, EPS))
-            a, b = min(mu, float(np.min(t))), max(mu, float(np.max(t)))
-        a, b = a - IMPORTANCE_TAIL * sigma, b + IMPORTANCE_TAIL * sigma
+    a, b = _cell_range(kind, args, obs)
     if not quant:
         h = (b - a) / n_grid
         mid = a + (np.arange(n_grid) + 0.5) * h
@@ -372,6 +378,22 @@ JOINT_KINDS = ('uniform', 'loguniform', 'normal', 'lognormal')
 JOINT_QUANT_KINDS = ('quniform', 'qloguniform', 'qnormal', 'qlognormal')
 # and with categorical=True (hp.randint and hp.choice: 'randint'; hp.pchoice: 'categorical')
 JOINT_CAT_KINDS = ('randint', 'categorical')
+
+
+def interaction_axis(kind, args, obs, n_grid):
+    """The axis tpe.interactions lays over one label of a pair (DESIGN.md
+    section 6b, "Pairwise interactions"): (y, h) -- the midpoints of n_grid
+    equal cells of width h in the working space, over the range
+    importance_cells gives the kind.  JOINT_KINDS only."""
+    n_grid = int(n_grid)
+    if n_grid < 1:
+        raise ValueError('n_grid must be at least 1')
+    if kind not in JOINT_KINDS:
+        raise ValueError('%r labels have no interaction axis' % (kind,))
+    with np.errstate(divide='ignore', invalid='ignore'):
+        a, b = _cell_range(kind, args, obs)
+        h = (b - a) / n_grid
+        return a + (np.arange(n_grid) + 0.5) * h, h
 
 
 def joint_cat_prior(kind, args):

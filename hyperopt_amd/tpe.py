@@ -54,7 +54,9 @@ suggestion).
 `importance(space, trials)` (not in the reference) tells which hyperparameters
 mattered: per label the variance of the model's good-trial probability under
 the label's observed values, from the same Parzen mixtures, summed on the
-device (`Engine.importance`).
+device (`Engine.importance`).  `interactions(space, trials)` tells which
+pairs of them interact: how far the joint model of two labels departs from
+the product of their one-label models (`Engine.interactions`).
 """
 import itertools
 import logging
@@ -842,6 +844,62 @@ def pareto_front(trials, objectives, constraints=None):
     return sorted((d for d, b, vi in zip(docs, by, v) if b == 0 and vi == 0), key=lambda d: d['tid'])
 
 
+def _quantile_split(fn, space, trials, quantile, n_grid, max_grid, device, objectives, constraints, labels=None):
+    """The common front of importance and interactions: the arguments checked
+    (n_grid an integer in [1, max_grid], max_grid None: no upper end; labels,
+    if given, names of joint-kind labels of the space), the domain (keyed by
+    objectives / constraints), the history gathered and its complete trials
+    split at the quantile.  Returns (specs, names, obs, tids, done,
+    splitter): obs as history.gather returns it, tids the complete trials',
+    done their mask over the gathered ones."""
+    objectives = check_objectives(objectives)
+    constraints = check_constraints(constraints, objectives)
+    if isinstance(quantile, bool) or not isinstance(quantile, (int, float, np.integer, np.floating)) \
+            or not 0.0 < quantile < 1.0:
+        raise ValueError('%s: quantile must lie in (0, 1), got %r' % (fn, quantile))
+    if isinstance(n_grid, bool) or not isinstance(n_grid, (int, np.integer)) or n_grid < 1 \
+            or (max_grid is not None and n_grid > max_grid):
+        raise ValueError('%s: n_grid must be an integer %s, got %r'
+                         % (fn, '>= 1' if max_grid is None else 'in [1, %d]' % max_grid, n_grid))
+    if labels is not None and (isinstance(labels, str) or not all(isinstance(k, str) for k in labels)):
+        raise ValueError('%s: labels must be a list of label names' % fn)
+    if not _labels.is_node(space) and hasattr(space, 'expr'):   # a Domain
+        domain = space
+    else:
+        from .base import Domain
+        domain = Domain(None, space)
+    specs = specs_of(domain)
+    names = list(specs)
+    for k in labels or ():
+        if k not in specs:
+            raise ValueError('%s: unknown label %r' % (fn, k))
+        if specs[k].kind not in _post.JOINT_KINDS:
+            raise ValueError('%s: label %r is of kind %r, not one of %r' % (fn, k, specs[k].kind, _post.JOINT_KINDS))
+
+    def engine():
+        return _engine.get_engine(device, 'f64', 'importance')
+    if objectives is not None or constraints is not None:
+        src = trials.trials
+        check_from = _history.has_from_tid(trials, names)
+        if constraints is None:
+            docs, F = objective_rows(src, objectives, domain, check_from=check_from)
+            G = None
+        else:
+            docs, F, G = objective_rows(src, objectives or ('loss',), domain, check_from=check_from,
+                                        constraints=constraints)
+        if len(docs) < 2:
+            raise ValueError('%s: needs at least 2 complete trials, got %d' % (fn, len(docs)))
+        domain = _KeyedDomain(domain, docs, objective_keys(F, 'auto', engine, G=G), src)
+    tids, losses, obs = _history.gather(domain, trials, names)
+    done = losses < np.inf                       # (pending and failed trials carry +inf)
+    tids, losses = tids[done], losses[done]
+    n = len(tids)
+    if n < 2:
+        raise ValueError('%s: needs at least 2 complete trials, got %d' % (fn, n))
+    splitter = _post.Splitter(tids, losses, 0.0, n_below=int(np.ceil(quantile * n)))
+    return specs, names, obs, tids, done, splitter
+
+
 def importance(space, trials, quantile=0.1, n_grid=4096, prior_weight=_default_prior_weight,
                normalize=True, curves=False, device=0, objectives=None, constraints=None):
     """Which hyperparameters mattered (not in the reference; Optuna's
@@ -885,42 +943,9 @@ def importance(space, trials, quantile=0.1, n_grid=4096, prior_weight=_default_p
     ValueError, before any engine is touched: quantile outside (0, 1), n_grid
     not an integer >= 1, fewer than 2 complete trials, and what
     check_objectives, check_constraints and objective_rows refuse."""
-    objectives = check_objectives(objectives)
-    constraints = check_constraints(constraints, objectives)
-    if isinstance(quantile, bool) or not isinstance(quantile, (int, float, np.integer, np.floating)) \
-            or not 0.0 < quantile < 1.0:
-        raise ValueError('importance: quantile must lie in (0, 1), got %r' % (quantile,))
-    if isinstance(n_grid, bool) or not isinstance(n_grid, (int, np.integer)) or n_grid < 1:
-        raise ValueError('importance: n_grid must be an integer >= 1, got %r' % (n_grid,))
-    if not _labels.is_node(space) and hasattr(space, 'expr'):   # a Domain
-        domain = space
-    else:
-        from .base import Domain
-        domain = Domain(None, space)
-    specs = specs_of(domain)
-    names = list(specs)
-
-    def engine():
-        return _engine.get_engine(device, 'f64', 'importance')
-    if objectives is not None or constraints is not None:
-        src = trials.trials
-        check_from = _history.has_from_tid(trials, names)
-        if constraints is None:
-            docs, F = objective_rows(src, objectives, domain, check_from=check_from)
-            G = None
-        else:
-            docs, F, G = objective_rows(src, objectives or ('loss',), domain, check_from=check_from,
-                                        constraints=constraints)
-        if len(docs) < 2:
-            raise ValueError('importance: needs at least 2 complete trials, got %d' % len(docs))
-        domain = _KeyedDomain(domain, docs, objective_keys(F, 'auto', engine, G=G), src)
-    tids, losses, obs = _history.gather(domain, trials, names)
-    done = losses < np.inf                       # (pending and failed trials carry +inf)
-    tids, losses = tids[done], losses[done]
+    specs, names, obs, tids, done, splitter = _quantile_split(
+        'importance', space, trials, quantile, n_grid, None, device, objectives, constraints)
     n = len(tids)
-    if n < 2:
-        raise ValueError('importance: needs at least 2 complete trials, got %d' % n)
-    splitter = _post.Splitter(tids, losses, 0.0, n_below=int(np.ceil(quantile * n)))
     posts, sel, cells, alphas, active = [], [], [], [], np.zeros(len(names))
     for li, (label, s) in enumerate(specs.items()):
         oi, ov = obs[label]
@@ -937,7 +962,7 @@ def importance(space, trials, quantile=0.1, n_grid=4096, prior_weight=_default_p
     raw = np.zeros(len(names))
     planes = None
     if sel:
-        eng = engine()
+        eng = _engine.get_engine(device, 'f64', 'importance')
         eng.set_posterior(*_post.pack(posts))
         out = eng.importance(sel, cells, alphas, want_planes=curves)
         v, planes = (out[0], out[1:]) if curves else (out, None)
@@ -960,6 +985,87 @@ def importance(space, trials, quantile=0.1, n_grid=4096, prior_weight=_default_p
             m = np.where(p > 0, lik / p, alphas[k])
         views[names[li]] = (x, w, p, m)
     return result, views
+
+
+def interactions(space, trials, quantile=0.1, n_grid=256, prior_weight=_default_prior_weight, device=0,
+                 labels=None, joint=False, objectives=None, constraints=None):
+    """Which pairs of hyperparameters interact (not in the reference):
+    {(label_d, label_e): interaction}, d before e in the space's order, sorted
+    descending, ties in pair order, NaN pairs last.
+
+    The complete trials are split at the quantile as importance splits them.
+    The labels of a dense continuous kind (posterior.JOINT_KINDS) are grouped
+    by the exact set of complete trials they are observed in; a pair is two
+    labels of one group that has nb >= 1 good and na >= 1 other trials, n_g =
+    nb + na, alpha = nb / n_g.  Its two joint mixtures are
+    posterior.joint_mixture's of the two labels with the Scott-rule bandwidth,
+    L and G their densities on the grid of the two labels'
+    posterior.interaction_axis (n_grid cells each, in the working space), L_d,
+    L_e, G_d, G_e the marginals, and per cell
+        p = alpha L + (1 - alpha) G,    m = alpha L / p,
+        m_ind = alpha L_d L_e / (alpha L_d L_e + (1 - alpha) G_d G_e)
+    -- the joint model's good-trial probability and the one independent TPE's
+    product of one-label models gives.  The pair's interaction is
+        H = h_d h_e sum_cells p (m - m_ind)^2,      returned: (n_g / n) H
+    (0 when both sides factorise over the two labels), raw like
+    importance(normalize=False)'s (n_d / n) V_d and comparable with it.
+    joint=True returns (interactions, {pair: (n_g / n) V}) with V = h_d h_e
+    sum_cells p (m - alpha)^2, the joint importance of the pair.  A pair whose
+    sums are NaN (a non-positive observation of a log kind) keeps NaN.
+
+    labels: only pairs among these labels.  One Engine.interactions call per
+    group sums every pair on the device (matrix products over the mixtures'
+    components; DESIGN.md section 6b, "Pairwise interactions"), on importance's
+    context (engine.get_engine(device, 'f64', 'importance')).  A space without
+    such a pair returns {}.
+
+    ValueError, before any engine is touched: quantile outside (0, 1), n_grid
+    not an integer in [1, 1024], fewer than 2 complete trials, a name in
+    labels that is unknown or not of a joint kind, and what check_objectives,
+    check_constraints and objective_rows refuse."""
+    specs, names, obs, tids, done, splitter = _quantile_split(
+        'interactions', space, trials, quantile, n_grid, _engine.L.TPE_INTERACTIONS_MAX_GRID, device, objectives,
+        constraints, labels)
+    n = len(tids)
+    chosen = [k for k in names if specs[k].kind in _post.JOINT_KINDS and (labels is None or k in labels)]
+    if not done.all():
+        obs = dict(obs)
+        for k in chosen:
+            oi, ov = obs[k]
+            keep = np.isin(oi, tids)
+            obs[k] = (oi[keep], ov[keep])
+    groups = {}
+    for k in chosen:
+        groups.setdefault(np.asarray(obs[k][0], dtype=np.int64).tobytes(), []).append(k)
+    found = []   # (position of d, position of e, (n_g / n) H, (n_g / n) V)
+    for g in groups.values():
+        nb, na = (len(o) for o in splitter.split(*obs[g[0]]))
+        if len(g) < 2 or nb < 1 or na < 1:
+            continue
+        # a label's columns are the same in every pair of the group: the first
+        # label's from its pair with the second, every other one's from its pair
+        # with the first
+        mixes = [_post.joint_mixture([specs[g[0]], specs[k]], obs, splitter, prior_weight, bandwidth='scott')
+                 for k in g[1:]]
+        below = (mixes[0].wb, np.column_stack([mixes[0].mub[:, 0]] + [m.mub[:, 1] for m in mixes]),
+                 np.column_stack([mixes[0].sigb[:, 0]] + [m.sigb[:, 1] for m in mixes]))
+        above = (mixes[0].wa, np.column_stack([mixes[0].mua[:, 0]] + [m.mua[:, 1] for m in mixes]),
+                 np.column_stack([mixes[0].siga[:, 0]] + [m.siga[:, 1] for m in mixes]))
+        axes = [_post.interaction_axis(specs[k].kind, specs[k].args, obs[k][1], n_grid) for k in g]
+        pri = [_post.joint_prior(specs[k].kind, specs[k].args) for k in g]
+        pairs = list(itertools.combinations(range(len(g)), 2))
+        H, V = _engine.get_engine(device, 'f64', 'importance').interactions([a[0] for a in axes], [a[1] for a in axes],
+                                     [p.low if p.bounded else np.nan for p in pri],
+                                     [p.high if p.bounded else np.nan for p in pri],
+                                     below, above, nb / (nb + na), pairs)
+        share = (nb + na) / n
+        found += [(names.index(g[d]), names.index(g[e]), share * H[i], share * V[i])
+                  for i, (d, e) in enumerate(pairs)]
+    found.sort(key=lambda f: (bool(np.isnan(f[2])), 0.0 if np.isnan(f[2]) else -f[2], f[0], f[1]))
+    result = {(names[d], names[e]): float(hv) for d, e, hv, _ in found}
+    if not joint:
+        return result
+    return result, {(names[d], names[e]): float(vv) for d, e, _, vv in found}
 
 
 def suggest(new_ids, domain, trials, seed,

@@ -881,6 +881,65 @@ int tpe_importance(tpe_ctx *ctx, int32_t n_sel, const int32_t *labels,
                    const int32_t *merge /* [n_sel] */, const double *alpha /* [n_sel] */,
                    double *v /* [n_sel] */, double *lb, double *la /* [cell_off[n_sel]] or NULL */);
 
+/* Pairwise interactions of the labels of one joint group (tpe.interactions;
+ * no reference counterpart).  The call is given the group's two joint
+ * mixtures -- per side K components (0: the prior) with weights w [K], means
+ * mu [K][n_dim] and sigmas sig [K][n_dim] in the labels' working space
+ * (posterior.joint_mixture) -- and per label an axis of n_grid equal cells:
+ * the midpoints y [n_dim][n_grid], the width h and the bounds low / high of
+ * the working space (NaN: the label is not bounded).  With
+ *     u_kd(y) = exp(-((y - mu_kd) / s_kd)^2 / 2) / (s_kd sqrt(2 pi))
+ *     m_kd    = Phi((high_d - mu_kd) / s_kd) - Phi((low_d - mu_kd) / s_kd), or 1
+ * (from the two tails on the side of the mean the interval lies on), per side
+ * and pair (d, e):
+ *     A      = sum_k (W_k m_kd) m_ke
+ *     L[i,j] = (sum_k (W_k u_kd(y_i)) u_ke(y_j)) / A       (G: the above side)
+ *     L_d[i] = (sum_k (W_k u_kd(y_i)) m_ke) / A            (L_e, G_d, G_e likewise)
+ * -- the sums over k are matrix products, run on the matrix cores -- and per
+ * cell, in this order, every operation rounded on its own, with
+ * om = 1 - alpha and ao = alpha om:
+ *     aL = alpha L;  p = aL + om G;             p == 0: the cell contributes 0
+ *     dev = (ao (L - G)) / p                    (= m - alpha, m = alpha L / p)
+ *     tv  = p (dev dev)
+ *     qi = alpha (L_d L_e);  ri = om (G_d G_e);  den = qi + ri
+ *     den == 0: dif = dev                       (m_ind = alpha)
+ *     else  mi = qi / den;  ci = ri / den       (m_ind, 1 - m_ind)
+ *           lo  = log L - log G
+ *           loi = (log L_d + log L_e) - (log G_d + log G_e)
+ *           lo or loi not finite:  dif = aL / p - mi
+ *           else dl = lo - loi
+ *             dl <= 0: t = expm1(dl);   dif =  ((mi ci) t) / (1 + mi t)
+ *             dl >  0: t = expm1(-dl);  dif = -((mi ci) t) / (1 + ci t)
+ *     th  = p (dif dif)
+ *     V[p] = (h_d h_e) sum_ij tv      the joint importance of the pair
+ *     H[p] = (h_d h_e) sum_ij th      the interaction: the variance the product
+ *                                     of the one-label models leaves out
+ * A NaN anywhere makes the pair's V and H NaN.  Every sum has a fixed order and
+ * a partial sum belongs to one 64 x 64 tile of one pair: V and H are the same
+ * bits on every run, alone or among other pairs, in any order.  L / G (both or
+ * neither): the planes [n_pairs][n_grid][n_grid].  The call needs no resident
+ * posterior and changes neither it nor the pool; one stream synchronisation; a
+ * multi-device context runs it on its primary device.  TPE_F64 contexts.
+ * TPE_ERR_ARG (tpe_last_error names the function): a NULL argument other than
+ * L / G; n_dim < 2; n_grid outside [1, TPE_INTERACTIONS_MAX_GRID]; Kb or Ka
+ * below 2; alpha outside (0, 1); a pair index out of range or a pair of a
+ * label with itself; a sigma that is not positive and finite.  On an error the
+ * outputs are untouched. */
+#define TPE_INTERACTIONS_MAX_GRID 1024
+int tpe_interactions(tpe_ctx *ctx, int32_t n_dim, int32_t n_grid,
+                     const double *y /* [n_dim][n_grid] */, const double *h /* [n_dim] */,
+                     const double *low, const double *high /* [n_dim], NaN: unbounded */,
+                     int64_t Kb, const double *wb, const double *mub, const double *sigb,
+                     int64_t Ka, const double *wa, const double *mua, const double *siga,
+                     double alpha, int32_t n_pairs, const int32_t *pairs /* [n_pairs][2] */,
+                     double *H, double *V /* [n_pairs] */,
+                     double *L, double *G /* [n_pairs][n_grid][n_grid] or NULL */);
+
+/* Device time (ms, HIP events on the context stream) of the pair kernel --
+ * the matrix products and the per-cell epilogue of every pair -- in the last
+ * tpe_interactions call that had pairs.  TPE_ERR_ARG before such a call. */
+int tpe_interactions_last_pair_ms(tpe_ctx *ctx, float *ms);
+
 /* Score a caller-supplied candidate set for one resident label (the parity
  * entry point: identical candidates in, both lpdf vectors and the winner
  * out).  lpdf_below / lpdf_above may be NULL. */
