@@ -28,7 +28,8 @@ SOURCES = [os.path.join(HERE, 'csrc', 'tpe_engine.hip'),
            os.path.join(HERE, 'csrc', 'tpe_pool.hip'),
            os.path.join(HERE, 'csrc', 'tpe_mo.hip'),
            os.path.join(HERE, 'csrc', 'tpe_importance.hip'),
-           os.path.join(HERE, 'csrc', 'tpe_interaction.hip')]
+           os.path.join(HERE, 'csrc', 'tpe_interaction.hip'),
+           os.path.join(HERE, 'csrc', 'tpe_cmodel.hip')]
 DEPS = SOURCES + [os.path.join(HERE, 'csrc', 'tpe_device.h'),
                   os.path.join(HERE, 'csrc', 'tpe_ctx.h'),
                   os.path.join(HERE, 'csrc', 'tpe_exp_table.h'),
@@ -37,6 +38,13 @@ TARGET = os.path.join(HERE, 'libhyperopt_tpe.so')
 
 FLAGS = ['--offload-arch=' + ARCH, '-O3', '-std=c++17', '-fPIC', '-shared',
          '-Wall', '-Wno-unused-function', '-I' + os.path.join(REPO, 'include')]
+# per-unit additions.  tpe_cmodel.hip: the compiler may not form packed-fp32
+# instructions (v_pk_add/mul/fma_f32) in new units -- the existing units use
+# them on purpose in one place, the fp32 screen, whose results carry an error
+# bound and are re-scored in fp64 (tpe_device.h).
+# The unit is fp64 throughout, so today the flag changes no instruction and no
+# resource figure; it keeps a later fp32 helper from being packed silently.
+EXTRA_FLAGS = {'tpe_cmodel.hip': ['-Xclang', '-target-feature', '-Xclang', '-packed-fp32-ops']}
 
 
 def source_hash(deps=DEPS):
@@ -48,6 +56,8 @@ def source_hash(deps=DEPS):
             h.update(f.read())
     # flags without the tree's absolute location (the GPU box unpacks it elsewhere)
     h.update(' '.join(f for f in FLAGS if not f.startswith('-I')).encode())
+    for name in sorted(EXTRA_FLAGS):
+        h.update((name + ' ' + ' '.join(EXTRA_FLAGS[name])).encode())
     return h.hexdigest()[:16]
 
 
@@ -77,7 +87,8 @@ def build_engine(force=False, verbose=True):
         objs, procs = [], []
         for src in SOURCES:
             obj = os.path.join(tmp, os.path.basename(src) + '.o')
-            cmd = [HIPCC] + [f for f in flags if f != '-shared'] + ['-c', '-o', obj, src]
+            cmd = ([HIPCC] + [f for f in flags if f != '-shared'] + EXTRA_FLAGS.get(os.path.basename(src), [])
+                   + ['-c', '-o', obj, src])
             if verbose:
                 print(' '.join(cmd), flush=True)
             procs.append(subprocess.Popen(cmd))

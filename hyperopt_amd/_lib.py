@@ -67,6 +67,9 @@ TPE_JOINT_STREAM = 0x7FFFFFFF
 TPE_JOINT_MAX_GROUPS = 64
 TPE_INTERACTIONS_MAX_GRID = 1024
 TPE_POOL_STREAM = 0x7FFFFFBF
+TPE_CMODEL_MAX = 8
+TPE_CMODEL_STREAM = 0x7FFF0000
+TPE_CMODEL_STREAM_SPAN = 4096
 TPE_JOINT_FLAG_TIE = 1
 TPE_JOINT_FLAG_CATEGORY = 2
 TPE_JOINT_FLAG_COUNT = 4
@@ -202,6 +205,10 @@ SIGNATURES = {
     'tpe_interactions': (ctypes.c_int, [_P, _I32, _I32, _P, _P, _P, _P, _I64, _P, _P, _P, _I64, _P, _P, _P,
                                         ctypes.c_double, _I32, _P, _P, _P, _P, _P]),
     'tpe_interactions_last_pair_ms': (ctypes.c_int, [_P, ctypes.POINTER(ctypes.c_float)]),
+    'tpe_cmodel_set': (ctypes.c_int, [_P, _I32, _P, _I32, _P, _P, _P, _I64]),
+    'tpe_cmodel_clear': (ctypes.c_int, [_P]),
+    'tpe_cmodel_score': (ctypes.c_int, [_P, _I32, _P, _I64, _P, _P, _P, _P]),
+    'tpe_cmodel_suggest_batch': (ctypes.c_int, [_P, _U64, _P, _I32, _I64, _P, _P]),
 }
 
 _lib = None

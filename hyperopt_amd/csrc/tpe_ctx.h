@@ -673,6 +673,9 @@ struct tpe_ctx {
     // the reusable buffers of tpe_interactions (tpe_interaction.hip)
     std::shared_ptr<void> inter;
 
+    // the constraint models and the buffers of their round (tpe_cmodel.hip)
+    std::shared_ptr<void> cmodel;
+
     int fail(int code, const std::string& m) {
         err = m;
         return code;

@@ -848,6 +848,61 @@ class Engine(object):
         return (v, [lb[off[s]:off[s + 1]] for s in range(len(labels))],
                 [la[off[s]:off[s + 1]] for s in range(len(labels))])
 
+    # -- constraint densities (c-TPE) -----------------------------------------
+    def cmodel_set(self, k, descs, weights, mus, sigmas, skip=()):
+        """Constraint model k in [1, 8] beside the resident posterior
+        (tpe_cmodel_set): the arguments of set_posterior, e.g.
+        posterior.pack's; the labels listed in `skip` (indices) are given no
+        mixture -- the model is left out of their rounds."""
+        descs = np.array(descs, dtype=DESC_DTYPE)
+        for l in skip:
+            descs[int(l)]['n_below'] = 0
+            descs[int(l)]['n_above'] = 0
+        w, m, s = _f64(weights), _f64(mus), _f64(sigmas)
+        self._check(self.lib.tpe_cmodel_set(self.h, int(k), _ptr(descs), len(descs), _ptr(w), _ptr(m), _ptr(s),
+                                            len(w)))
+
+    def cmodel_clear(self):
+        self._check(self.lib.tpe_cmodel_clear(self.h))
+
+    @staticmethod
+    def _cmodel_gammas(gammas, rows):
+        g = np.ones((rows, L.TPE_CMODEL_MAX + 1))
+        gammas = _f64(gammas).reshape(rows, -1)
+        if gammas.shape[1] > g.shape[1]:
+            raise ValueError('gammas: at most %d models' % g.shape[1])
+        g[:, :gammas.shape[1]] = gammas
+        return g
+
+    def cmodel_score(self, label, cand, gammas, want_lpdf=True):
+        """The acquisition a of the constraint-density round on supplied
+        candidates of one label (tpe_cmodel_score): gammas[k] the share of
+        model k's below set, model 0 the resident posterior (missing entries:
+        1).  Returns (a [n], ll [9, n], lg [9, n]); row k model k's lpdfs,
+        NaN for a model that is not set or skips the label."""
+        cand = _f64(cand).ravel()
+        g = self._cmodel_gammas(gammas, 1)
+        a = np.empty(len(cand))
+        ll = np.empty((g.shape[1], len(cand))) if want_lpdf else None
+        lg = np.empty((g.shape[1], len(cand))) if want_lpdf else None
+        self._check(self.lib.tpe_cmodel_score(self.h, int(label), _ptr(cand), len(cand), _ptr(g), _ptr(a),
+                                              _ptr(ll), _ptr(lg)))
+        return a, ll, lg
+
+    def cmodel_suggest(self, seed, rounds, n_candidates, gammas):
+        """One constraint-density round per entry of `rounds` over every
+        resident label (tpe_cmodel_suggest_batch): gammas [n_labels, <= 9].
+        Returns RESULT_DTYPE records [len(rounds), n_labels]: index the
+        candidate index j (draw j % n of the label's (j // n)-th model),
+        value its value, score a, lpdf_below / lpdf_above model 0's."""
+        rounds = np.ascontiguousarray(np.asarray(rounds, dtype=np.uint32)).ravel()
+        n_labels = self._labels()
+        g = self._cmodel_gammas(gammas, n_labels)
+        out = np.empty(len(rounds) * n_labels, dtype=RESULT_DTYPE)
+        self._check(self.lib.tpe_cmodel_suggest_batch(self.h, int(seed) & 0xFFFFFFFFFFFFFFFF, _ptr(rounds),
+                                                      len(rounds), int(n_candidates), _ptr(g), _ptr(out)))
+        return out.reshape(len(rounds), n_labels)
+
     def interactions(self, y, h, low, high, below, above, alpha, pairs, want_planes=False):
         """The pairwise interaction sums of one joint group (tpe_interactions):
         y [D, n_grid] the labels' cell midpoints and h [D] the cell widths

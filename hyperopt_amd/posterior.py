@@ -199,6 +199,67 @@ def mo_keys(F, counts=None, G=None):
     return keys
 
 
+CMODEL_MAX = MO_MAX_CONSTRAINTS   # constraint models of one call (tpe_cmodel_set's k = 1 .. 8)
+
+
+def cmodel_split(G, gamma, F=None, gamma_cap=DEFAULT_LF):
+    """The below sets of the constraint models (tpe.suggest's
+    constraint_model='density'): G [n, K] the complete trials' constraint
+    rows (c <= 0 satisfied), F [n, M] their objective rows if given.  A row
+    with a NaN in G or F is not live.  Returns (live [n] bool, [(below,
+    gamma_k)] per constraint): below [n] bool marks the live trials with
+    G[:, k] <= 0 and gamma_k is their share of the live trials; when no live
+    trial satisfies the constraint the below set is the n_below_of(n_live,
+    gamma) live trials of smallest G[:, k] (stable: ties by trial order) and
+    gamma_k that count over n_live; when every live trial satisfies it -- or
+    none is live -- the entry is (None, 1.0): the model is skipped."""
+    G = np.asarray(G, dtype=np.float64)
+    if G.ndim != 2 or not 1 <= G.shape[1] <= CMODEL_MAX:
+        raise ValueError('G must be [n, 1 .. %d constraints]' % CMODEL_MAX)
+    live = ~np.isnan(G).any(axis=1)
+    if F is not None:
+        F = np.asarray(F, dtype=np.float64)
+        if F.ndim != 2 or len(F) != len(G):
+            raise ValueError('F and G must have a row for every trial')
+        live &= ~np.isnan(F).any(axis=1)
+    n_live = int(np.count_nonzero(live))
+    out = []
+    for k in range(G.shape[1]):
+        ok = live & (G[:, k] <= 0.0)
+        n_ok = int(np.count_nonzero(ok))
+        if n_live == 0 or n_ok == n_live:
+            out.append((None, 1.0))
+            continue
+        if n_ok == 0:
+            n_ok = max(1, min(n_below_of(n_live, gamma, gamma_cap), n_live))
+            idx = np.flatnonzero(live)
+            ok = np.zeros(len(G), dtype=bool)
+            ok[idx[np.argsort(G[idx, k], kind='stable')[:n_ok]]] = True
+        out.append((ok, n_ok / n_live))
+    return live, out
+
+
+def cmodel_acquisition(ll, lg, gammas):
+    """a [n] = sum_k f(gamma_k, lg_k - ll_k) over the rows of ll, lg [M', n]
+    in order (tpe_cmodel_score's rule, float64, every operation on its own):
+        f(gamma, t) = -log(gamma + (1 - gamma) exp(t))            t <= 0
+                    = -(t + log((1 - gamma) + gamma exp(-t)))     t >  0
+    A NaN t makes a NaN; the larger a is the better candidate."""
+    ll = np.atleast_2d(np.asarray(ll, dtype=np.float64))
+    lg = np.atleast_2d(np.asarray(lg, dtype=np.float64))
+    gammas = np.asarray(gammas, dtype=np.float64).ravel()
+    if ll.shape != lg.shape or len(gammas) != len(ll):
+        raise ValueError('ll, lg must be [M, n] with one gamma per row')
+    a = np.zeros(ll.shape[1])
+    with np.errstate(invalid='ignore', over='ignore', divide='ignore'):
+        for g, l, u in zip(gammas, ll, lg):
+            t = u - l
+            neg = -np.log(g + (1.0 - g) * np.exp(np.minimum(t, 0.0)))
+            pos = -(t + np.log((1.0 - g) + g * np.exp(-np.maximum(t, 0.0))))
+            a = a + np.where(np.isnan(t), np.nan, np.where(t <= 0.0, neg, pos))
+    return a
+
+
 def linear_forgetting_weights(n, lf):
     if n == 0:
         return np.asarray([])

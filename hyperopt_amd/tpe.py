@@ -662,6 +662,56 @@ def _joint_build(eng, domain, trials, specs, gathered, gamma, prior_weight, grou
     return groups
 
 
+class _ConstraintRows(object):
+    """What a constraint_model='density' call hands to the call it makes on
+    the objective's column: the complete trials' tids, their rows F, G and the
+    constraints' names."""
+    __slots__ = ('tids', 'F', 'G', 'names')
+
+    def __init__(self, tids, F, G, names):
+        self.tids, self.F, self.G, self.names = tids, F, G, names
+
+
+def _cmodel_round(eng, domain, trials, specs, gathered, cm, gamma, prior_weight, seed, ids, n_candidates,
+                  n_docs):
+    """The constraint-density round of tpe.suggest (constraint_model=
+    'density') on an engine whose resident posterior is the objective's:
+    the constraint models of cm (the complete trials' tids and rows F, G)
+    built on the host and uploaded, one Engine.cmodel_suggest for every id.
+    Returns the results [len(ids), n_labels]."""
+    t0 = time.time()
+    labels = list(specs)
+    _, _, obs = gathered or _history.gather(domain, trials, labels)
+    live, split = _post.cmodel_split(cm.G, gamma, F=cm.F)
+    live_tids = cm.tids[live]
+    n_below = _post.n_below_of(n_docs, gamma) if n_docs else 0
+    gam0 = min(1.0, max(n_below, 1) / max(n_docs, 1))
+    gammas = np.ones((len(labels), _post.CMODEL_MAX + 1))
+    gammas[:, 0] = gam0
+    eng.cmodel_clear()
+    used = []
+    for k, (below, gk) in enumerate(split, 1):
+        if below is None:
+            continue
+        b_tids = cm.tids[below]
+        a_tids = np.setdiff1d(live_tids, b_tids)
+        posts, skip = [], []
+        for li, (label, sp) in enumerate(specs.items()):
+            b, a = _post.split_label(obs[label][0], obs[label][1], b_tids, a_tids)
+            if not (len(b) and len(a)):
+                skip.append(li)
+            posts.append(_post.label_posterior(label, sp.kind, sp.args, b, a, prior_weight))
+        eng.cmodel_set(k, *_post.pack(posts), skip=skip)
+        gammas[:, k] = gk
+        used.append('%s %.3g' % (cm.names[k - 1], gk))
+    t1 = time.time()
+    res = eng.cmodel_suggest(seed, ids, n_candidates, gammas)
+    logger.info('tpe.suggest: constraint densities: objective gamma %.3g; %s; models built in %.1f ms, '
+                'round %.1f ms' % (gam0, ', '.join(used) or 'every constraint satisfied by every trial',
+                                   (t1 - t0) * 1e3, (time.time() - t1) * 1e3))
+    return res
+
+
 def check_objectives(objectives):
     """tpe.suggest's `objectives` after validation: a tuple of 1 to
     posterior.MO_MAX_OBJECTIVES distinct result-dict keys, None for None.
@@ -1076,8 +1126,8 @@ def suggest(new_ids, domain, trials, seed,
             linear_forgetting=_default_linear_forgetting,
             precision='f64', device=0, batch=False, posterior_builder='auto', devices=None,
             multivariate=False, group=False, joint_quantized=False, joint_categorical=False,
-            joint_bandwidth='neighbour', fixed=None, pool=None, pool_candidates=None, pool_replace=False,
-            constraints=None, objectives=None):
+            joint_bandwidth='neighbour', fixed=None, pool=None, pool_candidates=None, constraint_model='rank',
+            pool_replace=False, constraints=None, objectives=None):
     """tpe.py:823-916.  Past the startup phase one document for new_ids[0],
     like the reference; `batch` (not in the reference) asks for one document
     per new_id:
@@ -1297,6 +1347,30 @@ def suggest(new_ids, domain, trials, seed,
     the best feasible trial.  With constraints=None every call returns what
     it returned before.
 
+    constraint_model='density' (with `constraints`; default 'rank', the rule
+    above) models every constraint with a pair of Parzen estimators of its
+    own, as c-TPE does (Watanabe & Hutter 2023; DESIGN.md section 6b,
+    "Constraint densities").  Feasibility leaves the objective's order: model
+    0 is the posterior of the call without `constraints` (the loss, or the
+    `objectives` keys without G), gamma_0 = n_below / n_valid.  Constraint k
+    splits the complete trials without a NaN by G[:, k] <= 0
+    (posterior.cmodel_split; gamma_k the satisfying share; none satisfying:
+    the n_below least-violating ones; all satisfying: the model is skipped)
+    and each label's observations by that membership into
+    posterior.label_posterior's mixtures, built on the host; a label without
+    an observation on one side skips the constraint.  Every label draws
+    n_EI_candidates from the below mixture of each of its models and takes
+    the candidate with the largest a(x) = sum_k -log(gamma_k + (1 - gamma_k)
+    g_k(x) / l_k(x)) (posterior.cmodel_acquisition): the search is pulled to
+    where the objective is good AND every constraint is likely satisfied.
+    One batched device round answers all ids (Engine.cmodel_suggest).  It
+    composes with objectives, fixed, batch=True, batch='pending' and the
+    startup phase.  ValueError, before any engine is touched: another
+    constraint_model, 'density' without constraints, with multivariate=True,
+    with a pool, or with more than one device.  On a history where every
+    trial satisfies every constraint the documents are those of the call
+    without `constraints`.
+
     precision='f32' runs the exact fp64 path: a round draws every candidate
     and proves all but ~0.5 % of them out of the race from per-sub-bin score
     bounds before any lpdf is summed, so scoring the rest in fp32 would save
@@ -1307,6 +1381,22 @@ def suggest(new_ids, domain, trials, seed,
     objectives = check_objectives(objectives)   # (first: nothing else has run when it raises)
     constraints = check_constraints(constraints, objectives)
     pool_candidates = check_pool_candidates(pool_candidates, pool)
+    # (the call on the objective's column that a 'density' call makes of itself
+    # hands the constraint rows on in the keyword's place)
+    _cmodel = constraint_model if isinstance(constraint_model, _ConstraintRows) else None
+    if _cmodel is None and constraint_model not in ('rank', 'density'):
+        raise ValueError("constraint_model must be 'rank' or 'density'")
+    density = constraint_model == 'density'
+    if density:
+        if constraints is None:
+            raise ValueError("constraint_model='density' needs constraints")
+        if multivariate:
+            raise ValueError("constraint_model='density' with multivariate=True is not supported")
+        if pool is not None:
+            raise ValueError("constraint_model='density' with a pool is not supported")
+        if devices and len(list(devices)) > 1:
+            raise ValueError("constraint_model='density' with devices=%r: it runs on one device"
+                             % (list(devices),))
     pool_kw = {} if pool_candidates is None else dict(pool_candidates=pool_candidates)   # (None is not handed on)
     if objectives is not None or constraints is not None:
         # the call below on another loss column: the keys once, from all the
@@ -1323,6 +1413,21 @@ def suggest(new_ids, domain, trials, seed,
             keys = objective_keys(F, builder, engine)
             logger.info('tpe.suggest: %d objectives, %d complete trials ranked, %.1f ms' % (
                 len(objectives), len(docs), (time.time() - t0) * 1e3))
+        elif density:
+            # the objective's order without feasibility; the constraint rows
+            # travel to the round, which models each of them (_cmodel_round)
+            docs, F, G = objective_rows(src, objectives or ('loss',), domain, check_from=check_from,
+                                        constraints=constraints)
+            cm = _ConstraintRows(np.asarray([d['tid'] for d in docs], dtype=np.int64), F, G, constraints)
+            inner = domain if objectives is None else _KeyedDomain(domain, docs, objective_keys(F, builder, engine),
+                                                                   src)
+            fx = {'fixed': fixed} if fixed else {}
+            return suggest(new_ids, inner, trials, seed, prior_weight=prior_weight,
+                           n_startup_jobs=n_startup_jobs, n_EI_candidates=n_EI_candidates, gamma=gamma,
+                           linear_forgetting=linear_forgetting, precision=precision, device=device, batch=batch,
+                           posterior_builder=posterior_builder, devices=devices, group=group,
+                           joint_quantized=joint_quantized, joint_categorical=joint_categorical,
+                           joint_bandwidth=joint_bandwidth, pool_replace=pool_replace, constraint_model=cm, **fx)
         else:
             names = objectives or ('loss',)
             docs, F, G = objective_rows(src, names, domain, check_from=check_from, constraints=constraints)
@@ -1382,6 +1487,8 @@ def suggest(new_ids, domain, trials, seed,
               joint_categorical=joint_categorical, joint_bandwidth=joint_bandwidth)
     if fixed:   # (an empty one is not handed on)
         kw['fixed'] = fixed
+    if _cmodel is not None:
+        kw['constraint_model'] = _cmodel
     taken = []
     if pool is not None:
         kw.update(pool=pool, pool_replace=pool_replace, **pool_kw)
@@ -1466,11 +1573,18 @@ def suggest(new_ids, domain, trials, seed,
         logger.info('tpe.suggest: %d trials, %d labels, pool of %d (%d taken)%s, %.1f ms' % (
             n_docs, len(specs), len(pool), len(taken), how, (time.time() - t0) * 1e3))
         return rval
-    _, res = _resident_posterior(eng, domain, trials, specs, view, gathered, gamma, prior_weight,
-                                 posterior_builder, n_candidates=n_EI_candidates, n_rounds=len(ids),
-                                 round_call=round_call, info=info)
-    if res is None:
-        res = round_call()
+    if _cmodel is not None:
+        # model 0 as the plain call builds it, then one round over every model
+        _resident_posterior(eng, domain, trials, specs, view, gathered, gamma, prior_weight,
+                            posterior_builder, info=info)
+        res = _cmodel_round(eng, domain, trials, specs, gathered, _cmodel, gamma, prior_weight, seed, ids,
+                            n_EI_candidates, n_docs)
+    else:
+        _, res = _resident_posterior(eng, domain, trials, specs, view, gathered, gamma, prior_weight,
+                                     posterior_builder, n_candidates=n_EI_candidates, n_rounds=len(ids),
+                                     round_call=round_call, info=info)
+        if res is None:
+            res = round_call()
     # the joint groups are built on the device(s) when this call's univariate
     # posterior was: from the resident history (on several devices, label
     # shards or not, every device builds its replica of every group)

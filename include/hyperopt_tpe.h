@@ -843,6 +843,78 @@ int tpe_mo_keys_constrained(tpe_ctx *ctx, const double *objectives /* [n][n_obj]
                             double *keys /* [n] */, int32_t *dominated_by /* [n] or NULL */,
                             int32_t *dominates /* [n] or NULL */, double *violation /* [n] or NULL */);
 
+/* ---- constraint densities (c-TPE) -------------------------------------------
+ * tpe.suggest(constraints=..., constraint_model='density'): besides the
+ * resident posterior (model 0, the objective's) a context holds up to eight
+ * constraint models k = 1 .. 8, each a below / above pair of mixtures per
+ * label (below: the trials that satisfy constraint k).  No reference
+ * counterpart (Watanabe & Hutter 2023, c-TPE, is the method).
+ *
+ * With M' the non-skipped models of a label in ascending k, ll_k / lg_k the
+ * lpdfs tpe_score defines under model k's below / above mixture,
+ * t_k = lg_k - ll_k and gamma_k in (0, 1] the share of the model's below set:
+ *     a(x) = sum_{k in M'} f(gamma_k, t_k)                 (fp64, ascending k)
+ *     f(gamma, t) = -log(gamma + (1 - gamma) exp(t))           t <= 0
+ *                 = -(t + log((1 - gamma) + gamma exp(-t)))    t >  0
+ * -- the log of the relative density ratio l / (gamma l + (1 - gamma) g), each
+ * operation rounded on its own; a NaN t_k makes a NaN.  The winner is
+ * broadcast_best's on a: the largest, NaN greatest, the lowest index on ties.
+ * With model 0 alone a is strictly decreasing in t_0: the plain round's winner.
+ *
+ * Candidates of a round: n |M'| per label; candidate j is draw j % n of model
+ * M'[j / n]'s below mixture, drawn exactly as tpe_suggest draws (Philox counter
+ * (g / 2, 0, stream, round), inverse CDF, truncation, quantization, categorical
+ * pick).  Model 0 draws with the label's own stream s -- its n candidates are
+ * the plain round's -- and model k >= 1 with
+ *     TPE_CMODEL_STREAM + (k - 1) TPE_CMODEL_STREAM_SPAN + s,
+ * a range [0x7FFF0000, 0x7FFF8000) disjoint from the labels' streams (which
+ * must lie below TPE_CMODEL_STREAM_SPAN here), the pick streams
+ * TPE_JOINT_STREAM - j and TPE_POOL_STREAM.
+ *
+ * tpe_cmodel_set: the arguments of tpe_set_posterior, folded the same way, for
+ * model k; a label with n_below = 0 or n_above = 0 is skipped for k (factor
+ * 1, no candidates).  The label count and every label's kind (and whether it is
+ * quantized) must be the resident posterior's, which must be set first.  The
+ * models stay until tpe_cmodel_clear, the next tpe_cmodel_set of the same k or
+ * tpe_ctx_destroy; a call that finds them set for another label count fails.
+ * tpe_cmodel_clear unsets them all (their buffers are kept).
+ *
+ * tpe_cmodel_score: a on n caller-supplied candidates of one label, through the
+ * round's own scoring kernels (the probe of the round, as tpe_score is of the
+ * plain one); ll_out / lg_out (both or neither) [9][n], row k model k's lpdfs,
+ * NaN rows for models that are unset or skip the label.  gammas[9], read for
+ * the label's models only.
+ *
+ * tpe_cmodel_suggest_batch: one round per rounds[r] over every label, one
+ * stream synchronisation.  gammas [n_labels][9]; results [n_rounds][n_labels]:
+ * index the candidate index j above, value its value, score a, lpdf_below /
+ * lpdf_above model 0's ll / lg of the winner.
+ *
+ * The lpdfs are summed per chunk of 1024 components and the chunks merged in
+ * ascending order: the same bits on every run, whatever the grid, and within
+ * the parity contract (1e-9 relative) of tpe_score's.
+ * TPE_ERR_ARG (tpe_last_error names the function): no resident posterior; a
+ * multi-device or TPE_F32 context; k outside [1, 8]; a label count or kind
+ * that differs; a gamma outside (0, 1]; a label stream of
+ * TPE_CMODEL_STREAM_SPAN or more; n outside [1, 2^20] (score), n_candidates
+ * outside [1, 2^16] or more than 65535 (round, label) cells (suggest); a NULL
+ * pointer where one is needed.  TPE_ERR_VALUE / TPE_ERR_TYPE as
+ * tpe_set_posterior (set) and tpe_score (score).  TPE_ERR_SAMPLE when a model's
+ * below mixture has no mass inside the bounds. */
+#define TPE_CMODEL_MAX 8
+#define TPE_CMODEL_STREAM 0x7FFF0000u
+#define TPE_CMODEL_STREAM_SPAN 4096u
+int tpe_cmodel_set(tpe_ctx *ctx, int32_t k, const tpe_label_desc *labels, int32_t n_labels,
+                   const double *weights, const double *mus, const double *sigmas,
+                   int64_t n_components);
+int tpe_cmodel_clear(tpe_ctx *ctx);
+int tpe_cmodel_score(tpe_ctx *ctx, int32_t label, const double *cand, int64_t n,
+                     const double *gammas /* [9] */, double *acq_out /* [n] */,
+                     double *ll_out, double *lg_out /* [9][n] or NULL */);
+int tpe_cmodel_suggest_batch(tpe_ctx *ctx, uint64_t seed, const uint32_t *rounds, int32_t n_rounds,
+                             int64_t n_candidates, const double *gammas /* [n_labels][9] */,
+                             tpe_label_result *results /* [n_rounds][n_labels] */);
+
 /* Hyperparameter importance from the resident posterior (tpe.importance;
  * no reference counterpart -- Optuna's PED-ANOVA evaluator is the nearest).
  * For each of the n_sel selected labels, with l / g its below / above mixture,

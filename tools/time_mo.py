@@ -4,6 +4,7 @@
     python tools/time_mo.py --gpus 1 --quality [--out FILE]
     python tools/time_mo.py --gpus 1 --constraints K [--out FILE]
     python tools/time_mo.py --gpus 1 --quality-constrained [--evals 100] [--out FILE]
+    python tools/time_mo.py --gpus 1 --density [--out FILE]
 
 * Engine.mo_keys (tpe_mo_keys: upload, all-pairs kernel, pack, radix sort,
   scatter, read-back; one synchronisation) at n in {1000, 10000, 50000} x M in
@@ -42,8 +43,16 @@ on loss + cost and for rand.suggest, over 10 seeds.
 --quality-constrained (reported, not asserted): minimise (x - 1)^2 + (y - 1)^2
 on [0, 1]^2 under c = x + y - 1 <= 0 (the optimum 0.5 lies on the boundary);
 the best feasible loss after --evals evaluations over --seeds seeds for
-tpe.suggest(constraints=('c',)), for tpe.suggest on loss + 10 max(c, 0) and for
-rand.suggest.
+tpe.suggest(constraints=('c',)), the same with constraint_model='density', for
+tpe.suggest on loss + 10 max(c, 0) and for rand.suggest; then the same four on a
+tighter problem of the same form, x + y <= 0.3 (4.5 % of the square feasible,
+optimum 1.445).
+
+--density (tpe.suggest(constraints=..., constraint_model='density')): a whole
+tpe.suggest step on the config-3 history with two constraints, 'rank' against
+'density', alternating in one process; Engine.cmodel_suggest alone on the models
+the step left on the engine; and the host time of building the two constraint
+models (posterior.label_posterior and pack for every label).
 
 Results are appended to --out as one JSON object per line."""
 import argparse
@@ -235,12 +244,61 @@ def constrained_step_times(args):
     return [rec]
 
 
+def density_step_times(args):
+    from hyperopt_amd import engine as E, history, posterior as P, tpe, workloads
+    from hyperopt_amd.base import Domain
+    names = ('c0', 'c1')
+    hist = workloads.mixed_history(32, 10000, seed=0)
+    trials = workloads.history_trials(hist)
+    G = np.random.RandomState(1).uniform(size=(len(trials.trials), 2)) - 0.6
+    for d, g in zip(trials.trials, G):
+        d['result'].update(zip(names, map(float, g)))
+    domain = Domain(lambda d: 0.0, workloads.hp_space(hist.labels))
+    n = len(trials.trials)
+    legs = dict(rank=lambda: tpe.suggest([n], domain, trials, 3, constraints=names),
+                density=lambda: tpe.suggest([n], domain, trials, 3, constraints=names, constraint_model='density'))
+    ts = {k: [] for k in legs}
+    for k in legs:
+        legs[k]()                      # warm-up
+    for _ in range(args.reps):         # alternating
+        for k in legs:
+            t0 = time.perf_counter()
+            legs[k]()
+            ts[k].append((time.perf_counter() - t0) * 1e3)
+    rec = dict(what='cmodel_step', labels=32, trials=n, K=2)
+    for k, v in ts.items():
+        rec[k] = dict(median_ms=float(np.median(v)), min_ms=float(min(v)), max_ms=float(max(v)), reps=len(v))
+    # the round alone, on the models the last density step left on the engine
+    eng = E.get_engine(0, 'f64')
+    gammas = np.full((32, 3), 0.4)
+    rec['cmodel_suggest'] = timed(lambda: eng.cmodel_suggest(3, [n], 24, gammas), args.reps)
+    # the host build of the two constraint models
+    specs = tpe.specs_of(domain)
+    tids, _, obs = history.gather(domain, trials, list(specs))
+    live, split = P.cmodel_split(G, 0.25)
+
+    def build():
+        for below, _ in split:
+            b_tids = tids[below]
+            a_tids = np.setdiff1d(tids[live], b_tids)
+            P.pack([P.label_posterior(k, sp.kind, sp.args, *P.split_label(obs[k][0], obs[k][1], b_tids, a_tids),
+                                      prior_weight=1.0) for k, sp in specs.items()])
+    rec['host_model_build'] = timed(build, max(3, args.reps // 4))
+    rec['step_difference_ms'] = rec['density']['median_ms'] - rec['rank']['median_ms']
+    print(json.dumps(rec), flush=True)
+    return [rec]
+
+
 def quality_constrained(args):
+    return [quality_constrained_at(args, 1.0), quality_constrained_at(args, 0.3)]
+
+
+def quality_constrained_at(args, limit):
     from hyperopt_amd import STATUS_OK, Trials, fmin, hp, rand, tpe
     space = {'x': hp.uniform('x', 0, 1), 'y': hp.uniform('y', 0, 1)}
 
     def parts(cfg):
-        return (cfg['x'] - 1) ** 2 + (cfg['y'] - 1) ** 2, cfg['x'] + cfg['y'] - 1
+        return (cfg['x'] - 1) ** 2 + (cfg['y'] - 1) ** 2, cfg['x'] + cfg['y'] - limit
 
     def constrained(cfg):
         f, c = parts(cfg)
@@ -250,8 +308,10 @@ def quality_constrained(args):
         f, c = parts(cfg)
         return {'loss': f + 10.0 * max(c, 0.0), 'f': f, 'c': c, 'status': STATUS_OK}
     algos = dict(constraints=(constrained, partial(tpe.suggest, constraints=('c',))),
+                 density=(constrained, partial(tpe.suggest, constraints=('c',), constraint_model='density')),
                  tpe_on_the_penalty=(penalised, tpe.suggest), random=(constrained, rand.suggest))
-    rec = dict(what='mo_quality_constrained', problem='(x-1)^2 + (y-1)^2 under x + y <= 1, optimum 0.5',
+    rec = dict(what='mo_quality_constrained',
+               problem='(x-1)^2 + (y-1)^2 under x + y <= %g, optimum %g' % (limit, 2 * (1 - limit / 2) ** 2),
                evaluations=args.evals, seeds=args.seeds)
     for name, (fn, algo) in algos.items():
         best, feasible = [], []
@@ -265,7 +325,7 @@ def quality_constrained(args):
                          max=float(np.nanmax(best)), feasible_trials_mean=float(np.mean(feasible)),
                          runs_without_a_feasible_trial=int(np.isnan(best).sum()))
     print(json.dumps(rec), flush=True)
-    return [rec]
+    return rec
 
 
 def hypervolume(F, ref):
@@ -324,6 +384,7 @@ def main():
     ap.add_argument('--quality', action='store_true')
     ap.add_argument('--constraints', type=int, default=0, metavar='K')
     ap.add_argument('--quality-constrained', action='store_true')
+    ap.add_argument('--density', action='store_true')
     ap.add_argument('--evals', type=int)
     ap.add_argument('--seeds', type=int, default=10)
     ap.add_argument('--out')
@@ -336,6 +397,8 @@ def main():
         ap.error('--constraints: 1 to 8 columns')
     if args.quality_constrained:
         recs = quality_constrained(args)
+    elif args.density:
+        recs = density_step_times(args)
     elif args.constraints:
         from hyperopt_amd.engine import Engine
         eng = Engine(0, 'f64')
