@@ -27,11 +27,13 @@ SOURCES = [os.path.join(HERE, 'csrc', 'tpe_engine.hip'),
            os.path.join(HERE, 'csrc', 'tpe_joint.hip'),
            os.path.join(HERE, 'csrc', 'tpe_pool.hip'),
            os.path.join(HERE, 'csrc', 'tpe_mo.hip'),
+           os.path.join(HERE, 'csrc', 'tpe_mo_hv.hip'),
            os.path.join(HERE, 'csrc', 'tpe_importance.hip'),
            os.path.join(HERE, 'csrc', 'tpe_interaction.hip'),
            os.path.join(HERE, 'csrc', 'tpe_cmodel.hip')]
 DEPS = SOURCES + [os.path.join(HERE, 'csrc', 'tpe_device.h'),
                   os.path.join(HERE, 'csrc', 'tpe_ctx.h'),
+                  os.path.join(HERE, 'csrc', 'tpe_mo_hv.h'),
                   os.path.join(HERE, 'csrc', 'tpe_exp_table.h'),
                   os.path.join(REPO, 'include', 'hyperopt_tpe.h')]
 TARGET = os.path.join(HERE, 'libhyperopt_tpe.so')
@@ -44,7 +46,9 @@ FLAGS = ['--offload-arch=' + ARCH, '-O3', '-std=c++17', '-fPIC', '-shared',
 # bound and are re-scored in fp64 (tpe_device.h).
 # The unit is fp64 throughout, so today the flag changes no instruction and no
 # resource figure; it keeps a later fp32 helper from being packed silently.
-EXTRA_FLAGS = {'tpe_cmodel.hip': ['-Xclang', '-target-feature', '-Xclang', '-packed-fp32-ops']}
+# tpe_mo_hv.hip (integers and fp64 comparisons): the same.
+_NO_PACKED_FP32 = ['-Xclang', '-target-feature', '-Xclang', '-packed-fp32-ops']
+EXTRA_FLAGS = {'tpe_cmodel.hip': _NO_PACKED_FP32, 'tpe_mo_hv.hip': _NO_PACKED_FP32}
 
 
 def source_hash(deps=DEPS):

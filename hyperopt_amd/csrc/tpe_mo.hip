@@ -45,6 +45,15 @@
 //   k_moc_scatter  keys[i] = p, and by, do of every live row from its key's
 //                  fields (an infeasible row's: the v pass's by, 0); dead
 //                  rows: NaN, -1, -1
+//
+// With the hypervolume tie-break (tpe_mo_keys_hv, two or three objectives):
+// either pipeline above with tpe_mo_hv.hip's pairs kernel in the place of
+// k_mo_pairs<M> -- it counts the rank coordinates as well -- and, behind the
+// scatter, its level search, compaction and selection, which rewrite the keys
+// of one level.  Buffers of the context that only this call allocates:
+//   rank  : uint32[M][n]   rows j with F[j][m] < F[i][m]
+//   lvl   : int32[2][n], lvl_r : uint32[M][n], flag : uint8[n]   the level
+//   hdr   : int32[4]; pick : int32[64]; gain : uint64[64]
 #include <hip/hip_runtime.h>
 #include <hipcub/hipcub.hpp>
 
@@ -54,6 +63,7 @@
 
 #include "../../include/hyperopt_tpe.h"
 #include "tpe_ctx.h"
+#include "tpe_mo_hv.h"
 
 using namespace tpe_rt;
 
@@ -206,6 +216,13 @@ struct MoState {
     DevBuf<double> in, v;
     DevBuf<int32_t> cntv;
     PinVec<double> in_h, v_h;
+    // tpe_mo_keys_hv alone
+    DevBuf<uint32_t> rank, lvl_r;
+    DevBuf<int32_t> lvl, hdr, pick;
+    DevBuf<unsigned char> flag;
+    DevBuf<unsigned long long> gain;
+    PinVec<int32_t> pick_h;                 // hdr, then pick
+    PinVec<unsigned long long> gain_h;
 };
 
 MoState* mo_of(tpe_ctx* ctx) {
@@ -371,6 +388,128 @@ int tpe_mo_keys_constrained(tpe_ctx* ctx, const double* objectives, int64_t n, i
     if (dominated_by) std::memcpy(dominated_by, S->cnt_h.data(), (size_t)n * sizeof(int32_t));
     if (dominates) std::memcpy(dominates, S->cnt_h.data() + n, (size_t)n * sizeof(int32_t));
     if (violation) std::memcpy(violation, S->v_h.data(), (size_t)n * sizeof(double));
+    return TPE_OK;
+}
+
+int tpe_mo_keys_hv(tpe_ctx* ctx, const double* objectives, int64_t n, int32_t n_obj, const double* constraints,
+                   int32_t n_con, int32_t n_select, double* keys, int32_t* dominated_by, int32_t* dominates,
+                   double* violation, int32_t* picked, uint64_t* gains, int32_t* n_picked) {
+    if (!ctx) return TPE_ERR_ARG;
+    if (!objectives || !keys) return ctx->fail(TPE_ERR_ARG, "tpe_mo_keys_hv: null pointer");
+    if (n < 1 || n > kMoMaxRows) return ctx->fail(TPE_ERR_ARG, "tpe_mo_keys_hv: n must be in [1, 2^20]");
+    if (n_obj != 2 && n_obj != 3) return ctx->fail(TPE_ERR_ARG, "tpe_mo_keys_hv: n_obj must be 2 or 3");
+    if (constraints && (n_con < 1 || n_con > kMoMaxCon))
+        return ctx->fail(TPE_ERR_ARG, "tpe_mo_keys_hv: n_con must be in [1, 8]");
+    if (n_select < 0 || n_select > kHvMaxPicks)
+        return ctx->fail(TPE_ERR_ARG, "tpe_mo_keys_hv: n_select must be in [0, 64]");
+    HIPCHK(ctx, hipSetDevice(ctx->device));
+    hipStream_t st = ctx->stream;
+    MoState* S = mo_of(ctx);
+    const int32_t N = (int32_t)n;
+    int32_t bits = 1;
+    while (((int64_t)1 << bits) <= n) ++bits;
+    // (n_select of 0 or past the rows: the keys are the old keys, nothing to select)
+    const bool select = n_select > 0 && n_select < n;
+    const size_t nf = (size_t)n * n_obj, ng = constraints ? (size_t)n * n_con : 0;
+    HIPCHK(ctx, S->in.reserve(nf + ng));
+    HIPCHK(ctx, S->in_h.resize(nf + ng));
+    HIPCHK(ctx, S->keys.reserve(n));
+    HIPCHK(ctx, S->cnt.reserve(2 * (size_t)n));
+    HIPCHK(ctx, S->key.reserve(n));
+    HIPCHK(ctx, S->key2.reserve(n));
+    HIPCHK(ctx, S->keys_h.resize(n));
+    HIPCHK(ctx, S->cnt_h.resize(2 * (size_t)n));
+    if (constraints) {
+        HIPCHK(ctx, S->v.reserve(n));
+        HIPCHK(ctx, S->cntv.reserve(2 * (size_t)n));
+        HIPCHK(ctx, S->v_h.resize(n));
+    }
+    HIPCHK(ctx, S->rank.reserve(nf));
+    HIPCHK(ctx, S->lvl_r.reserve(nf));
+    HIPCHK(ctx, S->lvl.reserve(2 * (size_t)n));
+    HIPCHK(ctx, S->flag.reserve(n));
+    HIPCHK(ctx, S->hdr.reserve(kHvHdr));
+    HIPCHK(ctx, S->pick.reserve(kHvMaxPicks));
+    HIPCHK(ctx, S->gain.reserve(kHvMaxPicks));
+    HIPCHK(ctx, S->pick_h.resize(kHvHdr + kHvMaxPicks));
+    HIPCHK(ctx, S->gain_h.resize(kHvMaxPicks));
+    size_t sort_bytes = 0;
+    hipcub::DoubleBuffer<uint64_t> kb(S->key.p, S->key2.p);
+    HIPCHK(ctx, hipcub::DeviceRadixSort::SortKeys(nullptr, sort_bytes, kb, (int)N, 0, 3 * bits, st));
+    HIPCHK(ctx, S->tmp.reserve(std::max<size_t>(sort_bytes, 1)));
+    double* d_F = S->in.p;
+    const double* d_G = S->in.p + nf;
+    int32_t* d_by = S->cnt.p;
+    int32_t* d_do = S->cnt.p + n;
+
+    // F (and G) in pinned memory: the call's one upload
+    std::memcpy(S->in_h.data(), objectives, nf * sizeof(double));
+    if (constraints) std::memcpy(S->in_h.data() + nf, constraints, ng * sizeof(double));
+    HIPCHK(ctx, hipMemcpyAsync(S->in.p, S->in_h.data(), (nf + ng) * sizeof(double), hipMemcpyHostToDevice, st));
+    HIPCHK(ctx, hipMemsetAsync(S->cnt.p, 0, 2 * (size_t)n * sizeof(int32_t), st));
+    HIPCHK(ctx, hipMemsetAsync(S->rank.p, 0, nf * sizeof(uint32_t), st));
+    const unsigned row_blocks = blocks_of(n, kBlock);
+    const unsigned slices = std::max(1u, std::min(row_blocks, (kMoBlocks + row_blocks - 1) / row_blocks));
+    const int32_t per_slice = (int32_t)((n + slices - 1) / slices);
+    const dim3 grid(row_blocks, blocks_of(n, per_slice));
+    if (constraints) {
+        HIPCHK(ctx, hipMemsetAsync(S->cntv.p, 0, 2 * (size_t)n * sizeof(int32_t), st));
+        hipLaunchKernelGGL(k_moc_prep, dim3(row_blocks), dim3(kBlock), 0, st, d_F, d_G, N, n_obj, n_con, S->v.p);
+        HIPCHK(ctx, hipGetLastError());
+    } else {
+        hv_launch_prep(st, d_F, N, n_obj);
+        HIPCHK(ctx, hipGetLastError());
+    }
+    // counts and rank coordinates among the rank rows (every other row of the
+    // device copy is NaN by now)
+    hv_launch_pairs(n_obj, grid, st, d_F, N, per_slice, d_by, d_do, S->rank.p);
+    HIPCHK(ctx, hipGetLastError());
+    if (constraints) {
+        launch_pairs<1>(grid, st, S->v.p, N, per_slice, S->cntv.p, S->cntv.p + n);
+        HIPCHK(ctx, hipGetLastError());
+        hipLaunchKernelGGL(k_moc_pack, dim3(row_blocks), dim3(kBlock), 0, st, S->v.p, N, bits, d_by, d_do,
+                           S->cntv.p, S->key.p);
+    } else {
+        hipLaunchKernelGGL(k_mo_pack, dim3(row_blocks), dim3(kBlock), 0, st, d_F, N, n_obj, bits, d_by, d_do,
+                           S->key.p);
+    }
+    HIPCHK(ctx, hipGetLastError());
+    HIPCHK(ctx, hipcub::DeviceRadixSort::SortKeys(S->tmp.p, sort_bytes, kb, (int)N, 0, 3 * bits, st));
+    if (constraints)
+        hipLaunchKernelGGL(k_moc_scatter, dim3(row_blocks), dim3(kBlock), 0, st, kb.Current(), N, bits, S->keys.p,
+                           d_by, d_do);
+    else
+        hipLaunchKernelGGL(k_mo_scatter, dim3(row_blocks), dim3(kBlock), 0, st, kb.Current(), N, bits, S->keys.p,
+                           d_by, d_do);
+    HIPCHK(ctx, hipGetLastError());
+    if (select) {
+        // the level at n_select, its picks, and the keys of its rows -- all on the device
+        hv_launch_select(n_obj, st, kb.Current(), N, bits, constraints ? S->v.p : nullptr, n_select, S->rank.p,
+                         S->hdr.p, S->lvl.p, S->lvl_r.p, S->flag.p, S->keys.p, S->pick.p, S->gain.p);
+        HIPCHK(ctx, hipGetLastError());
+        HIPCHK(ctx, hipMemcpyAsync(S->pick_h.data(), S->hdr.p, kHvHdr * sizeof(int32_t), hipMemcpyDeviceToHost, st));
+        HIPCHK(ctx, hipMemcpyAsync(S->pick_h.data() + kHvHdr, S->pick.p, kHvMaxPicks * sizeof(int32_t),
+                                   hipMemcpyDeviceToHost, st));
+        HIPCHK(ctx, hipMemcpyAsync(S->gain_h.data(), S->gain.p, kHvMaxPicks * sizeof(unsigned long long),
+                                   hipMemcpyDeviceToHost, st));
+    }
+    HIPCHK(ctx, hipMemcpyAsync(S->keys_h.data(), S->keys.p, n * sizeof(double), hipMemcpyDeviceToHost, st));
+    if (dominated_by || dominates)
+        HIPCHK(ctx, hipMemcpyAsync(S->cnt_h.data(), S->cnt.p, 2 * (size_t)n * sizeof(int32_t), hipMemcpyDeviceToHost,
+                                   st));
+    if (violation && constraints)
+        HIPCHK(ctx, hipMemcpyAsync(S->v_h.data(), S->v.p, n * sizeof(double), hipMemcpyDeviceToHost, st));
+    HIPCHK(ctx, hipStreamSynchronize(st));   // the call's one synchronisation
+    std::memcpy(keys, S->keys_h.data(), (size_t)n * sizeof(double));
+    if (dominated_by) std::memcpy(dominated_by, S->cnt_h.data(), (size_t)n * sizeof(int32_t));
+    if (dominates) std::memcpy(dominates, S->cnt_h.data() + n, (size_t)n * sizeof(int32_t));
+    if (violation && constraints) std::memcpy(violation, S->v_h.data(), (size_t)n * sizeof(double));
+    const int32_t q = select ? S->pick_h[2] : 0;
+    for (int32_t k = 0; k < n_select; ++k) {
+        if (picked) picked[k] = k < q ? S->pick_h[kHvHdr + k] : -1;
+        if (gains) gains[k] = k < q ? (uint64_t)S->gain_h[k] : 0;
+    }
+    if (n_picked) *n_picked = q;
     return TPE_OK;
 }
 

@@ -788,7 +788,7 @@ class Engine(object):
             out += (score,)
         return out
 
-    def mo_keys(self, F, want_counts=False, G=None):
+    def mo_keys(self, F, want_counts=False, G=None, tiebreak='dominates', n_select=0, want_picks=False):
         """The Pareto-compliant order of the objective vectors F [n, M], all
         minimised (tpe_mo_keys; posterior.mo_keys is its numpy restatement):
         keys [n] float64 -- row i's position under ascending dominated_by,
@@ -797,7 +797,15 @@ class Engine(object):
         row.  G [n, K] (constraints, <= 0 satisfied): the order with the
         feasible rows first and the infeasible ones by ascending violation
         (tpe_mo_keys_constrained); want_counts then returns (keys,
-        dominated_by, dominates, violation [n] float64)."""
+        dominated_by, dominates, violation [n] float64).
+        tiebreak='hypervolume' (tpe_mo_keys_hv; two or three objectives,
+        n_select in 0 .. 64): the level that straddles position n_select
+        reordered by greedy hypervolume subset selection, so that the first
+        n_select rows are the greedy subset (posterior.mo_keys states the
+        rule); want_picks appends (picked int32 [n_picked], gains uint64
+        [n_picked]), the picks' rows and exact gains in pick order."""
+        if tiebreak not in ('dominates', 'hypervolume'):
+            raise ValueError("tiebreak must be 'dominates' or 'hypervolume'")
         F = np.ascontiguousarray(F, dtype=np.float64)
         if F.ndim != 2:
             raise ValueError('F must be [n, n_objectives]')
@@ -805,6 +813,24 @@ class Engine(object):
         keys = np.empty(n)
         by = np.empty(n, dtype=np.int32) if want_counts else None
         do = np.empty(n, dtype=np.int32) if want_counts else None
+        if tiebreak == 'hypervolume':
+            if G is not None:
+                G = np.ascontiguousarray(G, dtype=np.float64)
+                if G.ndim != 2 or G.shape[0] != n:
+                    raise ValueError('G must be [n, n_constraints], a row for every row of F')
+            n_select = int(n_select)
+            v = np.empty(n) if want_counts and G is not None else None
+            picked = np.empty(max(n_select, 0), dtype=np.int32)
+            gains = np.empty(max(n_select, 0), dtype=np.uint64)
+            n_picked = ctypes.c_int32(0)
+            self._check(self.lib.tpe_mo_keys_hv(self.h, _ptr(F), n, F.shape[1], _ptr(G),
+                                                0 if G is None else G.shape[1], n_select, _ptr(keys), _ptr(by),
+                                                _ptr(do), _ptr(v), _ptr(picked), _ptr(gains),
+                                                ctypes.byref(n_picked)))
+            out = (keys,) + ((by, do) if want_counts else ()) + ((v,) if v is not None else ())
+            if want_picks:
+                out += (picked[:n_picked.value].copy(), gains[:n_picked.value].copy())
+            return out if len(out) > 1 else keys
         if G is None:
             self._check(self.lib.tpe_mo_keys(self.h, _ptr(F), n, F.shape[1], _ptr(keys), _ptr(by), _ptr(do)))
             return (keys, by, do) if want_counts else keys

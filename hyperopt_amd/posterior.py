@@ -180,7 +180,93 @@ def mo_counts(F, G=None):
     return by, do
 
 
-def mo_keys(F, counts=None, G=None):
+MO_HV_MAX_SELECT = 64     # tpe_mo_keys_hv's n_select (the picked set the kernel keeps in LDS)
+
+
+def _mo_union2(W, H):
+    """The cells in the union of the boxes [0, W[l, j]) x [0, H[l, j]) over j,
+    for every l: int64 [L].  By descending width the covered height is the
+    running maximum."""
+    o = np.argsort(-W, axis=1, kind='stable')
+    W = np.take_along_axis(W, o, axis=1)
+    H = np.maximum.accumulate(np.take_along_axis(H, o, axis=1), axis=1)
+    return ((W - np.concatenate([W[:, 1:], np.zeros_like(W[:, :1])], axis=1)) * H).sum(axis=1)
+
+
+def _mo_union(B):
+    """The same for boxes B [L, k, M] of two or three sides: slabs by
+    descending depth, each with the 2-D union of the boxes that reach it."""
+    if B.shape[2] == 2:
+        return _mo_union2(B[:, :, 0], B[:, :, 1])
+    B = np.take_along_axis(B, np.argsort(-B[:, :, 2], axis=1, kind='stable')[:, :, None], axis=1)
+    D = np.concatenate([B[:, :, 2], np.zeros_like(B[:, :1, 2])], axis=1)
+    vol = np.zeros(len(B), dtype=np.int64)
+    for j in range(B.shape[1]):
+        thick = D[:, j] - D[:, j + 1]
+        if thick.any():
+            vol += thick * _mo_union2(B[:, :j + 1, 0], B[:, :j + 1, 1])
+    return vol
+
+
+def mo_hypervolume_order(F, by, do, keys, n_select, G=None):
+    """The hypervolume tie-break of the below set (the numpy restatement of
+    tpe_mo_keys_hv, include/hyperopt_tpe.h): (keys, picked, gains).  F [n, 2
+    or 3]; by, do, keys those of mo_counts / mo_keys (with G when given).
+    The rank rows are the rows of the dominance pass (no NaN; feasible with
+    G), n_f of them; r[i][m] counts the rank rows with a smaller F[:, m], the
+    reference point is n_f on every axis and row i's box has the sides n_f -
+    r[i][m]; the hypervolume of a set is the number of integer cells its
+    boxes cover -- exact in int64 (below 2^60), invariant under increasing
+    maps of an objective.  When the rows at the positions n_select - 1 and
+    n_select share their `by` (and both are rank rows) the rows of that `by`
+    -- an antichain -- are the level, a its first position, and q = n_select -
+    a times the unpicked row with the largest gain HV(P + c) - HV(P) joins P
+    (ties: larger do, then smaller row); the picks take the positions a ..
+    a + q - 1 in pick order, the level's other rows follow in their old
+    order.  Otherwise, and for n_select <= 0 or >= the rows with a key, the
+    keys stay and nothing is picked."""
+    F = np.asarray(F, dtype=np.float64)
+    if F.ndim != 2 or F.shape[1] not in (2, 3):
+        raise ValueError("tiebreak='hypervolume' needs 2 or 3 objectives")
+    n_select = int(n_select)
+    if not 0 <= n_select <= MO_HV_MAX_SELECT:
+        raise ValueError('n_select must be in [0, %d]' % MO_HV_MAX_SELECT)
+    none = (keys, np.zeros(0, dtype=np.int32), np.zeros(0, dtype=np.uint64))
+    live = np.flatnonzero(by >= 0)
+    if n_select <= 0 or n_select >= len(live):
+        return none
+    ranked = ~np.isnan(F).any(axis=1) if G is None else mo_violation(G, F) == 0.0
+    order = np.empty(len(live), dtype=np.int64)
+    order[keys[live].astype(np.int64)] = live
+    s, t = order[n_select - 1], order[n_select]
+    if by[s] != by[t] or not (ranked[s] and ranked[t]):
+        return none
+    at = np.flatnonzero(by[order] == by[s])            # (contiguous: the order is by `by` first)
+    lev, a = order[at], int(at[0])
+    q = n_select - a
+    n_f = int(np.count_nonzero(ranked))
+    sides = np.empty((len(lev), F.shape[1]), dtype=np.int64)
+    for m in range(F.shape[1]):
+        sides[:, m] = n_f - np.searchsorted(np.sort(F[ranked, m]), F[lev, m], side='left')
+    vol = sides.prod(axis=1)
+    left = np.ones(len(lev), dtype=bool)
+    picks, gains = [], []
+    for _ in range(q):
+        cand = np.flatnonzero(left)
+        gain = vol[cand].copy()
+        if picks:
+            gain -= _mo_union(np.minimum(sides[cand][:, None, :], sides[picks][None, :, :]))
+        best = cand[np.lexsort((lev[cand], -do[lev[cand]].astype(np.int64), -gain))[0]]
+        gains.append(int(gain[cand == best][0]))
+        picks.append(int(best))
+        left[best] = False
+    out = keys.copy()
+    out[lev[picks]] = a + np.arange(q, dtype=np.float64)
+    out[lev[left]] = a + q + np.arange(int(left.sum()), dtype=np.float64)
+    return out, lev[picks].astype(np.int32), np.asarray(gains, dtype=np.uint64)
+
+
+def mo_keys(F, counts=None, G=None, tiebreak='dominates', n_select=0):
     """The Pareto-compliant total order of the objective vectors F [n, M] as
     one loss column: keys[i] is row i's position, 0 .. as a float64, under
     ascending by, then descending do, then ascending i (mo_counts; by is 0
@@ -190,12 +276,19 @@ def mo_keys(F, counts=None, G=None):
     split by them never meets a tie.  M = 1: the stable argsort rank.
     With the constraint rows G the counts are mo_counts(F, G)'s: the feasible
     rows first, in their order among themselves, then the infeasible ones by
-    ascending violation and position -- the same three-field order."""
+    ascending violation and position -- the same three-field order.
+    tiebreak='hypervolume' (M 2 or 3): the level that straddles position
+    n_select reordered so that the first n_select rows are the greedy
+    hypervolume subset (mo_hypervolume_order; the kernel's integers)."""
+    if tiebreak not in ('dominates', 'hypervolume'):
+        raise ValueError("tiebreak must be 'dominates' or 'hypervolume'")
     by, do = mo_counts(F, G) if counts is None else counts
     keys = np.full(len(by), np.nan)
     valid = np.flatnonzero(by >= 0)
     order = np.lexsort((valid, -do[valid].astype(np.int64), by[valid]))
     keys[valid[order]] = np.arange(len(valid), dtype=np.float64)
+    if tiebreak == 'hypervolume':
+        return mo_hypervolume_order(F, by, do, keys, n_select, G)[0]
     return keys
 
 

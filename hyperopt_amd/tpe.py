@@ -815,17 +815,47 @@ def objective_rows(docs, objectives, domain=None, check_from=True, constraints=N
 _misc_of = operator.itemgetter('misc')
 
 
-def objective_keys(F, builder='auto', engine=None, G=None):
+def objective_keys(F, builder='auto', engine=None, G=None, tiebreak='dominates', n_select=0):
     """posterior.mo_keys(F) by the builder the call selects: 'host' numpy,
     'device' the kernel (Engine.mo_keys on `engine`, a callable returning the
     Engine), 'auto' the kernel from MO_DEVICE_MIN_TRIALS rows on.  The same
     integers either way.  G: the constraint rows (posterior.mo_keys(F, G=G),
-    Engine.mo_keys(F, G=G))."""
+    Engine.mo_keys(F, G=G)).  tiebreak, n_select: handed to either builder."""
+    kw = {} if G is None else dict(G=G)
+    if tiebreak != 'dominates':
+        kw.update(tiebreak=tiebreak, n_select=n_select)
     if len(F) and (builder == 'device' or (builder == 'auto' and len(F) >= MO_DEVICE_MIN_TRIALS)):
         if len(F) > _post.MO_MAX_ROWS:
             raise ValueError('objectives: at most %d complete trials' % _post.MO_MAX_ROWS)
-        return engine().mo_keys(F) if G is None else engine().mo_keys(F, G=G)
-    return _post.mo_keys(F) if G is None else _post.mo_keys(F, G=G)
+        return engine().mo_keys(F, **kw)
+    return _post.mo_keys(F, **kw)
+
+
+def check_mo_tiebreak(mo_tiebreak, objectives, constraint_model='rank'):
+    """tpe.suggest's `mo_tiebreak` after validation (`objectives` validated):
+    'dominates' or 'hypervolume', the latter with two or three objectives and
+    without constraint_model='density'."""
+    if mo_tiebreak not in ('dominates', 'hypervolume'):
+        raise ValueError("mo_tiebreak must be 'dominates' or 'hypervolume'")
+    if mo_tiebreak == 'hypervolume':
+        if objectives is None:
+            raise ValueError("mo_tiebreak='hypervolume' needs objectives")
+        if len(objectives) not in (2, 3):
+            raise ValueError("mo_tiebreak='hypervolume' needs 2 or 3 objectives, got %d" % len(objectives))
+        if constraint_model == 'density':
+            raise ValueError("mo_tiebreak='hypervolume' with constraint_model='density' is not supported")
+    return mo_tiebreak
+
+
+def _hv_keywords(mo_tiebreak, F, G, gamma):
+    """objective_keys' tiebreak and n_select of a call: n_select is the below
+    set's size for the rows that get a key (no NaN in F or G)."""
+    if mo_tiebreak != 'hypervolume':
+        return {}
+    live = ~np.isnan(F).any(axis=1)
+    if G is not None:
+        live &= ~np.isnan(G).any(axis=1)
+    return dict(tiebreak='hypervolume', n_select=_post.n_below_of(int(np.count_nonzero(live)), gamma))
 
 
 class _KeyedDomain(object):
@@ -1127,7 +1157,7 @@ def suggest(new_ids, domain, trials, seed,
             precision='f64', device=0, batch=False, posterior_builder='auto', devices=None,
             multivariate=False, group=False, joint_quantized=False, joint_categorical=False,
             joint_bandwidth='neighbour', fixed=None, pool=None, pool_candidates=None, constraint_model='rank',
-            pool_replace=False, constraints=None, objectives=None):
+            mo_tiebreak='dominates', pool_replace=False, constraints=None, objectives=None):
     """tpe.py:823-916.  Past the startup phase one document for new_ids[0],
     like the reference; `batch` (not in the reference) asks for one document
     per new_id:
@@ -1323,6 +1353,27 @@ def suggest(new_ids, domain, trials, seed,
     documents.  tpe.pareto_front(trials, objectives) lists the front.  With
     objectives=None every call returns what it returned before.
 
+    mo_tiebreak='hypervolume' (with two or three `objectives`; default
+    'dominates', the order above) fills the below set by greedy hypervolume
+    subset selection, as MOTPE and Optuna's multi-objective TPE do, where the
+    second criterion decides it: when the level of equal dominated_by that
+    holds the below set's last trial holds more trials than fit, its trials
+    are taken one at a time by the largest hypervolume gain over the ones
+    already taken (ties: more trials dominated, then trial order), which
+    spreads the set over the front, extremes included, where descending
+    `dominates` fills it from the knee.  Hypervolumes are exact integers in
+    rank coordinates ("Hypervolume tie-break"): no
+    reference point, no normalisation, invariant under increasing maps of an
+    objective.  The set's size is posterior.n_below_of(trials with a key,
+    gamma).  Both builders give the same integers (posterior.mo_keys(...,
+    tiebreak='hypervolume', n_select=...), Engine.mo_keys likewise: the
+    kernel selects in one workgroup on the device), and the call is again the
+    plain call on the keys, so it composes with multivariate, fixed, pool,
+    batch, devices and constraints (rank model).  ValueError, before any
+    engine is touched: another value, 'hypervolume' without objectives, with
+    a number of objectives other than 2 or 3, or with
+    constraint_model='density'.
+
     constraints=('mem_over', 'lat_over') (not in the reference; Optuna's
     constraints_func) names 1 to 8 further result-dict keys, each a hard limit
     in Optuna's convention: c <= 0 satisfied, c > 0 violated by that amount --
@@ -1387,6 +1438,7 @@ def suggest(new_ids, domain, trials, seed,
     if _cmodel is None and constraint_model not in ('rank', 'density'):
         raise ValueError("constraint_model must be 'rank' or 'density'")
     density = constraint_model == 'density'
+    check_mo_tiebreak(mo_tiebreak, objectives, constraint_model)
     if density:
         if constraints is None:
             raise ValueError("constraint_model='density' needs constraints")
@@ -1410,7 +1462,7 @@ def suggest(new_ids, domain, trials, seed,
         check_from = _history.has_from_tid(trials, list(specs_of(domain)))
         if constraints is None:
             docs, F = objective_rows(src, objectives, domain, check_from=check_from)
-            keys = objective_keys(F, builder, engine)
+            keys = objective_keys(F, builder, engine, **_hv_keywords(mo_tiebreak, F, None, gamma))
             logger.info('tpe.suggest: %d objectives, %d complete trials ranked, %.1f ms' % (
                 len(objectives), len(docs), (time.time() - t0) * 1e3))
         elif density:
@@ -1431,7 +1483,7 @@ def suggest(new_ids, domain, trials, seed,
         else:
             names = objectives or ('loss',)
             docs, F, G = objective_rows(src, names, domain, check_from=check_from, constraints=constraints)
-            keys = objective_keys(F, builder, engine, G=G)
+            keys = objective_keys(F, builder, engine, G=G, **_hv_keywords(mo_tiebreak, F, G, gamma))
             if logger.isEnabledFor(logging.INFO):      # (the count is a pass over the rows)
                 logger.info('tpe.suggest: %d objectives, %d constraints, %d complete trials ranked, %d of them '
                             'feasible, %.1f ms' % (len(names), len(constraints), len(docs),

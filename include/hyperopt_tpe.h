@@ -843,6 +843,45 @@ int tpe_mo_keys_constrained(tpe_ctx *ctx, const double *objectives /* [n][n_obj]
                             double *keys /* [n] */, int32_t *dominated_by /* [n] or NULL */,
                             int32_t *dominates /* [n] or NULL */, double *violation /* [n] or NULL */);
 
+/* The hypervolume tie-break of the below set (tpe.suggest(mo_tiebreak=
+ * 'hypervolume'); greedy hypervolume subset selection, as MOTPE's below set):
+ * tpe_mo_keys' order -- tpe_mo_keys_constrained's when constraints is not NULL
+ * -- with the level that straddles position n_select reordered.  n_obj 2 or 3.
+ *   rank rows: the rows of the dominance pass (no NaN; feasible when
+ *       constraints are given), n_f of them;
+ *   r[i][m] = the rank rows j with F[j][m] < F[i][m] (IEEE <; equal values,
+ *       equal ranks); the reference point is n_f on every axis, row i's box has
+ *       the sides n_f - r[i][m] >= 1, and the hypervolume of a set is the number
+ *       of integer cells in the union of its boxes -- exact, unsigned 64-bit,
+ *       below 2^60, invariant under increasing maps of an objective;
+ *   the keys are the old keys when n_select <= 0, n_select >= the rows with a
+ *       key, the rows at the old positions n_select - 1 and n_select differ in
+ *       dominated_by, or either of them is infeasible; *n_picked = 0 then;
+ *   otherwise the level is the rows of that common dominated_by (an
+ *       antichain), a its first old position, q = n_select - a, and q times
+ *       the unpicked row c of the level with the largest gain(c) = HV(P + c) -
+ *       HV(P) joins P (empty at first); ties: the larger dominates, then the
+ *       smaller i.  The picks take the positions a .. a + q - 1 in pick order,
+ *       the level's other rows follow in their old order, every other row keeps
+ *       its key.  *n_picked = q.
+ * picked[n_select], gains[n_select]: the picks' rows and exact gains, -1 and 0
+ * past *n_picked; each may be NULL, as may n_picked, dominated_by, dominates
+ * and violation (written only with constraints).  One upload, one stream
+ * synchronisation; the level is found, compacted and searched on the device
+ * (one workgroup, two barriers a pick).  Its own reusable buffers (counted by
+ * tpe_device_bytes) are allocated by the first such call; the two calls above
+ * neither touch them nor change their results.
+ * TPE_ERR_ARG: a NULL objectives or keys; n < 1 or n > 2^20; n_obj not 2 or 3;
+ * n_con outside [1, 8] with constraints; n_select outside [0, 64].  On an
+ * error the outputs are untouched. */
+int tpe_mo_keys_hv(tpe_ctx *ctx, const double *objectives /* [n][n_obj] row-major */,
+                   int64_t n, int32_t n_obj,
+                   const double *constraints /* [n][n_con] row-major, or NULL */, int32_t n_con,
+                   int32_t n_select, double *keys /* [n] */, int32_t *dominated_by /* [n] or NULL */,
+                   int32_t *dominates /* [n] or NULL */, double *violation /* [n] or NULL */,
+                   int32_t *picked /* [n_select] or NULL */, uint64_t *gains /* [n_select] or NULL */,
+                   int32_t *n_picked /* or NULL */);
+
 /* ---- constraint densities (c-TPE) -------------------------------------------
  * tpe.suggest(constraints=..., constraint_model='density'): besides the
  * resident posterior (model 0, the objective's) a context holds up to eight

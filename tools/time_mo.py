@@ -54,6 +54,13 @@ tpe.suggest step on the config-3 history with two constraints, 'rank' against
 the step left on the engine; and the host time of building the two constraint
 models (posterior.label_posterior and pack for every label).
 
+--tiebreak hypervolume (tpe.suggest(mo_tiebreak='hypervolume')): the timing
+leg times Engine.mo_keys(F, tiebreak='hypervolume', n_select=n_below) against
+the default Engine.mo_keys(F), alternating, at the sizes above x 2 and 3
+objectives, with the level size and the picks of each input, and the worst case
+of a 100 000-row antichain (one level) at 3 objectives; with --quality it adds
+the row objectives_hypervolume to the ZDT1 table.
+
 Results are appended to --out as one JSON object per line."""
 import argparse
 import json
@@ -96,6 +103,38 @@ def key_times(eng, args):
                 rec['host'] = 'not measured'
             print(json.dumps(rec), flush=True)
             out.append(rec)
+    return out
+
+
+def hv_key_times(eng, args):
+    from hyperopt_amd import posterior as P
+    inputs = [('uniform', n, M, np.random.RandomState(n + M).uniform(size=(n, M))) for n in SIZES for M in (2, 3)]
+    u = np.random.RandomState(7).dirichlet(np.ones(3), 100000)
+    inputs.append(('antichain', 100000, 3, u))
+    out = []
+    for kind, n, M, F in inputs:
+        k = P.n_below_of(n, 0.25)
+        legs = dict(default=lambda: eng.mo_keys(F),
+                    hypervolume=lambda: eng.mo_keys(F, tiebreak='hypervolume', n_select=k))
+        ts = {name: [] for name in legs}
+        for name in legs:
+            legs[name]()               # warm-up
+        for _ in range(args.reps):     # alternating
+            for name in legs:
+                t0 = time.perf_counter()
+                legs[name]()
+                ts[name].append((time.perf_counter() - t0) * 1e3)
+        keys, by, do, picked, gains = eng.mo_keys(F, want_counts=True, tiebreak='hypervolume', n_select=k,
+                                                  want_picks=True)
+        rec = dict(what='mo_keys_hv', rows=kind, n=n, M=M, n_select=k, picks=len(picked),
+                   level=int(np.count_nonzero(by == by[picked[0]])) if len(picked) else 0)
+        for name, v in ts.items():
+            rec[name] = dict(median_ms=float(np.median(v)), min_ms=float(min(v)), max_ms=float(max(v)), reps=len(v))
+        rec['hypervolume_minus_default_ms'] = rec['hypervolume']['median_ms'] - rec['default']['median_ms']
+        if n <= args.host_max_n:
+            rec['same_keys'] = bool(np.array_equal(P.mo_keys(F, tiebreak='hypervolume', n_select=k), keys))
+        print(json.dumps(rec), flush=True)
+        out.append(rec)
     return out
 
 
@@ -361,6 +400,9 @@ def quality(args):
         return {'loss': f1 + f2, 'f1': f1, 'cost': f2, 'status': STATUS_OK}
     algos = dict(objectives=(both, partial(tpe.suggest, objectives=('loss', 'cost')), 'loss'),
                  tpe_on_the_sum=(summed, tpe.suggest, 'f1'), random=(both, rand.suggest, 'loss'))
+    if args.tiebreak == 'hypervolume':
+        algos['objectives_hypervolume'] = (both, partial(tpe.suggest, objectives=('loss', 'cost'),
+                                                         mo_tiebreak='hypervolume'), 'loss')
     rec = dict(what='mo_quality', problem='ZDT1, 4 dimensions', evaluations=args.evals, reference_point=ref.tolist(),
                seeds=args.seeds)
     for name, (fn, algo, first) in algos.items():
@@ -385,6 +427,7 @@ def main():
     ap.add_argument('--constraints', type=int, default=0, metavar='K')
     ap.add_argument('--quality-constrained', action='store_true')
     ap.add_argument('--density', action='store_true')
+    ap.add_argument('--tiebreak', choices=('dominates', 'hypervolume'), default='dominates')
     ap.add_argument('--evals', type=int)
     ap.add_argument('--seeds', type=int, default=10)
     ap.add_argument('--out')
@@ -407,6 +450,11 @@ def main():
         recs += constrained_step_times(args)
     elif args.quality:
         recs = quality(args)
+    elif args.tiebreak == 'hypervolume':
+        from hyperopt_amd.engine import Engine
+        eng = Engine(0, 'f64')
+        recs = hv_key_times(eng, args)
+        eng.close()
     else:
         from hyperopt_amd.engine import Engine
         eng = Engine(0, 'f64')
