@@ -30,10 +30,12 @@ SOURCES = [os.path.join(HERE, 'csrc', 'tpe_engine.hip'),
            os.path.join(HERE, 'csrc', 'tpe_mo_hv.hip'),
            os.path.join(HERE, 'csrc', 'tpe_importance.hip'),
            os.path.join(HERE, 'csrc', 'tpe_interaction.hip'),
+           os.path.join(HERE, 'csrc', 'tpe_interaction_mixed.hip'),
            os.path.join(HERE, 'csrc', 'tpe_cmodel.hip')]
 DEPS = SOURCES + [os.path.join(HERE, 'csrc', 'tpe_device.h'),
                   os.path.join(HERE, 'csrc', 'tpe_ctx.h'),
                   os.path.join(HERE, 'csrc', 'tpe_mo_hv.h'),
+                  os.path.join(HERE, 'csrc', 'tpe_interaction.h'),
                   os.path.join(HERE, 'csrc', 'tpe_exp_table.h'),
                   os.path.join(REPO, 'include', 'hyperopt_tpe.h')]
 TARGET = os.path.join(HERE, 'libhyperopt_tpe.so')
@@ -47,8 +49,10 @@ FLAGS = ['--offload-arch=' + ARCH, '-O3', '-std=c++17', '-fPIC', '-shared',
 # The unit is fp64 throughout, so today the flag changes no instruction and no
 # resource figure; it keeps a later fp32 helper from being packed silently.
 # tpe_mo_hv.hip (integers and fp64 comparisons): the same.
+# tpe_interaction_mixed.hip (fp64 throughout): the same.
 _NO_PACKED_FP32 = ['-Xclang', '-target-feature', '-Xclang', '-packed-fp32-ops']
-EXTRA_FLAGS = {'tpe_cmodel.hip': _NO_PACKED_FP32, 'tpe_mo_hv.hip': _NO_PACKED_FP32}
+EXTRA_FLAGS = {'tpe_cmodel.hip': _NO_PACKED_FP32, 'tpe_mo_hv.hip': _NO_PACKED_FP32,
+               'tpe_interaction_mixed.hip': _NO_PACKED_FP32}
 
 
 def source_hash(deps=DEPS):

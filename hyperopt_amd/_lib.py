@@ -66,6 +66,9 @@ TPE_OPT_JOINT_CAP = 26
 TPE_JOINT_STREAM = 0x7FFFFFFF
 TPE_JOINT_MAX_GROUPS = 64
 TPE_INTERACTIONS_MAX_GRID = 1024
+TPE_AXIS_DENSE = 0
+TPE_AXIS_QUANTIZED = 1
+TPE_AXIS_CATEGORICAL = 2
 TPE_POOL_STREAM = 0x7FFFFFBF
 TPE_CMODEL_MAX = 8
 TPE_CMODEL_STREAM = 0x7FFF0000
@@ -205,6 +208,8 @@ SIGNATURES = {
     'tpe_importance': (ctypes.c_int, [_P, _I32, _P, _P, _P, _P, _P, _P, _P, _P, _P]),
     'tpe_interactions': (ctypes.c_int, [_P, _I32, _I32, _P, _P, _P, _P, _I64, _P, _P, _P, _I64, _P, _P, _P,
                                         ctypes.c_double, _I32, _P, _P, _P, _P, _P]),
+    'tpe_interactions_mixed': (ctypes.c_int, [_P, _I32, _P, _P, _P, _I64, _I64, _P, _P, _P, _I64, _P, _P, _P,
+                                              ctypes.c_double, ctypes.c_double, _I32, _P, _P, _P, _P, _P, _P]),
     'tpe_interactions_last_pair_ms': (ctypes.c_int, [_P, ctypes.POINTER(ctypes.c_float)]),
     'tpe_cmodel_set': (ctypes.c_int, [_P, _I32, _P, _I32, _P, _P, _P, _I64]),
     'tpe_cmodel_clear': (ctypes.c_int, [_P]),

@@ -51,6 +51,8 @@
 // chain, lanes by a shuffle tree, waves and tiles ascending -- and a partial
 // belongs to one pair's tile, so H and V are the same bits from run to run,
 // alone or among other pairs, and with the pairs in any order.
+// int_mass, int_accumulate, int_terms, the tile's epilogue and the per-context buffers live in
+// tpe_interaction.h, shared with tpe_interaction_mixed.hip.
 #include <hip/hip_runtime.h>
 
 #include <cmath>
@@ -60,24 +62,9 @@
 
 #include "../../include/hyperopt_tpe.h"
 #include "tpe_ctx.h"
+#include "tpe_interaction.h"
 
 namespace {
-
-constexpr int kIntTile = 64;   // cells per tile edge (4 waves of 32 x 32)
-constexpr int kIntKC = 16;     // components per LDS chunk
-// LDS row stride in doubles: 80 * 8 B = 2.5 x 256 B, so the four component
-// rows a wave reads in one ds_read_b64 start 32 banks apart
-constexpr int kIntLD = 80;
-constexpr int kIntThreads = 256;
-constexpr int kIntMargSplit = 4;   // k slices of a marginal, combined ascending
-
-typedef double v4d __attribute__((ext_vector_type(4)));
-
-struct IntSide {
-    const double *w, *mu, *sig;   // [Kp] (zero padded), [K][n_dim] x2
-    double *U, *mass;             // [n_dim][Kp][Gp], [n_dim][Kp]
-    int64_t K, Kp;
-};
 
 struct IntArgs {
     IntSide side[2];
@@ -88,19 +75,6 @@ struct IntArgs {
     int32_t n_dim, n_grid, Gp, n_pairs;
     double alpha;
 };
-
-// 1 - Phi(x) = erfc(x / sqrt 2) / 2
-__device__ __forceinline__ double int_tail(double x) { return 0.5 * erfc(x / 1.4142135623730951); }
-
-// Phi((high - mu)/s) - Phi((low - mu)/s) from the two tails on the side of the
-// mean the interval lies on
-__device__ __forceinline__ double int_mass(double mu, double s, double low, double high) {
-#pragma clang fp contract(off)
-    const double a = (low - mu) / s, b = (high - mu) / s;
-    if (a >= 0.0) return int_tail(a) - int_tail(b);
-    if (b <= 0.0) return int_tail(-b) - int_tail(-a);
-    return 1.0 - int_tail(-a) - int_tail(b);
-}
 
 // grid (ceil(Kp Gp / 256), n_dim, 2)
 __global__ __launch_bounds__(kIntThreads) void k_int_factor(IntArgs a) {
@@ -179,99 +153,6 @@ __global__ __launch_bounds__(kIntThreads) void k_int_marg(IntArgs a) {
     }
 }
 
-// One side's acc += (W U_d)^T U_e over every chunk of its components.  As / Bs:
-// the two LDS buffers of each factor tile.  A chunk is 16 x 64 doubles per
-// tile: a thread moves two double2 of each.
-__device__ __forceinline__ void int_accumulate(const IntSide& S, int Gp, int d, int e, int i0, int j0,
-                                               double (*As)[kIntKC][kIntLD], double (*Bs)[kIntKC][kIntLD],
-                                               v4d (&acc)[2][2]) {
-    const double* Ud = S.U + (int64_t)d * S.Kp * Gp + i0;
-    const double* Ue = S.U + (int64_t)e * S.Kp * Gp + j0;
-    const int t = threadIdx.x, lane = t & 63, wave = t >> 6;
-    const int wr = (wave >> 1) * 32, wc = (wave & 1) * 32;
-    const int row[2] = {t >> 5, (t + kIntThreads) >> 5}, col = (t & 31) * 2;
-    const int nchunks = (int)(S.Kp / kIntKC);
-    double2 ra[2], rb[2];
-    double wk[2];
-    auto fetch = [&](int c) {
-#pragma unroll
-        for (int r = 0; r < 2; ++r) {
-            const int64_t k = (int64_t)c * kIntKC + row[r];
-            ra[r] = *reinterpret_cast<const double2*>(Ud + k * Gp + col);
-            rb[r] = *reinterpret_cast<const double2*>(Ue + k * Gp + col);
-            wk[r] = S.w[k];
-        }
-    };
-    auto stage = [&](int buf) {
-#pragma unroll
-        for (int r = 0; r < 2; ++r) {
-            As[buf][row[r]][col] = wk[r] * ra[r].x;
-            As[buf][row[r]][col + 1] = wk[r] * ra[r].y;
-            Bs[buf][row[r]][col] = rb[r].x;
-            Bs[buf][row[r]][col + 1] = rb[r].y;
-        }
-    };
-    fetch(0);
-    stage(0);
-    __syncthreads();
-    for (int c = 0; c < nchunks; ++c) {
-        const int buf = c & 1;
-        if (c + 1 < nchunks) fetch(c + 1);
-#pragma unroll
-        for (int kk = 0; kk < kIntKC; kk += 4) {
-            // operand lanes: A[i = lane % 16][k = lane / 16], B[k = lane / 16][j = lane % 16]
-            const int kr = kk + (lane >> 4), x = lane & 15;
-            const double a0 = As[buf][kr][wr + x], a1 = As[buf][kr][wr + 16 + x];
-            const double b0 = Bs[buf][kr][wc + x], b1 = Bs[buf][kr][wc + 16 + x];
-            acc[0][0] = __builtin_amdgcn_mfma_f64_16x16x4f64(a0, b0, acc[0][0], 0, 0, 0);
-            acc[0][1] = __builtin_amdgcn_mfma_f64_16x16x4f64(a0, b1, acc[0][1], 0, 0, 0);
-            acc[1][0] = __builtin_amdgcn_mfma_f64_16x16x4f64(a1, b0, acc[1][0], 0, 0, 0);
-            acc[1][1] = __builtin_amdgcn_mfma_f64_16x16x4f64(a1, b1, acc[1][1], 0, 0, 0);
-        }
-        // (the other buffer was last read before the previous barrier)
-        if (c + 1 < nchunks) stage(buf ^ 1);
-        __syncthreads();
-    }
-}
-
-// the two terms of one cell (the header comment's sequence)
-__device__ __forceinline__ void int_terms(double L, double G, double Ld, double Le, double Gd, double Ge, double lLd,
-                                          double lLe, double lGd, double lGe, double alpha, double om, double ao,
-                                          double& tv, double& th) {
-#pragma clang fp contract(off)
-    const double aL = alpha * L;
-    const double p = aL + om * G;
-    if (p == 0.0) {
-        tv = th = 0.0;
-        return;
-    }
-    const double dev = (ao * (L - G)) / p;
-    tv = p * (dev * dev);
-    const double qi = alpha * (Ld * Le), ri = om * (Gd * Ge), den = qi + ri;
-    double dif;
-    if (den == 0.0) {
-        dif = dev;
-    } else {
-        const double mi = qi / den, ci = ri / den;
-        const double lo = log(L) - log(G);
-        const double loi = (lLd + lLe) - (lGd + lGe);
-        const double inf = __builtin_inf();
-        if (!(fabs(lo) < inf) || !(fabs(loi) < inf)) {
-            dif = aL / p - mi;
-        } else {
-            const double dl = lo - loi;
-            if (dl <= 0.0) {
-                const double t = expm1(dl);
-                dif = ((mi * ci) * t) / (1.0 + mi * t);
-            } else {
-                const double t = expm1(-dl);
-                dif = -((mi * ci) * t) / (1.0 + ci * t);
-            }
-        }
-    }
-    th = p * (dif * dif);
-}
-
 // grid (n_pairs, tile rows, tile columns)
 template <bool PLANES>
 __global__ __launch_bounds__(kIntThreads) void k_int_pair(IntArgs a) {
@@ -285,64 +166,18 @@ __global__ __launch_bounds__(kIntThreads) void k_int_pair(IntArgs a) {
     for (int bi = 0; bi < 2; ++bi)
 #pragma unroll
         for (int bj = 0; bj < 2; ++bj) accL[bi][bj] = accG[bi][bj] = v4d{0.0, 0.0, 0.0, 0.0};
-    int_accumulate(a.side[0], a.Gp, d, e, i0, j0, As, Bs, accL);
-    int_accumulate(a.side[1], a.Gp, d, e, i0, j0, As, Bs, accG);
+#pragma unroll
+    for (int s = 0; s < 2; ++s) {
+        const IntSide& S = a.side[s];
+        int_accumulate(S.U + (int64_t)d * S.Kp * a.Gp + i0, a.Gp, S.U + (int64_t)e * S.Kp * a.Gp + j0, a.Gp, S.w,
+                       (int)(S.Kp / kIntKC), As, Bs, s ? accG : accL);
+    }
 
-    // accumulator lanes: register r of a block holds D[i = 4 r + lane / 16][j = lane % 16] (settled by the plane
-    // tests at n_grid 15 .. 17: with 4 (lane / 16) + r the rows of a block come out permuted)
-    const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6;
-    const int wr = (wave >> 1) * 32, wc = (wave & 1) * 32;
-    const double alpha = a.alpha, om = 1.0 - alpha, ao = alpha * om;
-    const double Ab = a.A[2 * p], Aa = a.A[2 * p + 1];
-    const double* mg = a.marg + (int64_t)p * 4 * a.Gp;
-    const double* lg = a.lmarg + (int64_t)p * 4 * a.Gp;
-    double sv = 0.0, sh = 0.0;
-#pragma unroll
-    for (int bi = 0; bi < 2; ++bi) {
-#pragma unroll
-        for (int bj = 0; bj < 2; ++bj) {
-            const int j = j0 + wc + bj * 16 + (lane & 15);
-            const double Le = mg[a.Gp + j], Ge = mg[3 * a.Gp + j], lLe = lg[a.Gp + j], lGe = lg[3 * a.Gp + j];
-#pragma unroll
-            for (int r = 0; r < 4; ++r) {
-                const int i = i0 + wr + bi * 16 + 4 * r + (lane >> 4);
-                if (i < a.n_grid && j < a.n_grid) {
-                    const double L = accL[bi][bj][r] / Ab, G = accG[bi][bj][r] / Aa;
-                    double tv, th;
-                    int_terms(L, G, mg[i], Le, mg[2 * a.Gp + i], Ge, lg[i], lLe, lg[2 * a.Gp + i], lGe, alpha, om, ao,
-                              tv, th);
-                    sv += tv;
-                    sh += th;
-                    if (PLANES) {
-                        const int64_t at = ((int64_t)p * a.n_grid + i) * a.n_grid + j;
-                        a.planeL[at] = L;
-                        a.planeG[at] = G;
-                    }
-                }
-            }
-        }
-    }
-#pragma unroll
-    for (int off = 32; off > 0; off >>= 1) {
-        sv += __shfl_down(sv, off, 64);
-        sh += __shfl_down(sh, off, 64);
-    }
-    if (lane == 0) {
-        ws[0][wave] = sv;
-        ws[1][wave] = sh;
-    }
-    __syncthreads();
-    if (threadIdx.x == 0) {
-        double v = ws[0][0], h = ws[1][0];
-#pragma unroll
-        for (int w = 1; w < kIntThreads / 64; ++w) {
-            v += ws[0][w];
-            h += ws[1][w];
-        }
-        const int64_t at = ((int64_t)p * gridDim.y + ti) * gridDim.z + tj;
-        a.part[2 * at] = v;
-        a.part[2 * at + 1] = h;
-    }
+    const int64_t cells = (int64_t)p * a.n_grid * a.n_grid;
+    int_tile_epilogue<PLANES>(accL, accG, i0, j0, a.n_grid, a.n_grid, a.A[2 * p], a.A[2 * p + 1],
+                              a.marg + (int64_t)p * 4 * a.Gp, a.lmarg + (int64_t)p * 4 * a.Gp, a.Gp, a.alpha,
+                              PLANES ? a.planeL + cells : nullptr, PLANES ? a.planeG + cells : nullptr, ws,
+                              a.part + 2 * (((int64_t)p * gridDim.y + ti) * gridDim.z + tj));
 }
 
 // out[p] = (V, H): from 0.0 the pair's partials in ascending tile order, then
@@ -360,26 +195,6 @@ __global__ __launch_bounds__(kIntThreads) void k_int_sum(IntArgs a, int32_t tile
     a.out[2 * p] = hh * v;
     a.out[2 * p + 1] = hh * h;
 }
-
-struct IntState {
-    tpe_rt::DevBuf<double> y, geo, w[2], mu[2], sig[2], U[2], mass[2], A, marg, lmarg, part, out, pl, pg;
-    tpe_rt::DevBuf<int32_t> pairs;
-    tpe_rt::PinVec<double> out_h;
-    hipEvent_t ev[2] = {};   // the bracket of the last call's k_int_pair (tpe_interactions_last_pair_ms)
-    bool timed = false;
-    ~IntState() {
-        for (hipEvent_t e : ev)
-            if (e) (void)hipEventDestroy(e);
-    }
-};
-
-IntState* int_of(tpe_ctx* ctx) {
-    if (!ctx->inter)
-        ctx->inter = std::shared_ptr<void>(new IntState(), [](void* q) { delete static_cast<IntState*>(q); });
-    return static_cast<IntState*>(ctx->inter.get());
-}
-
-inline int64_t round_up(int64_t n, int64_t to) { return (n + to - 1) / to * to; }
 
 }  // namespace
 
@@ -413,8 +228,8 @@ int tpe_interactions(tpe_ctx* ctx, int32_t n_dim, int32_t n_grid, const double* 
     }
     if (n_pairs == 0) return TPE_OK;
 
-    const int32_t Gp = (int32_t)round_up(n_grid, kIntTile), nt = Gp / kIntTile;
-    const int64_t K[2] = {Kb, Ka}, Kp[2] = {round_up(Kb, kIntKC), round_up(Ka, kIntKC)};
+    const int32_t Gp = (int32_t)int_round_up(n_grid, kIntTile), nt = Gp / kIntTile;
+    const int64_t K[2] = {Kb, Ka}, Kp[2] = {int_round_up(Kb, kIntKC), int_round_up(Ka, kIntKC)};
     const double* w_in[2] = {wb, wa};
     const double* mu_in[2] = {mub, mua};
     const double* sig_in[2] = {sigb, siga};

@@ -60,6 +60,11 @@ JOINT_DIM_DTYPE = np.dtype({'names': ['kind', 'flags', 'low', 'high', 'stream'],
 assert JOINT_DIM_DTYPE.itemsize == ctypes.sizeof(L.JointDim)
 
 
+AXIS_DTYPE = np.dtype([('kind', '<i4'), ('n_cells', '<i4'), ('log', '<i4'), ('upper', '<i4'), ('x_off', '<i8'),
+                       ('p_off', '<i8'), ('measure', '<f8'), ('low', '<f8'), ('high', '<f8'), ('step', '<f8')])
+assert AXIS_DTYPE.itemsize == 64   # tpe_interaction_axis
+
+
 def bounds_flags(low, high, q):
     f = 0
     if low is not None:
@@ -962,6 +967,53 @@ class Engine(object):
                                               len(wa), _ptr(wa), _ptr(mua), _ptr(siga),
                                               float(alpha), P, _ptr(pairs), _ptr(H), _ptr(V), _ptr(L), _ptr(G)))
         return (H, V, L, G) if want_planes else (H, V)
+
+    def interactions_mixed(self, axes, below, above, prior_weight, alpha, pairs, want_planes=False):
+        """Engine.interactions for a group that may hold quantized and
+        categorical labels (tpe_interactions_mixed): axes a
+        posterior.InteractionAxis per label; below / above the sides' (W [K],
+        mu [K, D], sigma [K, D]) of posterior.joint_mixture(quantized=True,
+        categorical=True) -- a categorical column of the means holds the
+        observed categories; prior_weight that of the categorical kernels.
+        Returns (H, V) [P]; want_planes adds two lists of the pairs' planes,
+        pair (d, e)'s of shape [cells of d, cells of e]."""
+        D = len(axes)
+        rec = np.zeros(D, dtype=AXIS_DTYPE)
+        xs, ps = [], []
+        for d, ax in enumerate(axes):
+            x = _f64(ax.x).ravel()
+            rec[d] = (ax.kind, len(x), bool(ax.log), ax.upper, sum(len(v) for v in xs), sum(len(v) for v in ps),
+                      ax.measure, ax.low, ax.high, ax.step)
+            xs.append(x)
+            if ax.p is not None:
+                ps.append(_f64(ax.p).ravel())
+        x, cat_p = _f64(np.concatenate(xs)) if xs else np.zeros(0), _f64(np.concatenate(ps)) if ps else np.zeros(0)
+        sides = []
+        for side in (below, above):
+            w, mu, sig = _f64(side[0]).ravel(), _f64(side[1]), _f64(side[2])
+            if mu.shape != (len(w), D) or sig.shape != mu.shape:
+                raise ValueError('interactions_mixed: a side is (W [K], mu [K, D], sigma [K, D])')
+            sides.append((w, mu, sig))
+        pairs = np.ascontiguousarray(pairs, dtype=np.int32).reshape(-1, 2)
+        P = len(pairs)
+        H, V = np.zeros(P), np.zeros(P)
+        off = L = G = None
+        if want_planes:
+            inside = ((pairs >= 0) & (pairs < D)).all(axis=1)   # (a pair out of range is the library's to refuse)
+            cells = [int(rec['n_cells'][d]) * int(rec['n_cells'][e]) if ok else 0 for (d, e), ok in zip(pairs, inside)]
+            off = np.concatenate([[0], np.cumsum(cells)]).astype(np.int64)
+            L, G = np.empty(max(int(off[-1]), 1)), np.empty(max(int(off[-1]), 1))
+        (wb, mub, sigb), (wa, mua, siga) = sides
+        self._check(self.lib.tpe_interactions_mixed(self.h, D, _ptr(rec), _ptr(x), _ptr(cat_p), len(cat_p),
+                                                    len(wb), _ptr(wb), _ptr(mub), _ptr(sigb),
+                                                    len(wa), _ptr(wa), _ptr(mua), _ptr(siga),
+                                                    float(prior_weight), float(alpha), P, _ptr(pairs), _ptr(H), _ptr(V),
+                                                    _ptr(off), _ptr(L), _ptr(G)))
+        if not want_planes:
+            return H, V
+        shape = lambda k: (int(rec['n_cells'][pairs[k, 0]]), int(rec['n_cells'][pairs[k, 1]]))
+        return (H, V, [L[off[k]:off[k + 1]].reshape(shape(k)) for k in range(P)],
+                [G[off[k]:off[k + 1]].reshape(shape(k)) for k in range(P)])
 
     def interactions_last_pair_ms(self):
         """Device ms of the pair kernel in the last interactions call."""

@@ -550,6 +550,35 @@ def interaction_axis(kind, args, obs, n_grid):
         return a + (np.arange(n_grid) + 0.5) * h, h
 
 
+# One label's axis under tpe.interactions(mixed=True), the fields of the
+# library's tpe_interaction_axis: kind (TPE_AXIS_*), the cell points x, the
+# measure of a cell, the working-space bounds (NaN: not bounded), log (a
+# quantized label whose working space is log x), the cell step merge q of a
+# quantized label (0.0 otherwise), the number of categories (0: not
+# categorical) and their prior p (None).
+InteractionAxis = collections.namedtuple('InteractionAxis', 'kind x measure low high log step upper p')
+
+
+def interaction_axis_record(kind, args, obs, n_grid):
+    """The InteractionAxis of a label of any joint kind (DESIGN.md section 6b,
+    "Pairwise interactions"): a dense label keeps interaction_axis (n_grid
+    midpoints in the working space, measure h); a quantized or categorical one
+    takes importance_cells' cells with measure 1 -- a categorical label one
+    cell per category, a quantized one ceil(S / merge) cells of merge
+    consecutive support values, whose step is merge q."""
+    if kind in JOINT_CAT_KINDS:
+        upper, p = joint_cat_prior(kind, args)
+        x, _, _ = importance_cells(kind, args, obs, n_grid)
+        return InteractionAxis(L.TPE_AXIS_CATEGORICAL, x, 1.0, np.nan, np.nan, False, 0.0, upper, p)
+    pri = joint_prior(kind, args, quantized=True)
+    low, high = (pri.low, pri.high) if pri.bounded else (np.nan, np.nan)
+    if kind in JOINT_QUANT_KINDS:
+        x, _, merge = importance_cells(kind, args, obs, n_grid)
+        return InteractionAxis(L.TPE_AXIS_QUANTIZED, x, 1.0, low, high, pri.log, merge * pri.q, 0, None)
+    y, h = interaction_axis(kind, args, obs, n_grid)
+    return InteractionAxis(L.TPE_AXIS_DENSE, y, h, low, high, False, 0.0, 0, None)
+
+
 def joint_cat_prior(kind, args):
     """(upper, p) of a categorical joint-group label: p uniform for
     'randint', the label's own for 'categorical'."""

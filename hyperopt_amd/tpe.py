@@ -924,10 +924,11 @@ def pareto_front(trials, objectives, constraints=None):
     return sorted((d for d, b, vi in zip(docs, by, v) if b == 0 and vi == 0), key=lambda d: d['tid'])
 
 
-def _quantile_split(fn, space, trials, quantile, n_grid, max_grid, device, objectives, constraints, labels=None):
+def _quantile_split(fn, space, trials, quantile, n_grid, max_grid, device, objectives, constraints, labels=None,
+                    kinds=_post.JOINT_KINDS):
     """The common front of importance and interactions: the arguments checked
     (n_grid an integer in [1, max_grid], max_grid None: no upper end; labels,
-    if given, names of joint-kind labels of the space), the domain (keyed by
+    if given, names of labels of the space whose kind is among `kinds`), the domain (keyed by
     objectives / constraints), the history gathered and its complete trials
     split at the quantile.  Returns (specs, names, obs, tids, done,
     splitter): obs as history.gather returns it, tids the complete trials',
@@ -953,8 +954,8 @@ def _quantile_split(fn, space, trials, quantile, n_grid, max_grid, device, objec
     for k in labels or ():
         if k not in specs:
             raise ValueError('%s: unknown label %r' % (fn, k))
-        if specs[k].kind not in _post.JOINT_KINDS:
-            raise ValueError('%s: label %r is of kind %r, not one of %r' % (fn, k, specs[k].kind, _post.JOINT_KINDS))
+        if specs[k].kind not in kinds:
+            raise ValueError('%s: label %r is of kind %r, not one of %r' % (fn, k, specs[k].kind, kinds))
 
     def engine():
         return _engine.get_engine(device, 'f64', 'importance')
@@ -1068,7 +1069,7 @@ def importance(space, trials, quantile=0.1, n_grid=4096, prior_weight=_default_p
 
 
 def interactions(space, trials, quantile=0.1, n_grid=256, prior_weight=_default_prior_weight, device=0,
-                 labels=None, joint=False, objectives=None, constraints=None):
+                 labels=None, joint=False, objectives=None, constraints=None, mixed=False):
     """Which pairs of hyperparameters interact (not in the reference):
     {(label_d, label_e): interaction}, d before e in the space's order, sorted
     descending, ties in pair order, NaN pairs last.
@@ -1099,15 +1100,40 @@ def interactions(space, trials, quantile=0.1, n_grid=256, prior_weight=_default_
     context (engine.get_engine(device, 'f64', 'importance')).  A space without
     such a pair returns {}.
 
+    mixed=True: the quantized and the categorical labels take part too
+    (posterior.JOINT_QUANT_KINDS and JOINT_CAT_KINDS: hp.quniform, hp.randint,
+    hp.choice, ...), grouped and paired the same way and named in `labels`
+    like the others.  The mixtures are joint_mixture's with quantized=True,
+    categorical=True -- the joint model tpe.suggest(joint_quantized=True,
+    joint_categorical=True) samples from; each label's axis is
+    posterior.interaction_axis_record's: a dense label's as above, a
+    categorical label one cell per category, a quantized label the cells of
+    posterior.importance_cells (at most n_grid, each the mass of its rounding
+    interval), both with cell measure 1 in place of h.  Left out, with one
+    logger.info each, as tpe.suggest leaves them out of joint groups: a
+    'categorical' label whose p has a zero entry, and a categorical label
+    with more than 1024 categories.  One Engine.interactions_mixed call per
+    group; a pair of two dense labels has the value mixed=False gives it.
+
     ValueError, before any engine is touched: quantile outside (0, 1), n_grid
     not an integer in [1, 1024], fewer than 2 complete trials, a name in
     labels that is unknown or not of a joint kind, and what check_objectives,
     check_constraints and objective_rows refuse."""
+    kinds = _post.JOINT_KINDS + ((_post.JOINT_QUANT_KINDS + _post.JOINT_CAT_KINDS) if mixed else ())
     specs, names, obs, tids, done, splitter = _quantile_split(
         'interactions', space, trials, quantile, n_grid, _engine.L.TPE_INTERACTIONS_MAX_GRID, device, objectives,
-        constraints, labels)
+        constraints, labels, kinds)
     n = len(tids)
-    chosen = [k for k in names if specs[k].kind in _post.JOINT_KINDS and (labels is None or k in labels)]
+    chosen = [k for k in names if specs[k].kind in kinds and (labels is None or k in labels)]
+    for k in [k for k in chosen if specs[k].kind in _post.JOINT_CAT_KINDS]:
+        upper, p = _post.joint_cat_prior(specs[k].kind, specs[k].args)
+        if upper > _engine.L.TPE_INTERACTIONS_MAX_GRID:
+            logger.info('interactions: label %r has %d categories, more than %d: left out', k, upper,
+                        _engine.L.TPE_INTERACTIONS_MAX_GRID)
+            chosen.remove(k)
+        elif not np.all((p > 0.0) & np.isfinite(p)):
+            logger.info('interactions: categorical label %r has a zero prior probability: left out', k)
+            chosen.remove(k)
     if not done.all():
         obs = dict(obs)
         for k in chosen:
@@ -1125,19 +1151,24 @@ def interactions(space, trials, quantile=0.1, n_grid=256, prior_weight=_default_
         # a label's columns are the same in every pair of the group: the first
         # label's from its pair with the second, every other one's from its pair
         # with the first
-        mixes = [_post.joint_mixture([specs[g[0]], specs[k]], obs, splitter, prior_weight, bandwidth='scott')
-                 for k in g[1:]]
+        mixes = [_post.joint_mixture([specs[g[0]], specs[k]], obs, splitter, prior_weight, quantized=mixed,
+                                     categorical=mixed, bandwidth='scott') for k in g[1:]]
         below = (mixes[0].wb, np.column_stack([mixes[0].mub[:, 0]] + [m.mub[:, 1] for m in mixes]),
                  np.column_stack([mixes[0].sigb[:, 0]] + [m.sigb[:, 1] for m in mixes]))
         above = (mixes[0].wa, np.column_stack([mixes[0].mua[:, 0]] + [m.mua[:, 1] for m in mixes]),
                  np.column_stack([mixes[0].siga[:, 0]] + [m.siga[:, 1] for m in mixes]))
-        axes = [_post.interaction_axis(specs[k].kind, specs[k].args, obs[k][1], n_grid) for k in g]
-        pri = [_post.joint_prior(specs[k].kind, specs[k].args) for k in g]
         pairs = list(itertools.combinations(range(len(g)), 2))
-        H, V = _engine.get_engine(device, 'f64', 'importance').interactions([a[0] for a in axes], [a[1] for a in axes],
-                                     [p.low if p.bounded else np.nan for p in pri],
-                                     [p.high if p.bounded else np.nan for p in pri],
-                                     below, above, nb / (nb + na), pairs)
+        eng = _engine.get_engine(device, 'f64', 'importance')
+        if mixed:
+            axes = [_post.interaction_axis_record(specs[k].kind, specs[k].args, obs[k][1], n_grid) for k in g]
+            H, V = eng.interactions_mixed(axes, below, above, prior_weight, nb / (nb + na), pairs)
+        else:
+            axes = [_post.interaction_axis(specs[k].kind, specs[k].args, obs[k][1], n_grid) for k in g]
+            pri = [_post.joint_prior(specs[k].kind, specs[k].args) for k in g]
+            H, V = eng.interactions([a[0] for a in axes], [a[1] for a in axes],
+                                    [p.low if p.bounded else np.nan for p in pri],
+                                    [p.high if p.bounded else np.nan for p in pri],
+                                    below, above, nb / (nb + na), pairs)
         share = (nb + na) / n
         found += [(names.index(g[d]), names.index(g[e]), share * H[i], share * V[i])
                   for i, (d, e) in enumerate(pairs)]

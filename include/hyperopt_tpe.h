@@ -1051,6 +1051,71 @@ int tpe_interactions(tpe_ctx *ctx, int32_t n_dim, int32_t n_grid,
  * tpe_interactions call that had pairs.  TPE_ERR_ARG before such a call. */
 int tpe_interactions_last_pair_ms(tpe_ctx *ctx, float *ms);
 
+/* tpe_interactions for a group whose labels may be quantized or categorical
+ * (tpe.interactions(mixed=True)).  The mixtures are posterior.joint_mixture's
+ * with quantized=True, categorical=True: a categorical label's column of the
+ * means holds the observed categories.  Every label has an axis of its own:
+ * n_cells cells with the points x[x_off ..] and one measure, and per cell i
+ * the factor u_kd(i) of component k
+ *   TPE_AXIS_DENSE        the density at the midpoint y_i = x[x_off + i] (above);
+ *                         measure the cell width h_d
+ *   TPE_AXIS_QUANTIZED    the mass of the rounding interval of the label value
+ *                         x_i with the step `step` (= merge q: a cell of
+ *                         posterior.importance_cells merges `merge` support
+ *                         values): ub = x_i + step / 2, lb = x_i - step / 2;
+ *                         log == 0: clipped to [low, high] when bounded;
+ *                         log != 0: clipped to [exp low, exp high] when bounded,
+ *                         lb = max(0, lb), ub = log max(ub, 1e-12), lb likewise;
+ *                         u = Phi((ub - mu_kd)/s_kd) - Phi((lb - mu_kd)/s_kd), 0
+ *                         when ub <= lb, from the tails on the side of the mean
+ *                         the interval lies on.  No Jacobian; measure 1
+ *   TPE_AXIS_CATEGORICAL  r_kd[i] of tpe_joint_set_group, evaluated in linear
+ *                         space, each operation rounded on its own:
+ *                         a = (upper prior_weight) / K_S;  k = 0: p[i];
+ *                         k >= 1: ([i == mu_kd] + a p[i]) / (1 + a),
+ *                         p = cat_p + p_off; measure 1
+ * m_kd is the mass inside [low, high] (1 without bounds) for the first two
+ * kinds and 1 for a categorical axis.  A, L, G, the marginals, the per-cell
+ * sequence, V and H are tpe_interactions', the cell area measure_d measure_e.
+ * An axis of at most 16 cells is narrow: a narrow axis is one 16-row operand
+ * of the matrix instruction rather than a padded 64-cell tile; a dense x dense
+ * pair returns tpe_interactions' bits.  The same bits on every run, alone or
+ * among other pairs, in any order.  L / G (both or neither): pair p's planes
+ * [n_cells_d][n_cells_e] at plane_off[p], the offsets ascending from 0 and
+ * not overlapping.  One stream synchronisation; no resident posterior is
+ * touched; a multi-device context runs it on its primary device; TPE_F64
+ * contexts.  tpe_interactions_last_pair_ms covers the call's pair kernels.
+ * TPE_ERR_ARG: what tpe_interactions refuses; an unknown kind; n_cells outside
+ * [1, TPE_INTERACTIONS_MAX_GRID]; upper != n_cells or a prior outside cat_p for
+ * a categorical axis; a categorical mean that is no integer in [0, upper); a
+ * quantized step or a measure that is not positive and finite; a prior entry
+ * or a prior_weight that is not positive and finite; bad plane offsets.  Not
+ * checked, as tpe_interactions checks neither: low against high, and x_off +
+ * n_cells against the length of x, which the call is not given.  On an error
+ * the outputs are untouched. */
+#define TPE_AXIS_DENSE 0
+#define TPE_AXIS_QUANTIZED 1
+#define TPE_AXIS_CATEGORICAL 2
+typedef struct tpe_interaction_axis {
+    int32_t kind;      /* TPE_AXIS_* */
+    int32_t n_cells;   /* G_d */
+    int32_t log;       /* quantized: the working space is log x */
+    int32_t upper;     /* categorical: the number of categories (= n_cells) */
+    int64_t x_off;     /* the cell points: x[x_off .. x_off + n_cells) */
+    int64_t p_off;     /* categorical: the prior, cat_p[p_off .. p_off + upper) */
+    double measure;    /* of a cell: h_d, or 1 */
+    double low, high;  /* working-space bounds, NaN: not bounded */
+    double step;       /* quantized: merge q */
+} tpe_interaction_axis;
+int tpe_interactions_mixed(tpe_ctx *ctx, int32_t n_dim, const tpe_interaction_axis *axes /* [n_dim] */,
+                           const double *x, const double *cat_p, int64_t n_cat_p,
+                           int64_t Kb, const double *wb, const double *mub, const double *sigb,
+                           int64_t Ka, const double *wa, const double *mua, const double *siga,
+                           double prior_weight, double alpha,
+                           int32_t n_pairs, const int32_t *pairs /* [n_pairs][2] */,
+                           double *H, double *V /* [n_pairs] */,
+                           const int64_t *plane_off /* [n_pairs], with L / G */, double *L, double *G);
+
 /* Score a caller-supplied candidate set for one resident label (the parity
  * entry point: identical candidates in, both lpdf vectors and the winner
  * out).  lpdf_below / lpdf_above may be NULL. */
