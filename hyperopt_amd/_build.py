@@ -28,6 +28,7 @@ SOURCES = [os.path.join(HERE, 'csrc', 'tpe_engine.hip'),
            os.path.join(HERE, 'csrc', 'tpe_pool.hip'),
            os.path.join(HERE, 'csrc', 'tpe_mo.hip'),
            os.path.join(HERE, 'csrc', 'tpe_mo_hv.hip'),
+           os.path.join(HERE, 'csrc', 'tpe_mo_hvx.hip'),
            os.path.join(HERE, 'csrc', 'tpe_importance.hip'),
            os.path.join(HERE, 'csrc', 'tpe_interaction.hip'),
            os.path.join(HERE, 'csrc', 'tpe_interaction_mixed.hip'),
@@ -35,6 +36,7 @@ SOURCES = [os.path.join(HERE, 'csrc', 'tpe_engine.hip'),
 DEPS = SOURCES + [os.path.join(HERE, 'csrc', 'tpe_device.h'),
                   os.path.join(HERE, 'csrc', 'tpe_ctx.h'),
                   os.path.join(HERE, 'csrc', 'tpe_mo_hv.h'),
+                  os.path.join(HERE, 'csrc', 'tpe_mo_hvx.h'),
                   os.path.join(HERE, 'csrc', 'tpe_interaction.h'),
                   os.path.join(HERE, 'csrc', 'tpe_exp_table.h'),
                   os.path.join(REPO, 'include', 'hyperopt_tpe.h')]
@@ -50,9 +52,13 @@ FLAGS = ['--offload-arch=' + ARCH, '-O3', '-std=c++17', '-fPIC', '-shared',
 # resource figure; it keeps a later fp32 helper from being packed silently.
 # tpe_mo_hv.hip (integers and fp64 comparisons): the same.
 # tpe_interaction_mixed.hip (fp64 throughout): the same.
+# tpe_mo_hvx.hip (fp64 throughout): the same, and no contraction into fused
+# multiply-adds -- its sums are stated operation by operation, each rounded on
+# its own, and posterior.mo_exclusive gives the same bits.
 _NO_PACKED_FP32 = ['-Xclang', '-target-feature', '-Xclang', '-packed-fp32-ops']
 EXTRA_FLAGS = {'tpe_cmodel.hip': _NO_PACKED_FP32, 'tpe_mo_hv.hip': _NO_PACKED_FP32,
-               'tpe_interaction_mixed.hip': _NO_PACKED_FP32}
+               'tpe_interaction_mixed.hip': _NO_PACKED_FP32,
+               'tpe_mo_hvx.hip': _NO_PACKED_FP32 + ['-ffp-contract=off']}
 
 
 def source_hash(deps=DEPS):

@@ -62,6 +62,7 @@ TPE_OPT_PK_SLICED = 23
 TPE_OPT_DEFER_REPORT = 24
 TPE_OPT_LABEL_SHARDS = 25
 TPE_OPT_JOINT_CAP = 26
+TPE_OPT_MO_HVX_CAP = 27
 
 TPE_JOINT_STREAM = 0x7FFFFFFF
 TPE_JOINT_MAX_GROUPS = 64
@@ -205,6 +206,7 @@ SIGNATURES = {
     'tpe_mo_keys': (ctypes.c_int, [_P, _P, _I64, _I32, _P, _P, _P]),
     'tpe_mo_keys_constrained': (ctypes.c_int, [_P, _P, _I64, _I32, _P, _I32, _P, _P, _P, _P]),
     'tpe_mo_keys_hv': (ctypes.c_int, [_P, _P, _I64, _I32, _P, _I32, _I32, _P, _P, _P, _P, _P, _P, _P]),
+    'tpe_mo_exclusive': (ctypes.c_int, [_P, _P, _I64, _I32, _P, _P, _I32, _I32, _P, _P]),
     'tpe_importance': (ctypes.c_int, [_P, _I32, _P, _P, _P, _P, _P, _P, _P, _P, _P]),
     'tpe_interactions': (ctypes.c_int, [_P, _I32, _I32, _P, _P, _P, _P, _I64, _P, _P, _P, _I64, _P, _P, _P,
                                         ctypes.c_double, _I32, _P, _P, _P, _P, _P]),

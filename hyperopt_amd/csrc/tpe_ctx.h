@@ -454,6 +454,7 @@ struct Options {
     int64_t whole_n = 0;
     int32_t whole_rounds = 0;
     int64_t joint_flat_cap = 0;          // TPE_OPT_JOINT_CAP (0: tpe_joint.hip's kJFlatCap)
+    int64_t mo_hvx_cap = 0;              // TPE_OPT_MO_HVX_CAP (0: tpe_mo_hvx.h's kHvxCap)
     // the two capacities the engine itself adapts, after a round overflowed
     // them and before it runs again (run_round)
     double hot_cap_div = 16.0;           // TPE_OPT_HOT_DIV: hot lists hold n / hot_cap_div per cell (shrinks)

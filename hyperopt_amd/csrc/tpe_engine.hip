@@ -5723,6 +5723,11 @@ TPE_DEV int tpe1_set_option(tpe_ctx* ctx, int32_t option, int64_t value) {
                 return ctx->fail(TPE_ERR_ARG, "joint flat candidate cap must be in [0, 2^30]");
             ctx->opt.joint_flat_cap = value;
             break;
+        case TPE_OPT_MO_HVX_CAP:
+            if (value < 0 || value > 1024)
+                return ctx->fail(TPE_ERR_ARG, "exclusive-hypervolume kept-set capacity must be in [0, 1024]");
+            ctx->opt.mo_hvx_cap = value;
+            break;
         case TPE_OPT_BX_SPLIT:
             if (value < 0 || value > 8) return ctx->fail(TPE_ERR_ARG, "index window split must be in [0, 8]");
             ctx->opt.bx_split = (int32_t)value;

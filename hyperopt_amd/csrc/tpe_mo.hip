@@ -54,6 +54,13 @@
 //   rank  : uint32[M][n]   rows j with F[j][m] < F[i][m]
 //   lvl   : int32[2][n], lvl_r : uint32[M][n], flag : uint8[n]   the level
 //   hdr   : int32[4]; pick : int32[64]; gain : uint64[64]
+//
+// The exclusive hypervolumes of raw rows against a reference point
+// (tpe_mo_exclusive, two or three objectives): the upload of the constrained
+// call, k_moc_prep when constraints are given, then tpe_mo_hvx.hip's kernels.
+// Buffers of the context that only this call allocates:
+//   xflag : int32[n]  0 live, 1 weakly dominated within its J, 2 not valid
+//   xlive : int32[n]  the live rows; xhdr : int32[2]; excl : double[n]
 #include <hip/hip_runtime.h>
 #include <hipcub/hipcub.hpp>
 
@@ -64,6 +71,7 @@
 #include "../../include/hyperopt_tpe.h"
 #include "tpe_ctx.h"
 #include "tpe_mo_hv.h"
+#include "tpe_mo_hvx.h"
 
 using namespace tpe_rt;
 
@@ -223,6 +231,11 @@ struct MoState {
     DevBuf<unsigned long long> gain;
     PinVec<int32_t> pick_h;                 // hdr, then pick
     PinVec<unsigned long long> gain_h;
+    // tpe_mo_exclusive alone
+    DevBuf<int32_t> xflag, xlive, xhdr;
+    DevBuf<double> excl;
+    PinVec<double> excl_h;
+    PinVec<int32_t> xhdr_h;
 };
 
 MoState* mo_of(tpe_ctx* ctx) {
@@ -510,6 +523,62 @@ int tpe_mo_keys_hv(tpe_ctx* ctx, const double* objectives, int64_t n, int32_t n_
         if (gains) gains[k] = k < q ? (uint64_t)S->gain_h[k] : 0;
     }
     if (n_picked) *n_picked = q;
+    return TPE_OK;
+}
+
+int tpe_mo_exclusive(tpe_ctx* ctx, const double* objectives, int64_t n, int32_t n_obj, const double* reference,
+                     const double* constraints, int32_t n_con, int32_t mode, double* excl, int32_t* n_overflow) {
+    if (!ctx) return TPE_ERR_ARG;
+    if (!objectives || !reference || !excl) return ctx->fail(TPE_ERR_ARG, "tpe_mo_exclusive: null pointer");
+    if (n < 1 || n > kMoMaxRows) return ctx->fail(TPE_ERR_ARG, "tpe_mo_exclusive: n must be in [1, 2^20]");
+    if (n_obj != 2 && n_obj != 3) return ctx->fail(TPE_ERR_ARG, "tpe_mo_exclusive: n_obj must be 2 or 3");
+    if (constraints && (n_con < 1 || n_con > kMoMaxCon))
+        return ctx->fail(TPE_ERR_ARG, "tpe_mo_exclusive: n_con must be in [1, 8]");
+    if (mode != 0 && mode != 1) return ctx->fail(TPE_ERR_ARG, "tpe_mo_exclusive: mode must be 0 or 1");
+    HvxRef ref{};
+    for (int m = 0; m < n_obj; ++m) {
+        ref.r[m] = reference[m];
+        if (!(reference[m] - reference[m] == 0.0))
+            return ctx->fail(TPE_ERR_ARG, "tpe_mo_exclusive: the reference point must be finite");
+    }
+    HIPCHK(ctx, hipSetDevice(ctx->device));
+    hipStream_t st = ctx->stream;
+    MoState* S = mo_of(ctx);
+    const int32_t N = (int32_t)n;
+    const size_t nf = (size_t)n * n_obj, ng = constraints ? (size_t)n * n_con : 0;
+    HIPCHK(ctx, S->in.reserve(nf + ng));
+    HIPCHK(ctx, S->in_h.resize(nf + ng));
+    if (constraints) HIPCHK(ctx, S->v.reserve(n));
+    HIPCHK(ctx, S->xflag.reserve(n));
+    HIPCHK(ctx, S->xlive.reserve(n));
+    HIPCHK(ctx, S->xhdr.reserve(kHvxHdr));
+    HIPCHK(ctx, S->excl.reserve(n));
+    HIPCHK(ctx, S->excl_h.resize(n));
+    HIPCHK(ctx, S->xhdr_h.resize(kHvxHdr));
+    double* d_F = S->in.p;
+
+    // F (and G) in pinned memory: the call's one upload
+    std::memcpy(S->in_h.data(), objectives, nf * sizeof(double));
+    if (constraints) std::memcpy(S->in_h.data() + nf, constraints, ng * sizeof(double));
+    HIPCHK(ctx, hipMemcpyAsync(S->in.p, S->in_h.data(), (nf + ng) * sizeof(double), hipMemcpyHostToDevice, st));
+    const unsigned row_blocks = blocks_of(n, kBlock);
+    const unsigned slices = std::max(1u, std::min(row_blocks, (kMoBlocks + row_blocks - 1) / row_blocks));
+    const int32_t per_slice = (int32_t)((n + slices - 1) / slices);
+    const dim3 grid(row_blocks, blocks_of(n, per_slice));
+    if (constraints) {
+        // the rows that are dead or infeasible: NaN on the device copy
+        hipLaunchKernelGGL(k_moc_prep, dim3(row_blocks), dim3(kBlock), 0, st, d_F, S->in.p + nf, N, n_obj, n_con,
+                           S->v.p);
+        HIPCHK(ctx, hipGetLastError());
+    }
+    const int32_t cap = ctx->opt.mo_hvx_cap > 0 ? (int32_t)ctx->opt.mo_hvx_cap : kHvxCap;
+    hvx_launch(n_obj, st, d_F, N, ref, mode, cap, grid, per_slice, S->xflag.p, S->xlive.p, S->xhdr.p, S->excl.p);
+    HIPCHK(ctx, hipGetLastError());
+    HIPCHK(ctx, hipMemcpyAsync(S->excl_h.data(), S->excl.p, n * sizeof(double), hipMemcpyDeviceToHost, st));
+    HIPCHK(ctx, hipMemcpyAsync(S->xhdr_h.data(), S->xhdr.p, kHvxHdr * sizeof(int32_t), hipMemcpyDeviceToHost, st));
+    HIPCHK(ctx, hipStreamSynchronize(st));   // the call's one synchronisation
+    std::memcpy(excl, S->excl_h.data(), (size_t)n * sizeof(double));
+    if (n_overflow) *n_overflow = S->xhdr_h[1];
     return TPE_OK;
 }
 

@@ -847,6 +847,40 @@ class Engine(object):
                                                      _ptr(keys), _ptr(by), _ptr(do), _ptr(v)))
         return (keys, by, do, v) if want_counts else keys
 
+    def mo_exclusive(self, F, reference, mode, G=None, want_overflow=False):
+        """The exclusive hypervolumes of the rows of F [n, 2 or 3] against
+        `reference` (tpe_mo_exclusive; posterior.mo_exclusive states the rule
+        and gives the same bits): excl [n] float64, mode 'before' the gain of
+        each row over the valid rows before it, 'others' its contribution
+        among all valid rows.  G [n, K]: the constraint rows, a row with a
+        violation is not valid.  The rows whose kept set outgrew the kernel's
+        LDS capacity (NaN from the device, counted by it) are recomputed by the
+        numpy builder; want_overflow returns (excl, their number)."""
+        from . import posterior as _post
+        if mode not in _post.MO_EXCLUSIVE_MODES:
+            raise ValueError("mode must be 'before' or 'others'")
+        F = np.ascontiguousarray(F, dtype=np.float64)
+        if F.ndim != 2:
+            raise ValueError('F must be [n, n_objectives]')
+        n = F.shape[0]
+        ref = np.ascontiguousarray(reference, dtype=np.float64).ravel()
+        if len(ref) != F.shape[1]:
+            raise ValueError('reference must have a value for every objective')
+        if G is not None:
+            G = np.ascontiguousarray(G, dtype=np.float64)
+            if G.ndim != 2 or G.shape[0] != n:
+                raise ValueError('G must be [n, n_constraints], a row for every row of F')
+        excl = np.empty(n)
+        n_over = ctypes.c_int32(0)
+        self._check(self.lib.tpe_mo_exclusive(self.h, _ptr(F), n, F.shape[1], _ptr(ref), _ptr(G),
+                                              0 if G is None else G.shape[1],
+                                              _post.MO_EXCLUSIVE_MODES.index(mode), _ptr(excl),
+                                              ctypes.byref(n_over)))
+        if n_over.value:
+            rows = np.flatnonzero(np.isnan(excl))
+            excl[rows] = _post.mo_exclusive(F, ref, mode, G=G, rows=rows)[rows]
+        return (excl, n_over.value) if want_overflow else excl
+
     def importance(self, labels, cells, alpha, want_planes=False):
         """The importance sums of resident labels (tpe_importance): labels the
         label indices, each once; cells one (x, w, merge) per label
@@ -1096,7 +1130,8 @@ class Engine(object):
                'aux_families': L.TPE_OPT_AUX_FAMILIES,
                'bx_split': L.TPE_OPT_BX_SPLIT, 'bx_t': L.TPE_OPT_BX_T,
                'pk_sliced': L.TPE_OPT_PK_SLICED, 'defer_report': L.TPE_OPT_DEFER_REPORT,
-               'label_shards': L.TPE_OPT_LABEL_SHARDS, 'joint_cap': L.TPE_OPT_JOINT_CAP}
+               'label_shards': L.TPE_OPT_LABEL_SHARDS, 'joint_cap': L.TPE_OPT_JOINT_CAP,
+               'mo_hvx_cap': L.TPE_OPT_MO_HVX_CAP}
 
     def set_option(self, name, value):
         """Engine switches (include/hyperopt_tpe.h TPE_OPT_*): 'screen',

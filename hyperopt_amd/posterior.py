@@ -266,6 +266,96 @@ def mo_hypervolume_order(F, by, do, keys, n_select, G=None):
     return out, lev[picks].astype(np.int32), np.asarray(gains, dtype=np.uint64)
 
 
+MO_EXCLUSIVE_MODES = ('before', 'others')
+
+
+def mo_hv_valid(F, reference, G=None):
+    """The rows of F [n, M] that count for the hypervolume against
+    `reference`: every objective finite and below the reference on its axis
+    and, with the constraint rows G, mo_violation == 0.  bool [n]."""
+    F = np.asarray(F, dtype=np.float64)
+    with np.errstate(invalid='ignore'):
+        valid = (np.isfinite(F) & (F < np.asarray(reference, dtype=np.float64))).all(axis=1)
+    if G is not None:
+        valid &= mo_violation(G, F) == 0.0
+    return valid
+
+
+def _mo_minimal(C):
+    """The distinct minimal elements of the rows of C [k, M] -- the rows that
+    no other row lies weakly below, one of equal rows.  In lexicographic order
+    the first row left is minimal; it takes out every row weakly above it."""
+    C = C[np.lexsort(C.T[::-1])]
+    left = np.ones(len(C), dtype=bool)
+    kept, p = [], 0
+    while p < len(C):
+        step = int(np.argmax(left[p:]))
+        if not left[p + step]:
+            break
+        p += step
+        kept.append(p)
+        left[p:] &= ~(C[p:] >= C[p]).all(axis=1)
+    return C[kept]
+
+
+def _mo_uncovered(a, r, K):
+    """The volume of the box [a, r) that the boxes [K[j], r) leave uncovered,
+    K [k, M] the kept points (inside the box, mutually non-dominated) -- the
+    sums of tpe_mo_exclusive, operation by operation.  M = 2: the scan by
+    ascending x.  M = 3: slabs by ascending z; slab s holds the points of
+    z-rank < s, and its area is that scan, every slab at once."""
+    k, M = K.shape
+    if M == 3:
+        K = K[np.argsort(K[:, 2], kind='stable')]
+        z = np.concatenate([a[2:], K[:, 2], r[2:]])
+        lim = np.arange(k + 1)
+    else:
+        lim = np.array([k])
+    cx, cy, area = np.full(len(lim), a[0]), np.full(len(lim), r[1]), np.zeros(len(lim))
+    for p in np.lexsort((K[:, 1], K[:, 0])):
+        x, y = K[p, 0], K[p, 1]
+        step = (p < lim) & (y < cy)
+        area[step] = area[step] + (x - cx[step]) * (cy[step] - a[1])
+        cx[step], cy[step] = x, y
+    area = area + (r[0] - cx) * (cy - a[1])
+    if M == 2:
+        return float(area[0])
+    return float(np.cumsum((z[1:] - z[:-1]) * area)[-1])    # (cumsum: left to right)
+
+
+def mo_exclusive(F, reference, mode, G=None, rows=None):
+    """The exclusive hypervolumes of the rows of F [n, 2 or 3], all minimised,
+    against `reference` (the numpy restatement of tpe_mo_exclusive,
+    include/hyperopt_tpe.h, and its bits): float64 [n].  With box(i) = prod_m
+    [F[i, m], reference[m]) and HV(S) the volume of the union of the boxes of S,
+    excl[i] = HV(J + i) - HV(J), J the valid rows (mo_hv_valid) before i for
+    mode 'before' -- the hypervolume gained by trial i -- and every other valid
+    row for 'others' -- row i's contribution.  0 for a row that is not valid.
+    A row that a row of J weakly dominates has 0; for every other one the rows
+    of J are clipped to F[i], the minimal clipped rows kept and the uncovered
+    part of box(i) summed from non-negative terms (_mo_uncovered).
+    rows: only these rows are computed (Engine.mo_exclusive's overflow rows)."""
+    F = np.asarray(F, dtype=np.float64)
+    if F.ndim != 2 or F.shape[1] not in (2, 3):
+        raise ValueError('F must be [n, 2 or 3 objectives]')
+    r = np.asarray(reference, dtype=np.float64)
+    if r.shape != (F.shape[1],) or not np.isfinite(r).all():
+        raise ValueError('reference must be %d finite values' % F.shape[1])
+    if mode not in MO_EXCLUSIVE_MODES:
+        raise ValueError("mode must be 'before' or 'others'")
+    valid = mo_hv_valid(F, r, G)
+    idx = np.flatnonzero(valid)
+    Fv = F[idx]
+    excl = np.zeros(len(F))
+    for i in (idx if rows is None else [i for i in rows if valid[i]]):
+        pos = int(np.searchsorted(idx, i))
+        J = Fv[:pos] if mode == 'before' else np.delete(Fv, pos, axis=0)
+        if len(J) and (J <= F[i]).all(axis=1).any():
+            continue
+        excl[i] = _mo_uncovered(F[i], r, _mo_minimal(np.maximum(J, F[i])))
+    return excl
+
+
 def mo_keys(F, counts=None, G=None, tiebreak='dominates', n_select=0):
     """The Pareto-compliant total order of the objective vectors F [n, M] as
     one loss column: keys[i] is row i's position, 0 .. as a float64, under

@@ -924,6 +924,91 @@ def pareto_front(trials, objectives, constraints=None):
     return sorted((d for d, b, vi in zip(docs, by, v) if b == 0 and vi == 0), key=lambda d: d['tid'])
 
 
+def hypervolume(trials, objectives, reference=None, constraints=None, history=False, contributions=False,
+                builder='auto', device=0):
+    """The hypervolume indicator of the complete trials under 2 or 3
+    objectives, all minimised (not in the reference; the number Optuna's
+    plot_hypervolume_history draws): a dict with
+        hypervolume    the volume of the union of the boxes [F[i], reference)
+                       of the valid rows, 0.0 when there is none;
+        reference      the reference point used, a tuple;
+        tids           the complete trials' tids, ascending -- the rows;
+        skipped        the rows that are not valid;
+        history        (history=True) float64 [len(tids)]: np.cumsum of the
+                       gains, gain[t] = HV(valid rows up to t) - HV(valid rows
+                       before t), summed in trial order;
+        contributions  (contributions=True) {tid: HV(all) - HV(all but tid)}
+                       for the rows where that is positive -- members of the
+                       front that are no copy of another one -- largest first,
+                       ties by tid.
+    hypervolume is history[-1].  Rows as objective_rows gives them ('loss' read
+    as result.get('loss')), in tid order.  A row is valid when every objective
+    is finite, it lies below the reference on every axis and, with
+    `constraints` (result keys, <= 0 satisfied, as pareto_front), its
+    violation is 0.  reference: one finite float per objective; None: per
+    objective, over the rows that are finite (and feasible), max + 0.1 (max -
+    min), max + 1.0 when max == min (zeros without such a row).
+
+    posterior.mo_exclusive states the rule and is builder='host';
+    builder='device' is Engine.mo_exclusive on importance's engine (the history
+    tpe.suggest keeps resident stays where it is), 'auto' the device from
+    MO_DEVICE_MIN_TRIALS complete trials on.  The same bits either way.
+
+    ValueError, before any engine is touched: what check_objectives,
+    check_constraints and objective_rows refuse, a number of objectives other
+    than 2 or 3, a reference of another length or with a non-finite entry, an
+    unknown builder."""
+    objectives = check_objectives(objectives)
+    if objectives is None or len(objectives) not in (2, 3):
+        raise ValueError('hypervolume needs 2 or 3 objectives, got %d' % len(objectives or ()))
+    constraints = check_constraints(constraints, objectives)
+    if builder not in ('auto', 'host', 'device'):
+        raise ValueError("hypervolume: builder must be 'auto', 'host' or 'device'")
+    M = len(objectives)
+    if reference is not None:
+        try:
+            reference = np.asarray(reference, dtype=np.float64)
+        except (TypeError, ValueError):
+            raise ValueError('hypervolume: reference must be %d finite floats' % M)
+        if reference.shape != (M,) or not np.isfinite(reference).all():
+            raise ValueError('hypervolume: reference must be %d finite floats' % M)
+    docs = sorted(trials.trials, key=operator.itemgetter('tid'))
+    if constraints is None:
+        docs, F = objective_rows(docs, objectives)
+        G = None
+    else:
+        docs, F, G = objective_rows(docs, objectives, constraints=constraints)
+    if len(docs) > _post.MO_MAX_ROWS:
+        raise ValueError('objectives: at most %d complete trials' % _post.MO_MAX_ROWS)
+    if reference is None:
+        ok = np.isfinite(F).all(axis=1)
+        if G is not None:
+            ok &= _post.mo_violation(G, F) == 0.0
+        reference = np.zeros(M)
+        if ok.any():
+            hi, lo = F[ok].max(axis=0), F[ok].min(axis=0)
+            reference = np.where(hi > lo, hi + 0.1 * (hi - lo), hi + 1.0)
+    valid = _post.mo_hv_valid(F, reference, G)
+    on_device = len(F) and (builder == 'device' or (builder == 'auto' and len(F) >= MO_DEVICE_MIN_TRIALS))
+
+    def exclusive(mode):
+        if not valid.any():
+            return np.zeros(len(F))
+        if on_device:
+            return _engine.get_engine(device, 'f64', 'importance').mo_exclusive(F, reference, mode, G=G)
+        return _post.mo_exclusive(F, reference, mode, G=G)
+    curve = np.cumsum(exclusive('before'))
+    out = dict(hypervolume=float(curve[-1]) if len(curve) else 0.0, reference=tuple(reference.tolist()),
+               tids=[d['tid'] for d in docs], skipped=int(len(F) - np.count_nonzero(valid)))
+    if history:
+        out['history'] = curve
+    if contributions:
+        c = exclusive('others')
+        rows = sorted(np.flatnonzero(c > 0).tolist(), key=lambda i: (-c[i], out['tids'][i]))
+        out['contributions'] = {out['tids'][i]: float(c[i]) for i in rows}
+    return out
+
+
 def _quantile_split(fn, space, trials, quantile, n_grid, max_grid, device, objectives, constraints, labels=None,
                     kinds=_post.JOINT_KINDS):
     """The common front of importance and interactions: the arguments checked

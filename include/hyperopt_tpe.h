@@ -882,6 +882,52 @@ int tpe_mo_keys_hv(tpe_ctx *ctx, const double *objectives /* [n][n_obj] row-majo
                    int32_t *picked /* [n_select] or NULL */, uint64_t *gains /* [n_select] or NULL */,
                    int32_t *n_picked /* or NULL */);
 
+/* The hypervolume indicator's exclusive volumes (tpe.hypervolume): raw
+ * objective values, all minimised, against a reference point.  n_obj 2 or 3.
+ * No reference counterpart (the indicator of Zitzler & Thiele; Optuna's
+ * plot_hypervolume_history draws the same curve).
+ *   valid rows: every objective finite, F[i][m] < reference[m] on every axis
+ *       and, when constraints is not NULL, violation 0 as
+ *       tpe_mo_keys_constrained defines it (a NaN constraint: not valid);
+ *   box(i) = prod_m [F[i][m], reference[m]); HV(S) = the volume of the union of
+ *       the boxes of S; J(i) = the valid rows before i (mode 0) or every other
+ *       valid row (mode 1);
+ *   excl[i] = HV(J(i) + i) - HV(J(i)) for a valid row, 0 for every other row.
+ *       Mode 0: the gain of row i in trial order -- the running sum is the
+ *       hypervolume history.  Mode 1: the row's contribution (0 for a dominated
+ *       row and for each of two equal rows).
+ * A row that a row of J(i) weakly dominates has excl exactly 0.  For every other
+ * valid row, with a = F[i]: the rows of J(i) are clipped to a (max per axis),
+ * the distinct minimal elements of the clipped rows kept, and
+ *   n_obj 2: scanning the kept points by ascending first axis from (cx, cy) =
+ *       (a_0, reference_1) with A = 0, a point (x, y) with y < cy adds
+ *       (x - cx) (cy - a_1) and becomes (cx, cy); finally A += (reference_0 -
+ *       cx) (cy - a_1); excl = A;
+ *   n_obj 3: the kept points by ascending third axis z_0 <= .. <= z_{k-1}, slab
+ *       s = 0 .. k between z_{s-1} and z_s (z_{-1} = a_2, z_k = reference_2) has
+ *       the area A_s of that scan over the kept points of rank < s, and excl =
+ *       sum over ascending s of (z_s - z_{s-1}) A_s
+ * -- fp64, every operation rounded on its own in the order written (no fused
+ * multiply-add), only non-negative terms: the same bits on every run and the
+ * bits of posterior.mo_exclusive.  Integer-valued inputs below 2^53 in every
+ * product and sum give the exact integers.
+ * A live row's kept set is held in LDS, at most 1024 points
+ * (TPE_OPT_MO_HVX_CAP lowers it); a row whose set outgrows that gets excl[i] =
+ * NaN and counts in *n_overflow (the caller recomputes those rows; no valid
+ * result is a NaN for objectives whose differences are finite).  n_overflow
+ * may be NULL.  One upload, one stream synchronisation, no cooperative launch.
+ * Its own reusable buffers (counted by tpe_device_bytes) are allocated by the
+ * first such call; the tpe_mo_keys calls neither touch them nor change their
+ * results.  A multi-device context runs it on its primary device.
+ * TPE_ERR_ARG: a NULL objectives, reference or excl; n < 1 or n > 2^20; n_obj
+ * not 2 or 3; a reference entry that is not finite; n_con outside [1, 8] with
+ * constraints; mode not 0 or 1.  On an error the outputs are untouched. */
+int tpe_mo_exclusive(tpe_ctx *ctx, const double *objectives /* [n][n_obj] row-major */,
+                     int64_t n, int32_t n_obj, const double *reference /* [n_obj] */,
+                     const double *constraints /* [n][n_con] row-major, or NULL */, int32_t n_con,
+                     int32_t mode /* 0: rows before i, 1: every other row */,
+                     double *excl /* [n] */, int32_t *n_overflow /* or NULL */);
+
 /* ---- constraint densities (c-TPE) -------------------------------------------
  * tpe.suggest(constraints=..., constraint_model='density'): besides the
  * resident posterior (model 0, the objective's) a context holds up to eight
@@ -1319,6 +1365,9 @@ int tpe_screen_probe(tpe_ctx *ctx, int32_t label, const double *cand, int64_t n,
  *                   launch of tpe_joint_suggest_batch; the rounds run in
  *                   chunks within it (same rows; tests; 0: the default,
  *                   at most 2^30)                                      [2^20]
+ *   TPE_OPT_MO_HVX_CAP  points of a live row's kept set tpe_mo_exclusive
+ *                   holds in LDS before it reports the row in n_overflow
+ *                   (tests; 0: the default, at most 1024)              [1024]
  *   TPE_OPT_WIN_GROUPS  label groups of a windowed round, each sorted on a
  *                   second stream while the previous one is screened
  *                   (0: one group; the chip is busy either way)          [0]
@@ -1358,6 +1407,7 @@ int tpe_screen_probe(tpe_ctx *ctx, int32_t label, const double *cand, int64_t n,
 #define TPE_OPT_DEFER_REPORT 24
 #define TPE_OPT_LABEL_SHARDS 25
 #define TPE_OPT_JOINT_CAP 26
+#define TPE_OPT_MO_HVX_CAP 27
 int tpe_set_option(tpe_ctx *ctx, int32_t option, int64_t value);
 
 /* Build now what the resident posterior's first round(s) of n_candidates

@@ -5,6 +5,7 @@
     python tools/time_mo.py --gpus 1 --constraints K [--out FILE]
     python tools/time_mo.py --gpus 1 --quality-constrained [--evals 100] [--out FILE]
     python tools/time_mo.py --gpus 1 --density [--out FILE]
+    python tools/time_mo.py --gpus 1 --indicator [--host-max-n 10000] [--out FILE]
 
 * Engine.mo_keys (tpe_mo_keys: upload, all-pairs kernel, pack, radix sort,
   scatter, read-back; one synchronisation) at n in {1000, 10000, 50000} x M in
@@ -60,6 +61,14 @@ the default Engine.mo_keys(F), alternating, at the sizes above x 2 and 3
 objectives, with the level size and the picks of each input, and the worst case
 of a 100 000-row antichain (one level) at 3 objectives; with --quality it adds
 the row objectives_hypervolume to the ZDT1 table.
+
+--indicator (tpe.hypervolume): Engine.mo_exclusive (tpe_mo_exclusive: upload,
+validity, domination pass, live-row list, a workgroup per live row, read-back)
+against posterior.mo_exclusive, the numpy builder, alternating, at the sizes
+above x 2 and 3 objectives x both modes, and on a 3000-row antichain at 3
+objectives (every row live); median of --reps calls, the numpy builder up to
+--host-max-n rows; with the live rows, the overflow count and whether both give
+the same bits.
 
 Results are appended to --out as one JSON object per line."""
 import argparse
@@ -367,18 +376,41 @@ def quality_constrained_at(args, limit):
     return rec
 
 
-def hypervolume(F, ref):
-    """The area dominated by the rows of F [n, 2] inside the box below `ref`."""
-    F = F[(F < ref).all(axis=1)]
-    if not len(F):
-        return 0.0
-    F = F[np.lexsort((F[:, 1], F[:, 0]))]
-    area, low = 0.0, ref[1]
-    for f1, f2 in F:
-        if f2 < low:
-            area += (ref[0] - f1) * (low - f2)
-            low = f2
-    return float(area)
+def indicator_times(args):
+    """tpe.hypervolume's two columns (Engine.mo_exclusive against posterior.mo_exclusive), alternating."""
+    from hyperopt_amd import posterior as P
+    from hyperopt_amd.engine import Engine
+    eng = Engine(0, 'f64')
+    inputs = [('uniform', n, M, np.random.RandomState(n + M).uniform(size=(n, M))) for n in SIZES for M in (2, 3)]
+    t = np.arange(3000.0)
+    inputs.append(('antichain', 3000, 3, np.column_stack([t, 3000 - t, np.random.RandomState(7).uniform(size=3000)])))
+    out = []
+    for kind, n, M, F in inputs:
+        ref = tuple((F.max(axis=0) + 0.1 * (F.max(axis=0) - F.min(axis=0))).tolist())
+        for mode in P.MO_EXCLUSIVE_MODES:
+            legs = dict(device=lambda: eng.mo_exclusive(F, ref, mode, want_overflow=True))
+            if n <= args.host_max_n:   # (the numpy builder takes half a minute a call and more at 50 000 rows)
+                legs['host'] = lambda: P.mo_exclusive(F, ref, mode)
+            ts = {name: [] for name in legs}
+            got = {name: legs[name]() for name in legs}               # warm-up
+            for _ in range(args.reps):                                 # alternating
+                for name in legs:
+                    t0 = time.perf_counter()
+                    legs[name]()
+                    ts[name].append((time.perf_counter() - t0) * 1e3)
+            rec = dict(what='mo_exclusive', rows=kind, n=n, M=M, mode=mode,
+                       live=int(np.count_nonzero(got['device'][0])), n_overflow=int(got['device'][1]))
+            for name, v in ts.items():
+                rec[name] = dict(median_ms=float(np.median(v)), min_ms=float(min(v)), max_ms=float(max(v)), reps=len(v))
+            if 'host' in legs:
+                rec['same_bits'] = bool(np.array_equal(got['device'][0], got['host']))
+                rec['host_over_device'] = rec['host']['median_ms'] / rec['device']['median_ms']
+            else:
+                rec['host'] = 'not measured'
+            print(json.dumps(rec), flush=True)
+            out.append(rec)
+    eng.close()
+    return out
 
 
 def quality(args):
@@ -410,8 +442,7 @@ def quality(args):
         for seed in range(args.seeds):
             trials = Trials()
             fmin(fn, space, algo=algo, max_evals=args.evals, trials=trials, rstate=np.random.RandomState(seed))
-            F = np.array([(d['result'][first], d['result']['cost']) for d in trials.trials])
-            hv.append(hypervolume(F, ref))
+            hv.append(tpe.hypervolume(trials, (first, 'cost'), reference=ref)['hypervolume'])
         rec[name] = dict(mean=float(np.mean(hv)), min=float(min(hv)), max=float(max(hv)),
                          std=float(np.std(hv)))
     print(json.dumps(rec), flush=True)
@@ -427,6 +458,7 @@ def main():
     ap.add_argument('--constraints', type=int, default=0, metavar='K')
     ap.add_argument('--quality-constrained', action='store_true')
     ap.add_argument('--density', action='store_true')
+    ap.add_argument('--indicator', action='store_true')
     ap.add_argument('--tiebreak', choices=('dominates', 'hypervolume'), default='dominates')
     ap.add_argument('--evals', type=int)
     ap.add_argument('--seeds', type=int, default=10)
@@ -438,7 +470,9 @@ def main():
         args.evals = 100 if args.quality_constrained else 200
     if args.constraints and not 1 <= args.constraints <= 8:
         ap.error('--constraints: 1 to 8 columns')
-    if args.quality_constrained:
+    if args.indicator:
+        recs = indicator_times(args)
+    elif args.quality_constrained:
         recs = quality_constrained(args)
     elif args.density:
         recs = density_step_times(args)
