@@ -56,9 +56,10 @@
 //   hdr   : int32[4]; pick : int32[64]; gain : uint64[64]
 //
 // The exclusive hypervolumes of raw rows against a reference point
-// (tpe_mo_exclusive, two or three objectives): the upload of the constrained
-// call, k_moc_prep when constraints are given, then tpe_mo_hvx.hip's kernels.
-// Buffers of the context that only this call allocates:
+// (tpe_mo_exclusive, two or three objectives; tpe_mo_exclusive4, four): the
+// upload of the constrained call, k_moc_prep when constraints are given, then
+// tpe_mo_hvx.hip's kernels or tpe_mo_hvx4.hip's.  Buffers of the context that
+// only these calls allocate, whichever comes first (the same for both):
 //   xflag : int32[n]  0 live, 1 weakly dominated within its J, 2 not valid
 //   xlive : int32[n]  the live rows; xhdr : int32[2]; excl : double[n]
 #include <hip/hip_runtime.h>
@@ -72,6 +73,7 @@
 #include "tpe_ctx.h"
 #include "tpe_mo_hv.h"
 #include "tpe_mo_hvx.h"
+#include "tpe_mo_hvx4.h"
 
 using namespace tpe_rt;
 
@@ -231,7 +233,7 @@ struct MoState {
     DevBuf<unsigned long long> gain;
     PinVec<int32_t> pick_h;                 // hdr, then pick
     PinVec<unsigned long long> gain_h;
-    // tpe_mo_exclusive alone
+    // tpe_mo_exclusive and tpe_mo_exclusive4 alone
     DevBuf<int32_t> xflag, xlive, xhdr;
     DevBuf<double> excl;
     PinVec<double> excl_h;
@@ -263,6 +265,71 @@ void launch_pairs_of(int32_t n_obj, dim3 grid, hipStream_t st, const double* F, 
         case 7: launch_pairs<7>(grid, st, F, n, per_slice, by, dom); break;
         default: launch_pairs<8>(grid, st, F, n, per_slice, by, dom); break;
     }
+}
+
+// tpe_mo_exclusive (n_obj 2 or 3: tpe_mo_hvx.hip) and tpe_mo_exclusive4 (n_obj 4:
+// tpe_mo_hvx4.hip) behind their n_obj checks: the same arguments, errors (under
+// the entry's name `who`), upload, buffers and read-back.
+int mo_exclusive_run(tpe_ctx* ctx, const char* who, const double* objectives, int64_t n, int32_t n_obj,
+                     const double* reference, const double* constraints, int32_t n_con, int32_t mode, double* excl,
+                     int32_t* n_overflow) {
+    const std::string name(who);
+    if (!objectives || !reference || !excl) return ctx->fail(TPE_ERR_ARG, name + ": null pointer");
+    if (n < 1 || n > kMoMaxRows) return ctx->fail(TPE_ERR_ARG, name + ": n must be in [1, 2^20]");
+    if (constraints && (n_con < 1 || n_con > kMoMaxCon))
+        return ctx->fail(TPE_ERR_ARG, name + ": n_con must be in [1, 8]");
+    if (mode != 0 && mode != 1) return ctx->fail(TPE_ERR_ARG, name + ": mode must be 0 or 1");
+    Hvx4Ref ref4{};
+    for (int m = 0; m < n_obj; ++m) {
+        ref4.r[m] = reference[m];
+        if (!(reference[m] - reference[m] == 0.0))
+            return ctx->fail(TPE_ERR_ARG, name + ": the reference point must be finite");
+    }
+    const HvxRef ref{{ref4.r[0], ref4.r[1], ref4.r[2]}};
+    HIPCHK(ctx, hipSetDevice(ctx->device));
+    hipStream_t st = ctx->stream;
+    MoState* S = mo_of(ctx);
+    const int32_t N = (int32_t)n;
+    const size_t nf = (size_t)n * n_obj, ng = constraints ? (size_t)n * n_con : 0;
+    HIPCHK(ctx, S->in.reserve(nf + ng));
+    HIPCHK(ctx, S->in_h.resize(nf + ng));
+    if (constraints) HIPCHK(ctx, S->v.reserve(n));
+    HIPCHK(ctx, S->xflag.reserve(n));
+    HIPCHK(ctx, S->xlive.reserve(n));
+    HIPCHK(ctx, S->xhdr.reserve(kHvxHdr));
+    HIPCHK(ctx, S->excl.reserve(n));
+    HIPCHK(ctx, S->excl_h.resize(n));
+    HIPCHK(ctx, S->xhdr_h.resize(kHvxHdr));
+    double* d_F = S->in.p;
+
+    // F (and G) in pinned memory: the call's one upload
+    std::memcpy(S->in_h.data(), objectives, nf * sizeof(double));
+    if (constraints) std::memcpy(S->in_h.data() + nf, constraints, ng * sizeof(double));
+    HIPCHK(ctx, hipMemcpyAsync(S->in.p, S->in_h.data(), (nf + ng) * sizeof(double), hipMemcpyHostToDevice, st));
+    const unsigned row_blocks = blocks_of(n, kBlock);
+    const unsigned slices = std::max(1u, std::min(row_blocks, (kMoBlocks + row_blocks - 1) / row_blocks));
+    const int32_t per_slice = (int32_t)((n + slices - 1) / slices);
+    const dim3 grid(row_blocks, blocks_of(n, per_slice));
+    if (constraints) {
+        // the rows that are dead or infeasible: NaN on the device copy
+        hipLaunchKernelGGL(k_moc_prep, dim3(row_blocks), dim3(kBlock), 0, st, d_F, S->in.p + nf, N, n_obj, n_con,
+                           S->v.p);
+        HIPCHK(ctx, hipGetLastError());
+    }
+    if (n_obj == 4) {
+        const int32_t cap = ctx->opt.mo_hvx_cap > 0 ? (int32_t)ctx->opt.mo_hvx_cap : kHvx4Cap;
+        hvx4_launch(st, d_F, N, ref4, mode, cap, grid, per_slice, S->xflag.p, S->xlive.p, S->xhdr.p, S->excl.p);
+    } else {
+        const int32_t cap = ctx->opt.mo_hvx_cap > 0 ? (int32_t)ctx->opt.mo_hvx_cap : kHvxCap;
+        hvx_launch(n_obj, st, d_F, N, ref, mode, cap, grid, per_slice, S->xflag.p, S->xlive.p, S->xhdr.p, S->excl.p);
+    }
+    HIPCHK(ctx, hipGetLastError());
+    HIPCHK(ctx, hipMemcpyAsync(S->excl_h.data(), S->excl.p, n * sizeof(double), hipMemcpyDeviceToHost, st));
+    HIPCHK(ctx, hipMemcpyAsync(S->xhdr_h.data(), S->xhdr.p, kHvxHdr * sizeof(int32_t), hipMemcpyDeviceToHost, st));
+    HIPCHK(ctx, hipStreamSynchronize(st));   // the call's one synchronisation
+    std::memcpy(excl, S->excl_h.data(), (size_t)n * sizeof(double));
+    if (n_overflow) *n_overflow = S->xhdr_h[1];
+    return TPE_OK;
 }
 
 }  // namespace
@@ -529,57 +596,17 @@ int tpe_mo_keys_hv(tpe_ctx* ctx, const double* objectives, int64_t n, int32_t n_
 int tpe_mo_exclusive(tpe_ctx* ctx, const double* objectives, int64_t n, int32_t n_obj, const double* reference,
                      const double* constraints, int32_t n_con, int32_t mode, double* excl, int32_t* n_overflow) {
     if (!ctx) return TPE_ERR_ARG;
-    if (!objectives || !reference || !excl) return ctx->fail(TPE_ERR_ARG, "tpe_mo_exclusive: null pointer");
-    if (n < 1 || n > kMoMaxRows) return ctx->fail(TPE_ERR_ARG, "tpe_mo_exclusive: n must be in [1, 2^20]");
     if (n_obj != 2 && n_obj != 3) return ctx->fail(TPE_ERR_ARG, "tpe_mo_exclusive: n_obj must be 2 or 3");
-    if (constraints && (n_con < 1 || n_con > kMoMaxCon))
-        return ctx->fail(TPE_ERR_ARG, "tpe_mo_exclusive: n_con must be in [1, 8]");
-    if (mode != 0 && mode != 1) return ctx->fail(TPE_ERR_ARG, "tpe_mo_exclusive: mode must be 0 or 1");
-    HvxRef ref{};
-    for (int m = 0; m < n_obj; ++m) {
-        ref.r[m] = reference[m];
-        if (!(reference[m] - reference[m] == 0.0))
-            return ctx->fail(TPE_ERR_ARG, "tpe_mo_exclusive: the reference point must be finite");
-    }
-    HIPCHK(ctx, hipSetDevice(ctx->device));
-    hipStream_t st = ctx->stream;
-    MoState* S = mo_of(ctx);
-    const int32_t N = (int32_t)n;
-    const size_t nf = (size_t)n * n_obj, ng = constraints ? (size_t)n * n_con : 0;
-    HIPCHK(ctx, S->in.reserve(nf + ng));
-    HIPCHK(ctx, S->in_h.resize(nf + ng));
-    if (constraints) HIPCHK(ctx, S->v.reserve(n));
-    HIPCHK(ctx, S->xflag.reserve(n));
-    HIPCHK(ctx, S->xlive.reserve(n));
-    HIPCHK(ctx, S->xhdr.reserve(kHvxHdr));
-    HIPCHK(ctx, S->excl.reserve(n));
-    HIPCHK(ctx, S->excl_h.resize(n));
-    HIPCHK(ctx, S->xhdr_h.resize(kHvxHdr));
-    double* d_F = S->in.p;
+    return mo_exclusive_run(ctx, "tpe_mo_exclusive", objectives, n, n_obj, reference, constraints, n_con, mode, excl,
+                            n_overflow);
+}
 
-    // F (and G) in pinned memory: the call's one upload
-    std::memcpy(S->in_h.data(), objectives, nf * sizeof(double));
-    if (constraints) std::memcpy(S->in_h.data() + nf, constraints, ng * sizeof(double));
-    HIPCHK(ctx, hipMemcpyAsync(S->in.p, S->in_h.data(), (nf + ng) * sizeof(double), hipMemcpyHostToDevice, st));
-    const unsigned row_blocks = blocks_of(n, kBlock);
-    const unsigned slices = std::max(1u, std::min(row_blocks, (kMoBlocks + row_blocks - 1) / row_blocks));
-    const int32_t per_slice = (int32_t)((n + slices - 1) / slices);
-    const dim3 grid(row_blocks, blocks_of(n, per_slice));
-    if (constraints) {
-        // the rows that are dead or infeasible: NaN on the device copy
-        hipLaunchKernelGGL(k_moc_prep, dim3(row_blocks), dim3(kBlock), 0, st, d_F, S->in.p + nf, N, n_obj, n_con,
-                           S->v.p);
-        HIPCHK(ctx, hipGetLastError());
-    }
-    const int32_t cap = ctx->opt.mo_hvx_cap > 0 ? (int32_t)ctx->opt.mo_hvx_cap : kHvxCap;
-    hvx_launch(n_obj, st, d_F, N, ref, mode, cap, grid, per_slice, S->xflag.p, S->xlive.p, S->xhdr.p, S->excl.p);
-    HIPCHK(ctx, hipGetLastError());
-    HIPCHK(ctx, hipMemcpyAsync(S->excl_h.data(), S->excl.p, n * sizeof(double), hipMemcpyDeviceToHost, st));
-    HIPCHK(ctx, hipMemcpyAsync(S->xhdr_h.data(), S->xhdr.p, kHvxHdr * sizeof(int32_t), hipMemcpyDeviceToHost, st));
-    HIPCHK(ctx, hipStreamSynchronize(st));   // the call's one synchronisation
-    std::memcpy(excl, S->excl_h.data(), (size_t)n * sizeof(double));
-    if (n_overflow) *n_overflow = S->xhdr_h[1];
-    return TPE_OK;
+int tpe_mo_exclusive4(tpe_ctx* ctx, const double* objectives, int64_t n, int32_t n_obj, const double* reference,
+                      const double* constraints, int32_t n_con, int32_t mode, double* excl, int32_t* n_overflow) {
+    if (!ctx) return TPE_ERR_ARG;
+    if (n_obj != 4) return ctx->fail(TPE_ERR_ARG, "tpe_mo_exclusive4: n_obj must be 4");
+    return mo_exclusive_run(ctx, "tpe_mo_exclusive4", objectives, n, n_obj, reference, constraints, n_con, mode, excl,
+                            n_overflow);
 }
 
 }  // extern "C"

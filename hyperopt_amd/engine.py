@@ -848,8 +848,9 @@ class Engine(object):
         return (keys, by, do, v) if want_counts else keys
 
     def mo_exclusive(self, F, reference, mode, G=None, want_overflow=False):
-        """The exclusive hypervolumes of the rows of F [n, 2 or 3] against
-        `reference` (tpe_mo_exclusive; posterior.mo_exclusive states the rule
+        """The exclusive hypervolumes of the rows of F [n, 2, 3 or 4] against
+        `reference` (tpe_mo_exclusive, four columns: tpe_mo_exclusive4;
+        posterior.mo_exclusive states the rule
         and gives the same bits): excl [n] float64, mode 'before' the gain of
         each row over the valid rows before it, 'others' its contribution
         among all valid rows.  G [n, K]: the constraint rows, a row with a
@@ -872,10 +873,9 @@ class Engine(object):
                 raise ValueError('G must be [n, n_constraints], a row for every row of F')
         excl = np.empty(n)
         n_over = ctypes.c_int32(0)
-        self._check(self.lib.tpe_mo_exclusive(self.h, _ptr(F), n, F.shape[1], _ptr(ref), _ptr(G),
-                                              0 if G is None else G.shape[1],
-                                              _post.MO_EXCLUSIVE_MODES.index(mode), _ptr(excl),
-                                              ctypes.byref(n_over)))
+        entry = self.lib.tpe_mo_exclusive4 if F.shape[1] == 4 else self.lib.tpe_mo_exclusive
+        self._check(entry(self.h, _ptr(F), n, F.shape[1], _ptr(ref), _ptr(G), 0 if G is None else G.shape[1],
+                          _post.MO_EXCLUSIVE_MODES.index(mode), _ptr(excl), ctypes.byref(n_over)))
         if n_over.value:
             rows = np.flatnonzero(np.isnan(excl))
             excl[rows] = _post.mo_exclusive(F, ref, mode, G=G, rows=rows)[rows]

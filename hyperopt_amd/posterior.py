@@ -303,8 +303,11 @@ def _mo_uncovered(a, r, K):
     K [k, M] the kept points (inside the box, mutually non-dominated) -- the
     sums of tpe_mo_exclusive, operation by operation.  M = 2: the scan by
     ascending x.  M = 3: slabs by ascending z; slab s holds the points of
-    z-rank < s, and its area is that scan, every slab at once."""
+    z-rank < s, and its area is that scan, every slab at once.  M = 4
+    (tpe_mo_exclusive4): _mo_uncovered4."""
     k, M = K.shape
+    if M == 4:
+        return _mo_uncovered4(a, r, K)
     if M == 3:
         K = K[np.argsort(K[:, 2], kind='stable')]
         z = np.concatenate([a[2:], K[:, 2], r[2:]])
@@ -323,10 +326,38 @@ def _mo_uncovered(a, r, K):
     return float(np.cumsum((z[1:] - z[:-1]) * area)[-1])    # (cumsum: left to right)
 
 
+def _mo_uncovered4(a, r, K):
+    """_mo_uncovered for four axes x, y, z, w, the sums of tpe_mo_exclusive4:
+    the kept points by ascending w (stable) -- a point's position is its w-rank
+    -- and, separately, by ascending z (stable): its z-rank.  Cell (t, s), t, s
+    = 0 .. k, holds the points of w-rank < t and z-rank < s; its area A[t, s] is
+    the M = 2 scan over them by (x, y), every cell at once.  V[t] = the sum over
+    ascending s of (z_s - z_{s-1}) A[t, s]; the result the sum over ascending t
+    of (w_t - w_{t-1}) V[t].  (Equal w or z: either order, the slab between
+    them has thickness 0 and its term is 0.)"""
+    k = len(K)
+    K = K[np.argsort(K[:, 3], kind='stable')]
+    zord = np.argsort(K[:, 2], kind='stable')
+    zrank = np.empty(k, dtype=np.int64)
+    zrank[zord] = np.arange(k)
+    w = np.concatenate([a[3:], K[:, 3], r[3:]])
+    z = np.concatenate([a[2:3], K[zord, 2], r[2:3]])
+    t, s = np.arange(k + 1)[:, None], np.arange(k + 1)[None, :]
+    cx, cy, area = np.full((k + 1, k + 1), a[0]), np.full((k + 1, k + 1), r[1]), np.zeros((k + 1, k + 1))
+    for p in np.lexsort((K[:, 1], K[:, 0])):
+        x, y = K[p, 0], K[p, 1]
+        step = (p < t) & (zrank[p] < s) & (y < cy)
+        area[step] = area[step] + (x - cx[step]) * (cy[step] - a[1])
+        cx[step], cy[step] = x, y
+    area = area + (r[0] - cx) * (cy - a[1])
+    V = np.cumsum((z[1:] - z[:-1]) * area, axis=1)[:, -1]     # (cumsum: left to right)
+    return float(np.cumsum((w[1:] - w[:-1]) * V)[-1])
+
+
 def mo_exclusive(F, reference, mode, G=None, rows=None):
-    """The exclusive hypervolumes of the rows of F [n, 2 or 3], all minimised,
-    against `reference` (the numpy restatement of tpe_mo_exclusive,
-    include/hyperopt_tpe.h, and its bits): float64 [n].  With box(i) = prod_m
+    """The exclusive hypervolumes of the rows of F [n, 2, 3 or 4], all minimised,
+    against `reference` (the numpy restatement of tpe_mo_exclusive and
+    tpe_mo_exclusive4, include/hyperopt_tpe.h, and their bits): float64 [n].  With box(i) = prod_m
     [F[i, m], reference[m]) and HV(S) the volume of the union of the boxes of S,
     excl[i] = HV(J + i) - HV(J), J the valid rows (mo_hv_valid) before i for
     mode 'before' -- the hypervolume gained by trial i -- and every other valid
@@ -336,8 +367,8 @@ def mo_exclusive(F, reference, mode, G=None, rows=None):
     part of box(i) summed from non-negative terms (_mo_uncovered).
     rows: only these rows are computed (Engine.mo_exclusive's overflow rows)."""
     F = np.asarray(F, dtype=np.float64)
-    if F.ndim != 2 or F.shape[1] not in (2, 3):
-        raise ValueError('F must be [n, 2 or 3 objectives]')
+    if F.ndim != 2 or F.shape[1] not in (2, 3, 4):
+        raise ValueError('F must be [n, 2, 3 or 4 objectives]')
     r = np.asarray(reference, dtype=np.float64)
     if r.shape != (F.shape[1],) or not np.isfinite(r).all():
         raise ValueError('reference must be %d finite values' % F.shape[1])

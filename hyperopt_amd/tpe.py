@@ -926,7 +926,7 @@ def pareto_front(trials, objectives, constraints=None):
 
 def hypervolume(trials, objectives, reference=None, constraints=None, history=False, contributions=False,
                 builder='auto', device=0):
-    """The hypervolume indicator of the complete trials under 2 or 3
+    """The hypervolume indicator of the complete trials under 2, 3 or 4
     objectives, all minimised (not in the reference; the number Optuna's
     plot_hypervolume_history draws): a dict with
         hypervolume    the volume of the union of the boxes [F[i], reference)
@@ -956,11 +956,11 @@ def hypervolume(trials, objectives, reference=None, constraints=None, history=Fa
 
     ValueError, before any engine is touched: what check_objectives,
     check_constraints and objective_rows refuse, a number of objectives other
-    than 2 or 3, a reference of another length or with a non-finite entry, an
+    than 2, 3 or 4, a reference of another length or with a non-finite entry, an
     unknown builder."""
     objectives = check_objectives(objectives)
-    if objectives is None or len(objectives) not in (2, 3):
-        raise ValueError('hypervolume needs 2 or 3 objectives, got %d' % len(objectives or ()))
+    if objectives is None or len(objectives) not in (2, 3, 4):
+        raise ValueError('hypervolume needs 2, 3 or 4 objectives, got %d' % len(objectives or ()))
     constraints = check_constraints(constraints, objectives)
     if builder not in ('auto', 'host', 'device'):
         raise ValueError("hypervolume: builder must be 'auto', 'host' or 'device'")

@@ -928,6 +928,35 @@ int tpe_mo_exclusive(tpe_ctx *ctx, const double *objectives /* [n][n_obj] row-ma
                      int32_t mode /* 0: rows before i, 1: every other row */,
                      double *excl /* [n] */, int32_t *n_overflow /* or NULL */);
 
+/* tpe_mo_exclusive with four objectives (an addition to ABI version 5; its
+ * kernels are a unit of their own, tpe_mo_hvx4.hip).  The arguments, the valid
+ * rows, J(i), excl, the modes, the constraints, n_overflow and the buffers are
+ * tpe_mo_exclusive's; n_obj must be 4.  For a valid row that no row of J(i)
+ * weakly dominates, with a = F[i] and the axes named x, y, z, w: the rows of
+ * J(i) clipped to a, the distinct minimal elements kept -- k points -- and
+ *   w-rank: a kept point's position by ascending fourth axis, w_0 <= .. <=
+ *       w_{k-1}; z-rank: its position by ascending third axis, z_0 <= .. <=
+ *       z_{k-1} (equal keys in any order: they bound a slab of thickness 0);
+ *   cell (t, s), t, s = 0 .. k: A[t][s] = the n_obj 2 scan above over the kept
+ *       points of w-rank < t and z-rank < s, by ascending (x, y);
+ *   V[t] = sum over ascending s of (z_s - z_{s-1}) A[t][s], z_{-1} = a_2, z_k =
+ *       reference_2;
+ *   excl = sum over ascending t of (w_t - w_{t-1}) V[t], w_{-1} = a_3, w_k =
+ *       reference_3
+ * -- fp64, every difference, product and sum rounded on its own in this order,
+ * only non-negative terms: the bits of posterior.mo_exclusive, exact integers
+ * for integer-valued inputs below 2^53, and otherwise within (3 m + 8) 2^-53 of
+ * the exact value, relatively, m the rows of J(i).
+ * The kept set is held in LDS, at most 512 points (TPE_OPT_MO_HVX_CAP lowers
+ * it, values above 512 mean 512); a row past that: NaN, counted in *n_overflow.
+ * TPE_ERR_ARG as tpe_mo_exclusive, with n_obj not 4; the message names this
+ * entry.  On an error the outputs are untouched. */
+int tpe_mo_exclusive4(tpe_ctx *ctx, const double *objectives /* [n][4] row-major */,
+                      int64_t n, int32_t n_obj /* 4 */, const double *reference /* [4] */,
+                      const double *constraints /* [n][n_con] row-major, or NULL */, int32_t n_con,
+                      int32_t mode /* 0: rows before i, 1: every other row */,
+                      double *excl /* [n] */, int32_t *n_overflow /* or NULL */);
+
 /* ---- constraint densities (c-TPE) -------------------------------------------
  * tpe.suggest(constraints=..., constraint_model='density'): besides the
  * resident posterior (model 0, the objective's) a context holds up to eight
@@ -1367,7 +1396,8 @@ int tpe_screen_probe(tpe_ctx *ctx, int32_t label, const double *cand, int64_t n,
  *                   at most 2^30)                                      [2^20]
  *   TPE_OPT_MO_HVX_CAP  points of a live row's kept set tpe_mo_exclusive
  *                   holds in LDS before it reports the row in n_overflow
- *                   (tests; 0: the default, at most 1024)              [1024]
+ *                   (tests; 0: the default, at most 1024; tpe_mo_exclusive4:
+                   at most 512)                                       [1024]
  *   TPE_OPT_WIN_GROUPS  label groups of a windowed round, each sorted on a
  *                   second stream while the previous one is screened
  *                   (0: one group; the chip is busy either way)          [0]

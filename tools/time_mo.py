@@ -5,7 +5,7 @@
     python tools/time_mo.py --gpus 1 --constraints K [--out FILE]
     python tools/time_mo.py --gpus 1 --quality-constrained [--evals 100] [--out FILE]
     python tools/time_mo.py --gpus 1 --density [--out FILE]
-    python tools/time_mo.py --gpus 1 --indicator [--host-max-n 10000] [--out FILE]
+    python tools/time_mo.py --gpus 1 --indicator [--indicator-m 4] [--host-max-n 10000] [--out FILE]
 
 * Engine.mo_keys (tpe_mo_keys: upload, all-pairs kernel, pack, radix sort,
   scatter, read-back; one synchronisation) at n in {1000, 10000, 50000} x M in
@@ -65,10 +65,11 @@ the row objectives_hypervolume to the ZDT1 table.
 --indicator (tpe.hypervolume): Engine.mo_exclusive (tpe_mo_exclusive: upload,
 validity, domination pass, live-row list, a workgroup per live row, read-back)
 against posterior.mo_exclusive, the numpy builder, alternating, at the sizes
-above x 2 and 3 objectives x both modes, and on a 3000-row antichain at 3
-objectives (every row live); median of --reps calls, the numpy builder up to
---host-max-n rows; with the live rows, the overflow count and whether both give
-the same bits.
+above x 2, 3 and 4 objectives x both modes (4: tpe_mo_exclusive4), on a
+3000-row antichain at 3 objectives and on the 2736 integer points of [0, 16)^4
+with sum 30 at 4 (every row live); median of --reps calls, the numpy builder up
+to --host-max-n rows; with the live rows, the overflow count and whether both
+give the same bits.  --indicator-m M keeps the rows with M objectives.
 
 Results are appended to --out as one JSON object per line."""
 import argparse
@@ -384,6 +385,13 @@ def indicator_times(args):
     inputs = [('uniform', n, M, np.random.RandomState(n + M).uniform(size=(n, M))) for n in SIZES for M in (2, 3)]
     t = np.arange(3000.0)
     inputs.append(('antichain', 3000, 3, np.column_stack([t, 3000 - t, np.random.RandomState(7).uniform(size=3000)])))
+    # M = 4 (tpe_mo_exclusive4): the same sizes, and the 2736 integer points of [0, 16)^4 with sum 30, shuffled
+    inputs += [('uniform', n, 4, np.random.RandomState(n + 4).uniform(size=(n, 4))) for n in SIZES]
+    grid = np.indices((16,) * 4).reshape(4, -1).T
+    lattice = np.random.RandomState(7).permutation(grid[grid.sum(axis=1) == 30]).astype(float)
+    inputs.append(('antichain', len(lattice), 4, lattice))
+    if args.indicator_m:
+        inputs = [i for i in inputs if i[2] == args.indicator_m]
     out = []
     for kind, n, M, F in inputs:
         ref = tuple((F.max(axis=0) + 0.1 * (F.max(axis=0) - F.min(axis=0))).tolist())
@@ -459,6 +467,7 @@ def main():
     ap.add_argument('--quality-constrained', action='store_true')
     ap.add_argument('--density', action='store_true')
     ap.add_argument('--indicator', action='store_true')
+    ap.add_argument('--indicator-m', type=int, default=0, metavar='M', help='--indicator: only the rows with M objectives')
     ap.add_argument('--tiebreak', choices=('dominates', 'hypervolume'), default='dominates')
     ap.add_argument('--evals', type=int)
     ap.add_argument('--seeds', type=int, default=10)
