@@ -28,6 +28,7 @@ SOURCES = [os.path.join(HERE, 'csrc', 'tpe_engine.hip'),
            os.path.join(HERE, 'csrc', 'tpe_pool.hip'),
            os.path.join(HERE, 'csrc', 'tpe_mo.hip'),
            os.path.join(HERE, 'csrc', 'tpe_mo_hv.hip'),
+           os.path.join(HERE, 'csrc', 'tpe_mo_hvs.hip'),
            os.path.join(HERE, 'csrc', 'tpe_mo_hvx.hip'),
            os.path.join(HERE, 'csrc', 'tpe_mo_hvx4.hip'),
            os.path.join(HERE, 'csrc', 'tpe_importance.hip'),
@@ -37,6 +38,7 @@ SOURCES = [os.path.join(HERE, 'csrc', 'tpe_engine.hip'),
 DEPS = SOURCES + [os.path.join(HERE, 'csrc', 'tpe_device.h'),
                   os.path.join(HERE, 'csrc', 'tpe_ctx.h'),
                   os.path.join(HERE, 'csrc', 'tpe_mo_hv.h'),
+                  os.path.join(HERE, 'csrc', 'tpe_mo_hvs.h'),
                   os.path.join(HERE, 'csrc', 'tpe_mo_hvx.h'),
                   os.path.join(HERE, 'csrc', 'tpe_mo_hvx4.h'),
                   os.path.join(HERE, 'csrc', 'tpe_interaction.h'),
@@ -53,6 +55,7 @@ FLAGS = ['--offload-arch=' + ARCH, '-O3', '-std=c++17', '-fPIC', '-shared',
 # The unit is fp64 throughout, so today the flag changes no instruction and no
 # resource figure; it keeps a later fp32 helper from being packed silently.
 # tpe_mo_hv.hip (integers and fp64 comparisons): the same.
+# tpe_mo_hvs.hip (integers and fp64 comparisons): the same.
 # tpe_interaction_mixed.hip (fp64 throughout): the same.
 # tpe_mo_hvx.hip (fp64 throughout): the same, and no contraction into fused
 # multiply-adds -- its sums are stated operation by operation, each rounded on
@@ -60,6 +63,7 @@ FLAGS = ['--offload-arch=' + ARCH, '-O3', '-std=c++17', '-fPIC', '-shared',
 # tpe_mo_hvx4.hip (its four-objective counterpart): the same two.
 _NO_PACKED_FP32 = ['-Xclang', '-target-feature', '-Xclang', '-packed-fp32-ops']
 EXTRA_FLAGS = {'tpe_cmodel.hip': _NO_PACKED_FP32, 'tpe_mo_hv.hip': _NO_PACKED_FP32,
+               'tpe_mo_hvs.hip': _NO_PACKED_FP32,
                'tpe_interaction_mixed.hip': _NO_PACKED_FP32,
                'tpe_mo_hvx.hip': _NO_PACKED_FP32 + ['-ffp-contract=off'],
                'tpe_mo_hvx4.hip': _NO_PACKED_FP32 + ['-ffp-contract=off']}

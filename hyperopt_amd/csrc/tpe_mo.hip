@@ -55,6 +55,15 @@
 //   lvl   : int32[2][n], lvl_r : uint32[M][n], flag : uint8[n]   the level
 //   hdr   : int32[4]; pick : int32[64]; gain : uint64[64]
 //
+// With the sampled hypervolume tie-break (tpe_mo_keys_hvs, two to eight
+// objectives): the same call with tpe_mo_hvs.hip's pairs kernel, level search
+// and compaction; the host then reads the header (the level's size L, the
+// picks q, n_f: a second synchronisation in the call), sizes the coverage matrix
+// to that level and enqueues exactly q picks.  Buffers of the context that
+// only this call allocates, growing only:
+//   hvs_bits : uint64[S / 64][L]   hvs_pts : uint32[M][S]   hvs_lo : uint32[8]
+//   hvs_cov  : uint64[S / 64]      hvs_gain : uint32[L]     hvs_pick_t : int32[64]
+//
 // The exclusive hypervolumes of raw rows against a reference point
 // (tpe_mo_exclusive, two or three objectives; tpe_mo_exclusive4, four): the
 // upload of the constrained call, k_moc_prep when constraints are given, then
@@ -72,6 +81,7 @@
 #include "../../include/hyperopt_tpe.h"
 #include "tpe_ctx.h"
 #include "tpe_mo_hv.h"
+#include "tpe_mo_hvs.h"
 #include "tpe_mo_hvx.h"
 #include "tpe_mo_hvx4.h"
 
@@ -233,6 +243,10 @@ struct MoState {
     DevBuf<unsigned long long> gain;
     PinVec<int32_t> pick_h;                 // hdr, then pick
     PinVec<unsigned long long> gain_h;
+    // tpe_mo_keys_hvs alone
+    DevBuf<uint64_t> hvs_bits, hvs_cov;
+    DevBuf<uint32_t> hvs_pts, hvs_lo, hvs_gain;
+    DevBuf<int32_t> hvs_pick_t;
     // tpe_mo_exclusive and tpe_mo_exclusive4 alone
     DevBuf<int32_t> xflag, xlive, xhdr;
     DevBuf<double> excl;
@@ -329,6 +343,183 @@ int mo_exclusive_run(tpe_ctx* ctx, const char* who, const double* objectives, in
     HIPCHK(ctx, hipStreamSynchronize(st));   // the call's one synchronisation
     std::memcpy(excl, S->excl_h.data(), (size_t)n * sizeof(double));
     if (n_overflow) *n_overflow = S->xhdr_h[1];
+    return TPE_OK;
+}
+
+// tpe_mo_keys_hv (n_samples 0: the exact gains, tpe_mo_hv.hip) and
+// tpe_mo_keys_hvs (n_samples > 0: the sampled ones, tpe_mo_hvs.hip) behind
+// their n_obj and n_samples checks: the same arguments, errors (under the
+// entry's name `who`), upload, dominance, sort and scatter pipeline and
+// read-back.
+int mo_keys_hv_run(tpe_ctx* ctx, const char* who, const double* objectives, int64_t n, int32_t n_obj,
+                   const double* constraints, int32_t n_con, int32_t n_select, int32_t n_samples, double* keys,
+                   int32_t* dominated_by, int32_t* dominates, double* violation, int32_t* picked, uint64_t* gains,
+                   int32_t* n_picked) {
+    const std::string name(who);
+    const bool sampled = n_samples > 0;
+    if (!objectives || !keys) return ctx->fail(TPE_ERR_ARG, name + ": null pointer");
+    if (n < 1 || n > kMoMaxRows) return ctx->fail(TPE_ERR_ARG, name + ": n must be in [1, 2^20]");
+    if (constraints && (n_con < 1 || n_con > kMoMaxCon))
+        return ctx->fail(TPE_ERR_ARG, name + ": n_con must be in [1, 8]");
+    if (n_select < 0 || n_select > kHvMaxPicks)
+        return ctx->fail(TPE_ERR_ARG, name + ": n_select must be in [0, 64]");
+    HIPCHK(ctx, hipSetDevice(ctx->device));
+    hipStream_t st = ctx->stream;
+    MoState* S = mo_of(ctx);
+    const int32_t N = (int32_t)n;
+    int32_t bits = 1;
+    while (((int64_t)1 << bits) <= n) ++bits;
+    // (n_select of 0 or past the rows: the keys are the old keys, nothing to select)
+    const bool select = n_select > 0 && n_select < n;
+    const size_t nf = (size_t)n * n_obj, ng = constraints ? (size_t)n * n_con : 0;
+    HIPCHK(ctx, S->in.reserve(nf + ng));
+    HIPCHK(ctx, S->in_h.resize(nf + ng));
+    HIPCHK(ctx, S->keys.reserve(n));
+    HIPCHK(ctx, S->cnt.reserve(2 * (size_t)n));
+    HIPCHK(ctx, S->key.reserve(n));
+    HIPCHK(ctx, S->key2.reserve(n));
+    HIPCHK(ctx, S->keys_h.resize(n));
+    HIPCHK(ctx, S->cnt_h.resize(2 * (size_t)n));
+    if (constraints) {
+        HIPCHK(ctx, S->v.reserve(n));
+        HIPCHK(ctx, S->cntv.reserve(2 * (size_t)n));
+        HIPCHK(ctx, S->v_h.resize(n));
+    }
+    HIPCHK(ctx, S->rank.reserve(nf));
+    HIPCHK(ctx, S->lvl_r.reserve(nf));
+    HIPCHK(ctx, S->lvl.reserve(2 * (size_t)n));
+    HIPCHK(ctx, S->flag.reserve(n));
+    HIPCHK(ctx, S->hdr.reserve(kHvHdr));
+    HIPCHK(ctx, S->pick.reserve(kHvMaxPicks));
+    HIPCHK(ctx, S->gain.reserve(kHvMaxPicks));
+    HIPCHK(ctx, S->pick_h.resize(kHvHdr + kHvMaxPicks));
+    HIPCHK(ctx, S->gain_h.resize(kHvMaxPicks));
+    size_t sort_bytes = 0;
+    hipcub::DoubleBuffer<uint64_t> kb(S->key.p, S->key2.p);
+    HIPCHK(ctx, hipcub::DeviceRadixSort::SortKeys(nullptr, sort_bytes, kb, (int)N, 0, 3 * bits, st));
+    HIPCHK(ctx, S->tmp.reserve(std::max<size_t>(sort_bytes, 1)));
+    double* d_F = S->in.p;
+    const double* d_G = S->in.p + nf;
+    int32_t* d_by = S->cnt.p;
+    int32_t* d_do = S->cnt.p + n;
+
+    // F (and G) in pinned memory: the call's one upload
+    std::memcpy(S->in_h.data(), objectives, nf * sizeof(double));
+    if (constraints) std::memcpy(S->in_h.data() + nf, constraints, ng * sizeof(double));
+    HIPCHK(ctx, hipMemcpyAsync(S->in.p, S->in_h.data(), (nf + ng) * sizeof(double), hipMemcpyHostToDevice, st));
+    HIPCHK(ctx, hipMemsetAsync(S->cnt.p, 0, 2 * (size_t)n * sizeof(int32_t), st));
+    HIPCHK(ctx, hipMemsetAsync(S->rank.p, 0, nf * sizeof(uint32_t), st));
+    const unsigned row_blocks = blocks_of(n, kBlock);
+    const unsigned slices = std::max(1u, std::min(row_blocks, (kMoBlocks + row_blocks - 1) / row_blocks));
+    const int32_t per_slice = (int32_t)((n + slices - 1) / slices);
+    const dim3 grid(row_blocks, blocks_of(n, per_slice));
+    if (constraints) {
+        HIPCHK(ctx, hipMemsetAsync(S->cntv.p, 0, 2 * (size_t)n * sizeof(int32_t), st));
+        hipLaunchKernelGGL(k_moc_prep, dim3(row_blocks), dim3(kBlock), 0, st, d_F, d_G, N, n_obj, n_con, S->v.p);
+        HIPCHK(ctx, hipGetLastError());
+    } else {
+        hv_launch_prep(st, d_F, N, n_obj);
+        HIPCHK(ctx, hipGetLastError());
+    }
+    // counts and rank coordinates among the rank rows (every other row of the
+    // device copy is NaN by now)
+    if (sampled)
+        hvs_launch_pairs(n_obj, grid, st, d_F, N, per_slice, d_by, d_do, S->rank.p);
+    else
+        hv_launch_pairs(n_obj, grid, st, d_F, N, per_slice, d_by, d_do, S->rank.p);
+    HIPCHK(ctx, hipGetLastError());
+    if (constraints) {
+        launch_pairs<1>(grid, st, S->v.p, N, per_slice, S->cntv.p, S->cntv.p + n);
+        HIPCHK(ctx, hipGetLastError());
+        hipLaunchKernelGGL(k_moc_pack, dim3(row_blocks), dim3(kBlock), 0, st, S->v.p, N, bits, d_by, d_do,
+                           S->cntv.p, S->key.p);
+    } else {
+        hipLaunchKernelGGL(k_mo_pack, dim3(row_blocks), dim3(kBlock), 0, st, d_F, N, n_obj, bits, d_by, d_do,
+                           S->key.p);
+    }
+    HIPCHK(ctx, hipGetLastError());
+    HIPCHK(ctx, hipcub::DeviceRadixSort::SortKeys(S->tmp.p, sort_bytes, kb, (int)N, 0, 3 * bits, st));
+    if (constraints)
+        hipLaunchKernelGGL(k_moc_scatter, dim3(row_blocks), dim3(kBlock), 0, st, kb.Current(), N, bits, S->keys.p,
+                           d_by, d_do);
+    else
+        hipLaunchKernelGGL(k_mo_scatter, dim3(row_blocks), dim3(kBlock), 0, st, kb.Current(), N, bits, S->keys.p,
+                           d_by, d_do);
+    HIPCHK(ctx, hipGetLastError());
+    if (select && sampled) {
+        // the level at n_select on the device; its size sizes the coverage
+        // matrix and its q the picks, so the header comes back first
+        HvsBufs b{};
+        b.sorted = kb.Current();
+        b.v = constraints ? S->v.p : nullptr;
+        b.rank = S->rank.p;
+        b.hdr = S->hdr.p;
+        b.lvl = S->lvl.p;
+        b.lvl_r = S->lvl_r.p;
+        b.flag = S->flag.p;
+        b.pick = S->pick.p;
+        b.gain = S->gain.p;
+        b.keys = S->keys.p;
+        hvs_launch_level(n_obj, st, b, N, bits, n_select);
+        HIPCHK(ctx, hipGetLastError());
+        HIPCHK(ctx, hipMemcpyAsync(S->pick_h.data(), S->hdr.p, kHvHdr * sizeof(int32_t), hipMemcpyDeviceToHost, st));
+        HIPCHK(ctx, hipStreamSynchronize(st));   // the first of the call's two synchronisations
+        const int32_t a = S->pick_h[0], L = S->pick_h[1] - a, q = S->pick_h[2], n_f = S->pick_h[3];
+        if (q > 0) {
+            const size_t W = (size_t)n_samples / 64;
+            if ((uint64_t)L * (uint64_t)n_samples > ((uint64_t)1 << 33))
+                return ctx->fail(TPE_ERR_ARG, name + ": the coverage matrix of a level of L = " + std::to_string(L) +
+                                                  " rows and n_samples = " + std::to_string(n_samples) +
+                                                  " exceeds 1 GiB (L * n_samples > 2^33)");
+            HIPCHK(ctx, S->hvs_bits.reserve(W * (size_t)L));
+            HIPCHK(ctx, S->hvs_pts.reserve((size_t)n_obj * n_samples));
+            HIPCHK(ctx, S->hvs_cov.reserve(W));
+            HIPCHK(ctx, S->hvs_gain.reserve(L));
+            HIPCHK(ctx, S->hvs_lo.reserve(kHvsMaxObj));
+            HIPCHK(ctx, S->hvs_pick_t.reserve(kHvsMaxPicks));
+            b.bits = S->hvs_bits.p;
+            b.pts = S->hvs_pts.p;
+            b.covered = S->hvs_cov.p;
+            b.cgain = S->hvs_gain.p;
+            b.lo = S->hvs_lo.p;
+            b.pick_t = S->hvs_pick_t.p;
+            HIPCHK(ctx, hipMemsetAsync(S->hvs_cov.p, 0, W * sizeof(uint64_t), st));
+            HIPCHK(ctx, hipMemsetAsync(S->hvs_gain.p, 0, (size_t)L * sizeof(uint32_t), st));
+            hvs_launch_select(n_obj, st, b, N, a, L, q, n_f, n_samples);
+            HIPCHK(ctx, hipGetLastError());
+            HIPCHK(ctx, hipMemcpyAsync(S->pick_h.data() + kHvHdr, S->pick.p, q * sizeof(int32_t),
+                                       hipMemcpyDeviceToHost, st));
+            HIPCHK(ctx, hipMemcpyAsync(S->gain_h.data(), S->gain.p, q * sizeof(unsigned long long),
+                                       hipMemcpyDeviceToHost, st));
+        }
+    } else if (select) {
+        // the level at n_select, its picks, and the keys of its rows -- all on the device
+        hv_launch_select(n_obj, st, kb.Current(), N, bits, constraints ? S->v.p : nullptr, n_select, S->rank.p,
+                         S->hdr.p, S->lvl.p, S->lvl_r.p, S->flag.p, S->keys.p, S->pick.p, S->gain.p);
+        HIPCHK(ctx, hipGetLastError());
+        HIPCHK(ctx, hipMemcpyAsync(S->pick_h.data(), S->hdr.p, kHvHdr * sizeof(int32_t), hipMemcpyDeviceToHost, st));
+        HIPCHK(ctx, hipMemcpyAsync(S->pick_h.data() + kHvHdr, S->pick.p, kHvMaxPicks * sizeof(int32_t),
+                                   hipMemcpyDeviceToHost, st));
+        HIPCHK(ctx, hipMemcpyAsync(S->gain_h.data(), S->gain.p, kHvMaxPicks * sizeof(unsigned long long),
+                                   hipMemcpyDeviceToHost, st));
+    }
+    HIPCHK(ctx, hipMemcpyAsync(S->keys_h.data(), S->keys.p, n * sizeof(double), hipMemcpyDeviceToHost, st));
+    if (dominated_by || dominates)
+        HIPCHK(ctx, hipMemcpyAsync(S->cnt_h.data(), S->cnt.p, 2 * (size_t)n * sizeof(int32_t), hipMemcpyDeviceToHost,
+                                   st));
+    if (violation && constraints)
+        HIPCHK(ctx, hipMemcpyAsync(S->v_h.data(), S->v.p, n * sizeof(double), hipMemcpyDeviceToHost, st));
+    HIPCHK(ctx, hipStreamSynchronize(st));   // the call's one synchronisation (sampled: its second)
+    std::memcpy(keys, S->keys_h.data(), (size_t)n * sizeof(double));
+    if (dominated_by) std::memcpy(dominated_by, S->cnt_h.data(), (size_t)n * sizeof(int32_t));
+    if (dominates) std::memcpy(dominates, S->cnt_h.data() + n, (size_t)n * sizeof(int32_t));
+    if (violation && constraints) std::memcpy(violation, S->v_h.data(), (size_t)n * sizeof(double));
+    const int32_t q = select ? S->pick_h[2] : 0;
+    for (int32_t k = 0; k < n_select; ++k) {
+        if (picked) picked[k] = k < q ? S->pick_h[kHvHdr + k] : -1;
+        if (gains) gains[k] = k < q ? (uint64_t)S->gain_h[k] : 0;
+    }
+    if (n_picked) *n_picked = q;
     return TPE_OK;
 }
 
@@ -475,122 +666,20 @@ int tpe_mo_keys_hv(tpe_ctx* ctx, const double* objectives, int64_t n, int32_t n_
                    int32_t n_con, int32_t n_select, double* keys, int32_t* dominated_by, int32_t* dominates,
                    double* violation, int32_t* picked, uint64_t* gains, int32_t* n_picked) {
     if (!ctx) return TPE_ERR_ARG;
-    if (!objectives || !keys) return ctx->fail(TPE_ERR_ARG, "tpe_mo_keys_hv: null pointer");
-    if (n < 1 || n > kMoMaxRows) return ctx->fail(TPE_ERR_ARG, "tpe_mo_keys_hv: n must be in [1, 2^20]");
     if (n_obj != 2 && n_obj != 3) return ctx->fail(TPE_ERR_ARG, "tpe_mo_keys_hv: n_obj must be 2 or 3");
-    if (constraints && (n_con < 1 || n_con > kMoMaxCon))
-        return ctx->fail(TPE_ERR_ARG, "tpe_mo_keys_hv: n_con must be in [1, 8]");
-    if (n_select < 0 || n_select > kHvMaxPicks)
-        return ctx->fail(TPE_ERR_ARG, "tpe_mo_keys_hv: n_select must be in [0, 64]");
-    HIPCHK(ctx, hipSetDevice(ctx->device));
-    hipStream_t st = ctx->stream;
-    MoState* S = mo_of(ctx);
-    const int32_t N = (int32_t)n;
-    int32_t bits = 1;
-    while (((int64_t)1 << bits) <= n) ++bits;
-    // (n_select of 0 or past the rows: the keys are the old keys, nothing to select)
-    const bool select = n_select > 0 && n_select < n;
-    const size_t nf = (size_t)n * n_obj, ng = constraints ? (size_t)n * n_con : 0;
-    HIPCHK(ctx, S->in.reserve(nf + ng));
-    HIPCHK(ctx, S->in_h.resize(nf + ng));
-    HIPCHK(ctx, S->keys.reserve(n));
-    HIPCHK(ctx, S->cnt.reserve(2 * (size_t)n));
-    HIPCHK(ctx, S->key.reserve(n));
-    HIPCHK(ctx, S->key2.reserve(n));
-    HIPCHK(ctx, S->keys_h.resize(n));
-    HIPCHK(ctx, S->cnt_h.resize(2 * (size_t)n));
-    if (constraints) {
-        HIPCHK(ctx, S->v.reserve(n));
-        HIPCHK(ctx, S->cntv.reserve(2 * (size_t)n));
-        HIPCHK(ctx, S->v_h.resize(n));
-    }
-    HIPCHK(ctx, S->rank.reserve(nf));
-    HIPCHK(ctx, S->lvl_r.reserve(nf));
-    HIPCHK(ctx, S->lvl.reserve(2 * (size_t)n));
-    HIPCHK(ctx, S->flag.reserve(n));
-    HIPCHK(ctx, S->hdr.reserve(kHvHdr));
-    HIPCHK(ctx, S->pick.reserve(kHvMaxPicks));
-    HIPCHK(ctx, S->gain.reserve(kHvMaxPicks));
-    HIPCHK(ctx, S->pick_h.resize(kHvHdr + kHvMaxPicks));
-    HIPCHK(ctx, S->gain_h.resize(kHvMaxPicks));
-    size_t sort_bytes = 0;
-    hipcub::DoubleBuffer<uint64_t> kb(S->key.p, S->key2.p);
-    HIPCHK(ctx, hipcub::DeviceRadixSort::SortKeys(nullptr, sort_bytes, kb, (int)N, 0, 3 * bits, st));
-    HIPCHK(ctx, S->tmp.reserve(std::max<size_t>(sort_bytes, 1)));
-    double* d_F = S->in.p;
-    const double* d_G = S->in.p + nf;
-    int32_t* d_by = S->cnt.p;
-    int32_t* d_do = S->cnt.p + n;
+    return mo_keys_hv_run(ctx, "tpe_mo_keys_hv", objectives, n, n_obj, constraints, n_con, n_select, 0, keys,
+                          dominated_by, dominates, violation, picked, gains, n_picked);
+}
 
-    // F (and G) in pinned memory: the call's one upload
-    std::memcpy(S->in_h.data(), objectives, nf * sizeof(double));
-    if (constraints) std::memcpy(S->in_h.data() + nf, constraints, ng * sizeof(double));
-    HIPCHK(ctx, hipMemcpyAsync(S->in.p, S->in_h.data(), (nf + ng) * sizeof(double), hipMemcpyHostToDevice, st));
-    HIPCHK(ctx, hipMemsetAsync(S->cnt.p, 0, 2 * (size_t)n * sizeof(int32_t), st));
-    HIPCHK(ctx, hipMemsetAsync(S->rank.p, 0, nf * sizeof(uint32_t), st));
-    const unsigned row_blocks = blocks_of(n, kBlock);
-    const unsigned slices = std::max(1u, std::min(row_blocks, (kMoBlocks + row_blocks - 1) / row_blocks));
-    const int32_t per_slice = (int32_t)((n + slices - 1) / slices);
-    const dim3 grid(row_blocks, blocks_of(n, per_slice));
-    if (constraints) {
-        HIPCHK(ctx, hipMemsetAsync(S->cntv.p, 0, 2 * (size_t)n * sizeof(int32_t), st));
-        hipLaunchKernelGGL(k_moc_prep, dim3(row_blocks), dim3(kBlock), 0, st, d_F, d_G, N, n_obj, n_con, S->v.p);
-        HIPCHK(ctx, hipGetLastError());
-    } else {
-        hv_launch_prep(st, d_F, N, n_obj);
-        HIPCHK(ctx, hipGetLastError());
-    }
-    // counts and rank coordinates among the rank rows (every other row of the
-    // device copy is NaN by now)
-    hv_launch_pairs(n_obj, grid, st, d_F, N, per_slice, d_by, d_do, S->rank.p);
-    HIPCHK(ctx, hipGetLastError());
-    if (constraints) {
-        launch_pairs<1>(grid, st, S->v.p, N, per_slice, S->cntv.p, S->cntv.p + n);
-        HIPCHK(ctx, hipGetLastError());
-        hipLaunchKernelGGL(k_moc_pack, dim3(row_blocks), dim3(kBlock), 0, st, S->v.p, N, bits, d_by, d_do,
-                           S->cntv.p, S->key.p);
-    } else {
-        hipLaunchKernelGGL(k_mo_pack, dim3(row_blocks), dim3(kBlock), 0, st, d_F, N, n_obj, bits, d_by, d_do,
-                           S->key.p);
-    }
-    HIPCHK(ctx, hipGetLastError());
-    HIPCHK(ctx, hipcub::DeviceRadixSort::SortKeys(S->tmp.p, sort_bytes, kb, (int)N, 0, 3 * bits, st));
-    if (constraints)
-        hipLaunchKernelGGL(k_moc_scatter, dim3(row_blocks), dim3(kBlock), 0, st, kb.Current(), N, bits, S->keys.p,
-                           d_by, d_do);
-    else
-        hipLaunchKernelGGL(k_mo_scatter, dim3(row_blocks), dim3(kBlock), 0, st, kb.Current(), N, bits, S->keys.p,
-                           d_by, d_do);
-    HIPCHK(ctx, hipGetLastError());
-    if (select) {
-        // the level at n_select, its picks, and the keys of its rows -- all on the device
-        hv_launch_select(n_obj, st, kb.Current(), N, bits, constraints ? S->v.p : nullptr, n_select, S->rank.p,
-                         S->hdr.p, S->lvl.p, S->lvl_r.p, S->flag.p, S->keys.p, S->pick.p, S->gain.p);
-        HIPCHK(ctx, hipGetLastError());
-        HIPCHK(ctx, hipMemcpyAsync(S->pick_h.data(), S->hdr.p, kHvHdr * sizeof(int32_t), hipMemcpyDeviceToHost, st));
-        HIPCHK(ctx, hipMemcpyAsync(S->pick_h.data() + kHvHdr, S->pick.p, kHvMaxPicks * sizeof(int32_t),
-                                   hipMemcpyDeviceToHost, st));
-        HIPCHK(ctx, hipMemcpyAsync(S->gain_h.data(), S->gain.p, kHvMaxPicks * sizeof(unsigned long long),
-                                   hipMemcpyDeviceToHost, st));
-    }
-    HIPCHK(ctx, hipMemcpyAsync(S->keys_h.data(), S->keys.p, n * sizeof(double), hipMemcpyDeviceToHost, st));
-    if (dominated_by || dominates)
-        HIPCHK(ctx, hipMemcpyAsync(S->cnt_h.data(), S->cnt.p, 2 * (size_t)n * sizeof(int32_t), hipMemcpyDeviceToHost,
-                                   st));
-    if (violation && constraints)
-        HIPCHK(ctx, hipMemcpyAsync(S->v_h.data(), S->v.p, n * sizeof(double), hipMemcpyDeviceToHost, st));
-    HIPCHK(ctx, hipStreamSynchronize(st));   // the call's one synchronisation
-    std::memcpy(keys, S->keys_h.data(), (size_t)n * sizeof(double));
-    if (dominated_by) std::memcpy(dominated_by, S->cnt_h.data(), (size_t)n * sizeof(int32_t));
-    if (dominates) std::memcpy(dominates, S->cnt_h.data() + n, (size_t)n * sizeof(int32_t));
-    if (violation && constraints) std::memcpy(violation, S->v_h.data(), (size_t)n * sizeof(double));
-    const int32_t q = select ? S->pick_h[2] : 0;
-    for (int32_t k = 0; k < n_select; ++k) {
-        if (picked) picked[k] = k < q ? S->pick_h[kHvHdr + k] : -1;
-        if (gains) gains[k] = k < q ? (uint64_t)S->gain_h[k] : 0;
-    }
-    if (n_picked) *n_picked = q;
-    return TPE_OK;
+int tpe_mo_keys_hvs(tpe_ctx* ctx, const double* objectives, int64_t n, int32_t n_obj, const double* constraints,
+                    int32_t n_con, int32_t n_select, int32_t n_samples, double* keys, int32_t* dominated_by,
+                    int32_t* dominates, double* violation, int32_t* picked, uint64_t* gains, int32_t* n_picked) {
+    if (!ctx) return TPE_ERR_ARG;
+    if (n_obj < 2 || n_obj > kHvsMaxObj) return ctx->fail(TPE_ERR_ARG, "tpe_mo_keys_hvs: n_obj must be in [2, 8]");
+    if (n_samples < 64 || n_samples > (1 << 20) || n_samples % 64)
+        return ctx->fail(TPE_ERR_ARG, "tpe_mo_keys_hvs: n_samples must be a multiple of 64 in [64, 2^20]");
+    return mo_keys_hv_run(ctx, "tpe_mo_keys_hvs", objectives, n, n_obj, constraints, n_con, n_select, n_samples, keys,
+                          dominated_by, dominates, violation, picked, gains, n_picked);
 }
 
 int tpe_mo_exclusive(tpe_ctx* ctx, const double* objectives, int64_t n, int32_t n_obj, const double* reference,

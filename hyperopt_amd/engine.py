@@ -793,7 +793,8 @@ class Engine(object):
             out += (score,)
         return out
 
-    def mo_keys(self, F, want_counts=False, G=None, tiebreak='dominates', n_select=0, want_picks=False):
+    def mo_keys(self, F, want_counts=False, G=None, tiebreak='dominates', n_select=0, want_picks=False,
+                n_samples=65536):
         """The Pareto-compliant order of the objective vectors F [n, M], all
         minimised (tpe_mo_keys; posterior.mo_keys is its numpy restatement):
         keys [n] float64 -- row i's position under ascending dominated_by,
@@ -808,9 +809,13 @@ class Engine(object):
         reordered by greedy hypervolume subset selection, so that the first
         n_select rows are the greedy subset (posterior.mo_keys states the
         rule); want_picks appends (picked int32 [n_picked], gains uint64
-        [n_picked]), the picks' rows and exact gains in pick order."""
-        if tiebreak not in ('dominates', 'hypervolume'):
-            raise ValueError("tiebreak must be 'dominates' or 'hypervolume'")
+        [n_picked]), the picks' rows and exact gains in pick order.
+        tiebreak='hypervolume_mc' (tpe_mo_keys_hvs; two to eight objectives):
+        the same with each gain counted on n_samples fixed sample points (a
+        multiple of 64 in 64 .. 2^20; posterior.mo_hypervolume_mc_order states
+        the rule); the gains are those counts."""
+        if tiebreak not in ('dominates', 'hypervolume', 'hypervolume_mc'):
+            raise ValueError("tiebreak must be 'dominates', 'hypervolume' or 'hypervolume_mc'")
         F = np.ascontiguousarray(F, dtype=np.float64)
         if F.ndim != 2:
             raise ValueError('F must be [n, n_objectives]')
@@ -818,7 +823,7 @@ class Engine(object):
         keys = np.empty(n)
         by = np.empty(n, dtype=np.int32) if want_counts else None
         do = np.empty(n, dtype=np.int32) if want_counts else None
-        if tiebreak == 'hypervolume':
+        if tiebreak != 'dominates':
             if G is not None:
                 G = np.ascontiguousarray(G, dtype=np.float64)
                 if G.ndim != 2 or G.shape[0] != n:
@@ -828,10 +833,12 @@ class Engine(object):
             picked = np.empty(max(n_select, 0), dtype=np.int32)
             gains = np.empty(max(n_select, 0), dtype=np.uint64)
             n_picked = ctypes.c_int32(0)
-            self._check(self.lib.tpe_mo_keys_hv(self.h, _ptr(F), n, F.shape[1], _ptr(G),
-                                                0 if G is None else G.shape[1], n_select, _ptr(keys), _ptr(by),
-                                                _ptr(do), _ptr(v), _ptr(picked), _ptr(gains),
-                                                ctypes.byref(n_picked)))
+            head = (self.h, _ptr(F), n, F.shape[1], _ptr(G), 0 if G is None else G.shape[1], n_select)
+            tail = (_ptr(keys), _ptr(by), _ptr(do), _ptr(v), _ptr(picked), _ptr(gains), ctypes.byref(n_picked))
+            if tiebreak == 'hypervolume':
+                self._check(self.lib.tpe_mo_keys_hv(*(head + tail)))
+            else:
+                self._check(self.lib.tpe_mo_keys_hvs(*(head + (int(n_samples),) + tail)))
             out = (keys,) + ((by, do) if want_counts else ()) + ((v,) if v is not None else ())
             if want_picks:
                 out += (picked[:n_picked.value].copy(), gains[:n_picked.value].copy())

@@ -266,6 +266,105 @@ def mo_hypervolume_order(F, by, do, keys, n_select, G=None):
     return out, lev[picks].astype(np.int32), np.asarray(gains, dtype=np.uint64)
 
 
+MO_HVS_STREAM = 0x7FFFFFBE                # TPE_MO_HVS_STREAM
+MO_HVS_KEY = (0x4D4F4856, 0x53414D50)     # TPE_MO_HVS_KEY0, TPE_MO_HVS_KEY1
+MO_HVS_SAMPLES = 65536                    # tpe.suggest's mo_samples
+MO_HVS_MAX_SAMPLES = 1 << 20
+MO_HVS_MAX_BITS = 1 << 33                 # level rows x samples: a coverage matrix of 1 GiB
+_POP8 = np.unpackbits(np.arange(256, dtype=np.uint8)[:, None], axis=1).sum(axis=1).astype(np.uint8)
+
+
+def _philox4x32_10(c0, c1, c2, c3, k0, k1):
+    """Philox4x32-10 over arrays of counters: the four output words, uint64
+    arrays holding 32-bit values."""
+    u, m32 = np.uint64, np.uint64(0xFFFFFFFF)
+    c = [np.asarray(v, dtype=u) & m32 for v in np.broadcast_arrays(c0, c1, c2, c3)]
+    k0, k1 = u(k0), u(k1)
+    for _ in range(10):
+        p0, p1 = u(0xD2511F53) * c[0], u(0xCD9E8D57) * c[2]     # (32 x 32 bits: no overflow in 64)
+        c = [(p1 >> u(32)) ^ c[1] ^ k0, p1 & m32, (p0 >> u(32)) ^ c[3] ^ k1, p0 & m32]
+        k0, k1 = (k0 + u(0x9E3779B9)) & m32, (k1 + u(0xBB67AE85)) & m32
+    return c
+
+
+def mo_hvs_points(lo, n_f, n_samples):
+    """The sample points of the sampled tie-break: int64 [n_samples, M], x[s][m]
+    = lo[m] + ((uint64)word * (n_f - lo[m]) >> 32) with word = word m % 4 of
+    Philox4x32-10 under the counter (s, m / 4, 0, MO_HVS_STREAM) and the key
+    MO_HVS_KEY."""
+    s = np.arange(n_samples, dtype=np.uint64)
+    x = np.empty((n_samples, len(lo)), dtype=np.int64)
+    for blk in range((len(lo) + 3) // 4):
+        words = _philox4x32_10(s, blk, 0, MO_HVS_STREAM, *MO_HVS_KEY)
+        for m in range(4 * blk, min(4 * blk + 4, len(lo))):
+            x[:, m] = int(lo[m]) + ((words[m % 4] * np.uint64(n_f - int(lo[m]))) >> np.uint64(32)).astype(np.int64)
+    return x
+
+
+def mo_hypervolume_mc_order(F, by, do, keys, n_select, n_samples, G=None):
+    """The sampled hypervolume tie-break of the below set (the numpy
+    restatement of tpe_mo_keys_hvs, include/hyperopt_tpe.h): (keys, picked,
+    gains).  F [n, 2 .. 8]; everything but the gain is mo_hypervolume_order's:
+    the rank rows, n_f, r[i][m], the level, a, q, when the keys stay, the pick
+    positions.  With lo[m] the level's smallest rank on axis m the n_samples
+    points of mo_hvs_points(lo, n_f, n_samples) lie in [lo, n_f), the bounding
+    box of the level's boxes; row c covers a point x when r[c][m] <= x[m] on
+    every axis, and gain(c | P) counts the points c covers and no row of P
+    does (HypE's estimator on one fixed sample).  Ties, the frequent all-zero
+    case among them: larger do, then smaller row.  Integers: the kernel's."""
+    F = np.asarray(F, dtype=np.float64)
+    if F.ndim != 2 or not 2 <= F.shape[1] <= MO_MAX_OBJECTIVES:
+        raise ValueError("tiebreak='hypervolume_mc' needs 2 .. %d objectives" % MO_MAX_OBJECTIVES)
+    n_select, n_samples = int(n_select), int(n_samples)
+    if not 0 <= n_select <= MO_HV_MAX_SELECT:
+        raise ValueError('n_select must be in [0, %d]' % MO_HV_MAX_SELECT)
+    if not 64 <= n_samples <= MO_HVS_MAX_SAMPLES or n_samples % 64:
+        raise ValueError('n_samples must be a multiple of 64 in [64, %d]' % MO_HVS_MAX_SAMPLES)
+    none = (keys, np.zeros(0, dtype=np.int32), np.zeros(0, dtype=np.uint64))
+    live = np.flatnonzero(by >= 0)
+    if n_select <= 0 or n_select >= len(live):
+        return none
+    ranked = ~np.isnan(F).any(axis=1) if G is None else mo_violation(G, F) == 0.0
+    order = np.empty(len(live), dtype=np.int64)
+    order[keys[live].astype(np.int64)] = live
+    s, t = order[n_select - 1], order[n_select]
+    if by[s] != by[t] or not (ranked[s] and ranked[t]):
+        return none
+    at = np.flatnonzero(by[order] == by[s])            # (contiguous: the order is by `by` first)
+    lev, a = order[at], int(at[0])
+    q = n_select - a
+    if len(lev) * n_samples > MO_HVS_MAX_BITS:
+        raise ValueError('a level of L = %d rows with n_samples = %d: the coverage matrix exceeds 1 GiB'
+                         % (len(lev), n_samples))
+    n_f = int(np.count_nonzero(ranked))
+    r = np.empty((len(lev), F.shape[1]), dtype=np.int64)
+    for m in range(F.shape[1]):
+        r[:, m] = np.searchsorted(np.sort(F[ranked, m]), F[lev, m], side='left')
+    x = mo_hvs_points(r.min(axis=0), n_f, n_samples)
+    # one bit per (row, sample), 4096 samples at a time
+    bits = np.empty((len(lev), n_samples // 8), dtype=np.uint8)
+    for s0 in range(0, n_samples, 4096):
+        cov = np.ones((len(lev), min(4096, n_samples - s0)), dtype=bool)
+        for m in range(F.shape[1]):
+            cov &= r[:, m, None] <= x[None, s0:s0 + 4096, m]
+        bits[:, s0 // 8:(s0 + 4096) // 8] = np.packbits(cov, axis=1)
+    covered = np.zeros(n_samples // 8, dtype=np.uint8)
+    left = np.ones(len(lev), dtype=bool)
+    picks, gains = [], []
+    for _ in range(q):
+        cand = np.flatnonzero(left)
+        gain = _POP8[bits[cand] & ~covered].sum(axis=1, dtype=np.int64)
+        best = cand[np.lexsort((lev[cand], -do[lev[cand]].astype(np.int64), -gain))[0]]
+        gains.append(int(gain[cand == best][0]))
+        picks.append(int(best))
+        left[best] = False
+        covered |= bits[best]
+    out = keys.copy()
+    out[lev[picks]] = a + np.arange(q, dtype=np.float64)
+    out[lev[left]] = a + q + np.arange(int(left.sum()), dtype=np.float64)
+    return out, lev[picks].astype(np.int32), np.asarray(gains, dtype=np.uint64)
+
+
 MO_EXCLUSIVE_MODES = ('before', 'others')
 
 
@@ -387,7 +486,7 @@ def mo_exclusive(F, reference, mode, G=None, rows=None):
     return excl
 
 
-def mo_keys(F, counts=None, G=None, tiebreak='dominates', n_select=0):
+def mo_keys(F, counts=None, G=None, tiebreak='dominates', n_select=0, n_samples=MO_HVS_SAMPLES):
     """The Pareto-compliant total order of the objective vectors F [n, M] as
     one loss column: keys[i] is row i's position, 0 .. as a float64, under
     ascending by, then descending do, then ascending i (mo_counts; by is 0
@@ -400,9 +499,11 @@ def mo_keys(F, counts=None, G=None, tiebreak='dominates', n_select=0):
     ascending violation and position -- the same three-field order.
     tiebreak='hypervolume' (M 2 or 3): the level that straddles position
     n_select reordered so that the first n_select rows are the greedy
-    hypervolume subset (mo_hypervolume_order; the kernel's integers)."""
-    if tiebreak not in ('dominates', 'hypervolume'):
-        raise ValueError("tiebreak must be 'dominates' or 'hypervolume'")
+    hypervolume subset (mo_hypervolume_order; the kernel's integers).
+    tiebreak='hypervolume_mc' (M 2 .. 8): the same with the gains counted on
+    n_samples fixed sample points (mo_hypervolume_mc_order)."""
+    if tiebreak not in ('dominates', 'hypervolume', 'hypervolume_mc'):
+        raise ValueError("tiebreak must be 'dominates', 'hypervolume' or 'hypervolume_mc'")
     by, do = mo_counts(F, G) if counts is None else counts
     keys = np.full(len(by), np.nan)
     valid = np.flatnonzero(by >= 0)
@@ -410,6 +511,8 @@ def mo_keys(F, counts=None, G=None, tiebreak='dominates', n_select=0):
     keys[valid[order]] = np.arange(len(valid), dtype=np.float64)
     if tiebreak == 'hypervolume':
         return mo_hypervolume_order(F, by, do, keys, n_select, G)[0]
+    if tiebreak == 'hypervolume_mc':
+        return mo_hypervolume_mc_order(F, by, do, keys, n_select, n_samples, G)[0]
     return keys
 
 

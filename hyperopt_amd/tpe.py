@@ -815,15 +815,19 @@ def objective_rows(docs, objectives, domain=None, check_from=True, constraints=N
 _misc_of = operator.itemgetter('misc')
 
 
-def objective_keys(F, builder='auto', engine=None, G=None, tiebreak='dominates', n_select=0):
+def objective_keys(F, builder='auto', engine=None, G=None, tiebreak='dominates', n_select=0,
+                   n_samples=_post.MO_HVS_SAMPLES):
     """posterior.mo_keys(F) by the builder the call selects: 'host' numpy,
     'device' the kernel (Engine.mo_keys on `engine`, a callable returning the
     Engine), 'auto' the kernel from MO_DEVICE_MIN_TRIALS rows on.  The same
     integers either way.  G: the constraint rows (posterior.mo_keys(F, G=G),
-    Engine.mo_keys(F, G=G)).  tiebreak, n_select: handed to either builder."""
+    Engine.mo_keys(F, G=G)).  tiebreak, n_select, n_samples ('hypervolume_mc'
+    alone): handed to either builder."""
     kw = {} if G is None else dict(G=G)
     if tiebreak != 'dominates':
         kw.update(tiebreak=tiebreak, n_select=n_select)
+    if tiebreak == 'hypervolume_mc':
+        kw.update(n_samples=n_samples)
     if len(F) and (builder == 'device' or (builder == 'auto' and len(F) >= MO_DEVICE_MIN_TRIALS)):
         if len(F) > _post.MO_MAX_ROWS:
             raise ValueError('objectives: at most %d complete trials' % _post.MO_MAX_ROWS)
@@ -831,12 +835,27 @@ def objective_keys(F, builder='auto', engine=None, G=None, tiebreak='dominates',
     return _post.mo_keys(F, **kw)
 
 
-def check_mo_tiebreak(mo_tiebreak, objectives, constraint_model='rank'):
+def check_mo_tiebreak(mo_tiebreak, objectives, constraint_model='rank', mo_samples=_post.MO_HVS_SAMPLES):
     """tpe.suggest's `mo_tiebreak` after validation (`objectives` validated):
-    'dominates' or 'hypervolume', the latter with two or three objectives and
-    without constraint_model='density'."""
-    if mo_tiebreak not in ('dominates', 'hypervolume'):
-        raise ValueError("mo_tiebreak must be 'dominates' or 'hypervolume'")
+    'dominates', 'hypervolume' (two or three objectives) or 'hypervolume_mc'
+    (two to eight; mo_samples a multiple of 64 in 64 .. 2^20), the latter two
+    without constraint_model='density'; mo_samples only with 'hypervolume_mc'."""
+    if mo_tiebreak not in ('dominates', 'hypervolume', 'hypervolume_mc'):
+        raise ValueError("mo_tiebreak must be 'dominates', 'hypervolume' or 'hypervolume_mc'")
+    if mo_tiebreak == 'hypervolume_mc':
+        if objectives is None:
+            raise ValueError("mo_tiebreak='hypervolume_mc' needs objectives")
+        if not 2 <= len(objectives) <= _post.MO_MAX_OBJECTIVES:
+            raise ValueError("mo_tiebreak='hypervolume_mc' needs 2 .. %d objectives, got %d"
+                             % (_post.MO_MAX_OBJECTIVES, len(objectives)))
+        if constraint_model == 'density':
+            raise ValueError("mo_tiebreak='hypervolume_mc' with constraint_model='density' is not supported")
+        if (not isinstance(mo_samples, (int, np.integer)) or isinstance(mo_samples, bool) or mo_samples % 64
+                or not 64 <= mo_samples <= _post.MO_HVS_MAX_SAMPLES):
+            raise ValueError("mo_tiebreak='hypervolume_mc': mo_samples must be a multiple of 64 in [64, %d]"
+                             % _post.MO_HVS_MAX_SAMPLES)
+    elif isinstance(mo_samples, bool) or mo_samples != _post.MO_HVS_SAMPLES:
+        raise ValueError("mo_samples needs mo_tiebreak='hypervolume_mc'")
     if mo_tiebreak == 'hypervolume':
         if objectives is None:
             raise ValueError("mo_tiebreak='hypervolume' needs objectives")
@@ -847,15 +866,19 @@ def check_mo_tiebreak(mo_tiebreak, objectives, constraint_model='rank'):
     return mo_tiebreak
 
 
-def _hv_keywords(mo_tiebreak, F, G, gamma):
-    """objective_keys' tiebreak and n_select of a call: n_select is the below
-    set's size for the rows that get a key (no NaN in F or G)."""
-    if mo_tiebreak != 'hypervolume':
+def _hv_keywords(mo_tiebreak, F, G, gamma, mo_samples=_post.MO_HVS_SAMPLES):
+    """objective_keys' tiebreak, n_select and (for 'hypervolume_mc') n_samples
+    of a call: n_select is the below set's size for the rows that get a key
+    (no NaN in F or G)."""
+    if mo_tiebreak == 'dominates':
         return {}
     live = ~np.isnan(F).any(axis=1)
     if G is not None:
         live &= ~np.isnan(G).any(axis=1)
-    return dict(tiebreak='hypervolume', n_select=_post.n_below_of(int(np.count_nonzero(live)), gamma))
+    kw = dict(tiebreak=mo_tiebreak, n_select=_post.n_below_of(int(np.count_nonzero(live)), gamma))
+    if mo_tiebreak == 'hypervolume_mc':
+        kw.update(n_samples=int(mo_samples))
+    return kw
 
 
 class _KeyedDomain(object):
@@ -1273,7 +1296,8 @@ def suggest(new_ids, domain, trials, seed,
             precision='f64', device=0, batch=False, posterior_builder='auto', devices=None,
             multivariate=False, group=False, joint_quantized=False, joint_categorical=False,
             joint_bandwidth='neighbour', fixed=None, pool=None, pool_candidates=None, constraint_model='rank',
-            mo_tiebreak='dominates', pool_replace=False, constraints=None, objectives=None):
+            mo_samples=_post.MO_HVS_SAMPLES, mo_tiebreak='dominates', pool_replace=False, constraints=None,
+            objectives=None):
     """tpe.py:823-916.  Past the startup phase one document for new_ids[0],
     like the reference; `batch` (not in the reference) asks for one document
     per new_id:
@@ -1490,6 +1514,23 @@ def suggest(new_ids, domain, trials, seed,
     a number of objectives other than 2 or 3, or with
     constraint_model='density'.
 
+    mo_tiebreak='hypervolume_mc' (two to eight `objectives`) is the same
+    selection with a sampled hypervolume, HypE's estimator: from four
+    objectives on nearly every trial is on the front, the whole below set is
+    chosen by the tie-break, and an exact union volume is out of reach.
+    mo_samples points (default 65536; a multiple of 64 in 64 .. 2^20) are
+    drawn once inside the bounding box of the level's boxes, in the same rank
+    coordinates, from a fixed Philox stream -- no seed: the order stays a
+    function of the trials alone -- and a trial's gain is the number of points
+    its box covers and no taken trial's does (same ties).  Integers again, so
+    both builders agree bit for bit (posterior.mo_hypervolume_mc_order;
+    Engine.mo_keys(..., tiebreak='hypervolume_mc', n_samples=...): a bit matrix
+    of trials x points built by wave ballots, two small launches a pick;
+    DESIGN.md section 6b, "Sampled hypervolume tie-break").  ValueError, before
+    any engine is touched: without objectives, with fewer than 2 or more than
+    8, with constraint_model='density', a bad mo_samples, or mo_samples given
+    with another mo_tiebreak.
+
     constraints=('mem_over', 'lat_over') (not in the reference; Optuna's
     constraints_func) names 1 to 8 further result-dict keys, each a hard limit
     in Optuna's convention: c <= 0 satisfied, c > 0 violated by that amount --
@@ -1554,7 +1595,7 @@ def suggest(new_ids, domain, trials, seed,
     if _cmodel is None and constraint_model not in ('rank', 'density'):
         raise ValueError("constraint_model must be 'rank' or 'density'")
     density = constraint_model == 'density'
-    check_mo_tiebreak(mo_tiebreak, objectives, constraint_model)
+    check_mo_tiebreak(mo_tiebreak, objectives, constraint_model, mo_samples)
     if density:
         if constraints is None:
             raise ValueError("constraint_model='density' needs constraints")
@@ -1578,7 +1619,7 @@ def suggest(new_ids, domain, trials, seed,
         check_from = _history.has_from_tid(trials, list(specs_of(domain)))
         if constraints is None:
             docs, F = objective_rows(src, objectives, domain, check_from=check_from)
-            keys = objective_keys(F, builder, engine, **_hv_keywords(mo_tiebreak, F, None, gamma))
+            keys = objective_keys(F, builder, engine, **_hv_keywords(mo_tiebreak, F, None, gamma, mo_samples))
             logger.info('tpe.suggest: %d objectives, %d complete trials ranked, %.1f ms' % (
                 len(objectives), len(docs), (time.time() - t0) * 1e3))
         elif density:
@@ -1599,7 +1640,7 @@ def suggest(new_ids, domain, trials, seed,
         else:
             names = objectives or ('loss',)
             docs, F, G = objective_rows(src, names, domain, check_from=check_from, constraints=constraints)
-            keys = objective_keys(F, builder, engine, G=G, **_hv_keywords(mo_tiebreak, F, G, gamma))
+            keys = objective_keys(F, builder, engine, G=G, **_hv_keywords(mo_tiebreak, F, G, gamma, mo_samples))
             if logger.isEnabledFor(logging.INFO):      # (the count is a pass over the rows)
                 logger.info('tpe.suggest: %d objectives, %d constraints, %d complete trials ranked, %d of them '
                             'feasible, %.1f ms' % (len(names), len(constraints), len(docs),

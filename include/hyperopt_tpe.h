@@ -882,6 +882,44 @@ int tpe_mo_keys_hv(tpe_ctx *ctx, const double *objectives /* [n][n_obj] row-majo
                    int32_t *picked /* [n_select] or NULL */, uint64_t *gains /* [n_select] or NULL */,
                    int32_t *n_picked /* or NULL */);
 
+/* The sampled hypervolume tie-break of the below set (tpe.suggest(mo_tiebreak=
+ * 'hypervolume_mc'); an addition to ABI version 5; HypE's estimator, Bader &
+ * Zitzler 2011): tpe_mo_keys_hv for n_obj 2 .. 8, with the gain of a row counted
+ * on n_samples fixed sample points.  by, do, the old order, the rank rows, n_f,
+ * r[i][m], the level, a, q, the conditions under which the keys stay, the pick
+ * positions, the order of the level's other rows, the constraints and every
+ * output are tpe_mo_keys_hv's.  The gain, with c = 0 .. L - 1 the level's rows:
+ *   lo[m] = min_c r[c][m], span[m] = n_f - lo[m] (>= 1): [lo, n_f) is the
+ *       bounding box of the union of the level's boxes;
+ *   sample s = 0 .. n_samples - 1: x[s][m] = lo[m] + ((uint64)word * span[m] >>
+ *       32), word = word m % 4 of philox4x32_10 with the counter (s, m / 4, 0,
+ *       TPE_MO_HVS_STREAM) and the key (TPE_MO_HVS_KEY0, TPE_MO_HVS_KEY1) -- no
+ *       seed: the keys are a function of the trials alone;
+ *   row c covers s iff r[c][m] <= x[s][m] for every m;
+ *   gain(c | P) = the samples c covers and no row of P covers; the largest gain
+ *       is picked, ties (all gains 0 among them): the larger dominates, then the
+ *       smaller i.  gains[] reports these counts.
+ * Integers throughout: the same bits on every run and the bits of
+ * posterior.mo_hypervolume_mc_order.  The coverage matrix (one bit per level
+ * row and sample) is sized to the level found, so the call reads the level's
+ * header back first: two stream synchronisations, none between picks.  Its own
+ * reusable buffers (counted by tpe_device_bytes, growing only) are allocated by
+ * the first such call.
+ * TPE_ERR_ARG: everything tpe_mo_keys_hv refuses, with n_obj outside [2, 8];
+ * n_samples not a multiple of 64 in [64, 2^20]; a level of L rows with L *
+ * n_samples > 2^33 (a matrix past 1 GiB; the message names L and n_samples).
+ * On an error the outputs are untouched. */
+#define TPE_MO_HVS_STREAM 0x7FFFFFBEu   /* the stream below TPE_POOL_STREAM */
+#define TPE_MO_HVS_KEY0 0x4D4F4856u     /* "MOHV" */
+#define TPE_MO_HVS_KEY1 0x53414D50u     /* "SAMP" */
+int tpe_mo_keys_hvs(tpe_ctx *ctx, const double *objectives /* [n][n_obj] row-major */,
+                    int64_t n, int32_t n_obj,
+                    const double *constraints /* [n][n_con] row-major, or NULL */, int32_t n_con,
+                    int32_t n_select, int32_t n_samples, double *keys /* [n] */,
+                    int32_t *dominated_by /* [n] or NULL */, int32_t *dominates /* [n] or NULL */,
+                    double *violation /* [n] or NULL */, int32_t *picked /* [n_select] or NULL */,
+                    uint64_t *gains /* [n_select] or NULL */, int32_t *n_picked /* or NULL */);
+
 /* The hypervolume indicator's exclusive volumes (tpe.hypervolume): raw
  * objective values, all minimised, against a reference point.  n_obj 2 or 3.
  * No reference counterpart (the indicator of Zitzler & Thiele; Optuna's

@@ -62,6 +62,16 @@ objectives, with the level size and the picks of each input, and the worst case
 of a 100 000-row antichain (one level) at 3 objectives; with --quality it adds
 the row objectives_hypervolume to the ZDT1 table.
 
+--tiebreak hypervolume_mc (tpe.suggest(mo_tiebreak='hypervolume_mc')): the
+timing leg times Engine.mo_keys(F, tiebreak='hypervolume_mc', n_select=n_below,
+n_samples=--samples) against the default Engine.mo_keys(F), alternating, at
+the sizes above x --objectives M (default 4 and 8), with the level size, the
+picks, the bytes of the coverage matrix and, up to --host-max-n rows, whether
+the numpy builder gives the same keys; with --quality it runs DTLZ2 with four
+objectives in six dimensions under 'dominates', 'hypervolume_mc' and random
+search and reports the hypervolume dominated (tpe.hypervolume, reference 1.5
+on every axis).
+
 --indicator (tpe.hypervolume): Engine.mo_exclusive (tpe_mo_exclusive: upload,
 validity, domination pass, live-row list, a workgroup per live row, read-back)
 against posterior.mo_exclusive, the numpy builder, alternating, at the sizes
@@ -146,6 +156,72 @@ def hv_key_times(eng, args):
         print(json.dumps(rec), flush=True)
         out.append(rec)
     return out
+
+
+def hvs_key_times(eng, args):
+    from hyperopt_amd import posterior as P
+    S = args.samples
+    out = []
+    for n in SIZES:
+        for M in ((args.objectives,) if args.objectives else (4, 8)):
+            F = np.random.RandomState(n + M).uniform(size=(n, M))
+            k = P.n_below_of(n, 0.25)
+            legs = dict(default=lambda: eng.mo_keys(F),
+                        hypervolume_mc=lambda: eng.mo_keys(F, tiebreak='hypervolume_mc', n_select=k, n_samples=S))
+            ts = {name: [] for name in legs}
+            for name in legs:
+                legs[name]()               # warm-up
+            for _ in range(args.reps):     # alternating
+                for name in legs:
+                    t0 = time.perf_counter()
+                    legs[name]()
+                    ts[name].append((time.perf_counter() - t0) * 1e3)
+            keys, by, do, picked, gains = eng.mo_keys(F, want_counts=True, tiebreak='hypervolume_mc', n_select=k,
+                                                      n_samples=S, want_picks=True)
+            level = int(np.count_nonzero(by == by[picked[0]])) if len(picked) else 0
+            rec = dict(what='mo_keys_hvs', rows='uniform', n=n, M=M, n_select=k, n_samples=S, picks=len(picked),
+                       level=level, matrix_bytes=level * S // 8, first_gains=[int(g) for g in gains[:3]])
+            for name, v in ts.items():
+                rec[name] = dict(median_ms=float(np.median(v)), min_ms=float(min(v)), max_ms=float(max(v)),
+                                 reps=len(v))
+            rec['hypervolume_mc_minus_default_ms'] = rec['hypervolume_mc']['median_ms'] - rec['default']['median_ms']
+            if n <= args.host_max_n:
+                t0 = time.perf_counter()
+                host = P.mo_keys(F, tiebreak='hypervolume_mc', n_select=k, n_samples=S)
+                rec['host_ms'] = (time.perf_counter() - t0) * 1e3
+                rec['same_keys'] = bool(np.array_equal(host, keys))
+            print(json.dumps(rec), flush=True)
+            out.append(rec)
+    return out
+
+
+def quality4(args):
+    """DTLZ2, four objectives, six dimensions: the hypervolume dominated."""
+    from hyperopt_amd import STATUS_OK, Trials, fmin, hp, rand, tpe
+    names = ('loss', 'f1', 'f2', 'f3')
+    space = {'x%d' % i: hp.uniform('x%d' % i, 0, 1) for i in range(6)}
+
+    def dtlz2(cfg):
+        x = np.array([cfg['x%d' % i] for i in range(6)])
+        g = float(((x[3:] - 0.5) ** 2).sum())
+        c, s = np.cos(0.5 * np.pi * x[:3]), np.sin(0.5 * np.pi * x[:3])
+        f = (1 + g) * np.array([c[0] * c[1] * c[2], c[0] * c[1] * s[2], c[0] * s[1], s[0]])
+        return dict(zip(names, f.tolist()), status=STATUS_OK)
+    algos = dict(dominates=partial(tpe.suggest, objectives=names),
+                 hypervolume_mc=partial(tpe.suggest, objectives=names, mo_tiebreak='hypervolume_mc',
+                                        mo_samples=args.samples),
+                 random=rand.suggest)
+    rec = dict(what='mo_quality4', problem='DTLZ2, 4 objectives, 6 dimensions', evaluations=args.evals,
+               reference_point=[1.5] * 4, seeds=args.seeds, n_samples=args.samples)
+    for name, algo in algos.items():
+        hv = []
+        for seed in range(args.seeds):
+            trials = Trials()
+            fmin(dtlz2, space, algo=algo, max_evals=args.evals, trials=trials, rstate=np.random.RandomState(seed))
+            hv.append(tpe.hypervolume(trials, names, reference=[1.5] * 4)['hypervolume'])
+        rec[name] = dict(mean=float(np.mean(hv)), min=float(min(hv)), max=float(max(hv)), std=float(np.std(hv)))
+    print(json.dumps(rec), flush=True)
+    return [rec]
 
 
 def crossover(eng, args):
@@ -468,7 +544,9 @@ def main():
     ap.add_argument('--density', action='store_true')
     ap.add_argument('--indicator', action='store_true')
     ap.add_argument('--indicator-m', type=int, default=0, metavar='M', help='--indicator: only the rows with M objectives')
-    ap.add_argument('--tiebreak', choices=('dominates', 'hypervolume'), default='dominates')
+    ap.add_argument('--tiebreak', choices=('dominates', 'hypervolume', 'hypervolume_mc'), default='dominates')
+    ap.add_argument('--objectives', type=int, default=0, metavar='M', help='--tiebreak hypervolume_mc: only M objectives')
+    ap.add_argument('--samples', type=int, default=65536, metavar='S', help='--tiebreak hypervolume_mc: n_samples')
     ap.add_argument('--evals', type=int)
     ap.add_argument('--seeds', type=int, default=10)
     ap.add_argument('--out')
@@ -492,7 +570,12 @@ def main():
         eng.close()
         recs += constrained_step_times(args)
     elif args.quality:
-        recs = quality(args)
+        recs = quality4(args) if args.tiebreak == 'hypervolume_mc' else quality(args)
+    elif args.tiebreak == 'hypervolume_mc':
+        from hyperopt_amd.engine import Engine
+        eng = Engine(0, 'f64')
+        recs = hvs_key_times(eng, args)
+        eng.close()
     elif args.tiebreak == 'hypervolume':
         from hyperopt_amd.engine import Engine
         eng = Engine(0, 'f64')
