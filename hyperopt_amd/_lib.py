@@ -74,6 +74,7 @@ TPE_POOL_STREAM = 0x7FFFFFBF
 TPE_CMODEL_MAX = 8
 TPE_CMODEL_STREAM = 0x7FFF0000
 TPE_CMODEL_STREAM_SPAN = 4096
+TPE_SPLIT_TILE = 1024        # components of a split build's mixture per workgroup
 TPE_JOINT_FLAG_TIE = 1
 TPE_JOINT_FLAG_CATEGORY = 2
 TPE_JOINT_FLAG_COUNT = 4
@@ -165,6 +166,7 @@ SIGNATURES = {
     'tpe_build_posterior_resident_ordered': (ctypes.c_int, [_P, _P, _I64, _I64, _D, _D, _I32, _P, _P, _P,
                                                             _P, _P]),
     'tpe_rebuild_labels': (ctypes.c_int, [_P, _P, _I64, _I64, _D, _D, _I32, _P, _P, _P, _I32, _P, _P]),
+    'tpe_build_split_resident': (ctypes.c_int, [_P, _P, _I64, _D, _I32, _P, _P, _P, _P, _P]),
     'tpe_last_build_ms': (ctypes.c_int, [_P, ctypes.POINTER(ctypes.c_float)]),
     'tpe_build_report': (ctypes.c_int, [_P, ctypes.POINTER(ctypes.c_int32), ctypes.c_void_p]),
     'tpe_last_screen': (ctypes.c_int, [_P, _P, _P, ctypes.POINTER(ctypes.c_float)]),

@@ -868,6 +868,81 @@ __device__ void cat_bincount_few(const double* __restrict__ list, int64_t n, int
     if (tid < upper) out[tid] = bsum[tid];
 }
 
+// The categorical pseudocount posterior (tpe.py:581-617) of one observation
+// list, by every thread of one kParzenBlock workgroup: k_parzen's and
+// k_split_finish's categorical branch.  Output: upper weights at w + o (mu and
+// sigma zero).
+__device__ __forceinline__ void parzen_categorical(const tpe_label_spec& sp, const double* __restrict__ cat_p,
+                                                   const double* __restrict__ list, int64_t n, int64_t o, double pw,
+                                                   int32_t lf, double* __restrict__ w, double* __restrict__ mu,
+                                                   double* __restrict__ sigma, double* __restrict__ leaf_sum) {
+#pragma clang fp contract(off)
+    const int tid = threadIdx.x;
+    // weights = linear_forgetting_weights(len(obs)); counts = bincount(obs,
+    // minlength=upper, weights) -- each bin a sequential sum in observation
+    // order; pseudocounts; / np.sum(pseudocounts).  Up to kCatFewBins bins:
+    // ordered compaction by bin, then one lane per bin adds its run
+    // (cat_bincount_few).  More bins: one wave per bin; ballots over the list
+    // find the bin's observations in order, and the wave adds their weights
+    // one by one through scalar registers (v_readlane) -- the sequential
+    // order of np.bincount.  The list goes through LDS as bin ids, kCatChunk
+    // observations at a time (coalesced loads by the whole block; the waves
+    // then scan LDS).
+    const int32_t upper = sp.upper;
+    const LFRamp ramp = lf_ramp(n, lf);
+    const int wave = tid >> 6, lane = tid & 63;
+    __shared__ int32_t cbin[kCatChunk];
+    for (int b = tid; b < upper; b += kParzenBlock) w[o + b] = 0.0;
+    if (upper <= kCatFewBins) {
+        cat_bincount_few(list, n, upper, ramp, w + o, cbin);
+    } else {   // many bins: one wave per bin walks the list
+        for (int64_t c0 = 0; c0 < n; c0 += kCatChunk) {
+            const int64_t m = n - c0 < kCatChunk ? n - c0 : kCatChunk;
+            for (int64_t i = tid; i < m; i += kParzenBlock) {
+                const double v = list[c0 + i];   // (int64_t)v == b for some bin b, else -1
+                cbin[i] = (v > -1.0 && v < (double)upper) ? (int32_t)(int64_t)v : -1;
+            }
+            __syncthreads();
+            for (int b = wave; b < upper; b += kParzenBlock / 64) {
+                double cnt = w[o + b];
+                for (int64_t i0 = 0; i0 < m; i0 += 64) {
+                    const int64_t i = i0 + lane;
+                    const bool hit = i < m && cbin[i] == b;
+                    uint64_t hm = __ballot(hit);
+                    if (!hm) continue;
+                    const double wl = hit ? lf_weight(c0 + i, ramp) : 0.0;
+                    int64_t bits;
+                    __builtin_memcpy(&bits, &wl, 8);
+                    const int lo = (int)(uint32_t)bits, hi = (int)(uint32_t)(bits >> 32);
+                    while (hm) {
+                        const int j = __builtin_ctzll(hm);
+                        hm &= hm - 1;
+                        const uint64_t vb =
+                            ((uint64_t)(uint32_t)__builtin_amdgcn_readlane(hi, j) << 32) |
+                            (uint32_t)__builtin_amdgcn_readlane(lo, j);
+                        double v;
+                        __builtin_memcpy(&v, &vb, 8);
+                        cnt += v;
+                    }
+                }
+                if (lane == 0) w[o + b] = cnt;
+            }
+            __syncthreads();
+        }
+    }
+    __syncthreads();
+    for (int b = tid; b < upper; b += kParzenBlock) {
+        const double c = w[o + b];
+        const double pseudo = sp.randint ? c + pw
+                                         : c + (double)upper * (pw * cat_p[sp.p_off + b]);
+        w[o + b] = pseudo;
+        mu[o + b] = 0.0;
+        sigma[o + b] = 0.0;
+    }
+    const double tot = block_np_sum(w + o, upper, leaf_sum + o);
+    for (int b = tid; b < upper; b += kParzenBlock) w[o + b] = w[o + b] / tot;
+}
+
 // adaptive_parzen_normal (tpe.py:404-477) / categorical pseudocounts
 // (tpe.py:581-617) of one (label, side).  Output: (w, mu, sigma) at
 // mix_off[2 l + side], component count in kcount[2 l + side].
@@ -891,71 +966,9 @@ __global__ __launch_bounds__(kParzenBlock) void k_parzen(
     __shared__ int32_t bi[kMaxLF];
 
     if (sp.kind == TPE_CATEGORICAL) {
-        // weights = linear_forgetting_weights(len(obs)); counts = bincount(obs,
-        // minlength=upper, weights) -- each bin a sequential sum in
-        // observation order; pseudocounts; / np.sum(pseudocounts)
-        // Up to kCatFewBins bins: ordered compaction by bin, then one lane
-        // per bin adds its run (cat_bincount_few).  More bins: one wave per
-        // bin; ballots over the list find the bin's observations in order,
-        // and the wave adds their weights one by one through scalar registers
-        // (v_readlane) -- the sequential order of np.bincount.  The list goes
-        // through LDS as bin ids, kCatChunk observations at a time (coalesced
-        // loads by the whole block; the waves then scan LDS).
-        const double* list = side == 0 ? below_val + (size_t)l * kMaxLF : keys_unsorted + off;
-        const int32_t upper = sp.upper;
-        const LFRamp ramp = lf_ramp(n, lf);
-        const int wave = tid >> 6, lane = tid & 63;
-        __shared__ int32_t cbin[kCatChunk];
-        for (int b = tid; b < upper; b += kParzenBlock) w[o + b] = 0.0;
-        if (upper <= kCatFewBins) {
-            cat_bincount_few(list, n, upper, ramp, w + o, cbin);
-        } else {   // many bins: one wave per bin walks the list
-            for (int64_t c0 = 0; c0 < n; c0 += kCatChunk) {
-                const int64_t m = n - c0 < kCatChunk ? n - c0 : kCatChunk;
-                for (int64_t i = tid; i < m; i += kParzenBlock) {
-                    const double v = list[c0 + i];   // (int64_t)v == b for some bin b, else -1
-                    cbin[i] = (v > -1.0 && v < (double)upper) ? (int32_t)(int64_t)v : -1;
-                }
-                __syncthreads();
-                for (int b = wave; b < upper; b += kParzenBlock / 64) {
-                    double cnt = w[o + b];
-                    for (int64_t i0 = 0; i0 < m; i0 += 64) {
-                        const int64_t i = i0 + lane;
-                        const bool hit = i < m && cbin[i] == b;
-                        uint64_t hm = __ballot(hit);
-                        if (!hm) continue;
-                        const double wl = hit ? lf_weight(c0 + i, ramp) : 0.0;
-                        int64_t bits;
-                        __builtin_memcpy(&bits, &wl, 8);
-                        const int lo = (int)(uint32_t)bits, hi = (int)(uint32_t)(bits >> 32);
-                        while (hm) {
-                            const int j = __builtin_ctzll(hm);
-                            hm &= hm - 1;
-                            const uint64_t vb =
-                                ((uint64_t)(uint32_t)__builtin_amdgcn_readlane(hi, j) << 32) |
-                                (uint32_t)__builtin_amdgcn_readlane(lo, j);
-                            double v;
-                            __builtin_memcpy(&v, &vb, 8);
-                            cnt += v;
-                        }
-                    }
-                    if (lane == 0) w[o + b] = cnt;
-                }
-                __syncthreads();
-            }
-        }
-        __syncthreads();
-        for (int b = tid; b < upper; b += kParzenBlock) {
-            const double c = w[o + b];
-            const double pseudo = sp.randint ? c + pw
-                                             : c + (double)upper * (pw * cat_p[sp.p_off + b]);
-            w[o + b] = pseudo;
-            mu[o + b] = 0.0;
-            sigma[o + b] = 0.0;
-        }
-        const double tot = block_np_sum(w + o, upper, leaf_sum + o);
-        for (int b = tid; b < upper; b += kParzenBlock) w[o + b] = w[o + b] / tot;
-        if (tid == 0) kcount[2 * l + side] = upper;
+        parzen_categorical(sp, cat_p, side == 0 ? below_val + (size_t)l * kMaxLF : keys_unsorted + off, n, o, pw, lf,
+                           w, mu, sigma, leaf_sum);
+        if (tid == 0) kcount[2 * l + side] = sp.upper;
         return;
     }
 
@@ -1120,6 +1133,270 @@ __global__ __launch_bounds__(kParzenBlock) void k_parzen(
         }
     }
     if (tid == 0) kcount[2 * l + side] = (int32_t)K;
+}
+
+// ------------------------------------------------------- the split build --
+// tpe_build_split_resident: both sides of every label are lists of any
+// length, chosen by one byte per trial position (1 below, 2 above, else
+// neither).  k_split_partition walks a label's history once per view and
+// leaves both sides' lists; k_split_parzen spreads one (label, side) over
+// tiles of kSplitTile components; k_split_finish normalises (and builds the
+// categorical labels); k_fold_terms and k_fold follow as in every build.
+
+// an observation's side and its rank in that side's list, in one word:
+// below rank r -> r, above rank r -> ~r, neither -> kNoSide
+constexpr int32_t kNoSide = INT32_MIN;
+
+// One workgroup per label.  Phase A, observation (tid) order: every
+// observation's rank within its own side's list -- the index its
+// linear-forgetting weight is taken at; categorical labels get both lists
+// themselves, in observation order.  Phase B, value order: the sorted view
+// compacted into the two sorted lists (key, side rank) in the same pass.
+__global__ __launch_bounds__(kPartBlock) void k_split_partition(
+    const tpe_label_spec* __restrict__ specs, const int64_t* __restrict__ p_off,
+    const int32_t* __restrict__ cnt, const int32_t* __restrict__ p_trial,
+    const double* __restrict__ p_val, const double* __restrict__ s_key,
+    const int32_t* __restrict__ s_idx, const uint8_t* __restrict__ side_of, int64_t T,
+    int32_t* __restrict__ srank, double* __restrict__ keys_b, int32_t* __restrict__ idx_b,
+    double* __restrict__ keys_a, int32_t* __restrict__ idx_a, int32_t* __restrict__ counts,
+    int32_t* __restrict__ err) {
+    const int l = blockIdx.x, tid = threadIdx.x, lane = tid & 63, wv = tid >> 6;
+    const int64_t off = p_off[l], M = cnt[l];
+    const bool cat = specs[l].kind == TPE_CATEGORICAL;
+    constexpr int kW = kPartBlock / 64;
+    __shared__ int base_b, base_a;
+    __shared__ int wbu[kPartU][kW], wau[kPartU][kW];
+    const uint64_t lt = (1ull << lane) - 1ull;
+    int nb = 0, na = 0;
+    for (int phase = 0; phase < (cat ? 1 : 2); ++phase) {
+        __syncthreads();
+        if (tid == 0) base_b = base_a = 0;
+        __syncthreads();
+        // kPartU sub-chunks of kPartBlock entries per step, their loads issued
+        // together, one barrier pair for all of them (as k_partition)
+        for (int64_t c0 = 0; c0 < M; c0 += (int64_t)kPartU * kPartBlock) {
+            int32_t ix[kPartU];   // phase A: trial position; phase B: observation index
+            double vv[kPartU];
+#pragma unroll
+            for (int u = 0; u < kPartU; ++u) {
+                const int64_t i = c0 + (int64_t)u * kPartBlock + tid;
+                ix[u] = i < M ? (phase ? s_idx[off + i] : p_trial[off + i]) : -1;
+                vv[u] = i < M ? (phase ? s_key[off + i] : p_val[off + i]) : 0.0;
+            }
+            int32_t r[kPartU];    // phase B: the observation's word from phase A
+            bool isb[kPartU], isa[kPartU];
+#pragma unroll
+            for (int u = 0; u < kPartU; ++u) {
+                const int64_t i = c0 + (int64_t)u * kPartBlock + tid;
+                isb[u] = isa[u] = false;
+                r[u] = kNoSide;
+                if (i >= M) continue;
+                if (phase) {
+                    r[u] = srank[off + ix[u]];
+                    isb[u] = r[u] >= 0;
+                    isa[u] = r[u] < 0 && r[u] != kNoSide;
+                } else if (ix[u] >= 0 && ix[u] < T) {
+                    const uint8_t s = side_of[ix[u]];
+                    isb[u] = s == 1;
+                    isa[u] = s == 2;
+                } else if (ix[u] >= T) {
+                    atomicOr(err, 1);
+                }
+            }
+            uint64_t bb[kPartU], ba[kPartU];
+#pragma unroll
+            for (int u = 0; u < kPartU; ++u) {
+                bb[u] = __ballot(isb[u]);
+                ba[u] = __ballot(isa[u]);
+                if (lane == 0) {
+                    wbu[u][wv] = __popcll(bb[u]);
+                    wau[u][wv] = __popcll(ba[u]);
+                }
+            }
+            __syncthreads();
+            int ob = base_b, oa = base_a;
+#pragma unroll
+            for (int u = 0; u < kPartU; ++u) {
+                int pb = ob, pa = oa;   // this sub-chunk's wave offsets
+                for (int w = 0; w < wv; ++w) {
+                    pb += wbu[u][w];
+                    pa += wau[u][w];
+                }
+                pb += __popcll(bb[u] & lt);
+                pa += __popcll(ba[u] & lt);
+                const int64_t i = c0 + (int64_t)u * kPartBlock + tid;
+                if (phase) {          // (pb <= pa + pb <= i < M: inside the label's region)
+                    if (isb[u]) {
+                        keys_b[off + pb] = vv[u];
+                        idx_b[off + pb] = r[u];
+                    } else if (isa[u]) {
+                        keys_a[off + pa] = vv[u];
+                        idx_a[off + pa] = ~r[u];
+                    }
+                } else if (cat) {
+                    if (isb[u]) keys_b[off + pb] = vv[u];
+                    else if (isa[u]) keys_a[off + pa] = vv[u];
+                } else if (i < M) {
+                    srank[off + i] = isb[u] ? pb : (isa[u] ? ~pa : kNoSide);
+                }
+                for (int w = 0; w < kW; ++w) {   // (the sub-chunk's totals)
+                    ob += wbu[u][w];
+                    oa += wau[u][w];
+                }
+            }
+            __syncthreads();
+            if (tid == 0) {
+                base_b = ob;
+                base_a = oa;
+            }
+            __syncthreads();
+        }
+        nb = base_b;
+        na = base_a;
+    }
+    if (tid == 0) {
+        counts[2 * l] = nb;
+        counts[2 * l + 1] = na;
+    }
+}
+
+// adaptive_parzen_normal (tpe.py:404-477) of one tile of one (label, side):
+// grid (tiles, 2, labels), a tile kSplitTile slots of the mixture (the sorted
+// observations with the prior inserted).  The tile finds the prior's slot by
+// binary search (np.searchsorted, side 'left'), stages its slots' values and
+// one neighbour on each end in LDS, and writes mu, the clipped gap sigma and
+// the unnormalised weight of every slot -- k_parzen's arithmetic per slot,
+// elementwise, so the tiling does not show in the result.  A supplied order
+// (np.argsort of the side's list) replaces the ranks of the sorted list;
+// ties[l] bit `side` reports equal mus under a ramp without one.
+constexpr int kSplitTile = TPE_SPLIT_TILE;
+constexpr int kSplitParzenBlock = 256;
+static_assert((kSplitTile & (kSplitTile - 1)) == 0 && kSplitTile % kSplitParzenBlock == 0, "tile shape");
+__global__ __launch_bounds__(kSplitParzenBlock) void k_split_parzen(
+    const tpe_label_spec* __restrict__ specs, const int64_t* __restrict__ obs_off,
+    const int32_t* __restrict__ counts, const double* __restrict__ keys_b, const int32_t* __restrict__ idx_b,
+    const double* __restrict__ keys_a, const int32_t* __restrict__ idx_a, const int64_t* __restrict__ mix_off,
+    double prior_weight, int32_t lf, double* __restrict__ w, double* __restrict__ mu, double* __restrict__ sigma,
+    int32_t* __restrict__ kcount, const int64_t* __restrict__ order_off_b, const int32_t* __restrict__ order_b,
+    const int64_t* __restrict__ order_off_a, const int32_t* __restrict__ order_a, int32_t* __restrict__ ties,
+    int32_t* __restrict__ err) {
+#pragma clang fp contract(off)
+    const int l = blockIdx.z, side = blockIdx.y, tid = threadIdx.x;
+    const tpe_label_spec sp = specs[l];
+    if (sp.kind == TPE_CATEGORICAL) return;   // (k_split_finish)
+    const int64_t n = counts[2 * l + side], K = n + 1;
+    const int64_t j0 = (int64_t)blockIdx.x * kSplitTile;
+    if (j0 >= K) return;
+    const int64_t j1 = j0 + kSplitTile < K ? j0 + kSplitTile : K;
+    const int64_t o = mix_off[2 * l + side], off = obs_off[l];
+    const double* __restrict__ sk = (side ? keys_a : keys_b) + off;
+    const int32_t* __restrict__ si = (side ? idx_a : idx_b) + off;
+    bool supplied = false;
+    if (const int64_t* oo = side ? order_off_a : order_off_b) {
+        const int64_t b = oo[l], e = oo[l + 1];
+        if (e > b && e - b != n) {   // (built with the device's order; the build fails)
+            if (tid == 0 && blockIdx.x == 0) atomicOr(err, 8);
+        } else if (e > b) {
+            supplied = true;
+            si = (side ? order_a : order_b) + b;
+        }
+    }
+    const double pmu = sp.prior_mu, psig = sp.prior_sigma, pw = prior_weight;
+    __shared__ int64_t pos_sh;
+    if (tid == 0) {
+        int64_t lo = 0;
+        if (n == 1) {
+            lo = pmu < sk[0] ? 0 : 1;
+        } else if (n >= 2) {   // the number of sorted values < prior_mu
+            int64_t hi = n;
+            while (lo < hi) {
+                const int64_t mid = (lo + hi) >> 1;
+                if (sk[mid] < pmu) lo = mid + 1; else hi = mid;
+            }
+        }
+        pos_sh = lo;
+    }
+    __syncthreads();
+    const int64_t pos = pos_sh;
+    // slots j0 - 1 .. j1 (those inside the mixture) and the tile's ranks
+    __shared__ double sv[kSplitTile + 2];
+    __shared__ int32_t sr[kSplitTile];
+    const int m = (int)(j1 - j0);
+    for (int i = tid; i < m + 2; i += kSplitParzenBlock) {
+        const int64_t q = j0 - 1 + i;
+        sv[i] = (q < 0 || q >= K) ? 0.0 : (q < pos ? sk[q] : (q == pos ? pmu : sk[q - 1]));
+    }
+    for (int i = tid; i < m; i += kSplitParzenBlock) {
+        const int64_t j = j0 + i;
+        sr[i] = j == pos ? 0 : si[j < pos ? j : j - 1];
+    }
+    __syncthreads();
+    const bool use_lf = lf > 0 && lf < n;
+    const LFRamp ramp = lf_ramp(n, lf);
+    const double maxsigma = psig / 1.0;
+    const double minsigma = psig / fmin(100.0, 1.0 + (double)K);
+    bool dep = false;
+    for (int i = tid; i < m; i += kSplitParzenBlock) {
+        const int64_t j = j0 + i;
+        const double vm = sv[i], v0 = sv[i + 1], vp = sv[i + 2];
+        double s;
+        if (n == 0) {
+            s = psig;
+        } else if (n == 1) {
+            s = (j == pos) ? psig : psig * .5;
+        } else if (j == 0) {
+            s = vp - v0;
+        } else if (j == K - 1) {
+            s = v0 - vm;
+        } else {
+            s = np_maximum(v0 - vm, vp - v0);
+        }
+        s = np_minimum(np_maximum(s, minsigma), maxsigma);   // np.clip
+        double wt = pw;
+        if (j == pos) {
+            s = psig;
+        } else {
+            const int32_t r = sr[i];
+            if (r < 0 || r >= n) {   // (a supplied order out of range)
+                atomicOr(err, 8);
+                wt = 0.0;
+            } else {
+                wt = use_lf ? lf_weight(r, ramp) : 1.0;
+            }
+            // equal mus under a ramp: np.argsort's order of them decides
+            // which weight lands in which slot (see k_parzen)
+            if (j >= 1 && j - 1 != pos && v0 == vm) dep = true;
+        }
+        w[o + j] = wt;
+        mu[o + j] = v0;
+        sigma[o + j] = s;
+    }
+    if (use_lf && !supplied && __ballot(dep) && (tid & 63) == 0) atomicOr(ties + l, 1 << side);
+    if (blockIdx.x == 0 && tid == 0) kcount[2 * l + side] = (int32_t)K;
+}
+
+// weights / weights.sum() in numpy's pairwise order, one workgroup per (label,
+// side); a categorical label's whole posterior from the side's list in
+// observation order.
+__global__ __launch_bounds__(kParzenBlock) void k_split_finish(
+    const tpe_label_spec* __restrict__ specs, const double* __restrict__ cat_p,
+    const int64_t* __restrict__ obs_off, const int32_t* __restrict__ counts, const double* __restrict__ keys_b,
+    const double* __restrict__ keys_a, const int64_t* __restrict__ mix_off, double prior_weight, int32_t lf,
+    double* __restrict__ w, double* __restrict__ mu, double* __restrict__ sigma, int32_t* __restrict__ kcount,
+    double* __restrict__ leaf_sum) {
+#pragma clang fp contract(off)
+    const int l = blockIdx.x, side = blockIdx.y, tid = threadIdx.x;
+    const tpe_label_spec sp = specs[l];
+    const int64_t o = mix_off[2 * l + side];
+    if (sp.kind == TPE_CATEGORICAL) {
+        parzen_categorical(sp, cat_p, (side ? keys_a : keys_b) + obs_off[l], counts[2 * l + side], o, prior_weight,
+                           lf, w, mu, sigma, leaf_sum);
+        if (tid == 0) kcount[2 * l + side] = sp.upper;
+        return;
+    }
+    const int64_t K = (int64_t)counts[2 * l + side] + 1;
+    const double tot = block_np_sum(w + o, K, leaf_sum + o);
+    for (int64_t j = tid; j < K; j += kParzenBlock) w[o + j] = w[o + j] / tot;
 }
 
 __device__ __forceinline__ double dev_normal_cdf(double x, double m, double s) {
@@ -1743,7 +2020,7 @@ int finish_build(tpe_ctx* ctx, BuildTail& t, int32_t* ties_out, int32_t* n_below
     if (errh & 1) return ctx->fail(TPE_ERR_ARG, "observation trial position out of range");
     if (errh & 2) return ctx->fail(TPE_ERR_ARG, "more below observations than the below set (duplicate trial in a label?)");
     if (errh & 4) return ctx->fail(TPE_ERR_VALUE, "below weights sum to zero");
-    if (errh & 8) return ctx->fail(TPE_ERR_ARG, "supplied observation order does not fit the above set");
+    if (errh & 8) return ctx->fail(TPE_ERR_ARG, "supplied observation order does not fit the observation list it orders");
 
     std::vector<int32_t> cat;
     for (int m = 0; m < kNumModes; ++m) {
@@ -1781,6 +2058,47 @@ int finish_build(tpe_ctx* ctx, BuildTail& t, int32_t* ties_out, int32_t* n_below
     P.bx_prescan_ok = t.prescan && !P.bx_ready;
     if (t.arm_c > 0) return tpe1_prepare(ctx, t.arm_c, t.arm_r);
     return TPE_OK;
+}
+
+// The static DLabel fields of every label of the resident history and the
+// regions of its two mixtures and of its sampling records.  below_cap: the
+// components a continuous label's below mixture can hold (<= 0: as many as
+// its above mixture, the label's whole history and the prior).
+void layout_labels(const BuildBufs& B, int64_t below_cap, std::vector<DLabel>& dl, std::vector<int64_t>& mix,
+                   std::vector<int32_t>* grp, int64_t& total, int64_t& samp_total, int64_t& max_cap) {
+    const int32_t n_labels = (int32_t)B.specs_h.size();
+    dl.resize(n_labels);
+    mix.resize(2 * (size_t)n_labels);
+    for (int32_t l = 0; l < n_labels; ++l) {
+        const tpe_label_spec& s = B.specs_h[l];
+        DLabel& o = dl[l];
+        std::memset(&o, 0, sizeof(o));
+        const bool quant = (s.flags & TPE_HAS_Q) != 0;
+        int64_t cap_b, cap_a;
+        if (s.kind == TPE_CATEGORICAL) {
+            o.mode = CAT;
+            cap_b = cap_a = s.upper;
+        } else {
+            o.mode = s.kind == TPE_GMM1 ? (quant ? QUANT_GMM : DENSE_GMM) : (quant ? QUANT_LGMM : DENSE_LGMM);
+            cap_a = (int64_t)B.cnt_h[l] + 1;
+            cap_b = below_cap > 0 ? below_cap : cap_a;
+        }
+        o.flags = s.kind == TPE_CATEGORICAL ? 0 : (s.flags & (TPE_HAS_LOW | TPE_HAS_HIGH | TPE_HAS_Q));
+        o.low = s.low;
+        o.high = s.high;
+        o.q = s.q;
+        o.exp_low = std::exp(s.low);
+        o.exp_high = std::exp(s.high);
+        o.stream = (s.flags & TPE_HAS_STREAM) ? s.stream : l;
+        o.comp_b = mix[2 * l] = total;
+        total += cap_b;
+        o.comp_a = mix[2 * l + 1] = total;
+        total += cap_a;
+        max_cap = std::max(max_cap, std::max(cap_b, cap_a));
+        o.samp_off = samp_total;
+        samp_total += cap_b;
+        grp[o.mode].push_back(l);
+    }
 }
 
 int build_resident(tpe_ctx* ctx, const double* losses, int64_t n_trials, int64_t n_valid,
@@ -1850,40 +2168,11 @@ int build_resident(tpe_ctx* ctx, const double* losses, int64_t n_trials, int64_t
     }
 
     // static label fields, mixture / record regions
-    std::vector<DLabel> dl(n_labels);
-    std::vector<int64_t> mix(2 * (size_t)n_labels);
+    std::vector<DLabel> dl;
+    std::vector<int64_t> mix;
     std::vector<int32_t> grp[kNumModes];
     int64_t total = 0, samp_total = 0, max_cap = 1;
-    for (int32_t l = 0; l < n_labels; ++l) {
-        const tpe_label_spec& s = B.specs_h[l];
-        DLabel& o = dl[l];
-        std::memset(&o, 0, sizeof(o));
-        const bool quant = (s.flags & TPE_HAS_Q) != 0;
-        int64_t cap_b, cap_a;
-        if (s.kind == TPE_CATEGORICAL) {
-            o.mode = CAT;
-            cap_b = cap_a = s.upper;
-        } else {
-            o.mode = s.kind == TPE_GMM1 ? (quant ? QUANT_GMM : DENSE_GMM) : (quant ? QUANT_LGMM : DENSE_LGMM);
-            cap_b = lf + 1;
-            cap_a = (int64_t)B.cnt_h[l] + 1;
-        }
-        o.flags = s.kind == TPE_CATEGORICAL ? 0 : (s.flags & (TPE_HAS_LOW | TPE_HAS_HIGH | TPE_HAS_Q));
-        o.low = s.low;
-        o.high = s.high;
-        o.q = s.q;
-        o.exp_low = std::exp(s.low);
-        o.exp_high = std::exp(s.high);
-        o.stream = (s.flags & TPE_HAS_STREAM) ? s.stream : l;
-        o.comp_b = mix[2 * l] = total;
-        total += cap_b;
-        o.comp_a = mix[2 * l + 1] = total;
-        total += cap_a;
-        max_cap = std::max(max_cap, std::max(cap_b, cap_a));
-        o.samp_off = samp_total;
-        samp_total += cap_b;
-        grp[o.mode].push_back(l);
-    }
+    layout_labels(B, lf + 1, dl, mix, grp, total, samp_total, max_cap);
     const int64_t T = n_trials;
     HIPCHK(ctx, B.losses.reserve(std::max<int64_t>(T, 1)));
     HIPCHK(ctx, B.below.reserve(std::max<int64_t>(T, 1)));
@@ -2077,6 +2366,162 @@ int build_resident(tpe_ctx* ctx, const double* losses, int64_t n_trials, int64_t
     return finish_build(ctx, t, ties_out, n_below_out);
 }
 
+// tpe_build_split_resident: the resident history split by the caller's byte
+// per trial position; both orders and the tie report per side (see the
+// kernels above).  The below mixtures are as long as the above ones, so the
+// regions are laid out for the label's whole history on either side.
+int build_split(tpe_ctx* ctx, const uint8_t* side_h, int64_t n_trials, double prior_weight, int32_t lf,
+                const int64_t* order_off_below, const int32_t* order_below, const int64_t* order_off_above,
+                const int32_t* order_above, int32_t* ties_out) {
+    auto& B = ctx->build;
+    const std::string fn = "tpe_build_split_resident";
+    B.defer = false;
+    if (!B.hist_ready) return ctx->fail(TPE_ERR_ARG, fn + ": no resident history (tpe_history_reset)");
+    if (lf < 1) return ctx->fail(TPE_ERR_ARG, fn + ": linear forgetting must be at least 1");
+    if (n_trials < 0 || n_trials >= INT32_MAX || (n_trials > 0 && !side_h))
+        return ctx->fail(TPE_ERR_ARG, fn + ": bad trial arguments");
+    for (int64_t t = 0; t < n_trials; ++t)
+        if (side_h[t] > 2) return ctx->fail(TPE_ERR_ARG, fn + ": side must be 0, 1 or 2");
+    const int32_t n_labels = (int32_t)B.specs_h.size();
+    const int64_t* oo_h[2] = {order_off_below, order_off_above};
+    const int32_t* ord_h[2] = {order_below, order_above};
+    for (int sd = 0; sd < 2; ++sd) {
+        if (!oo_h[sd] || !ord_h[sd] || oo_h[sd][n_labels] <= 0) {
+            oo_h[sd] = nullptr;
+            continue;
+        }
+        for (int32_t l = 0; l < n_labels; ++l)
+            if (oo_h[sd][l + 1] < oo_h[sd][l] || oo_h[sd][l] < 0)
+                return ctx->fail(TPE_ERR_ARG, fn + ": order offsets must not decrease");
+    }
+    B.built_ok = false;   // (no label-subset rebuild follows a split build)
+    ctx->arm_c = ctx->arm_r = 0;   // an armed tpe_prepare is dropped: this build's index is not queued
+    ctx->resident.bx_prescan_ok = false;
+    HIPCHK(ctx, hipSetDevice(ctx->device));
+    Posterior& P = ctx->resident;
+    ctx->P = &ctx->resident;
+    hipStream_t st = ctx->stream;
+
+    BuildTail t;
+    int64_t total = 0, samp_total = 0, max_cap = 1;
+    layout_labels(B, 0, t.dl, t.mix, t.grp, total, samp_total, max_cap);
+    const int64_t T = n_trials, pool = std::max<int64_t>(B.pool_cap, 1);
+    HIPCHK(ctx, B.below.reserve(std::max<int64_t>(T, 1)));
+    HIPCHK(ctx, B.counts.reserve(2 * (size_t)n_labels));
+    HIPCHK(ctx, B.kcount.reserve(2 * (size_t)n_labels));
+    HIPCHK(ctx, B.keys.reserve(pool));
+    HIPCHK(ctx, B.idx.reserve(pool));
+    HIPCHK(ctx, B.keys_b.reserve(pool));   // the second pair of list buffers: reserved on first use
+    HIPCHK(ctx, B.idx_b.reserve(pool));
+    HIPCHK(ctx, B.arank.reserve(pool));
+    HIPCHK(ctx, B.w.reserve(total));
+    HIPCHK(ctx, B.mu.reserve(total));
+    HIPCHK(ctx, B.sigma.reserve(total));
+    HIPCHK(ctx, B.mix_off.reserve(2 * (size_t)n_labels));
+    HIPCHK(ctx, B.scratch.reserve(4 * (size_t)total));   // terms | leaf sums | constants | scales
+    HIPCHK(ctx, P.labels.reserve(n_labels));
+    HIPCHK(ctx, P.comps64.reserve(total));
+    HIPCHK(ctx, P.comps32.reserve(total));
+    HIPCHK(ctx, P.samp.reserve(samp_total));
+    HIPCHK(ctx, ctx->build_err.reserve(1));
+    HIPCHK(ctx, B.ties.reserve(n_labels + 1));
+    // the inputs in one staging block, one H2D copy and one scatter launch
+    std::vector<UpTask> up;
+    std::vector<const void*> up_src;
+    auto put = [&](const void* src, int64_t bytes, void* dst) {
+        if (bytes <= 0) return;
+        up.push_back(UpTask{0, (uint8_t*)dst, bytes, 0});
+        up_src.push_back(src);
+    };
+    put(nullptr, (n_labels + 1) * (int64_t)sizeof(int32_t), B.ties.p);
+    const int64_t* oo_d[2] = {nullptr, nullptr};
+    const int32_t* ord_d[2] = {nullptr, nullptr};
+    for (int sd = 0; sd < 2; ++sd) {
+        if (!oo_h[sd]) continue;
+        DevBuf<int64_t>& off = sd ? B.order_off : B.order_off_b;
+        DevBuf<int32_t>& ord = sd ? B.order : B.order_b;
+        HIPCHK(ctx, off.reserve(n_labels + 1));
+        HIPCHK(ctx, ord.reserve(oo_h[sd][n_labels]));
+        put(oo_h[sd], (n_labels + 1) * (int64_t)sizeof(int64_t), off.p);
+        put(ord_h[sd], oo_h[sd][n_labels] * (int64_t)sizeof(int32_t), ord.p);
+        oo_d[sd] = off.p;
+        ord_d[sd] = ord.p;
+    }
+    B.ord_cur.assign(n_labels, 0);
+    put(side_h, T, B.below.p);
+    put(t.mix.data(), (int64_t)t.mix.size() * (int64_t)sizeof(int64_t), B.mix_off.p);
+    put(t.dl.data(), n_labels * (int64_t)sizeof(DLabel), P.labels.p);
+    put(nullptr, sizeof(int32_t), ctx->build_err.p);
+    {
+        const int64_t head = ((int64_t)up.size() * (int64_t)sizeof(UpTask) + 255) / 256 * 256;
+        int64_t o = head, mx = 1;
+        for (size_t i = 0; i < up.size(); ++i) {
+            up[i].src = up_src[i] ? o : -1;
+            if (up_src[i]) o += (up[i].bytes + 15) / 16 * 16;
+            mx = std::max(mx, up[i].bytes);
+        }
+        if (B.up_pending) {   // (the previous build's copy out of the staging)
+            HIPCHK(ctx, hipEventSynchronize(B.ev_up));
+            B.up_pending = false;
+        }
+        HIPCHK(ctx, B.h_up.resize(o));
+        HIPCHK(ctx, B.d_up.reserve(o));
+        std::memcpy(B.h_up.data(), up.data(), up.size() * sizeof(UpTask));
+        for (size_t i = 0; i < up.size(); ++i)
+            if (up_src[i]) std::memcpy(B.h_up.data() + up[i].src, up_src[i], up[i].bytes);
+        HIPCHK(ctx, hipMemcpyAsync(B.d_up.p, B.h_up.data(), o, hipMemcpyHostToDevice, st));
+        if (!B.ev_up) HIPCHK(ctx, hipEventCreateWithFlags(&B.ev_up, hipEventDisableTiming));
+        HIPCHK(ctx, hipEventRecord(B.ev_up, st));
+        B.up_pending = true;
+        hipLaunchKernelGGL(k_build_inputs,
+                           dim3((unsigned)std::min<int64_t>((mx + 4 * kUpBlock - 1) / (4 * kUpBlock), 32),
+                                (unsigned)up.size()),
+                           dim3(kUpBlock), 0, st, (const UpTask*)B.d_up.p, B.d_up.p);
+        HIPCHK(ctx, hipGetLastError());
+    }
+
+    HIPCHK(ctx, hipEventRecord(ctx->ev0, st));
+    hipLaunchKernelGGL(k_split_partition, dim3(n_labels), dim3(kPartBlock), 0, st, B.specs.p, B.p_off.p, B.cnt.p,
+                       B.p_trial.p, B.p_val.p, B.s_key.p, B.s_idx.p, B.below.p, T, B.arank.p, B.keys_b.p,
+                       B.idx_b.p, B.keys.p, B.idx.p, B.counts.p, ctx->build_err.p);
+    hipLaunchKernelGGL(k_split_parzen, dim3((unsigned)((max_cap + kSplitTile - 1) / kSplitTile), 2, n_labels),
+                       dim3(kSplitParzenBlock), 0, st, B.specs.p, B.p_off.p, B.counts.p, B.keys_b.p, B.idx_b.p,
+                       B.keys.p, B.idx.p, B.mix_off.p, prior_weight, lf, B.w.p, B.mu.p, B.sigma.p, B.kcount.p,
+                       oo_d[0], ord_d[0], oo_d[1], ord_d[1], B.ties.p, ctx->build_err.p);
+    hipLaunchKernelGGL(k_split_finish, dim3(n_labels, 2), dim3(kParzenBlock), 0, st, B.specs.p, B.cat_p.p,
+                       B.p_off.p, B.counts.p, B.keys_b.p, B.keys.p, B.mix_off.p, prior_weight, lf, B.w.p, B.mu.p,
+                       B.sigma.p, B.kcount.p, B.scratch.p + total);
+    hipLaunchKernelGGL(k_fold_terms, dim3((unsigned)((max_cap + kTermBlock - 1) / kTermBlock), n_labels, 2),
+                       dim3(kTermBlock), 0, st, P.labels.p, B.kcount.p, B.mix_off.p, B.w.p, B.mu.p, B.sigma.p,
+                       B.scratch.p, B.scratch.p + 2 * total, B.scratch.p + 3 * total, (const int32_t*)nullptr);
+    hipLaunchKernelGGL(k_fold, dim3(n_labels), dim3(kParzenBlock), 0, st, P.labels.p, B.kcount.p, B.mix_off.p,
+                       B.w.p, B.mu.p, B.sigma.p, P.comps64.p, P.comps32.p, P.samp.p, B.scratch.p,
+                       B.scratch.p + 2 * total, B.scratch.p + 3 * total, B.scratch.p + total, ctx->build_err.p,
+                       (const int32_t*)nullptr);
+    HIPCHK(ctx, hipGetLastError());
+    HIPCHK(ctx, hipEventRecord(ctx->ev1, st));
+    const int64_t rep_dl = (int64_t)n_labels * (int64_t)sizeof(DLabel);
+    const int64_t rep_bytes = rep_dl + 16 + (int64_t)(n_labels + 1) * (int64_t)sizeof(int32_t);
+    HIPCHK(ctx, B.d_rep.reserve(rep_bytes));
+    HIPCHK(ctx, B.h_rep.resize(rep_bytes));
+    hipLaunchKernelGGL(k_build_report, dim3(1), dim3(kUpBlock), 0, st, (const uint32_t*)P.labels.p,
+                       (int32_t)(rep_dl / 4), ctx->build_err.p, B.ties.p, n_labels + 1, (uint32_t*)B.d_rep.p);
+    HIPCHK(ctx, hipGetLastError());
+    HIPCHK(ctx, hipMemcpyAsync(B.h_rep.data(), B.d_rep.p, rep_bytes, hipMemcpyDeviceToHost, st));
+    ctx->pin[0].bx_diff = 1;   // (an expansion index of the previous posterior does not survive)
+    t.st = st;
+    t.rep_dl = rep_dl;
+    t.n_labels = n_labels;
+    t.lf = lf;
+    t.n_below = -1;            // no one below set: tpe_build_report reads -1
+    t.n_trials = n_trials;
+    t.pw = prior_weight;
+    const int rc = finish_build(ctx, t, nullptr, nullptr);
+    B.built_ok = false;
+    if (!rc && ties_out) std::memcpy(ties_out, B.last_ties.data(), n_labels * sizeof(int32_t));
+    return rc;
+}
+
 }  // namespace
 
 int tpe_rt::settle_build(tpe_ctx* ctx) {
@@ -2131,6 +2576,17 @@ TPE_DEV int tpe1_rebuild_labels(tpe_ctx* ctx, const double* losses, int64_t n_tr
     if (!labels || n_only <= 0) return ctx->fail(TPE_ERR_ARG, "tpe_rebuild_labels: no labels");
     return build_resident(ctx, losses, n_trials, n_valid, gamma, prior_weight, lf, n_below_out, nullptr,
                           order_off, order, ties, labels, n_only);
+}
+
+int tpe_build_split_resident(tpe_ctx* ctx, const uint8_t* side, int64_t n_trials, double prior_weight, int32_t lf,
+                             const int64_t* order_off_below, const int32_t* order_below,
+                             const int64_t* order_off_above, const int32_t* order_above, int32_t* ties) {
+    if (!ctx) return TPE_ERR_ARG;
+    if (!ctx->peers.empty())
+        return ctx->fail(TPE_ERR_ARG, "tpe_build_split_resident: not available on a multi-device context");
+    TPE_SETTLE(ctx);
+    return build_split(ctx, side, n_trials, prior_weight, lf, order_off_below, order_below, order_off_above,
+                       order_above, ties);
 }
 
 TPE_DEV int tpe1_build_posterior(tpe_ctx* ctx, const tpe_label_spec* specs, int32_t n_labels,

@@ -347,6 +347,8 @@ struct BuildBufs {
     DevBuf<uint8_t> below;         // per trial: in the below set
     DevBuf<double> keys;           // per label: above observations (sorted / in order)
     DevBuf<int32_t> idx;           //   and their above-list rank
+    DevBuf<double> keys_b;         // the split build's below lists, as keys / idx hold the above ones
+    DevBuf<int32_t> idx_b;
     DevBuf<double> below_val;      // per label, <= lf below observations
     DevBuf<int32_t> counts;        // per label: below / above observation counts
     DevBuf<int32_t> kcount;        // per label: below / above component counts
@@ -356,6 +358,8 @@ struct BuildBufs {
     DevBuf<int32_t> ties;          // per label: mixtures that depend on a tie order; [L]: split tie
     DevBuf<int64_t> order_off;     // supplied np.argsort orders of the above observations
     DevBuf<int32_t> order;
+    DevBuf<int64_t> order_off_b;   // the same for the below observations (tpe_build_split_resident)
+    DevBuf<int32_t> order_b;
     int32_t n_labels = 0;          // labels of the last build (0: none resident)
     std::vector<int64_t> mix_h;    // host copy of mix_off
     // what the last build was of (a label-subset rebuild requires the same):
@@ -392,7 +396,8 @@ struct BuildBufs {
         idx.release(); below_val.release(); counts.release(); kcount.release(); w.release();
         mu.release(); sigma.release(); mix_off.release(); scratch.release(); ties.release();
         order_off.release(); order.release(); only.release(); split_key.release(); split_pos.release();
-        d_up.release(); d_rep.release(); d_stage.release();
+        d_up.release(); d_rep.release(); d_stage.release(); keys_b.release(); idx_b.release();
+        order_off_b.release(); order_b.release();
         if (ev_up) (void)hipEventDestroy(ev_up);
         ev_up = nullptr;
         up_pending = false;

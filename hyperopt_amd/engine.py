@@ -52,6 +52,7 @@ SPEC_DTYPE = np.dtype([('kind', '<i4'), ('flags', '<i4'), ('low', '<f8'), ('high
                        ('upper', '<i4'), ('randint', '<i4'), ('p_off', '<i8'),
                        ('stream', '<i4'), ('reserved', '<i4')])
 assert SPEC_DTYPE.itemsize == ctypes.sizeof(L.LabelSpec)
+SPLIT_TILE = L.TPE_SPLIT_TILE   # components of a build_split mixture per workgroup
 
 
 JOINT_DIM_DTYPE = np.dtype({'names': ['kind', 'flags', 'low', 'high', 'stream'],
@@ -292,6 +293,41 @@ class Engine(object):
             self.h, _ptr(losses), len(losses), int(n_valid), float(gamma), float(prior_weight), int(lf),
             _ptr(order_off), _ptr(order), _ptr(only), len(only), ctypes.byref(nb), _ptr(ties)))
         return nb.value, ties
+
+    def build_split(self, side, prior_weight, lf=25, orders_below=None, orders_above=None):
+        """The split build (tpe_build_split_resident): the posterior of the
+        resident history with side[t] per trial position -- 1 below, 2 above,
+        0 in neither set (posterior.Splitter.side's coding) -- and both sides
+        of any length.  orders_below / orders_above: (order_off, order), per
+        label np.argsort of that side's observations, an empty range keeping
+        the device's position order.  Returns ties[n_labels]: bit 0 (bit 1)
+        when the label's below (above) mixture depends on a tie order that was
+        not supplied (posterior.build_split_reference_order supplies it).
+        get_mixture reads the mixtures back.  One-device engines only."""
+        if isinstance(lf, bool) or not isinstance(lf, (int, np.integer)) or lf < 1:
+            raise ValueError('lf must be an integer >= 1, got %r' % (lf,))
+        if len(self.devices) != 1:
+            raise ValueError('build_split runs on a one-device engine')
+        side = np.ascontiguousarray(side, dtype=np.uint8)
+        if side.ndim != 1:
+            raise ValueError('side must be one byte per trial position')
+        L_ = self.hist_labels
+        ptrs = []
+        for o in (orders_below, orders_above):
+            if o is None:
+                ptrs += [None, None]
+                continue
+            off = np.ascontiguousarray(o[0], dtype=np.int64)
+            order = np.ascontiguousarray(o[1], dtype=np.int32)
+            if len(off) != L_ + 1 or off[-1] != len(order):
+                raise ValueError('order offsets must be n_labels + 1 long and end at len(order)')
+            ptrs += [off, order]
+        ties = np.zeros(L_, dtype=np.int32)
+        self._check(self.lib.tpe_build_split_resident(
+            self.h, _ptr(side), len(side), float(prior_weight), int(lf), _ptr(ptrs[0]), _ptr(ptrs[1]),
+            _ptr(ptrs[2]), _ptr(ptrs[3]), _ptr(ties)))
+        self.n_labels = self.hist_labels
+        return ties
 
     def build_report(self):
         """(n_below, ties) of the last build, applying a deferred rebuild's

@@ -1340,6 +1340,68 @@ def _build_reference_order(eng, losses, n_valid, gamma, prior_weight, lf, obs_of
     return nb, frozenset(need)
 
 
+# complete trials from which tpe.importance(builder='auto') builds its
+# mixtures on the device (Engine.build_split).  Measured (DESIGN.md section
+# 6b, "The split build"): at 32 labels the host builder wins at 100, 1000 and
+# 10000 trials; at 128 labels x 50000 trials the device builder's median is
+# 2 to 3 % lower but the two spreads overlap.  No measured size has the device
+# builder win outright, so 'auto' is the host builder at every size.
+IMPORTANCE_DEVICE_MIN_TRIALS = float('inf')
+
+
+def split_orders(side, obs_of, labels, which):
+    """(order_off, order) for Engine.build_split: for each label in `labels`,
+    np.argsort of its observations on side `which` (1 below, 2 above; side per
+    trial position) in observation order -- adaptive_parzen_normal's `order =
+    np.argsort(mus)` (tpe.py:433) on the same array; empty ranges elsewhere."""
+    side = np.asarray(side)
+    T = len(side)
+    parts, off = [], np.zeros(obs_of.n_labels + 1, dtype=np.int64)
+    for l in range(obs_of.n_labels):
+        n = 0
+        if l in labels:
+            pos, val = obs_of(l)
+            pos = np.asarray(pos, dtype=np.int64)
+            ok = (pos >= 0) & (pos < T)
+            sel = np.zeros(len(pos), dtype=bool)
+            sel[ok] = side[pos[ok]] == which
+            parts.append(np.argsort(np.asarray(val, dtype=np.float64)[sel]).astype(np.int32))
+            n = len(parts[-1])
+        off[l + 1] = off[l] + n
+    return off, (np.concatenate(parts) if parts else np.zeros(0, dtype=np.int32))
+
+
+def build_split_reference_order(eng, side, prior_weight, lf, obs_of):
+    """Engine.build_split whose mixtures follow the reference's tie order, as
+    build_reference_order does for the loss-rank split: the device reports the
+    mixtures that depend on the order of tied observations, the host computes
+    numpy's own np.argsort for those alone and the build runs again with them.
+    Returns (labels that needed a below order, labels that needed an above
+    order)."""
+    ties = eng.build_split(side, prior_weight, lf)
+    need_b = set(np.flatnonzero(ties & 1).tolist())
+    need_a = set(np.flatnonzero(ties & 2).tolist())
+    if need_b or need_a:
+        ties = eng.build_split(side, prior_weight, lf, split_orders(side, obs_of, need_b, 1),
+                               split_orders(side, obs_of, need_a, 2))
+        assert not np.any(ties)   # (the split is the caller's: an order cannot move an observation)
+    return frozenset(need_b), frozenset(need_a)
+
+
+def resident_posteriors(eng, labels, prior_weight):
+    """The mixtures a build left resident, as the LabelPosterior objects
+    label_posterior returns (labels = [(name, kind, args)] in the history's
+    order): pack() and Engine.set_posterior then fold them as they fold the
+    host builder's, so both give the same records."""
+    posts = []
+    for li, (name, kind, args) in enumerate(labels):
+        post = label_posterior(name, kind, args, [], [], prior_weight)   # (family, bounds, q)
+        below, above = eng.get_mixture(li, 0), eng.get_mixture(li, 1)
+        post.below, post.above = (below[0], above[0]) if kind in CATEGORICAL else (below, above)
+        posts.append(post)
+    return posts
+
+
 class _ObsOf(object):
     """obs_of(l) over CSR observation arrays (tpe_build_posterior's layout)."""
 

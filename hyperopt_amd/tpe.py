@@ -1089,8 +1089,11 @@ def _quantile_split(fn, space, trials, quantile, n_grid, max_grid, device, objec
     return specs, names, obs, tids, done, splitter
 
 
+IMPORTANCE_BUILDERS = ('auto', 'host', 'device')
+
+
 def importance(space, trials, quantile=0.1, n_grid=4096, prior_weight=_default_prior_weight,
-               normalize=True, curves=False, device=0, objectives=None, constraints=None):
+               normalize=True, curves=False, device=0, objectives=None, constraints=None, builder='auto'):
     """Which hyperparameters mattered (not in the reference; Optuna's
     get_param_importances with the PED-ANOVA evaluator asks the same
     question): {label: importance}, sorted descending, ties in label order.
@@ -1117,10 +1120,21 @@ def importance(space, trials, quantile=0.1, n_grid=4096, prior_weight=_default_p
     last in the dict and is left out of the normalising sum: the other
     labels' shares are those among themselves.
 
-    The mixtures of every label are uploaded to a context of their own
+    The mixtures of every label live on a context of their own
     (engine.get_engine(device, 'f64', 'importance'): the history tpe.suggest
     keeps resident on the 'main' one stays there) and one Engine.importance
-    call sums every label's cells on the device.
+    call sums every label's cells on the device.  builder: 'host' builds them
+    with posterior.label_posterior in numpy and uploads them; 'device' appends
+    the complete trials to that context's resident history and builds both
+    sides of every label there (Engine.build_split, with numpy's tie orders
+    where the device asks for them) -- the same mixtures, bit for bit; 'auto'
+    (default) takes 'device' from posterior.IMPORTANCE_DEVICE_MIN_TRIALS
+    complete trials on (infinite as measured so far: 'auto' is 'host'), and
+    'host' where the device builder does not serve:
+    a history it refuses (posterior.NonFiniteObservation) and a `device` that
+    is a list of several (the split build runs on one-device engines; the
+    host builder's upload serves a multi-device context as before).  An
+    explicit builder='device' raises in both cases (ValueError).
 
     curves=True returns (importances, {label: (x, w, p, m)}) for the labels
     with observations on both sides: the cells and, at each, the density p
@@ -1130,11 +1144,24 @@ def importance(space, trials, quantile=0.1, n_grid=4096, prior_weight=_default_p
     the trials with under the same keywords.
 
     ValueError, before any engine is touched: quantile outside (0, 1), n_grid
-    not an integer >= 1, fewer than 2 complete trials, and what
-    check_objectives, check_constraints and objective_rows refuse."""
+    not an integer >= 1, a builder that is none of the three, fewer than 2
+    complete trials, and what check_objectives, check_constraints and
+    objective_rows refuse."""
+    if builder not in IMPORTANCE_BUILDERS:
+        raise ValueError('importance: builder must be one of %r, got %r' % (IMPORTANCE_BUILDERS, builder))
     specs, names, obs, tids, done, splitter = _quantile_split(
         'importance', space, trials, quantile, n_grid, None, device, objectives, constraints)
     n = len(tids)
+    inputs = None
+    if builder == 'device' and len(_engine._devices(device)) != 1:
+        raise ValueError("importance: builder='device' runs on a one-device engine, got device=%r" % (device,))
+    if builder == 'device' or (builder == 'auto' and n >= _post.IMPORTANCE_DEVICE_MIN_TRIALS
+                               and len(_engine._devices(device)) == 1):
+        try:   # (the losses only say which trial positions exist: the split is the splitter's)
+            inputs = _post.device_inputs([(k, s.kind, s.args) for k, s in specs.items()], tids, np.zeros(n), obs)
+        except _post.NonFiniteObservation:
+            if builder == 'device':
+                raise
     posts, sel, cells, alphas, active = [], [], [], [], np.zeros(len(names))
     for li, (label, s) in enumerate(specs.items()):
         oi, ov = obs[label]
@@ -1142,7 +1169,8 @@ def importance(space, trials, quantile=0.1, n_grid=4096, prior_weight=_default_p
             keep = np.isin(oi, tids)
             oi, ov = oi[keep], ov[keep]
         b, a = splitter.split(oi, ov)
-        posts.append(_post.label_posterior(label, s.kind, s.args, b, a, prior_weight))
+        if inputs is None:
+            posts.append(_post.label_posterior(label, s.kind, s.args, b, a, prior_weight))
         active[li] = (len(b) + len(a)) / n
         if len(b) and len(a):
             sel.append(li)
@@ -1152,7 +1180,21 @@ def importance(space, trials, quantile=0.1, n_grid=4096, prior_weight=_default_p
     planes = None
     if sel:
         eng = _engine.get_engine(device, 'f64', 'importance')
-        eng.set_posterior(*_post.pack(posts))
+        if inputs is None:
+            eng.set_posterior(*_post.pack(posts))
+        else:
+            sp, cat_p, _, obs_off, obs_trial, obs_val = inputs
+            eng.history_reset(sp, cat_p)
+            eng.history_append(np.diff(obs_off), obs_trial, obs_val)
+            side = splitter.side[np.searchsorted(splitter.tids, tids)]   # per position in tids
+            _post.build_split_reference_order(eng, side, prior_weight, _post.DEFAULT_LF,
+                                              _post._ObsOf(obs_off, obs_trial, obs_val))
+            # the device's fold takes log and erf from the device library, the
+            # upload's from the host's: the same mixtures would give records a
+            # unit in the last place apart, so the built mixtures go through
+            # the upload's fold and both builders return the same floats
+            eng.set_posterior(*_post.pack(_post.resident_posteriors(
+                eng, [(k, s.kind, s.args) for k, s in specs.items()], prior_weight)))
         out = eng.importance(sel, cells, alphas, want_planes=curves)
         v, planes = (out[0], out[1:]) if curves else (out, None)
         raw[sel] = active[sel] * v

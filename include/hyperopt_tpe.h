@@ -316,6 +316,41 @@ int tpe_rebuild_labels(tpe_ctx *ctx, const double *losses, int64_t n_trials, int
                        const int32_t *order, const int32_t *labels, int32_t n_only,
                        int32_t *n_below_out, int32_t *ties);
 
+/* The split build: the posterior of the resident history (tpe_history_reset,
+ * tpe_history_append) under a split the caller chooses -- side[t] for every
+ * trial position t < n_trials: 1 below, 2 above, 0 in neither set (anything
+ * else is TPE_ERR_ARG).  Either side of a label may hold 0, 1, 2 or any number
+ * of observations, up to the label's whole history (the builds above keep at
+ * most 25 trials below).  Every label's two mixtures come out as
+ * adaptive_parzen_normal / the categorical pseudocounts give them for the two
+ * observation lists (hyperopt_amd/posterior.py label_posterior), and are
+ * left resident as the builds above leave theirs: tpe_get_mixture,
+ * tpe_importance, tpe_score and the rounds read them unchanged.  lf >= 1.
+ *   order_off_below / order_below, order_off_above / order_above (NULL: none
+ *       supplied): per side, as order_off / order of
+ *       tpe_build_posterior_resident_ordered -- label l's range is np.argsort
+ *       of that side's observations of the label (in observation order); an
+ *       empty range keeps the device's position order;
+ *   ties (may be NULL; n_labels entries): ties[l] bit 0 (bit 1) when label l's
+ *       below (above) mixture has equal mus while its linear-forgetting
+ *       weights differ and no order was supplied for it.
+ * Errors (TPE_ERR_ARG): an observation at a position >= n_trials, an order
+ * whose length differs from its list's or with an entry outside it, a
+ * multi-device context.  Records tpe_last_build_ms; tpe_build_report then
+ * reads n_below = -1 (a side has no one size) and these ties.  No
+ * tpe_rebuild_labels follows it: a caller with flagged labels builds again
+ * with their orders.  An armed tpe_prepare (tpe_arm_prepare) is dropped, not
+ * consumed: the expansion index of the previous posterior does not survive
+ * and none is queued.  To build several models of one history (one split per
+ * constraint, say) call it once per model and read or score each before the
+ * next.  A mixture is built TPE_SPLIT_TILE components per workgroup. */
+#define TPE_SPLIT_TILE 1024
+int tpe_build_split_resident(tpe_ctx *ctx, const uint8_t *side, int64_t n_trials,
+                             double prior_weight, int32_t lf,
+                             const int64_t *order_off_below, const int32_t *order_below,
+                             const int64_t *order_off_above, const int32_t *order_above,
+                             int32_t *ties);
+
 /* Read back one mixture of the resident posterior built by
  * tpe_build_posterior (side 0 below, 1 above): the (weights, mus, sigmas)
  * that adaptive_parzen_normal returns (categorical: p in weights).  *n

@@ -1,6 +1,7 @@
 """Timings of the hyperparameter importance (tpe.importance; needs the GPU).
 
     python tools/time_importance.py --gpus 1 [--configs 3,5] [--n-grid 4096] [--reps 10] [--out FILE]
+                                    [--builder host|device|both] [--sweep 100,1000,10000]
 
 On the histories of config 3 (workloads.mixed_history: 32 labels x 10000
 trials) and config 5 (128 labels x 50000 trials), quantile 0.1:
@@ -8,7 +9,11 @@ trials) and config 5 (128 labels x 50000 trials), quantile 0.1:
 * tpe.importance end to end on a Trials object holding the history (wall:
   the gather, the split, every label's mixtures on the host, the upload, the
   device call; median of --reps calls after a warm-up call -- the history
-  cache is warm, as it is in a running study);
+  cache is warm, as it is in a running study) -- per --builder; 'both' (the
+  default) alternates builder='host' and builder='device' call by call in
+  one process and records the split build's own device time
+  (tpe_last_build_ms) -- and, with --sweep, the same two at 32 labels and
+  each of the listed numbers of trials (nothing else is timed there);
 * Engine.importance alone on the posterior that call left resident (wall,
   cells uploaded, one synchronisation, v read back);
 * the alternative without the new kernels: the cells as a pool (Engine.pool_set
@@ -42,6 +47,71 @@ def timed(fn, reps):
         fn()
         ts.append((time.perf_counter() - t0) * 1e3)
     return dict(median_ms=float(np.median(ts)), min_ms=float(min(ts)), max_ms=float(max(ts)), reps=reps)
+
+
+def timed_builders(call, builders, reps):
+    """{builder: timing} of call(builder), the builders alternating call by
+    call after one warm-up call each."""
+    for b in builders:
+        call(b)
+    ts = {b: [] for b in builders}
+    for _ in range(reps):
+        for b in builders:
+            t0 = time.perf_counter()
+            call(b)
+            ts[b].append((time.perf_counter() - t0) * 1e3)
+    return {b: dict(median_ms=float(np.median(t)), min_ms=float(min(t)), max_ms=float(max(t)), reps=reps)
+            for b, t in ts.items()}
+
+
+def device_phases(domain, trials, args):
+    """builder='device' taken apart, its steps called one by one as
+    tpe.importance calls them (wall ms, median of --reps after a warm-up):
+    the gather and split, device_inputs, the history upload, the split
+    build(s) with the tie orders between them, the read-back of the mixtures,
+    the upload with its host fold -- and the device time of the split builds
+    of one call (tpe_last_build_ms after each, summed) with their number."""
+    from hyperopt_amd import posterior as P
+    from hyperopt_amd import tpe
+    from hyperopt_amd.engine import get_engine
+    eng = get_engine(0, 'f64', 'importance')
+    ts, dev = {}, []
+    build_split = eng.build_split
+
+    def counted(*a, **k):
+        out = build_split(*a, **k)
+        dev[-1].append(eng.last_build_ms())
+        return out
+    eng.build_split = counted
+    try:
+        for _ in range(args.reps + 1):
+            dev.append([])
+            t = [time.perf_counter()]
+            specs, names, obs, tids, done, splitter = tpe._quantile_split(
+                'importance', domain, trials, QUANTILE, args.n_grid, None, 0, None, None)
+            t.append(time.perf_counter())
+            labels = [(k, s.kind, s.args) for k, s in specs.items()]
+            sp, cat_p, _, off, otrial, oval = P.device_inputs(labels, tids, np.zeros(len(tids)), obs)
+            t.append(time.perf_counter())
+            eng.history_reset(sp, cat_p)
+            eng.history_append(np.diff(off), otrial, oval)
+            t.append(time.perf_counter())
+            side = splitter.side[np.searchsorted(splitter.tids, tids)]
+            P.build_split_reference_order(eng, side, 1.0, P.DEFAULT_LF, P._ObsOf(off, otrial, oval))
+            t.append(time.perf_counter())
+            posts = P.resident_posteriors(eng, labels, 1.0)
+            t.append(time.perf_counter())
+            eng.set_posterior(*P.pack(posts))
+            t.append(time.perf_counter())
+            for k, a, b in zip(('gather_split', 'device_inputs', 'history_upload', 'split_builds_and_orders',
+                                'mixture_readback', 'pack_set_posterior'), t, t[1:]):
+                ts.setdefault(k, []).append((b - a) * 1e3)
+    finally:
+        del eng.build_split
+    return dict(device_phases_ms={k: float(np.median(v[1:])) for k, v in ts.items()},
+                split_builds_per_call=len(dev[-1]),
+                split_build_device_ms=float(np.median([sum(d) for d in dev[1:]])),
+                split_build_device_ms_each=[float(x) for x in dev[-1]])
 
 
 def terms(lb, la, w, alpha):
@@ -87,7 +157,7 @@ def host_reference(posts, cells, alpha, labels):
     return out
 
 
-def run(n_labels, n_trials, args):
+def run(n_labels, n_trials, args, only_public=False):
     from hyperopt_amd import Domain, tpe
     from hyperopt_amd.engine import Engine, get_engine
     from hyperopt_amd.workloads import history_trials, hp_space, mixed_history
@@ -98,9 +168,17 @@ def run(n_labels, n_trials, args):
     domain = Domain(None, hp_space(hist.labels))
     rec['make_trials_s'] = time.perf_counter() - t0
     names = list(tpe.specs_of(domain))
-    rec['tpe_importance'] = timed(lambda: tpe.importance(domain, trials, quantile=QUANTILE, n_grid=args.n_grid),
-                                  args.reps)
-    got = tpe.importance(domain, trials, quantile=QUANTILE, n_grid=args.n_grid, normalize=False)
+    builders = ('host', 'device') if args.builder == 'both' else (args.builder,)
+    rec['tpe_importance'] = timed_builders(
+        lambda b: tpe.importance(domain, trials, quantile=QUANTILE, n_grid=args.n_grid, builder=b), builders, args.reps)
+    if 'device' in builders:
+        rec.update(device_phases(domain, trials, args))
+    if len(builders) == 2:
+        rec['device_below_every_host_run'] = bool(rec['tpe_importance']['device']['max_ms']
+                                                  < rec['tpe_importance']['host']['min_ms'])
+    if only_public:
+        return rec
+    got = tpe.importance(domain, trials, quantile=QUANTILE, n_grid=args.n_grid, normalize=False, builder='host')
     posts, cells, alpha = inputs(hist, args.n_grid)
     order = [[l[0] for l in hist.labels].index(k) for k in names]   # the engine's label order is the space's
     cells_e, alpha_e = [cells[i] for i in order], [alpha[i] for i in order]
@@ -159,11 +237,15 @@ def main():
     ap.add_argument('--reps', type=int, default=10)
     ap.add_argument('--host-labels', type=int, default=5)
     ap.add_argument('--out', default=None)
+    ap.add_argument('--builder', default='both', choices=('host', 'device', 'both'))
+    ap.add_argument('--sweep', default='', help='trial counts timed at 32 labels (tpe.importance alone)')
     args = ap.parse_args()
     shapes = {3: (32, 10000), 5: (128, 50000)}
     lines = []
-    for cfg in (int(c) for c in args.configs.split(',')):
-        rec = run(*shapes[cfg], args)
+    jobs = [(int(c), shapes[int(c)], False) for c in args.configs.split(',') if c]
+    jobs += [(None, (32, int(n)), True) for n in args.sweep.split(',') if n]
+    for cfg, shape, only_public in jobs:
+        rec = run(*shape, args, only_public=only_public)
         rec['config'] = cfg
         lines.append(json.dumps(rec))
         print(lines[-1], flush=True)
