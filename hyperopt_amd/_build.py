@@ -31,6 +31,7 @@ SOURCES = [os.path.join(HERE, 'csrc', 'tpe_engine.hip'),
            os.path.join(HERE, 'csrc', 'tpe_mo_hvs.hip'),
            os.path.join(HERE, 'csrc', 'tpe_mo_hvx.hip'),
            os.path.join(HERE, 'csrc', 'tpe_mo_hvx4.hip'),
+           os.path.join(HERE, 'csrc', 'tpe_mo_hvm.hip'),
            os.path.join(HERE, 'csrc', 'tpe_importance.hip'),
            os.path.join(HERE, 'csrc', 'tpe_interaction.hip'),
            os.path.join(HERE, 'csrc', 'tpe_interaction_mixed.hip'),
@@ -41,6 +42,7 @@ DEPS = SOURCES + [os.path.join(HERE, 'csrc', 'tpe_device.h'),
                   os.path.join(HERE, 'csrc', 'tpe_mo_hvs.h'),
                   os.path.join(HERE, 'csrc', 'tpe_mo_hvx.h'),
                   os.path.join(HERE, 'csrc', 'tpe_mo_hvx4.h'),
+                  os.path.join(HERE, 'csrc', 'tpe_mo_hvm.h'),
                   os.path.join(HERE, 'csrc', 'tpe_interaction.h'),
                   os.path.join(HERE, 'csrc', 'tpe_exp_table.h'),
                   os.path.join(REPO, 'include', 'hyperopt_tpe.h')]
@@ -61,12 +63,16 @@ FLAGS = ['--offload-arch=' + ARCH, '-O3', '-std=c++17', '-fPIC', '-shared',
 # multiply-adds -- its sums are stated operation by operation, each rounded on
 # its own, and posterior.mo_exclusive gives the same bits.
 # tpe_mo_hvx4.hip (its four-objective counterpart): the same two.
+# tpe_mo_hvm.hip (the sampled indicator): the same two -- its thresholds are an
+# fp64 difference, quotient and product, each rounded on its own, and
+# posterior.mo_hvm_thresholds gives the same integers.
 _NO_PACKED_FP32 = ['-Xclang', '-target-feature', '-Xclang', '-packed-fp32-ops']
 EXTRA_FLAGS = {'tpe_cmodel.hip': _NO_PACKED_FP32, 'tpe_mo_hv.hip': _NO_PACKED_FP32,
                'tpe_mo_hvs.hip': _NO_PACKED_FP32,
                'tpe_interaction_mixed.hip': _NO_PACKED_FP32,
                'tpe_mo_hvx.hip': _NO_PACKED_FP32 + ['-ffp-contract=off'],
-               'tpe_mo_hvx4.hip': _NO_PACKED_FP32 + ['-ffp-contract=off']}
+               'tpe_mo_hvx4.hip': _NO_PACKED_FP32 + ['-ffp-contract=off'],
+               'tpe_mo_hvm.hip': _NO_PACKED_FP32 + ['-ffp-contract=off']}
 
 
 def source_hash(deps=DEPS):

@@ -211,6 +211,7 @@ SIGNATURES = {
     'tpe_mo_keys_hvs': (ctypes.c_int, [_P, _P, _I64, _I32, _P, _I32, _I32, _I32, _P, _P, _P, _P, _P, _P, _P]),
     'tpe_mo_exclusive': (ctypes.c_int, [_P, _P, _I64, _I32, _P, _P, _I32, _I32, _P, _P]),
     'tpe_mo_exclusive4': (ctypes.c_int, [_P, _P, _I64, _I32, _P, _P, _I32, _I32, _P, _P]),
+    'tpe_mo_exclusive_mc': (ctypes.c_int, [_P, _P, _I64, _I32, _P, _P, _I32, _I32, _I32, _P, _P, _P]),
     'tpe_importance': (ctypes.c_int, [_P, _I32, _P, _P, _P, _P, _P, _P, _P, _P, _P]),
     'tpe_interactions': (ctypes.c_int, [_P, _I32, _I32, _P, _P, _P, _P, _I64, _P, _P, _P, _I64, _P, _P, _P,
                                         ctypes.c_double, _I32, _P, _P, _P, _P, _P]),

@@ -71,6 +71,13 @@
 // only these calls allocate, whichever comes first (the same for both):
 //   xflag : int32[n]  0 live, 1 weakly dominated within its J, 2 not valid
 //   xlive : int32[n]  the live rows; xhdr : int32[2]; excl : double[n]
+//
+// The sampled indicator (tpe_mo_exclusive_mc, two to eight objectives): the same
+// upload and k_moc_prep, then tpe_mo_hvm.hip's kernels; one read-back of the
+// counts with the covered samples and the alive rows behind them.  Buffers of
+// the context that only this call allocates, growing only:
+//   hvm_T : uint32[n + 4][8]   hvm_alive : uint8[n + 4]    hvm_lo : double[8]
+//   hvm_samp : uint64[S]       hvm_count : uint32[n + 2]
 #include <hip/hip_runtime.h>
 #include <hipcub/hipcub.hpp>
 
@@ -81,6 +88,7 @@
 #include "../../include/hyperopt_tpe.h"
 #include "tpe_ctx.h"
 #include "tpe_mo_hv.h"
+#include "tpe_mo_hvm.h"
 #include "tpe_mo_hvs.h"
 #include "tpe_mo_hvx.h"
 #include "tpe_mo_hvx4.h"
@@ -252,6 +260,12 @@ struct MoState {
     DevBuf<double> excl;
     PinVec<double> excl_h;
     PinVec<int32_t> xhdr_h;
+    // tpe_mo_exclusive_mc alone
+    DevBuf<uint32_t> hvm_T, hvm_count;
+    DevBuf<unsigned char> hvm_alive;
+    DevBuf<double> hvm_lo;
+    DevBuf<uint64_t> hvm_samp;
+    PinVec<uint32_t> hvm_count_h;
 };
 
 MoState* mo_of(tpe_ctx* ctx) {
@@ -696,6 +710,63 @@ int tpe_mo_exclusive4(tpe_ctx* ctx, const double* objectives, int64_t n, int32_t
     if (n_obj != 4) return ctx->fail(TPE_ERR_ARG, "tpe_mo_exclusive4: n_obj must be 4");
     return mo_exclusive_run(ctx, "tpe_mo_exclusive4", objectives, n, n_obj, reference, constraints, n_con, mode, excl,
                             n_overflow);
+}
+
+int tpe_mo_exclusive_mc(tpe_ctx* ctx, const double* objectives, int64_t n, int32_t n_obj, const double* reference,
+                        const double* constraints, int32_t n_con, int32_t mode, int32_t n_samples, uint64_t* count,
+                        uint64_t* covered, int32_t* n_alive) {
+    if (!ctx) return TPE_ERR_ARG;
+    if (!objectives || !reference || !count || !covered)
+        return ctx->fail(TPE_ERR_ARG, "tpe_mo_exclusive_mc: null pointer");
+    if (n < 1 || n > kMoMaxRows) return ctx->fail(TPE_ERR_ARG, "tpe_mo_exclusive_mc: n must be in [1, 2^20]");
+    if (n_obj < 2 || n_obj > kHvmMaxObj)
+        return ctx->fail(TPE_ERR_ARG, "tpe_mo_exclusive_mc: n_obj must be in [2, 8]");
+    if (constraints && (n_con < 1 || n_con > kMoMaxCon))
+        return ctx->fail(TPE_ERR_ARG, "tpe_mo_exclusive_mc: n_con must be in [1, 8]");
+    if (mode != 0 && mode != 1) return ctx->fail(TPE_ERR_ARG, "tpe_mo_exclusive_mc: mode must be 0 or 1");
+    if (n_samples < 64 || n_samples > (1 << 20) || n_samples % 64)
+        return ctx->fail(TPE_ERR_ARG, "tpe_mo_exclusive_mc: n_samples must be a multiple of 64 in [64, 2^20]");
+    HvmRef ref{};
+    for (int m = 0; m < n_obj; ++m) {
+        ref.r[m] = reference[m];
+        if (!(reference[m] - reference[m] == 0.0))
+            return ctx->fail(TPE_ERR_ARG, "tpe_mo_exclusive_mc: the reference point must be finite");
+    }
+    HIPCHK(ctx, hipSetDevice(ctx->device));
+    hipStream_t st = ctx->stream;
+    MoState* S = mo_of(ctx);
+    const int32_t N = (int32_t)n;
+    const size_t nf = (size_t)n * n_obj, ng = constraints ? (size_t)n * n_con : 0;
+    HIPCHK(ctx, S->in.reserve(nf + ng));
+    HIPCHK(ctx, S->in_h.resize(nf + ng));
+    if (constraints) HIPCHK(ctx, S->v.reserve(n));
+    HIPCHK(ctx, S->hvm_T.reserve(((size_t)n + kHvmStep) * kHvmRow));
+    HIPCHK(ctx, S->hvm_alive.reserve((size_t)n + kHvmStep));
+    HIPCHK(ctx, S->hvm_lo.reserve(kHvmMaxObj));
+    HIPCHK(ctx, S->hvm_samp.reserve((size_t)n_samples));
+    HIPCHK(ctx, S->hvm_count.reserve((size_t)n + kHvmTail));
+    HIPCHK(ctx, S->hvm_count_h.resize((size_t)n + kHvmTail));
+
+    // F (and G) in pinned memory: the call's one upload
+    std::memcpy(S->in_h.data(), objectives, nf * sizeof(double));
+    if (constraints) std::memcpy(S->in_h.data() + nf, constraints, ng * sizeof(double));
+    HIPCHK(ctx, hipMemcpyAsync(S->in.p, S->in_h.data(), (nf + ng) * sizeof(double), hipMemcpyHostToDevice, st));
+    if (constraints) {
+        // the rows that are dead or infeasible: NaN on the device copy
+        hipLaunchKernelGGL(k_moc_prep, dim3(blocks_of(n, kBlock)), dim3(kBlock), 0, st, S->in.p, S->in.p + nf, N,
+                           n_obj, n_con, S->v.p);
+        HIPCHK(ctx, hipGetLastError());
+    }
+    const HvmBufs b{S->in.p, S->hvm_lo.p, S->hvm_T.p, S->hvm_alive.p, S->hvm_samp.p, S->hvm_count.p};
+    HIPCHK(ctx, hvm_launch(n_obj, st, b, N, ref, mode, n_samples));
+    HIPCHK(ctx, hipGetLastError());
+    HIPCHK(ctx, hipMemcpyAsync(S->hvm_count_h.data(), S->hvm_count.p, ((size_t)n + kHvmTail) * sizeof(uint32_t),
+                               hipMemcpyDeviceToHost, st));
+    HIPCHK(ctx, hipStreamSynchronize(st));   // the call's one synchronisation
+    for (int64_t i = 0; i < n; ++i) count[i] = (uint64_t)S->hvm_count_h[(size_t)i];
+    *covered = (uint64_t)S->hvm_count_h[(size_t)n];
+    if (n_alive) *n_alive = (int32_t)S->hvm_count_h[(size_t)n + 1];
+    return TPE_OK;
 }
 
 }  // extern "C"

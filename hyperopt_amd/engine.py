@@ -924,6 +924,36 @@ class Engine(object):
             excl[rows] = _post.mo_exclusive(F, ref, mode, G=G, rows=rows)[rows]
         return (excl, n_over.value) if want_overflow else excl
 
+    def mo_exclusive_mc(self, F, reference, mode, n_samples, G=None):
+        """The sampled hypervolume indicator's counts of the rows of F [n, 2 ..
+        8] against `reference` (tpe_mo_exclusive_mc; posterior.mo_exclusive_mc
+        states the rule and gives the same integers): (count uint64 [n],
+        covered) on n_samples fixed sample points, a multiple of 64 in 64 ..
+        2^20.  mode 'before': count[i] = the samples whose first covering row
+        is i; 'others': those that row i alone covers.  G [n, K]: the
+        constraint rows, a row with a violation is not valid."""
+        from . import posterior as _post
+        if mode not in _post.MO_EXCLUSIVE_MODES:
+            raise ValueError("mode must be 'before' or 'others'")
+        F = np.ascontiguousarray(F, dtype=np.float64)
+        if F.ndim != 2:
+            raise ValueError('F must be [n, n_objectives]')
+        n = F.shape[0]
+        ref = np.ascontiguousarray(reference, dtype=np.float64).ravel()
+        if len(ref) != F.shape[1]:
+            raise ValueError('reference must have a value for every objective')
+        if G is not None:
+            G = np.ascontiguousarray(G, dtype=np.float64)
+            if G.ndim != 2 or G.shape[0] != n:
+                raise ValueError('G must be [n, n_constraints], a row for every row of F')
+        count = np.empty(n, dtype=np.uint64)
+        covered = ctypes.c_uint64(0)
+        self._check(self.lib.tpe_mo_exclusive_mc(self.h, _ptr(F), n, F.shape[1], _ptr(ref), _ptr(G),
+                                                 0 if G is None else G.shape[1],
+                                                 _post.MO_EXCLUSIVE_MODES.index(mode), int(n_samples), _ptr(count),
+                                                 ctypes.byref(covered), None))
+        return count, int(covered.value)
+
     def importance(self, labels, cells, alpha, want_planes=False):
         """The importance sums of resident labels (tpe_importance): labels the
         label indices, each once; cells one (x, w, merge) per label

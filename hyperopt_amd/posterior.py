@@ -486,6 +486,78 @@ def mo_exclusive(F, reference, mode, G=None, rows=None):
     return excl
 
 
+MO_HVM_STREAM = 0x7FFFFFBD                # TPE_MO_HVM_STREAM
+MO_HVM_CHUNK = 1 << 24                    # (alive row, sample) tests mo_exclusive_mc holds at a time
+
+
+def mo_hvm_thresholds(F, reference, G=None):
+    """The lattice of the sampled indicator (tpe_mo_exclusive_mc,
+    include/hyperopt_tpe.h): (T int64 [n, M], alive bool [n], V).  With lo[m]
+    the valid rows' (mo_hv_valid) minimum on axis m and span[m] = reference[m]
+    - lo[m], T[i][m] = ceil(((F[i][m] - lo[m]) / span[m]) * 2^32), every
+    operation rounded on its own; a valid row is alive unless some T is 2^32
+    (thin: it covers no sample).  V = prod_m span[m], multiplied in ascending
+    m; 0.0, with no row alive and T zero, when no row is valid."""
+    F = np.asarray(F, dtype=np.float64)
+    r = np.asarray(reference, dtype=np.float64)
+    valid = mo_hv_valid(F, r, G)
+    T = np.zeros(F.shape, dtype=np.int64)
+    if not valid.any():
+        return T, valid, 0.0
+    lo = F[valid].min(axis=0)
+    with np.errstate(over='ignore', invalid='ignore'):
+        span = r - lo
+        c = np.ceil(((F[valid] - lo) / span) * 4294967296.0)
+        T[valid] = np.where(c < 4294967296.0, c, 4294967296.0).astype(np.int64)   # (inf / inf: thin)
+        V = 1.0
+        for m in range(F.shape[1]):
+            V = V * float(span[m])
+    return T, valid & (T < (1 << 32)).all(axis=1), V
+
+
+def mo_exclusive_mc(F, reference, mode, n_samples, G=None):
+    """The sampled hypervolume indicator's counts (the numpy restatement of
+    tpe_mo_exclusive_mc, include/hyperopt_tpe.h, and its integers): (count
+    uint64 [n], covered).  F [n, 2 .. 8], all minimised.  Sample s has x[s][m] =
+    word m % 4 of Philox4x32-10 under the counter (s, m / 4, 0, MO_HVM_STREAM)
+    and the key MO_HVS_KEY; an alive row i (mo_hvm_thresholds) covers it when
+    x[s][m] >= T[i][m] on every axis.  'before': count[i] = the samples whose
+    first covering row is i; 'others': those that i alone covers.  covered =
+    the samples some row covers.  V * count / n_samples estimates
+    mo_exclusive's column, V * covered / n_samples the hypervolume."""
+    F = np.asarray(F, dtype=np.float64)
+    if F.ndim != 2 or not 2 <= F.shape[1] <= MO_MAX_OBJECTIVES:
+        raise ValueError('F must be [n, 2 .. %d objectives]' % MO_MAX_OBJECTIVES)
+    r = np.asarray(reference, dtype=np.float64)
+    if r.shape != (F.shape[1],) or not np.isfinite(r).all():
+        raise ValueError('reference must be %d finite values' % F.shape[1])
+    if mode not in MO_EXCLUSIVE_MODES:
+        raise ValueError("mode must be 'before' or 'others'")
+    n_samples = int(n_samples)
+    if not 64 <= n_samples <= MO_HVS_MAX_SAMPLES or n_samples % 64:
+        raise ValueError('n_samples must be a multiple of 64 in [64, %d]' % MO_HVS_MAX_SAMPLES)
+    T, alive, _ = mo_hvm_thresholds(F, r, G)
+    rows = np.flatnonzero(alive)
+    count = np.zeros(len(F), dtype=np.uint64)
+    if not len(rows):
+        return count, 0
+    Ta = T[rows].astype(np.uint64)
+    covered = 0
+    step = max(64, MO_HVM_CHUNK // len(rows) // 64 * 64)
+    for s0 in range(0, n_samples, step):
+        s = np.arange(s0, min(s0 + step, n_samples), dtype=np.uint64)
+        cov = np.ones((len(rows), len(s)), dtype=bool)
+        for blk in range((F.shape[1] + 3) // 4):
+            words = _philox4x32_10(s, blk, 0, MO_HVM_STREAM, *MO_HVS_KEY)
+            for m in range(4 * blk, min(4 * blk + 4, F.shape[1])):
+                cov &= words[m % 4][None, :] >= Ta[:, m, None]
+        k = cov.sum(axis=0)
+        covered += int(np.count_nonzero(k))
+        own = k > 0 if mode == 'before' else k == 1          # (argmax: the first covering row)
+        count += np.bincount(rows[cov.argmax(axis=0)[own]], minlength=len(F)).astype(np.uint64)
+    return count, covered
+
+
 def mo_keys(F, counts=None, G=None, tiebreak='dominates', n_select=0, n_samples=MO_HVS_SAMPLES):
     """The Pareto-compliant total order of the objective vectors F [n, M] as
     one loss column: keys[i] is row i's position, 0 .. as a float64, under

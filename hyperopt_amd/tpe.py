@@ -948,7 +948,7 @@ def pareto_front(trials, objectives, constraints=None):
 
 
 def hypervolume(trials, objectives, reference=None, constraints=None, history=False, contributions=False,
-                builder='auto', device=0):
+                builder='auto', device=0, method='exact', n_samples=None):
     """The hypervolume indicator of the complete trials under 2, 3 or 4
     objectives, all minimised (not in the reference; the number Optuna's
     plot_hypervolume_history draws): a dict with
@@ -977,12 +977,42 @@ def hypervolume(trials, objectives, reference=None, constraints=None, history=Fa
     tpe.suggest keeps resident stays where it is), 'auto' the device from
     MO_DEVICE_MIN_TRIALS complete trials on.  The same bits either way.
 
+    method='sampled' (2 to 8 objectives): the same dict estimated on n_samples
+    fixed Philox sample points (default posterior.MO_HVS_SAMPLES; a multiple
+    of 64 in 64 .. 2^20) of the box [lo, reference), lo the valid rows' minimum
+    per axis and V its volume: hypervolume = V covered / n_samples, history = V
+    cumsum(count) / n_samples with count[t] the samples that row t is the first
+    to cover, contributions = V count / n_samples with count the samples a row
+    alone covers (posterior.mo_exclusive_mc states the rule and is
+    builder='host'; builder='device' is Engine.mo_exclusive_mc; the counts are
+    integers, so the same dict either way, and the same on every call: there
+    is no seed).  Three more keys: method, n_samples, and stderr = V sqrt(p (1
+    - p) / n_samples), p = covered / n_samples, the binomial standard error
+    of hypervolume.
+
     ValueError, before any engine is touched: what check_objectives,
     check_constraints and objective_rows refuse, a number of objectives other
-    than 2, 3 or 4, a reference of another length or with a non-finite entry, an
-    unknown builder."""
+    than 2, 3 or 4 (method='sampled': outside 2 .. 8), a reference of another
+    length or with a non-finite entry, an unknown builder or method, n_samples
+    with method='exact' or not such a multiple of 64."""
+    if method not in ('exact', 'sampled'):
+        raise ValueError("hypervolume: method must be 'exact' or 'sampled'")
+    sampled = method == 'sampled'
+    if sampled:
+        if n_samples is None:
+            n_samples = _post.MO_HVS_SAMPLES
+        if (not isinstance(n_samples, (int, np.integer)) or isinstance(n_samples, bool) or n_samples % 64
+                or not 64 <= n_samples <= _post.MO_HVS_MAX_SAMPLES):
+            raise ValueError("hypervolume(method='sampled'): n_samples must be a multiple of 64 in [64, %d]"
+                             % _post.MO_HVS_MAX_SAMPLES)
+        n_samples = int(n_samples)
+    elif n_samples is not None:
+        raise ValueError("hypervolume: n_samples needs method='sampled'")
     objectives = check_objectives(objectives)
-    if objectives is None or len(objectives) not in (2, 3, 4):
+    if sampled and (objectives is None or not 2 <= len(objectives) <= _post.MO_MAX_OBJECTIVES):
+        raise ValueError("hypervolume(method='sampled') needs 2 .. %d objectives, got %d"
+                         % (_post.MO_MAX_OBJECTIVES, len(objectives or ())))
+    if not sampled and (objectives is None or len(objectives) not in (2, 3, 4)):
         raise ValueError('hypervolume needs 2, 3 or 4 objectives, got %d' % len(objectives or ()))
     constraints = check_constraints(constraints, objectives)
     if builder not in ('auto', 'host', 'device'):
@@ -1013,6 +1043,9 @@ def hypervolume(trials, objectives, reference=None, constraints=None, history=Fa
             reference = np.where(hi > lo, hi + 0.1 * (hi - lo), hi + 1.0)
     valid = _post.mo_hv_valid(F, reference, G)
     on_device = len(F) and (builder == 'device' or (builder == 'auto' and len(F) >= MO_DEVICE_MIN_TRIALS))
+    if sampled:
+        return _hypervolume_sampled(docs, F, G, reference, valid, on_device, device, n_samples, history,
+                                    contributions)
 
     def exclusive(mode):
         if not valid.any():
@@ -1027,6 +1060,31 @@ def hypervolume(trials, objectives, reference=None, constraints=None, history=Fa
         out['history'] = curve
     if contributions:
         c = exclusive('others')
+        rows = sorted(np.flatnonzero(c > 0).tolist(), key=lambda i: (-c[i], out['tids'][i]))
+        out['contributions'] = {out['tids'][i]: float(c[i]) for i in rows}
+    return out
+
+
+def _hypervolume_sampled(docs, F, G, reference, valid, on_device, device, S, history, contributions):
+    """hypervolume's dict under method='sampled': the integer counts from either
+    builder, scaled to volumes here."""
+    V = _post.mo_hvm_thresholds(F, reference, G)[2]
+
+    def counts(mode):
+        if not valid.any():
+            return np.zeros(len(F), dtype=np.uint64), 0
+        if on_device:
+            return _engine.get_engine(device, 'f64', 'importance').mo_exclusive_mc(F, reference, mode, S, G=G)
+        return _post.mo_exclusive_mc(F, reference, mode, S, G=G)
+    first, covered = counts('before')
+    p = covered / S
+    out = dict(hypervolume=V * float(covered) / S, reference=tuple(reference.tolist()),
+               tids=[d['tid'] for d in docs], skipped=int(len(F) - np.count_nonzero(valid)), method='sampled',
+               n_samples=S, stderr=V * float(np.sqrt(p * (1.0 - p) / S)))
+    if history:
+        out['history'] = V * np.cumsum(first).astype(np.float64) / S
+    if contributions:
+        c = V * counts('others')[0].astype(np.float64) / S
         rows = sorted(np.flatnonzero(c > 0).tolist(), key=lambda i: (-c[i], out['tids'][i]))
         out['contributions'] = {out['tids'][i]: float(c[i]) for i in rows}
     return out

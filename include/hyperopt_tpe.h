@@ -1030,6 +1030,48 @@ int tpe_mo_exclusive4(tpe_ctx *ctx, const double *objectives /* [n][4] row-major
                       int32_t mode /* 0: rows before i, 1: every other row */,
                       double *excl /* [n] */, int32_t *n_overflow /* or NULL */);
 
+/* The sampled hypervolume indicator (tpe.hypervolume(method='sampled'); an
+ * addition to ABI version 5; its kernels are a unit of their own,
+ * tpe_mo_hvm.hip): tpe_mo_exclusive's question for n_obj 2 .. 8, answered on
+ * n_samples fixed sample points and returned as integer counts.  The valid
+ * rows, the constraints and the modes are tpe_mo_exclusive's.
+ *   lo[m] = the minimum of F[i][m] over the valid rows; span[m] = reference[m] -
+ *       lo[m] (> 0); V = prod_m span[m], multiplied by the caller in ascending m;
+ *   T[i][m] = ceil(((F[i][m] - lo[m]) / span[m]) * 4294967296.0) -- fp64, the
+ *       difference, the quotient and the product each rounded on its own -- an
+ *       integer in [0, 2^32].  A valid row with some T[i][m] == 2^32 is thin: it
+ *       covers no sample.  Row i is alive when it is valid and not thin;
+ *   sample s = 0 .. n_samples - 1: x[s][m] = word m % 4 of philox4x32_10 with
+ *       the counter (s, m / 4, 0, TPE_MO_HVM_STREAM) and the key
+ *       (TPE_MO_HVS_KEY0, TPE_MO_HVS_KEY1) -- no seed: the counts are a function
+ *       of the rows alone;
+ *   an alive row i covers s iff x[s][m] >= T[i][m] for every m;
+ *   mode 0: first[s] = the smallest alive i covering s, count[i] = #{s :
+ *       first[s] == i} -- V cumsum(count) / n_samples estimates the hypervolume
+ *       history; mode 1: count[i] = the samples that exactly one alive row
+ *       covers, that row being i -- V count[i] / n_samples estimates row i's
+ *       contribution;
+ *   *covered = the samples some alive row covers (mode 0: the sum of count): V
+ *       *covered / n_samples estimates the hypervolume, with the binomial
+ *       standard error V sqrt(p (1 - p) / n_samples), p = *covered / n_samples.
+ *       The lattice of 2^32 steps per axis moves it by at most n_obj 2^-32 V.
+ * Integers from T on: the same bits on every run and the integers of
+ * posterior.mo_exclusive_mc.  *n_alive (may be NULL) = the alive rows.  One
+ * upload, one stream synchronisation, no cooperative launch.  Its own reusable
+ * buffers (counted by tpe_device_bytes, growing only) are allocated by the
+ * first such call.  A multi-device context runs it on its primary device.
+ * TPE_ERR_ARG: a NULL objectives, reference, count or covered; n < 1 or n >
+ * 2^20; n_obj outside [2, 8]; a reference entry that is not finite; n_con
+ * outside [1, 8] with constraints; mode not 0 or 1; n_samples not a multiple of
+ * 64 in [64, 2^20].  On an error the outputs are untouched. */
+#define TPE_MO_HVM_STREAM 0x7FFFFFBDu   /* the stream below TPE_MO_HVS_STREAM */
+int tpe_mo_exclusive_mc(tpe_ctx *ctx, const double *objectives /* [n][n_obj] row-major */,
+                        int64_t n, int32_t n_obj /* 2 .. 8 */, const double *reference /* [n_obj] */,
+                        const double *constraints /* [n][n_con] row-major, or NULL */, int32_t n_con,
+                        int32_t mode /* 0: rows before i, 1: every other row */, int32_t n_samples,
+                        uint64_t *count /* [n] */, uint64_t *covered /* [1] */,
+                        int32_t *n_alive /* or NULL */);
+
 /* ---- constraint densities (c-TPE) -------------------------------------------
  * tpe.suggest(constraints=..., constraint_model='density'): besides the
  * resident posterior (model 0, the objective's) a context holds up to eight

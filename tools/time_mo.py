@@ -6,6 +6,7 @@
     python tools/time_mo.py --gpus 1 --quality-constrained [--evals 100] [--out FILE]
     python tools/time_mo.py --gpus 1 --density [--out FILE]
     python tools/time_mo.py --gpus 1 --indicator [--indicator-m 4] [--host-max-n 10000] [--out FILE]
+    python tools/time_mo.py --gpus 1 --indicator --indicator-method sampled [--indicator-m 8] [--out FILE]
 
 * Engine.mo_keys (tpe_mo_keys: upload, all-pairs kernel, pack, radix sort,
   scatter, read-back; one synchronisation) at n in {1000, 10000, 50000} x M in
@@ -80,6 +81,12 @@ above x 2, 3 and 4 objectives x both modes (4: tpe_mo_exclusive4), on a
 with sum 30 at 4 (every row live); median of --reps calls, the numpy builder up
 to --host-max-n rows; with the live rows, the overflow count and whether both
 give the same bits.  --indicator-m M keeps the rows with M objectives.
+--indicator-method sampled (tpe.hypervolume(method='sampled')):
+Engine.mo_exclusive_mc (tpe_mo_exclusive_mc) at the sizes above x 4 and 8
+objectives (or --indicator-m, 2 .. 8) x 65 536 and 2^20 samples x both modes,
+alternating with posterior.mo_exclusive_mc where a call is at most 2^27 row x
+sample tests and, at four objectives, with the exact Engine.mo_exclusive; with
+the estimate, its standard error and the exact value.
 
 Results are appended to --out as one JSON object per line."""
 import argparse
@@ -497,6 +504,51 @@ def indicator_times(args):
     return out
 
 
+def sampled_indicator_times(args):
+    """tpe.hypervolume(method='sampled')'s two columns: Engine.mo_exclusive_mc against posterior.mo_exclusive_mc
+    (up to 2^27 row x sample tests a call) and, at four objectives, against the exact Engine.mo_exclusive --
+    alternating; the value is V x the column's sum / S (the hypervolume for 'before')."""
+    from hyperopt_amd import posterior as P
+    from hyperopt_amd.engine import Engine
+    eng = Engine(0, 'f64')
+    out = []
+    for n in SIZES:
+        for M in ([args.indicator_m] if args.indicator_m else [4, 8]):
+            F = np.random.RandomState(n + M).uniform(size=(n, M))
+            ref = tuple((F.max(axis=0) + 0.1 * (F.max(axis=0) - F.min(axis=0))).tolist())
+            V = P.mo_hvm_thresholds(F, ref)[2]
+            for S in (65536, 1 << 20):
+                for mode in P.MO_EXCLUSIVE_MODES:
+                    legs = dict(device=lambda: eng.mo_exclusive_mc(F, ref, mode, S))
+                    if n * S <= 1 << 27:
+                        legs['host'] = lambda: P.mo_exclusive_mc(F, ref, mode, S)
+                    if M == 4:
+                        legs['exact'] = lambda: eng.mo_exclusive(F, ref, mode)
+                    ts = {name: [] for name in legs}
+                    got = {name: legs[name]() for name in legs}               # warm-up
+                    for _ in range(args.reps):                                 # alternating
+                        for name in legs:
+                            t0 = time.perf_counter()
+                            legs[name]()
+                            ts[name].append((time.perf_counter() - t0) * 1e3)
+                    count, covered = got['device']
+                    p = covered / S
+                    rec = dict(what='mo_exclusive_mc', rows='uniform', n=n, M=M, S=S, mode=mode, covered=covered,
+                               owners=int(np.count_nonzero(count)), value=V * float(count.sum()) / S,
+                               stderr=V * float(np.sqrt(p * (1 - p) / S)))
+                    for name, v in ts.items():
+                        rec[name] = dict(median_ms=float(np.median(v)), min_ms=float(min(v)), max_ms=float(max(v)),
+                                         reps=len(v))
+                    if 'host' in legs:
+                        rec['same_counts'] = bool(np.array_equal(count, got['host'][0]) and covered == got['host'][1])
+                    if 'exact' in legs:
+                        rec['exact_value'] = float(np.sum(got['exact']))
+                    print(json.dumps(rec), flush=True)
+                    out.append(rec)
+    eng.close()
+    return out
+
+
 def quality(args):
     from hyperopt_amd import STATUS_OK, Trials, fmin, hp, rand, tpe
     space = {'x%d' % i: hp.uniform('x%d' % i, 0, 1) for i in range(4)}
@@ -544,6 +596,8 @@ def main():
     ap.add_argument('--density', action='store_true')
     ap.add_argument('--indicator', action='store_true')
     ap.add_argument('--indicator-m', type=int, default=0, metavar='M', help='--indicator: only the rows with M objectives')
+    ap.add_argument('--indicator-method', choices=('exact', 'sampled'), default='exact',
+                    help="--indicator: 'sampled' times tpe_mo_exclusive_mc at M in {4, 8} (--indicator-m: 2 .. 8)")
     ap.add_argument('--tiebreak', choices=('dominates', 'hypervolume', 'hypervolume_mc'), default='dominates')
     ap.add_argument('--objectives', type=int, default=0, metavar='M', help='--tiebreak hypervolume_mc: only M objectives')
     ap.add_argument('--samples', type=int, default=65536, metavar='S', help='--tiebreak hypervolume_mc: n_samples')
@@ -557,7 +611,11 @@ def main():
         args.evals = 100 if args.quality_constrained else 200
     if args.constraints and not 1 <= args.constraints <= 8:
         ap.error('--constraints: 1 to 8 columns')
-    if args.indicator:
+    if args.indicator and args.indicator_method == 'sampled':
+        if args.indicator_m and not 2 <= args.indicator_m <= 8:
+            ap.error('--indicator-m: 2 to 8 objectives')
+        recs = sampled_indicator_times(args)
+    elif args.indicator:
         recs = indicator_times(args)
     elif args.quality_constrained:
         recs = quality_constrained(args)
